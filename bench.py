@@ -15,8 +15,10 @@
   scaling  : weak -- every rank owns its own 100 k reads; with N > 1 each rank scans 1/N of the genome's
              positions and the seed-index entries are all-gathered over RCCL/xGMI before every rank builds
              its lookup structure; the align step has no cross-GPU dependency.
-  After the timed region the line also carries `overlap_strong`: one pass of the all-vs-all form below on
-  --overlap-reads reads (0 = skip), so that a run at N = 1, 2, 4, 8 shows the strong-scaling curve too.
+  With --full, after the timed region the line also carries `cpu_baseline` (the CPU oracle on --cpu-sample reads of
+  the same workload, rows compared) and `overlap_strong`: one pass of the all-vs-all form below on --overlap-reads
+  reads (0 = skip), so that a run at N = 1, 2, 4, 8 shows the strong-scaling curve too.  A plain run leaves both out
+  (null in the line): it sets up, warms up, times --steps steps and prints the line.
 
   --mode overlap
   workload : BASELINE.json configs[3] shape -- all-vs-all overlap of --overlap-reads synthetic 15 kb reads @15 %
@@ -28,6 +30,12 @@
   python bench.py --gpus N --steps K --warmup W          one process per GPU; with N > 1 and no WORLD_SIZE in the
   environment this process starts the N ranks itself (as child processes, before anything touches the GPU) and
   relays rank 0's line; under torch.distributed.run it is one of the ranks.  Prints ONE JSON line on rank 0.
+
+  --dump-outputs DIR   after the timed steps, rank 0 writes what the last timed step handed back as DIR/<name>.npy
+                       (float64): one file per column of the result rows (locate: one row per read; overlap: one row
+                       per overlap, a fixed seeded sample of them when they exceed the byte budget, row_index.npy then
+                       names the rows kept) and stats_<counter>.npy per counter of the step.  The inputs are seeded:
+                       the same arguments give the same inputs on every run, so two builds compare file for file.
 """
 import argparse
 import json
@@ -86,7 +94,36 @@ def parse():
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU work: every rank joins a gloo process group, the ranks are summed, rank 0 prints the census "
                          "(checks the launcher and the rendezvous on a box without GPUs)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs beyond the headline figure: the CPU baseline (--cpu-sample), the all-vs-all leg "
+                         "(--overlap-reads) and the CPU oracle's spot check of the all-vs-all rows (--overlap-check)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result rows and counters to DIR/<name>.npy (float64)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+DUMP_BYTES = 60 << 20        # --dump-outputs: data bytes of all files together, under 64 MB with the .npy headers
+
+
+def dump_outputs(d, rows, stats):
+    """--dump-outputs: one float64 .npy per column of `rows` (a structured array) and per counter (n_*) of `stats`.  Rows
+    beyond DUMP_BYTES are thinned to a fixed seeded sample; row_index.npy then holds the row numbers kept."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    names = rows.dtype.names
+    n = rows.size
+    if n * 8 * len(names) > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_BYTES // (8 * (len(names) + 1)), replace=False))
+        rows = rows[idx]
+        np.save(os.path.join(d, "row_index.npy"), idx.astype(np.float64))
+    for c in names:
+        np.save(os.path.join(d, f"{c}.npy"), rows[c].astype(np.float64))
+    for k, v in stats.items():
+        if k.startswith("n_"):
+            np.save(os.path.join(d, f"stats_{k}.npy"), np.array([v], np.float64))
 
 
 def socket_cores() -> int:
@@ -187,8 +224,9 @@ def launch_ranks(n: int) -> int:
 
 
 # ------------------------------------------------------------------------------------------------ all-vs-all leg
-def overlap_leg(a, ctx, rank, world, nthreads, steps, warmup):
-    """Strong-scaling all-vs-all (module docstring).  Returns the dict rank 0 reports (None on other ranks)."""
+def overlap_leg(a, ctx, rank, world, nthreads, steps, warmup, rows_out=None):
+    """Strong-scaling all-vs-all (module docstring).  Returns the dict rank 0 reports (None on other ranks); the rows of the
+    last step go to rows_out["ov"] when a dict is given."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -277,9 +315,11 @@ def overlap_leg(a, ctx, rank, world, nthreads, steps, warmup):
     # ---- outside the timed region: the oracle on sampled targets of this rank's shard, every read of the set a query --
     # capacity-sized slices, the scan's 32 rows, the cascade of windows and k_ovl_after are all live at this size
     spot = None
-    if rank == 0 and a.overlap_check > 0:
+    if rank == 0 and a.full and a.overlap_check > 0:
         spot = oracle_spot_check(ctx, S, last["ov"], r_lo, r_hi, n, rl, mask, a.R, trials, a.overlap_check, nthreads)
     S.close()
+    if rows_out is not None:
+        rows_out["ov"], rows_out["st"] = last["ov"], st
     if rank != 0:
         return None
     elapsed = float(allt[:, 0].max())
@@ -354,7 +394,7 @@ def guarded_overlap(a, ctx, rank, world, nthreads, headline):
     is visible to the launcher and in the run records.  (A single-rank exception is an ordinary result: the error is noted in
     the line and the run ends normally.)  headline: rank 0's finished line, None elsewhere."""
     import threading
-    if a.overlap_reads <= 0:
+    if not a.full or a.overlap_reads <= 0:
         return None
     done = threading.Event()
 
@@ -445,8 +485,11 @@ def run_rank(a):
         timer = threading.Timer(a.timeout, hung)
         timer.daemon = True
         timer.start()
-        ov = overlap_leg(a, ctx, rank, world, nthreads, a.steps, a.warmup)
+        last = {}
+        ov = overlap_leg(a, ctx, rank, world, nthreads, a.steps, a.warmup, rows_out=last)
         timer.cancel()
+        if rank == 0 and a.dump_outputs:
+            dump_outputs(a.dump_outputs, last["ov"], last["st"])
         if rank == 0:
             out = {"metric": METRIC, "value": ov["pairs_per_s"], "unit": "pairs/s", "n_gpus": world, "steps": a.steps,
                    "warmup": a.warmup, "ms_per_step": round(1e3 * ov["seconds_per_step"], 3), "higher_is_better": True,
@@ -468,7 +511,7 @@ def run_rank(a):
     genome = eng.synth_genome(2, a.genome)
     reads, offs, _ = eng.synth_reads(3 + 1000 * rank, genome, a.reads, a.read_len, 0.05, 0.05, 0.05, nthreads=nthreads)
     t_gen = time.time() - t0
-    cpu_reads = reads[: a.cpu_sample * a.read_len].copy() if rank == 0 else None
+    cpu_reads = reads[: a.cpu_sample * a.read_len].copy() if rank == 0 and a.full else None
     t0 = time.time()
     T = ctx.seqs_from_text(genome, np.array([0, genome.size], np.uint64), strict_acgt=True)
     Rd = ctx.seqs_from_text(reads, offs, strict_acgt=True)        # H2D + 2-bit pack on the GPU: now resident
@@ -592,9 +635,12 @@ def run_rank(a):
                              "reference_band_gcups counts the cells of the reference's 2*max_dst+1 band, processed_window_gcups the "
                              "cells inside the window the array really sweeps for the located reads"}
 
-    # ---- CPU baseline: the faithful oracle on this box's host cores, bounded sample of the same workload
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rows, st)
+
+    # ---- CPU baseline (--full): the faithful oracle on this box's host cores, bounded sample of the same workload
     cpu = None
-    if a.cpu_sample > 0 and world == 1:
+    if a.full and a.cpu_sample > 0 and world == 1:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         from oraclelib import Oracle
         orc = Oracle()

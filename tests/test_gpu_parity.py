@@ -1599,7 +1599,7 @@ def test_bench_two_ranks_share_the_gpu_and_agree_with_one(lib):
     from conftest import ROOT
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env["PBA_BENCH_SHARE_GPU"] = "1"
-    common = ["--reads", "3000", "--overlap-reads", "12000", "--steps", "1", "--warmup", "1", "--cpu-sample", "0"]
+    common = ["--reads", "3000", "--overlap-reads", "12000", "--steps", "1", "--warmup", "1", "--cpu-sample", "0", "--full"]
 
     def run(*args, rc=0):
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args, *common], env=env, capture_output=True, timeout=600)
