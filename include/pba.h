@@ -150,6 +150,14 @@ uint64_t pba_seqs_packed_bytes(const pba_seqs *s);
 int pba_seqs_lengths(const pba_seqs *s, uint32_t *lengths, uint32_t cap);
 /* unpack sequence i back to text (bin2text), for round-trip checks */
 int pba_seqs_get_text(pba_ctx *ctx, const pba_seqs *s, uint32_t i, char *text, size_t cap);
+/* A new set whose sequence i is rc(src i) -- reversed, then A<->T and C<->G (on the 2-bit codes: code ^ 3) -- where
+ * flip == NULL or flip[i] != 0 (flip: n host bytes), and src i unchanged otherwise.  The layout is pba_seqs_from_text's
+ * (16-byte aligned starts, zero pad bits), whatever layout src had (a binary read file's records included): byte for byte
+ * what pba_seqs_from_text makes of the same texts.  Packed bytes and bit planes are built on the device; no base goes
+ * through the host.  PBA_E_ALPHABET if src holds bytes outside ACGT (code 3 stands for N as well as T: no complement).
+ * The reference never reverse-complements a read; this feeds pba_overlap_strands (and pba_locate, for a caller who
+ * wants the other strand there). */
+int pba_seqs_revcomp(pba_ctx *ctx, const pba_seqs *src, const uint8_t *flip, pba_seqs **out);
 
 /* ------------------------------------------------------------------------ */
 /* Seed-hit index.  Replaces hash_table = hash_map<unsigned, list<int>>     */
@@ -444,6 +452,39 @@ void pba_probe_table_destroy(pba_probe_table *t);
 uint64_t pba_probe_table_entries(const pba_probe_table *t);
 int pba_overlap_all_table(pba_ctx *ctx, const pba_seqs *reads, uint32_t t_lo, uint32_t t_hi, const pba_probe_table *tab, double R,
                           int overlap_min, int kernel, pba_overlap *out, uint64_t cap, uint64_t *n_out, pba_overlap_stats *stats);
+
+/* Both strands.  A strand +1 overlap of target t and query q is exactly a pba_overlap_all row.  A strand -1 overlap is the
+ * same computation with the query's text replaced by rc(q) (pba_seqs_revcomp): its j, dir, ref_pos, cost and match lengths
+ * are those of target t against the set of reverse-complemented reads, so j and dir are in rc(q)'s own coordinates.  A read
+ * is never paired with itself on either strand.  Each row also carries half-open intervals on the FORWARD strand of each
+ * read (spaced_seed.cpp:274-276, ref_seq.h:282-286; slen = the query's length):
+ *   dir +1: target [ref_pos, ref_pos + matlen_a),            query [j, j + matlen_b)
+ *   dir -1: target [ref_pos + 16 - matlen_a, ref_pos + 16),  query [slen - j - matlen_b, slen - j)
+ *   strand -1: the query interval [b0, b1) above is that of rc(q), and is given as [slen - b1, slen - b0). */
+typedef struct {
+    int32_t target, query, strand;        /* strand +1 / -1 */
+    int32_t j, dir, ref_pos;              /* as pba_overlap, in the coordinates of the query text that was walked */
+    int32_t cost, matlen_a, matlen_b;
+    int32_t t_beg, t_end, q_beg, q_end;   /* half-open, forward strand of each read */
+} pba_strand_overlap;
+
+/* strands: 1 = +1 only, 2 = -1 only, 3 = both.  reads_rc: rc of every read of `reads` (pba_seqs_revcomp with flip == NULL),
+ * or NULL to have it built inside.  A reads_rc of another count or other lengths is refused (PBA_E_INVALID); one with the
+ * same lengths but other bases cannot be told apart cheaply and gives the -1 rows of whatever it holds.  Rows sorted by
+ * (target, query, strand), +1 before -1.  stats[0] / stats[1]: the +1 / -1 pass.  Same limits as pba_overlap_all; cap
+ * bounds the rows of each pass and of the merged list: *n_out = rows found on both strands (may exceed cap: then only cap
+ * are written).  PBA_E_ALPHABET for sets with bytes outside ACGT. */
+int pba_overlap_strands(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t t_lo, uint32_t t_hi,
+                        uint32_t mask, double R, int max_trial, int overlap_min, int kernel, int strands,
+                        pba_strand_overlap *out, uint64_t cap, uint64_t *n_out, pba_overlap_stats stats[2]);
+/* The range / multi-GPU form: tab_fwd built from pba_overlap_probes(reads, ...) entries, tab_rc from
+ * pba_overlap_probes(reads_rc, ...) entries (either may be NULL to skip that strand; tab_rc needs reads_rc).  A rank
+ * reverse-complements its gathered read set locally and emits the probes of its rc queries: no new exchange.  A table
+ * belongs to the set whose probes filled it. */
+int pba_overlap_strands_table(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t t_lo, uint32_t t_hi,
+                              const pba_probe_table *tab_fwd, const pba_probe_table *tab_rc, double R, int overlap_min,
+                              int kernel, pba_strand_overlap *out, uint64_t cap, uint64_t *n_out,
+                              pba_overlap_stats stats[2]);
 
 const char *pba_strerror(int status);
 

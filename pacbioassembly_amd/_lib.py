@@ -87,6 +87,7 @@ SYMBOLS = {
     "pba_seqs_packed_bytes": (C.c_uint64, [_P]),
     "pba_seqs_lengths": (C.c_int, [_P, _P, C.c_uint32]),
     "pba_seqs_get_text": (C.c_int, [_P, _P, C.c_uint32, C.c_char_p, C.c_size_t]),
+    "pba_seqs_revcomp": (C.c_int, [_P, _P, _P, C.POINTER(_P)]),
     "pba_index_build": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_P)]),
     "pba_index_scan": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, _P, C.c_uint64,
                                  C.POINTER(C.c_uint64)]),
@@ -118,6 +119,10 @@ SYMBOLS = {
     "pba_probe_table_entries": (C.c_uint64, [_P]),
     "pba_overlap_all_table": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_double, C.c_int, C.c_int, _P, C.c_uint64,
                                         C.POINTER(C.c_uint64), _P]),
+    "pba_overlap_strands": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64), _P]),
+    "pba_overlap_strands_table": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_double, C.c_int, C.c_int, _P,
+                                            C.c_uint64, C.POINTER(C.c_uint64), _P]),
     "pba_cons_create": (C.c_int, [_P, C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "pba_cons_destroy": (None, [_P]),
     "pba_cons_extent": (C.c_int, [_P, _P]),

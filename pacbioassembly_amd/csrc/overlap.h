@@ -24,6 +24,11 @@
 //                  success): pairs = candidates - those
 //   k_ovl_count / k_ovl_fill : the row-sweep kernel's form (the cross-check: no prefilter, no windows): every candidate is
 //                  written, sorted and walked
+// Strands (pba_overlap_strands): the queries' bases may come from another set than the targets' -- the reverse complement
+// of the same reads, which has the same count and the same lengths.  Only what reads QUERY BASES takes that set (Q): the
+// probes (k_probe_emit and k_pt_ctx are handed it as their one set), the walk and its prefilters, k_ovl_after.  Lengths,
+// and so the candidate decode and every count, are the same in either set and are read from the target set.  The scan and
+// the row-sweep count / fill read the targets and the probe table only.  The forward entry points pass one set twice.
 #ifndef PBA_OVERLAP_H
 #define PBA_OVERLAP_H
 
@@ -129,7 +134,7 @@ k_pt_fill(const uint64_t *in, uint64_t n, ProbeTab T, uint32_t *cursor, uint32_t
     if (HASHED) T.pkey[slot] = key;
 }
 
-// prec[i] once the entries are in place and the read set is at hand (ProbeTab above)
+// prec[i] once the entries are in place and the read set is at hand (ProbeTab above): Rd = the set whose probes filled the table
 static __global__ void __launch_bounds__(256)
 k_pt_ctx(ProbeTab T, SeqSetDev Rd, uint32_t n_entries) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -591,12 +596,18 @@ __device__ __forceinline__ void ovl_emit(pba_overlap *out, unsigned long long ca
 // skipped and (target - t_lo, candidate index) goes to redo_out.
 // Second launch (redo_in != nullptr, full_band): one parked (target, query) per work item, resumed at the parked
 // candidate with the reference band until the first success or the end of the query's candidates.
+// Rd: the targets (and every length); Q: the queries' bases -- Rd itself (k_ovl_walk, the forward entry points: it has the
+// signature and, the body being inlined with Q = Rd, the code it had before there was a Q; one kernel for both made the
+// forward walk 1 % slower at 200 k reads, 447.5 -> 452.7 ms) or the reads' reverse complement (k_ovl_walk_rc).
+#define PBA_OVL_WALK_PARAMS                                                                                                  \
+    uint32_t t_lo, uint32_t n_items, const uint2 *items, const uint32_t *cand_off, const uint32_t *cand_cnt,                 \
+        const uint64_t *cand, OvlCfg cfg, int full_band, const uint2 *redo_in, uint2 *redo_out, unsigned long long redo_cap, \
+        unsigned long long *n_redo_out, pba_overlap *out, unsigned long long cap, unsigned long long *n_out,                 \
+        unsigned long long *n_pairs, uint32_t *queue
+#define PBA_OVL_WALK_ARGS \
+    t_lo, n_items, items, cand_off, cand_cnt, cand, cfg, full_band, redo_in, redo_out, redo_cap, n_redo_out, out, cap, n_out, n_pairs, queue
 template <int NB>
-static __global__ void __launch_bounds__(PBA_WAVE * (NB ? 4 : 1), NB == 0 ? 1 : (NB <= 2 ? PBA_OVL_OCC12 : (NB <= 4 ? PBA_OVL_OCC34 : 3)))
-k_ovl_walk(SeqSetDev Rd, uint32_t t_lo, uint32_t n_items, const uint2 *items, const uint32_t *cand_off, const uint32_t *cand_cnt,
-           const uint64_t *cand, OvlCfg cfg, int full_band, const uint2 *redo_in, uint2 *redo_out, unsigned long long redo_cap,
-           unsigned long long *n_redo_out, pba_overlap *out, unsigned long long cap, unsigned long long *n_out,
-           unsigned long long *n_pairs, uint32_t *queue) {
+__device__ __forceinline__ void ovl_walk(const SeqSetDev &Rd, const SeqSetDev &Q, PBA_OVL_WALK_PARAMS) {
     extern __shared__ __align__(16) uint8_t lds_all[];
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / PBA_WAVE));
     uint16_t *lds = (uint16_t *)(lds_all + (size_t)wave * cfg.row_cap * 2);
@@ -641,7 +652,7 @@ k_ovl_walk(SeqSetDev Rd, uint32_t t_lo, uint32_t n_items, const uint2 *items, co
                 const HeadTail ht(ref_len);
                 const OvlCand m = ovl_decode(Rd, ref_len, ht, cd, cfg);
                 const bool fail2 = prefilter64(act && m.ok, fetch_of(Rd, t, m.r_off, m.fwd ? 1 : -1), m.r_len,
-                                               fetch_of(Rd, act ? m.q : 0u, m.s_off, m.fwd ? 1 : -1), m.s_len, cfg.R);
+                                               fetch_of(Q, act ? m.q : 0u, m.s_off, m.fwd ? 1 : -1), m.s_len, cfg.R);
                 const uint64_t f2 = __builtin_amdgcn_ballot_w64(fail2);
                 if (l0) { s2_fail[wave][k][0] = (uint32_t)f2; s2_fail[wave][k][1] = (uint32_t)(f2 >> 32); }
             }
@@ -660,7 +671,7 @@ k_ovl_walk(SeqSetDev Rd, uint32_t t_lo, uint32_t n_items, const uint2 *items, co
                 const OvlCand m = ovl_decode(Rd, ref_len, ht, cd, cfg);
                 AlnOut po;
                 const int fr = prefilter32(act && m.ok, fetch_of(Rd, t, m.r_off, m.fwd ? 1 : -1), m.r_len,
-                                           fetch_of(Rd, act ? m.q : 0u, m.s_off, m.fwd ? 1 : -1), m.s_len, cfg.R, 0, 0, pre_t, po);
+                                           fetch_of(Q, act ? m.q : 0u, m.s_off, m.fwd ? 1 : -1), m.s_len, cfg.R, 0, 0, pre_t, po);
                 const uint64_t f1 = __builtin_amdgcn_ballot_w64(fr != 0);
                 const uint64_t s1 = __builtin_amdgcn_ballot_w64(act && m.ok && fr == 0);
                 if (l0) { s2_fail[wave][k][0] = (uint32_t)f1; s2_fail[wave][k][1] = (uint32_t)(f1 >> 32); }
@@ -682,7 +693,7 @@ k_ovl_walk(SeqSetDev Rd, uint32_t t_lo, uint32_t n_items, const uint2 *items, co
                 const HeadTail ht(ref_len);
                 const OvlCand m = ovl_decode(Rd, ref_len, ht, cd, cfg);
                 const bool fail2 = prefilter64(have, fetch_of(Rd, t, m.r_off, m.fwd ? 1 : -1), m.r_len,
-                                               fetch_of(Rd, have ? m.q : 0u, m.s_off, m.fwd ? 1 : -1), m.s_len, cfg.R);
+                                               fetch_of(Q, have ? m.q : 0u, m.s_off, m.fwd ? 1 : -1), m.s_len, cfg.R);
                 if (fail2) atomicOr(&s2_fail[wave][k][ln >> 5], 1u << (ln & 31u));
             }
             __builtin_amdgcn_wave_barrier();
@@ -729,7 +740,7 @@ k_ovl_walk(SeqSetDev Rd, uint32_t t_lo, uint32_t n_items, const uint2 *items, co
                 } else {
                     AlnOut po;
                     myfr = prefilter32(act && m.ok, ref.at(m.r_off, m.fwd ? 1 : -1), m.r_len,
-                                       fetch_of(Rd, act ? myq : 0u, m.s_off, m.fwd ? 1 : -1), m.s_len, cfg.R, 0, 0, pre_t, po);
+                                       fetch_of(Q, act ? myq : 0u, m.s_off, m.fwd ? 1 : -1), m.s_len, cfg.R, 0, 0, pre_t, po);
                 }
             }
             // Nearly every candidate has failed by now, so the group is not walked lane by lane: lane masks say where the
@@ -767,7 +778,7 @@ k_ovl_walk(SeqSetDev Rd, uint32_t t_lo, uint32_t n_items, const uint2 *items, co
                 if (q == done_q) continue;                                  // first success per (target, query) already taken
                 const OvlCand mk = ovl_decode_len(__builtin_amdgcn_readfirstlane((int)Rd.len[q]), ref_len, ht, cd, cfg);
                 const PackedFetch fa = ref.at(mk.r_off, mk.fwd ? 1 : -1);    // a = the target in the reference role (ref_seq.h:264)
-                const PackedFetch fb = fetch_of_uniform(Rd, q, mk.s_off, mk.fwd ? 1 : -1);
+                const PackedFetch fb = fetch_of_uniform(Q, q, mk.s_off, mk.fwd ? 1 : -1);
                 AlnOut o;
                 if constexpr (NB == 0) align_rowsweep(fa, mk.r_len, fb, mk.s_len, cfg.R, 0, 0, lds, cfg.row_cap, o);
                 else align_bitvec<NB, true>(fa, mk.r_len, fb, mk.s_len, cfg.R, 0, 0, full_band != 0, lds, cfg.row_cap, o);
@@ -790,6 +801,11 @@ k_ovl_walk(SeqSetDev Rd, uint32_t t_lo, uint32_t n_items, const uint2 *items, co
     }
     atomicAdd(n_pairs, l0 ? pairs : 0ull);
 }
+#define PBA_OVL_WALK_BOUNDS __launch_bounds__(PBA_WAVE * (NB ? 4 : 1), NB == 0 ? 1 : (NB <= 2 ? PBA_OVL_OCC12 : (NB <= 4 ? PBA_OVL_OCC34 : 3)))
+template <int NB>
+static __global__ void PBA_OVL_WALK_BOUNDS k_ovl_walk(SeqSetDev Rd, PBA_OVL_WALK_PARAMS) { ovl_walk<NB>(Rd, Rd, PBA_OVL_WALK_ARGS); }
+template <int NB>
+static __global__ void PBA_OVL_WALK_BOUNDS k_ovl_walk_rc(SeqSetDev Rd, SeqSetDev Q, PBA_OVL_WALK_PARAMS) { ovl_walk<NB>(Rd, Q, PBA_OVL_WALK_ARGS); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // What a success spares.  The reference walks a (target, query) run in order and stops at the first success
@@ -801,7 +817,7 @@ k_ovl_walk(SeqSetDev Rd, uint32_t t_lo, uint32_t n_items, const uint2 *items, co
 // pairs = totals[1] - sum over the overlaps.  (~10 k instructions per success, against ~700 k for the alignment itself.)
 #define PBA_OVL_AFTER_SLOTS 512                    // hash slots per wavefront for <= 126 probe keys
 static __global__ void __launch_bounds__(PBA_WAVE * 4)
-k_ovl_after(SeqSetDev Rd, const pba_overlap *ov, uint32_t n_ov, uint32_t mask, uint32_t t2, int overlap_min, unsigned long long *after) {
+k_ovl_after(SeqSetDev Rd, SeqSetDev Q, const pba_overlap *ov, uint32_t n_ov, uint32_t mask, uint32_t t2, int overlap_min, unsigned long long *after) {
     __shared__ uint32_t h_key[4][PBA_OVL_AFTER_SLOTS], h_cnt[4][PBA_OVL_AFTER_SLOTS];
     const uint32_t lane = threadIdx.x & (PBA_WAVE - 1), wave = threadIdx.x / PBA_WAVE;
     const uint32_t i = blockIdx.x * 4 + wave;
@@ -812,7 +828,7 @@ k_ovl_after(SeqSetDev Rd, const pba_overlap *ov, uint32_t n_ov, uint32_t mask, u
     const int tlen = (int)Rd.len[t], slen = (int)Rd.len[q];
     const TargetWalk tw(tlen);
     const int ord0 = tw.ord_of(o.ref_pos);
-    const uint8_t *tseq = Rd.packed + Rd.off[t], *qseq = Rd.packed + Rd.off[q];
+    const uint8_t *tseq = Rd.packed + Rd.off[t], *qseq = Q.packed + Q.off[q];
     for (uint32_t k = lane; k < PBA_OVL_AFTER_SLOTS; k += PBA_WAVE) { h_key[wave][k] = 0u; h_cnt[wave][k] = 0u; }   // key 0 = empty: no probe has it
     __builtin_amdgcn_wave_barrier();
     // the probes of q from jd* on: the success's own key, and the later ones into the table with their multiplicity

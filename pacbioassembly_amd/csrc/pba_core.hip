@@ -64,6 +64,39 @@ k_make_planes(const uint8_t *packed, const uint64_t *off, const uint32_t *len, c
     }
 }
 
+// Reverse complement of a set (pba_seqs_revcomp) into pba_seqs_from_text's layout: thread t owns packed dword t of the new
+// set (16 bases), found as in k_pack_text.  Output base k of sequence s is source base L - 1 - k with code ^ 3 (A<->T, C<->G)
+// where flip is null or flip[s] != 0, source base k otherwise.  The 16 source bases come from one unaligned 8-byte load (the
+// source may be a binary read file's byte-aligned records); reversing the order of 2-bit codes is a bit reversal followed by
+// a swap of the two bits of every code.  Pad bits stay 0, as k_pack_text leaves them.
+__global__ void __launch_bounds__(256)
+k_revcomp(const uint8_t *src, const uint64_t *src_off, const uint64_t *pk_off, const uint32_t *len, const uint8_t *flip, uint32_t n,
+          uint64_t total_dwords, uint8_t *packed) {
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total_dwords; t += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t byte = t * 4;
+        uint32_t lo = 0, hi = n;            // last s with pk_off[s] <= byte
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (pk_off[mid] <= byte) lo = mid; else hi = mid;
+        }
+        const uint32_t s = lo;
+        const uint32_t L = len[s];
+        const uint64_t w = (byte - pk_off[s]) >> 2;          // dword index inside the sequence
+        if (w * 16 >= L) continue;                           // alignment padding (zeroed with the arena)
+        const uint32_t nb = (uint32_t)min((uint64_t)16, (uint64_t)L - w * 16);
+        const bool rc = !flip || flip[s];
+        const uint64_t p = rc ? L - w * 16 - nb : w * 16;    // lowest source base of the dword's bases
+        const uint64_t be = __builtin_bswap64(ld_u64(src + src_off[s] + (p >> 2)));
+        uint32_t x = (uint32_t)((be << (2 * (p & 3))) >> 32);   // source base p in bits 31:30, p + 15 in bits 1:0
+        if (rc) {
+            x = __builtin_bitreverse32(x);
+            x = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);   // base p + 15 in bits 31:30 ... p in bits 1:0
+            x = ~(x << (2 * (16 - nb)));                     // base p + nb - 1 (= L - 1 - 16w) first, complemented
+        }
+        if (nb < 16) x &= ~(0xFFFFFFFFu >> (2 * nb));        // nothing past the end
+        *reinterpret_cast<uint32_t *>(packed + byte) = __builtin_bswap32(x);   // first base in bits 7:6 of the first byte
+    }
+}
 
 extern "C" {
 
@@ -364,6 +397,45 @@ int pba_seqs_from_device_packed(pba_ctx *ctx, const void *d_packed, uint64_t n_b
     if (e != hipSuccess) { pba_seqs_destroy(s); return ctx_fail(ctx, PBA_E_HIP, "pba_seqs_from_device_packed", e); }
     const int stp = seqs_planes(ctx, s);
     if (stp != PBA_OK) { pba_seqs_destroy(s); return stp; }
+    *out = s;
+    return PBA_OK;
+}
+
+int pba_seqs_revcomp(pba_ctx *ctx, const pba_seqs *src, const uint8_t *flip, pba_seqs **out) {
+    if (!ctx || !src || !out) return PBA_E_INVALID;
+    *out = nullptr;
+    if (src->non_acgt) PBA_FAIL(PBA_E_ALPHABET, "pba_seqs_revcomp: the set holds bytes outside ACGT (code 3 has no complement)");
+    HIPCHK(hipSetDevice(ctx->device));
+    const uint32_t n = src->n;
+    pba_seqs *s = new (std::nothrow) pba_seqs();
+    if (!s) PBA_FAIL(PBA_E_NOMEM, "pba_seqs");
+    s->ctx = ctx; s->n = n; s->max_len = src->max_len; s->non_acgt = false; s->d_alloc = nullptr; s->d_packed = nullptr; s->d_off = nullptr; s->d_len = nullptr; s->d_planes = nullptr; s->d_poff = nullptr; s->plane_words = 0;
+    struct Guard { pba_seqs *p; ~Guard() { if (p) pba_seqs_destroy(p); } } guard{s};
+    s->h_off.resize((size_t)n + 1); s->h_len.resize((size_t)n + 1);
+    uint64_t pk = 0;
+    for (uint32_t i = 0; i < n; ++i) {                      // pba_seqs_from_text's layout (seqs_pack)
+        const uint32_t L = src->h_len[i];
+        s->h_off[i] = pk; s->h_len[i] = L;
+        pk += (((uint64_t)L + 3) / 4 + 15) & ~15ull;
+    }
+    s->h_off[n] = pk; s->h_len[n] = 0;
+    int st = seqs_alloc(ctx, s, pk);
+    if (st != PBA_OK) return st;
+    HIPCHK(hipMemcpyAsync(s->d_off + n, &s->h_off[n], sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));   // (the bisection reads n + 1 offsets)
+    DevBuf d_flip;
+    if (flip && n) {
+        HIPCHK(hipMalloc(&d_flip.p, n));
+        HIPCHK(hipMemcpyAsync(d_flip.p, flip, n, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const uint64_t total_dwords = pk / 4;
+    if (total_dwords) {
+        hipLaunchKernelGGL(k_revcomp, dim3(elem_grid(total_dwords, 256)), dim3(256), 0, ctx->stream, src->d_packed, src->d_off, s->d_off,
+                           s->d_len, flip ? d_flip.as<uint8_t>() : nullptr, n, total_dwords, s->d_packed);
+        HIPCHK(hipGetLastError());
+    }
+    st = seqs_planes(ctx, s);                                 // (synchronises: d_flip and the host offsets outlive their copies)
+    if (st != PBA_OK) return st;
+    guard.p = nullptr;
     *out = s;
     return PBA_OK;
 }

@@ -4,11 +4,14 @@
 #include "pba_host.h"
 #include "overlap.h"
 
+#include <memory>
+
 // (the attribute belongs to the current device: remembered per ctx, so a second ctx on another GPU sets it there too)
 static void tu_attrs(pba_ctx *ctx) {
     if (ctx->attr_done & 4u) return;
     ctx->attr_done |= 4u;
     PBA_BIG_LDS(k_ovl_walk<0>);
+    PBA_BIG_LDS(k_ovl_walk_rc<0>);
 }
 
 extern "C" {
@@ -16,14 +19,19 @@ extern "C" {
 // ---------------------------------------------------------------------------------------------
 // host API: all-vs-all overlap
 // ---------------------------------------------------------------------------------------------
-#define PBA_OVL_WALK(NBV)                                                                                             \
-    hipLaunchKernelGGL((k_ovl_walk<NBV>), dim3(persistent_grid(ctx, n_items, (NBV) ? 4 : 1, lds)),                        \
-                       dim3(PBA_WAVE * ((NBV) ? 4 : 1)), lds * ((NBV) ? 4 : 1), ctx->stream, reads->dev(), t_lo, n_items,  \
+#define PBA_OVL_WALK_K(KERNEL, NBV, ...)                                                                              \
+    hipLaunchKernelGGL((KERNEL<NBV>), dim3(persistent_grid(ctx, n_items, (NBV) ? 4 : 1, lds)),                            \
+                       dim3(PBA_WAVE * ((NBV) ? 4 : 1)), lds * ((NBV) ? 4 : 1), ctx->stream, __VA_ARGS__, t_lo, n_items,  \
                        items, d_woff, d_wcnt, d_cand.as<uint64_t>(), ocfg, full_band,                                    \
                        redo_in, d_redo.as<uint2>(),                                                                      \
                        (unsigned long long)redo_cap, d_cnt64.as<unsigned long long>() + 2, d_out.as<pba_overlap>(),     \
                        (unsigned long long)dev_cap, d_cnt64.as<unsigned long long>(), d_cnt64.as<unsigned long long>() + 1, \
                        ctx->d_queue)
+#define PBA_OVL_WALK(NBV)                                                                                             \
+    do {                                                                                                              \
+        if (qset == reads) PBA_OVL_WALK_K(k_ovl_walk, NBV, reads->dev());                                             \
+        else PBA_OVL_WALK_K(k_ovl_walk_rc, NBV, reads->dev(), qset->dev());                                           \
+    } while (0)
 
 // the probe table of a read set (overlap.h: ProbeTab), built once and scanned by every target range
 struct pba_probe_table {
@@ -33,7 +41,8 @@ struct pba_probe_table {
     uint32_t t2;
     uint64_t n_entries;
     float build_ms;
-    // the read set prec[] was filled from (rec_reads == nullptr: not yet -- on first use, overlap.h: k_pt_ctx); a table belongs to
+    // the read set prec[] was filled from (rec_reads == nullptr: not yet -- on first use, overlap.h: k_pt_ctx): the QUERY set of the
+    // calls that scan it (the set whose probes filled the table: the reads, or their reverse complement); a table belongs to
     // one read set, and the arena's address and size are compared too, should a set have been replaced at the same address
     mutable const pba_seqs *rec_reads;
     mutable const uint8_t *rec_packed;
@@ -184,13 +193,17 @@ int pba_probe_table_create(pba_ctx *ctx, const void *d_probe_entries, uint64_t n
     return PBA_OK;
 }
 
-int pba_overlap_all_table(pba_ctx *ctx, const pba_seqs *reads, uint32_t t_lo, uint32_t t_hi, const pba_probe_table *tab, double R,
-                          int overlap_min, int kernel, pba_overlap *out, uint64_t cap, uint64_t *n_out, pba_overlap_stats *stats) {
-    if (!ctx || !reads || !tab || !n_out || (!out && cap) || t_lo > t_hi || t_hi > reads->n) return PBA_E_INVALID;
+// targets [t_lo, t_hi) of `reads` against the probe table of the queries `qset` (reads itself, or a set of the same count and
+// lengths whose bases the queries are walked with: pba_overlap_strands)
+static int overlap_table(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *qset, uint32_t t_lo, uint32_t t_hi,
+                         const pba_probe_table *tab, double R, int overlap_min, int kernel, pba_overlap *out, uint64_t cap,
+                         uint64_t *n_out, pba_overlap_stats *stats) {
+    if (!ctx || !reads || !qset || !tab || !n_out || (!out && cap) || t_lo > t_hi || t_hi > reads->n) return PBA_E_INVALID;
+    if (qset->n != reads->n) return PBA_E_INVALID;
     if (reads->n >= PBA_OVL_MAX_READS) PBA_FAIL(PBA_E_TOOLONG, "pba_overlap_all: at most 2^24 reads");
     if ((uint64_t)reads->n * tab->t2 >= PBA_OVL_MAX_PROBES) PBA_FAIL(PBA_E_TOOLONG, "pba_overlap_all: reads x 2 x max_trial must stay below 2^32");
     if (reads->max_len > (uint32_t)kMaxSeqLen) PBA_FAIL(PBA_E_TOOLONG, "read longer than the engine limit");
-    if (reads->non_acgt) PBA_FAIL(PBA_E_ALPHABET, "pba_overlap_all: the read set holds bytes outside ACGT");
+    if (reads->non_acgt || qset->non_acgt) PBA_FAIL(PBA_E_ALPHABET, "pba_overlap_all: the read set holds bytes outside ACGT");
     HIPCHK(hipSetDevice(ctx->device));
     tu_attrs(ctx);
     *n_out = 0;
@@ -224,14 +237,14 @@ int pba_overlap_all_table(pba_ctx *ctx, const pba_seqs *reads, uint32_t t_lo, ui
     uint64_t n_cand = 0, n_ok = 0;
     (void)hipEventRecord(ctx->ev[2], ctx->stream);
     if (fused) {
-        // 1. the records of the probe table from this read set, once per table
-        if (tab->rec_reads != reads || tab->rec_packed != reads->d_packed || tab->rec_bytes != reads->packed_bytes) {
+        // 1. the records of the probe table from the query set, once per table
+        if (tab->rec_reads != qset || tab->rec_packed != qset->d_packed || tab->rec_bytes != qset->packed_bytes) {
             if (!tab->T.prec) HIPCHK(hipMalloc((void **)&tab->T.prec, sizeof(uint4) * ((uint64_t)tab->n_entries + 1)));
             if (tab->n_entries)
-                hipLaunchKernelGGL(k_pt_ctx, dim3((uint32_t)((tab->n_entries + 255) / 256)), dim3(256), 0, ctx->stream, T, reads->dev(),
+                hipLaunchKernelGGL(k_pt_ctx, dim3((uint32_t)((tab->n_entries + 255) / 256)), dim3(256), 0, ctx->stream, T, qset->dev(),
                                    (uint32_t)tab->n_entries);
             HIPCHK(hipGetLastError());
-            tab->rec_reads = reads; tab->rec_packed = reads->d_packed; tab->rec_bytes = reads->packed_bytes;
+            tab->rec_reads = qset; tab->rec_packed = qset->d_packed; tab->rec_bytes = qset->packed_bytes;
         }
         // 2. the scan.  How much room a target's survivors need is not known before its candidates have been through their
         //    32 rows: the first range of a table runs the scan once without writing (needed[] only) and then with exact
@@ -544,7 +557,7 @@ int pba_overlap_all_table(pba_ctx *ctx, const pba_seqs *reads, uint32_t t_lo, ui
     unsigned long long h_after = 0;
     if (fused && h_cnt2[0]) {
         const uint32_t n_ov = (uint32_t)std::min<uint64_t>(h_cnt2[0], dev_cap);
-        hipLaunchKernelGGL(k_ovl_after, dim3((n_ov + 3) / 4), dim3(PBA_WAVE * 4), 0, ctx->stream, reads->dev(), d_out.as<pba_overlap>(), n_ov,
+        hipLaunchKernelGGL(k_ovl_after, dim3((n_ov + 3) / 4), dim3(PBA_WAVE * 4), 0, ctx->stream, reads->dev(), qset->dev(), d_out.as<pba_overlap>(), n_ov,
                            T.mask, t2, overlap_min, d_cnt64.as<unsigned long long>() + 6);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(&h_after, d_cnt64.as<unsigned long long>() + 6, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -588,4 +601,102 @@ int pba_overlap_all_table(pba_ctx *ctx, const pba_seqs *reads, uint32_t t_lo, ui
     return PBA_OK;
 }
 
+int pba_overlap_all_table(pba_ctx *ctx, const pba_seqs *reads, uint32_t t_lo, uint32_t t_hi, const pba_probe_table *tab, double R,
+                          int overlap_min, int kernel, pba_overlap *out, uint64_t cap, uint64_t *n_out, pba_overlap_stats *stats) {
+    return overlap_table(ctx, reads, reads, t_lo, t_hi, tab, R, overlap_min, kernel, out, cap, n_out, stats);
+}
+
+// ---------------------------------------------------------------------------------------------
+// host API: both strands.  The -1 pass is the forward machinery with the queries' bases taken from the reverse complement
+// of the reads (overlap.h: Q), against the probe table of that set; the rows of the two passes are merged and given
+// intervals on the forward strand of each read.
+// ---------------------------------------------------------------------------------------------
+// a row of one pass -> a strand row.  Intervals from the accessors of spaced_seed.cpp:274-276 and ref_seq.h:282-286: forward,
+// the target from the hit and the query from j; backward, the target up to hit + 16 and the query up to slen - j.  A -1 row's
+// query interval is in the coordinates of rc(q) and is mapped back to q's forward strand.
+static pba_strand_overlap strand_row(const pba_overlap &o, int strand, int qlen) {
+    pba_strand_overlap r;
+    r.target = o.target; r.query = o.query; r.strand = strand;
+    r.j = o.j; r.dir = o.dir; r.ref_pos = o.ref_pos; r.cost = o.cost; r.matlen_a = o.matlen_a; r.matlen_b = o.matlen_b;
+    int b0, b1;
+    if (o.dir > 0) { r.t_beg = o.ref_pos; r.t_end = o.ref_pos + o.matlen_a; b0 = o.j; b1 = o.j + o.matlen_b; }
+    else { r.t_beg = o.ref_pos + 16 - o.matlen_a; r.t_end = o.ref_pos + 16; b0 = qlen - o.j - o.matlen_b; b1 = qlen - o.j; }
+    r.q_beg = strand > 0 ? b0 : qlen - b1;
+    r.q_end = strand > 0 ? b1 : qlen - b0;
+    return r;
+}
+
+// the probe table of every read of `set`, built here (the single-GPU form of pba_overlap_all)
+static int own_table(pba_ctx *ctx, const pba_seqs *set, uint32_t mask, int max_trial, pba_probe_table **tab) {
+    const uint64_t pcap = (uint64_t)set->n * 2u * (uint32_t)max_trial;
+    DevBuf d_pent;
+    HIPCHK(hipMalloc(&d_pent.p, sizeof(uint64_t) * (pcap + 1)));
+    uint64_t n_pent = 0;
+    int rc = pba_overlap_probes(ctx, set, 0, set->n, mask, max_trial, d_pent.p, pcap, &n_pent);
+    if (rc != PBA_OK) return rc;
+    return pba_probe_table_create(ctx, d_pent.p, n_pent, mask, max_trial, tab);
+}
+
+int pba_overlap_strands_table(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t t_lo, uint32_t t_hi,
+                              const pba_probe_table *tab_fwd, const pba_probe_table *tab_rc, double R, int overlap_min,
+                              int kernel, pba_strand_overlap *out, uint64_t cap, uint64_t *n_out, pba_overlap_stats stats[2]) {
+    if (!ctx || !reads || !n_out || (!out && cap) || (!tab_fwd && !tab_rc) || (tab_rc && !reads_rc)) return PBA_E_INVALID;
+    if (reads_rc && (reads_rc->n != reads->n || reads_rc->h_len != reads->h_len))
+        PBA_FAIL(PBA_E_INVALID, "pba_overlap_strands: reads_rc differs from reads in count or lengths");
+    if (reads->non_acgt || (reads_rc && reads_rc->non_acgt)) PBA_FAIL(PBA_E_ALPHABET, "pba_overlap_strands: the read set holds bytes outside ACGT");
+    *n_out = 0;
+    pba_overlap_stats st[2];
+    memset(st, 0, sizeof st);
+    // (each pass may find up to cap rows; the rows are not initialised: at a million reads cap is tens of millions)
+    std::unique_ptr<pba_overlap[]> rows[2];
+    uint64_t n[2] = {0, 0};
+    const pba_probe_table *tabs[2] = {tab_fwd, tab_rc};
+    const pba_seqs *qsets[2] = {reads, reads_rc};
+    for (int k = 0; k < 2; ++k) {
+        if (!tabs[k]) continue;
+        rows[k].reset(new (std::nothrow) pba_overlap[std::max<uint64_t>(cap, 1)]);
+        if (!rows[k]) PBA_FAIL(PBA_E_NOMEM, "pba_overlap_strands: rows of a pass");
+        const int rc = overlap_table(ctx, reads, qsets[k], t_lo, t_hi, tabs[k], R, overlap_min, kernel, rows[k].get(), cap, &n[k], &st[k]);
+        if (rc != PBA_OK) return rc;
+    }
+    // merge by (target, query), +1 before -1 (each pass is sorted by (target, query))
+    const pba_overlap *a = rows[0].get(), *b = rows[1].get();
+    const uint64_t na = std::min(n[0], cap), nb = std::min(n[1], cap);
+    uint64_t i = 0, k = 0, o = 0;
+    for (; o < cap && (i < na || k < nb); ++o) {
+        const bool take_a = k >= nb || (i < na && (a[i].target != b[k].target ? a[i].target < b[k].target : a[i].query <= b[k].query));
+        if (take_a) { out[o] = strand_row(a[i], 1, (int)reads->h_len[a[i].query]); ++i; }
+        else { out[o] = strand_row(b[k], -1, (int)reads->h_len[b[k].query]); ++k; }
+    }
+    *n_out = n[0] + n[1];
+    if (stats) { stats[0] = st[0]; stats[1] = st[1]; }
+    return PBA_OK;
+}
+
+int pba_overlap_strands(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t t_lo, uint32_t t_hi,
+                        uint32_t mask, double R, int max_trial, int overlap_min, int kernel, int strands,
+                        pba_strand_overlap *out, uint64_t cap, uint64_t *n_out, pba_overlap_stats stats[2]) {
+    if (!ctx || !reads || !n_out || (!out && cap)) return PBA_E_INVALID;
+    if (strands < 1 || strands > 3) PBA_FAIL(PBA_E_INVALID, "pba_overlap_strands: strands must be 1 (+1), 2 (-1) or 3 (both)");
+    if (reads_rc && (reads_rc->n != reads->n || reads_rc->h_len != reads->h_len))
+        PBA_FAIL(PBA_E_INVALID, "pba_overlap_strands: reads_rc differs from reads in count or lengths");
+    if (reads->non_acgt || (reads_rc && reads_rc->non_acgt)) PBA_FAIL(PBA_E_ALPHABET, "pba_overlap_strands: the read set holds bytes outside ACGT");
+    if (max_trial < 1 || 2 * max_trial >= (1 << PBA_OVL_JD_BITS)) PBA_FAIL(PBA_E_INVALID, "max_trial must be in [1, 63]");
+    HIPCHK(hipSetDevice(ctx->device));
+    struct Own {
+        pba_seqs *rc = nullptr;
+        pba_probe_table *tab[2] = {nullptr, nullptr};
+        ~Own() { pba_probe_table_destroy(tab[0]); pba_probe_table_destroy(tab[1]); if (rc) pba_seqs_destroy(rc); }
+    } own;
+    int rc = PBA_OK;
+    if ((strands & 2) && !reads_rc) {
+        rc = pba_seqs_revcomp(ctx, reads, nullptr, &own.rc);
+        if (rc != PBA_OK) return rc;
+        reads_rc = own.rc;
+    }
+    if (strands & 1) { rc = own_table(ctx, reads, mask, max_trial, &own.tab[0]); if (rc != PBA_OK) return rc; }
+    if (strands & 2) { rc = own_table(ctx, reads_rc, mask, max_trial, &own.tab[1]); if (rc != PBA_OK) return rc; }
+    return pba_overlap_strands_table(ctx, reads, (strands & 2) ? reads_rc : nullptr, t_lo, t_hi, own.tab[0], own.tab[1], R,
+                                     overlap_min, kernel, out, cap, n_out, stats);
+}
 }  // extern "C"

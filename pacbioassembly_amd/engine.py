@@ -24,6 +24,9 @@ SS_ROW_DTYPE = np.dtype([(n, "<i4") for n in
                          ("read", "found", "j", "dir", "ref_pos", "cost", "matlen_a", "matlen_b", "n_trials",
                           "n_pairs")])
 OVERLAP_DTYPE = np.dtype([(n, "<i4") for n in ("target", "query", "j", "dir", "ref_pos", "cost", "matlen_a", "matlen_b")])
+# pba_strand_overlap: a pba_overlap row with its strand and half-open intervals on the forward strand of each read
+STRAND_OVERLAP_DTYPE = np.dtype([(n, "<i4") for n in ("target", "query", "strand", "j", "dir", "ref_pos", "cost", "matlen_a",
+                                                     "matlen_b", "t_beg", "t_end", "q_beg", "q_end")])
 assert PAIR_DTYPE.itemsize == C.sizeof(PbaPair) and RESULT_DTYPE.itemsize == C.sizeof(PbaResult)
 assert LOC_ROW_DTYPE.itemsize == C.sizeof(PbaLocRow) and SS_ROW_DTYPE.itemsize == C.sizeof(PbaSsRow)
 
@@ -208,6 +211,20 @@ class Context:
         h = C.c_void_p()
         self.check(self.lib.pba_seqs_from_device_packed(self.h, C.c_void_p(d_packed_ptr), n_bytes, _ptr(offsets), _ptr(lengths),
                                                         lengths.size, int(non_acgt), C.byref(h)), "seqs_from_device_packed")
+        return SeqSet(self, h)
+
+    def seqs_revcomp(self, S: "SeqSet", flip=None) -> "SeqSet":
+        """A new set whose sequence i is the reverse complement of S's where flip is None or flip[i] (pba_seqs_revcomp: on the
+        device, in pba_seqs_from_text's layout); the other sequences are copied as they are."""
+        h = C.c_void_p()
+        if flip is None:
+            fp = None
+        else:
+            flip = np.ascontiguousarray(flip, np.uint8)
+            if flip.size != S.count:
+                raise ValueError(f"flip has {flip.size} entries for {S.count} sequences")
+            fp = _ptr(flip)
+        self.check(self.lib.pba_seqs_revcomp(self.h, S.h, fp, C.byref(h)), "seqs_revcomp")
         return SeqSet(self, h)
 
     # -- index
@@ -434,6 +451,92 @@ def _overlap_all_sharded(self, reads, mask, R, max_trial=32, overlap_min=64, tar
     return out, (total or {})
 
 
+def _stats_pair(st2):
+    return [{k: getattr(st, k) for k, _ in _lib.PbaOverlapStats._fields_} for st in st2]
+
+
+def _overlap_strands(self, reads, mask, R, max_trial=32, overlap_min=64, strands=3, t_lo=0, t_hi=None, kernel=PBA_KERNEL_AUTO,
+                     cap=None, reads_rc=None):
+    """Overlaps on both strands (pba_overlap_strands): strands 1 = +1 only, 2 = -1 only (the queries reverse-complemented),
+    3 = both.  Returns (rows of STRAND_OVERLAP_DTYPE sorted by (target, query, strand), [stats of the +1 pass, of the -1 pass])."""
+    t_hi = reads.count if t_hi is None else t_hi
+    cap = cap if cap is not None else max(1, 2 * (t_hi - t_lo) * max(reads.count - 1, 1))
+    out = np.empty(cap, STRAND_OVERLAP_DTYPE)
+    n = C.c_uint64()
+    st2 = (_lib.PbaOverlapStats * 2)()
+    self.check(self.lib.pba_overlap_strands(self.h, reads.h, reads_rc.h if reads_rc is not None else None, t_lo, t_hi, mask, R,
+                                            max_trial, overlap_min, kernel, strands, _ptr(out), cap, C.byref(n), C.byref(st2)),
+               "overlap_strands")
+    return out[:min(int(n.value), cap)], _stats_pair(st2)
+
+
+def _overlap_strands_table(self, reads, reads_rc, tab_fwd, tab_rc, R, overlap_min=64, t_lo=0, t_hi=None, kernel=PBA_KERNEL_AUTO,
+                           cap=None):
+    """pba_overlap_strands_table: targets [t_lo, t_hi) against the probe table of the reads (tab_fwd) and of their reverse
+    complement reads_rc (tab_rc); either table may be None to skip its strand."""
+    t_hi = reads.count if t_hi is None else t_hi
+    cap = cap if cap is not None else max(1, 2 * (t_hi - t_lo) * max(reads.count - 1, 1))
+    out = np.empty(cap, STRAND_OVERLAP_DTYPE)
+    n = C.c_uint64()
+    st2 = (_lib.PbaOverlapStats * 2)()
+    self.check(self.lib.pba_overlap_strands_table(self.h, reads.h, reads_rc.h if reads_rc is not None else None, t_lo, t_hi,
+                                                  tab_fwd.h if tab_fwd is not None else None, tab_rc.h if tab_rc is not None else None,
+                                                  R, overlap_min, kernel, _ptr(out), cap, C.byref(n), C.byref(st2)), "overlap_strands_table")
+    return out[:min(int(n.value), cap)], _stats_pair(st2)
+
+
+def _overlap_strands_sharded(self, reads, mask, R, max_trial=32, overlap_min=64, targets_per_call=10000, kernel=PBA_KERNEL_AUTO,
+                             cap_per_target=None, t_lo=0, t_hi=None, strands=3, reads_rc=None, tables=None):
+    """overlap_all_sharded on both strands: the reverse complement of the reads (built here unless given) and the two probe
+    tables (built once here unless given as (tab_fwd, tab_rc), the multi-GPU form), then the targets [t_lo, t_hi) in ranges.
+    Same rows as one overlap_strands call."""
+    import torch
+    n = reads.count
+    t_hi = n if t_hi is None else t_hi
+    if strands not in (1, 2, 3):
+        raise ValueError("strands must be 1, 2 or 3")
+    if strands & 2 and reads_rc is None:
+        reads_rc = self.seqs_revcomp(reads)
+    own = tables is None
+    if own:
+        tables = []
+        for k, S in ((1, reads), (2, reads_rc)):
+            if not strands & k:
+                tables.append(None)
+                continue
+            slots = n * 2 * max_trial
+            probes = torch.full((max(slots, 1),), -1, dtype=torch.int64, device="cuda")
+            self.overlap_probes(S, 0, n, mask, max_trial, probes.data_ptr(), slots)
+            torch.cuda.synchronize()
+            tables.append(ProbeTable(self, probes.data_ptr(), probes.numel(), mask, max_trial))
+            del probes
+    tab_fwd, tab_rc = tables
+    parts, total = [], None
+    for lo in range(t_lo, t_hi, targets_per_call):
+        hi = min(t_hi, lo + targets_per_call)
+        cap = 2 * (hi - lo) * (cap_per_target or max(n - 1, 1))
+        ov, st2 = self.overlap_strands_table(reads, reads_rc if tab_rc is not None else None, tab_fwd, tab_rc, R, overlap_min,
+                                             lo, hi, kernel, cap)
+        parts.append(ov)
+        if total is None:
+            total = [dict(s) for s in st2]
+        else:
+            for tot, st in zip(total, st2):
+                for k in ("n_candidates", "n_pairs", "n_overlaps", "n_redo", "scan_ms", "sort_ms", "walk_ms", "n_big_targets",
+                          "n_prefiltered", "cap_fill", "cap_overflow", "n_listed"):
+                    tot[k] += st[k]
+                tot["wide_first"] = max(tot["wide_first"], st["wide_first"])
+    if own:
+        for t in tables:
+            if t is not None:
+                t.close()
+    out = np.concatenate(parts) if parts else np.zeros(0, STRAND_OVERLAP_DTYPE)
+    return out, (total or [{}, {}])
+
+
+Context.overlap_strands = _overlap_strands
+Context.overlap_strands_table = _overlap_strands_table
+Context.overlap_strands_sharded = _overlap_strands_sharded
 Context.overlap_all = _overlap_all
 Context.overlap_probes = _overlap_probes
 Context.overlap_all_probes = _overlap_all_probes
