@@ -486,6 +486,80 @@ int pba_overlap_strands_table(pba_ctx *ctx, const pba_seqs *reads, const pba_seq
                               int kernel, pba_strand_overlap *out, uint64_t cap, uint64_t *n_out,
                               pba_overlap_stats stats[2]);
 
+/* ------------------------------------------------------------------------ */
+/* Read correction from overlap pile-ups.  Not a loop the reference has, but  */
+/* built only from its pieces: every read t takes the reference role          */
+/* (ref_seq(T, len, false, weight), ref_seq.h:218-225: one vote box per base), */
+/* every overlap row of t is re-aligned with traceback and its path voted      */
+/* (elect / apply_edits, ref_seq.h:25-41, 352-362), and evolve()              */
+/* (ref_seq.h:317-349) gives the corrected read.  NO GROWTH: append / prepend  */
+/* (ref_seq.h:268-275) are not applied, the text the votes address is T        */
+/* throughout, so votes commute and the order of the rows does not matter.     */
+/* ------------------------------------------------------------------------ */
+/* Host arithmetic, no ctx: the pair of accessors a row stands for, as a locked spaced_seed round forms them
+ * (spaced_seed.cpp:274-285, ref_seq.h:282-286; slen = query_len):
+ *   dir +1: a forward from ref_pos, a_len = target_len - ref_pos;       b forward from j, b_len = slen - j
+ *   dir -1: a backward from ref_pos + 15, a_len = ref_pos + 16;         b backward from slen - j - 1, b_len = slen - j
+ * a_seq = row->target, b_seq = row->query: for a strand -1 row b indexes the set of reverse-complemented reads (the row's
+ * j and dir are in rc(q)'s coordinates already).  PBA_E_INVALID for a NULL, a strand or dir other than +1 / -1, or
+ * lengths that put an accessor outside its read. */
+int pba_overlap_row_pair(const pba_strand_overlap *row, uint32_t target_len, uint32_t query_len, pba_pair *out);
+
+/* The vote boxes of reads [t_lo, t_hi) in one device arena, one segment per target (no margins: there is no growth), filled
+ * on the device from the packed set.  20 bytes per base.  The counters are u16 halves bumped with 32-bit atomics on their
+ * dword: a selection counter holds weight + votes <= 65 535 (a vote beyond that would carry into the neighbouring counter
+ * instead of wrapping like the reference's unsigned short), so keep weight small next to 65 535 - coverage.  Box indices are 32-bit inside the kernels: a range of 2^31 bases or more is refused with PBA_E_TOOLONG
+ * (pba_correct_reads goes through such a range in chunks).  weight: the selection count of the read's own base, in
+ * [1, 0xFFFF] (with 0 a read without rows would evolve to nothing). */
+typedef struct pba_pileup pba_pileup;
+int pba_pileup_create(pba_ctx *ctx, const pba_seqs *reads, uint32_t t_lo, uint32_t t_hi, int weight, pba_pileup **out);
+void pba_pileup_destroy(pba_pileup *p);
+/* Vote n rows (any order, any mix of strands, any number of calls; every row's target in [t_lo, t_hi)).  reads is the set
+ * the pile-up was made from, reads_rc its reverse complement (pba_seqs_revcomp; may be NULL if no row has strand -1).
+ * res[k] (nullable) as pba_align_batch returns it.  Everything that can be checked on the host -- targets, strands,
+ * accessors inside their reads, the sets -- is checked before any vote: PBA_E_INVALID / PBA_E_ALPHABET leave the boxes as
+ * they were.  A row whose re-run disagrees with its cost / matlen_a / matlen_b (the rows are not overlaps of these sets
+ * under this R) is PBA_E_INVALID too, text in pba_ctx_error, but is found after the batch has voted: the pile-up is spent.
+ * The +1 rows and the -1 rows of a call are two batches.  A batch can still be refused where the host checks end --
+ * PBA_E_TOOLONG (band too wide for the voting kernel), PBA_E_NOMEM, PBA_E_HIP: if that happens after a batch of the call
+ * has voted, or with any status other than PBA_E_TOOLONG / PBA_E_INVALID, the boxes may hold part of the call's votes and the
+ * pile-up is spent as well (do not retry on it: make a new one). */
+int pba_pileup_vote(pba_ctx *ctx, pba_pileup *p, const pba_seqs *reads, const pba_seqs *reads_rc,
+                    const pba_strand_overlap *rows, uint64_t n, double R, pba_result *res);
+/* the boxes of one target as they stand (before evolve), layout of pba_cons_dump */
+int pba_pileup_dump(pba_ctx *ctx, const pba_pileup *p, uint32_t target, uint16_t *sel, uint16_t *sup, int32_t *tot, int cap,
+                    int32_t *n);
+typedef struct {
+    int32_t target, n_rows;        /* rows voted into this target */
+    int32_t len_in, len_out;
+} pba_correct_row;
+/* evolve every segment: the corrected reads as a NEW set (sequence k = target t_lo + k, pba_seqs_from_text's layout; a
+ * zero-length result is legal), written and packed on the device; rows_out (nullable): t_hi - t_lo entries.  Afterwards the
+ * pile-up is spent: its boxes are released, further vote / dump / evolve calls return PBA_E_INVALID. */
+int pba_pileup_evolve(pba_ctx *ctx, pba_pileup *p, pba_seqs **corrected, pba_correct_row *rows_out);
+/* The whole thing for targets [t_lo, t_hi): overlaps on the strands asked for (pba_overlap_strands, same arguments, limits
+ * and stats, summed over the chunks), vote, evolve.  The range is cut into chunks of consecutive targets so that the boxes
+ * (20 bytes per base, at most a quarter of the free device memory and fewer than 2^31 boxes) sit next to what the overlap
+ * call needs; a chunk the overlap call finds too large is halved.  The answer does not depend on the cut.
+ * The rows voted are the engine's own: should one not re-run to itself, that is an inconsistency inside the engine, not a bad
+ * argument, and is reported as PBA_E_HIP (text in pba_ctx_error), never as PBA_E_INVALID. */
+int pba_correct_reads(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t t_lo, uint32_t t_hi,
+                      uint32_t mask, double R, int max_trial, int overlap_min, int kernel, int strands, int weight,
+                      pba_seqs **corrected, pba_correct_row *rows_out, pba_overlap_stats stats[2]);
+/* The same with a ceiling on the boxes of one chunk (max_boxes bases; 0 = none): for a caller that shares the device with
+ * other allocations and wants the pile-up smaller than a quarter of what is free.  A chunk always holds at least one read. */
+int pba_correct_reads_budget(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t t_lo, uint32_t t_hi,
+                             uint32_t mask, double R, int max_trial, int overlap_min, int kernel, int strands, int weight,
+                             uint64_t max_boxes, pba_seqs **corrected, pba_correct_row *rows_out, pba_overlap_stats stats[2]);
+/* HIP-event timings (on the ctx's stream) of the most recent pba_correct_reads on this ctx, summed over its chunks */
+typedef struct {
+    float overlap_ms, vote_ms, evolve_ms;
+    uint32_t n_chunks;
+    uint64_t n_rows;               /* rows voted */
+    uint64_t n_bases_in, n_bases_out;
+} pba_correct_profile;
+int pba_ctx_last_correct_profile(const pba_ctx *ctx, pba_correct_profile *out);
+
 const char *pba_strerror(int status);
 
 #ifdef __cplusplus

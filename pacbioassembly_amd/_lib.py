@@ -44,6 +44,11 @@ class PbaProfile(C.Structure):
                 ("nb_first", C.c_uint32), ("nb_redo", C.c_uint32), ("n_first", C.c_uint32), ("n_redo", C.c_uint32)]
 
 
+class PbaCorrectProfile(C.Structure):
+    _fields_ = [("overlap_ms", C.c_float), ("vote_ms", C.c_float), ("evolve_ms", C.c_float), ("n_chunks", C.c_uint32),
+                ("n_rows", C.c_uint64), ("n_bases_in", C.c_uint64), ("n_bases_out", C.c_uint64)]
+
+
 class PbaSsRow(C.Structure):
     _fields_ = [(n, C.c_int32) for n in
                 ("read", "found", "j", "dir", "ref_pos", "cost", "matlen_a", "matlen_b", "n_trials", "n_pairs")]
@@ -137,6 +142,17 @@ SYMBOLS = {
     "pba_cons_evolve": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_int32)]),
     "pba_cons_dump": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_int32)]),
     "pba_cons_text": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_int32)]),
+    "pba_overlap_row_pair": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
+    "pba_pileup_create": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_P)]),
+    "pba_pileup_destroy": (None, [_P]),
+    "pba_pileup_vote": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.c_double, _P]),
+    "pba_pileup_dump": (C.c_int, [_P, _P, C.c_uint32, _P, _P, _P, C.c_int, C.POINTER(C.c_int32)]),
+    "pba_pileup_evolve": (C.c_int, [_P, _P, C.POINTER(_P), _P]),
+    "pba_correct_reads": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.POINTER(_P), _P, _P]),
+    "pba_correct_reads_budget": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_int, C.c_int, C.c_int,
+                                           C.c_int, C.c_int, C.c_uint64, C.POINTER(_P), _P, _P]),
+    "pba_ctx_last_correct_profile": (C.c_int, [_P, _P]),
     "pba_strerror": (C.c_char_p, [C.c_int]),
 }
 

@@ -101,11 +101,14 @@ k_trace_pairs(SeqSetDev A, SeqSetDev B, const pba_pair *pairs, const uint32_t *i
 // The same sweep and walk, but the path goes straight into the vote boxes of an unlocked reference (consensus.h:
 // VoteSink) -- ref_seq::try_align's align + OVERLAP_MIN gate + elect (ref_seq.h:264-267) for a batch, no script in
 // memory.  a is the reference: pair.a_pos is the position the votes start at.
-template <int NB, bool CK>
+// SEG: the boxes are a pile-up's arena (pba_pileup.hip), one segment per target read: pair q votes into the window of ITS
+// a_seq -- boxes [box_off[a_seq - t_lo], + len(a_seq)), the box of a_pos at that offset + a_pos (beg / pre / post unused).
+// The arena holds fewer than 2^31 boxes (the host refuses or chunks beyond that), so the window fits VoteSink's ints.
+template <int NB, bool CK, bool SEG = false>
 __global__ void __launch_bounds__(PBA_WAVE * 4, NB <= 4 ? (CK && NB <= 2 ? PBA_TR_OCC12 : 4) : 2)
 k_vote_pairs(SeqSetDev A, SeqSetDev B, const pba_pair *pairs, const uint32_t *ids, uint32_t n, AlignCfg cfg, int overlap_min,
              pba_result *out, uint32_t *scratch, uint64_t wave_words, uint64_t cap_words, ConsDev C, int beg, int pre, int post,
-             uint32_t *queue) {
+             uint32_t *queue, const unsigned long long *box_off, uint32_t t_lo) {
     extern __shared__ __align__(16) uint8_t lds_all[];
     __shared__ uint2 s_tile[4][CK ? PBA_BV_TILE_WORDS(NB) : 1];
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / PBA_WAVE));
@@ -120,7 +123,13 @@ k_vote_pairs(SeqSetDev A, SeqSetDev B, const pba_pair *pairs, const uint32_t *id
         const PackedFetch fa = fetch_of(A, pr.a_seq, pr.a_pos, fwd ? 1 : -1);
         const PackedFetch fb = fetch_of(B, pr.b_seq, pr.b_pos, (pr.flags & PBA_B_BACKWARD) ? -1 : 1);
         AlnOut o;
-        VoteSink sink{C, beg + pr.a_pos, pre, post, fwd, fb, 0, 0, 0, 0u};
+        int it0 = beg + pr.a_pos, w_pre = pre, w_post = post;
+        if constexpr (SEG) {
+            w_pre = (int)box_off[pr.a_seq - t_lo];
+            w_post = w_pre + (int)A.len[pr.a_seq];
+            it0 = w_pre + pr.a_pos;
+        }
+        VoteSink sink{C, it0, w_pre, w_post, fwd, fb, 0, 0, 0, 0u};
         if (align_bitvec_trace<NB, CK>(fa, pr.a_len, fb, pr.b_len, cfg.R, cfg.maxn, cfg.maxm, cfg.full_band != 0, (uint16_t *)lds,
                                        cfg.row_cap, mine, cap_words, overlap_min, sink, o, s_tile[wave]))
             sink.finish();
@@ -589,7 +598,8 @@ int pba_align_text_matrix(pba_ctx *ctx, const char *a, int a_fwd, int la, const 
 // paths go straight into its boxes, gated by overlap_min; ops / ops_off / nedit unused).
 int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R,
                        int maxn, int maxm, int kernel, pba_result *out, uint8_t *ops, const uint64_t *ops_off,
-                       int32_t *nedit, const pba_cons *vote, int overlap_min) {
+                       int32_t *nedit, const pba_cons *vote_cons, int overlap_min, const PileView *seg) {
+    const bool vote = vote_cons || seg;
     if (!ctx || !A || !B || (!pairs && n) || (!out && n) || (!vote && ((!ops_off && n) || (!nedit && n)))) return PBA_E_INVALID;
     if (n == 0) return PBA_OK;
     if (n > 0x7FFFFFFFull) PBA_FAIL(PBA_E_INVALID, "too many pairs in one batch");
@@ -615,7 +625,8 @@ int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pa
     int vbeg = 0, vpre = 0, vpost = 0;
     if (vote) {
         if (pl.nb1 == 0) PBA_FAIL(PBA_E_TOOLONG, "votes from the walk need the bit-vector kernel (band too wide)");
-        st = cons_vote_view(vote, &vdev, &vbeg, &vpre, &vpost);
+        if (seg) vdev = seg->dev;
+        else st = cons_vote_view(vote_cons, &vdev, &vbeg, &vpre, &vpost);
         if (st != PBA_OK) return st;
         ops_max = 0;                                             // no goal-first temporary
     }
@@ -664,7 +675,7 @@ int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pa
         // checkpoints + recomputation (default) or every step's words streamed to HBM (PBA_TRACE_STREAM=1: the round-1 form,
         // kept for comparison)
         const char *e_stream = getenv("PBA_TRACE_STREAM");
-        const bool ck = !(e_stream && atoi(e_stream) != 0);
+        const bool ck = seg || !(e_stream && atoi(e_stream) != 0);      // (a pile-up's votes: the checkpoint form only)
         std::vector<uint32_t> redo;
         for (int pass = 0; pass < 2; ++pass) {
             const int nb = pass ? pl.nb2 : pl.nb1;
@@ -697,18 +708,23 @@ int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pa
             }
             HIPCHK(hipMemsetAsync(ctx->d_queue, 0, sizeof(uint32_t), ctx->stream));
             (void)hipEventRecord(ctx->ev[pass ? 4 : 2], ctx->stream);
+#define K_SEG(NBV)                                                                                                    \
+    hipLaunchKernelGGL((k_vote_pairs<NBV, true, true>), dim3(grid), dim3(PBA_WAVE * 4), pl.lds * 4, ctx->stream, A->dev(), B->dev(), \
+                       d_pairs.as<pba_pair>(), ids, cnt, pl.cfg, overlap_min, d_out.as<pba_result>(),                  \
+                       d_scr, wave_words, cap_words, vdev, 0, 0, 0, ctx->d_queue, seg->box_off, seg->t_lo)
 #define K_TRACE2(NBV, CKV)                                                                                            \
     if (vote)                                                                                                         \
         hipLaunchKernelGGL((k_vote_pairs<NBV, CKV>), dim3(grid), dim3(PBA_WAVE * 4), pl.lds * 4, ctx->stream, A->dev(), B->dev(), \
                            d_pairs.as<pba_pair>(), ids, cnt, pl.cfg, overlap_min, d_out.as<pba_result>(),              \
-                           d_scr, wave_words, cap_words, vdev, vbeg, vpre, vpost, ctx->d_queue);        \
+                           d_scr, wave_words, cap_words, vdev, vbeg, vpre, vpost, ctx->d_queue,                        \
+                           (const unsigned long long *)nullptr, 0u);                                                  \
     else                                                                                                              \
         hipLaunchKernelGGL((k_trace_pairs<NBV, CKV>), dim3(grid), dim3(PBA_WAVE * 4), pl.lds * 4, ctx->stream, A->dev(), B->dev(), \
                            d_pairs.as<pba_pair>(), ids, cnt, pl.cfg, d_out.as<pba_result>(), d_scr,     \
                            wave_words, cap_words, d_ops.as<uint8_t>(), d_ooff.as<uint64_t>(), d_ne.as<int32_t>(),      \
                            ctx->d_queue)
 #define K_TRACE(NBV)                                                                                                  \
-    if (ck) { K_TRACE2(NBV, true); } else { K_TRACE2(NBV, false); }
+    if (seg) { K_SEG(NBV); } else if (ck) { K_TRACE2(NBV, true); } else { K_TRACE2(NBV, false); }
             switch (nb) {
                 case 1: K_TRACE(1); break;
                 case 2: K_TRACE(2); break;
@@ -719,6 +735,7 @@ int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pa
             }
 #undef K_TRACE
 #undef K_TRACE2
+#undef K_SEG
             (void)hipEventRecord(ctx->ev[pass ? 5 : 3], ctx->stream);
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpyAsync(out, d_out.p, sizeof(pba_result) * n, hipMemcpyDeviceToHost, ctx->stream));

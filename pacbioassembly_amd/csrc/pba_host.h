@@ -1,6 +1,6 @@
 // pba_host.h -- host-side objects and helpers shared by the translation units of libpba.so (pba_core.hip: context,
 // sequence sets, seed index; pba_align.hip: explicit pairs and edit scripts; pba_drivers.hip: the reference's ordered
-// first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting).  Internal: nothing here is part of
+// first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction).  Internal: nothing here is part of
 // the C ABI (include/pba.h).
 #ifndef PBA_HOST_H
 #define PBA_HOST_H
@@ -56,6 +56,7 @@ struct pba_ctx {
     // one index: the hipFree / hipMalloc pair of its 40 MB cost 0.2 ms of a 48 ms step)
     struct { void *ent; size_t ent_cap; void *off; size_t off_cap; void *ent2; size_t ent2_cap; } ix_cache;
     pba_profile prof;
+    pba_correct_profile cprof;   // the most recent pba_correct_reads
     char err[512];
 };
 
@@ -293,11 +294,17 @@ static inline void launch_seg_sort(pba_ctx *ctx, const uint64_t *src, uint64_t *
 extern "C" {
 // sort one oversize partition / candidate piece in global memory (pba_core.hip)
 PBA_INTERNAL int sort_partition_global(pba_ctx *ctx, uint64_t *d_part, uint32_t n);
-// edit scripts of a batch, or their votes (pba_align.hip)
+// edit scripts of a batch, or their votes (pba_align.hip): into the boxes of one reference (vote), or into the segment of
+// each pair's own target in a pile-up's box arena (seg; pba_pileup.hip)
 struct pba_cons;
+struct PileView {
+    ConsDev dev;                          // the arena (txt unused)
+    const unsigned long long *box_off;    // first box of target t at box_off[t - t_lo]
+    uint32_t t_lo;
+};
 PBA_INTERNAL int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R,
                              int maxn, int maxm, int kernel, pba_result *out, uint8_t *ops, const uint64_t *ops_off,
-                             int32_t *nedit, const pba_cons *vote, int overlap_min);
+                             int32_t *nedit, const pba_cons *vote, int overlap_min, const PileView *seg = nullptr);
 // the vote boxes a batch of walks votes into (pba_cons.hip)
 PBA_INTERNAL int cons_vote_view(const pba_cons *c, ConsDev *dev, int *beg, int *pre, int *post);
 // one locked round over a subset of the reads (pba_drivers.hip)

@@ -27,6 +27,8 @@ OVERLAP_DTYPE = np.dtype([(n, "<i4") for n in ("target", "query", "j", "dir", "r
 # pba_strand_overlap: a pba_overlap row with its strand and half-open intervals on the forward strand of each read
 STRAND_OVERLAP_DTYPE = np.dtype([(n, "<i4") for n in ("target", "query", "strand", "j", "dir", "ref_pos", "cost", "matlen_a",
                                                      "matlen_b", "t_beg", "t_end", "q_beg", "q_end")])
+# pba_correct_row: one per target of a corrected range
+CORRECT_ROW_DTYPE = np.dtype([(n, "<i4") for n in ("target", "n_rows", "len_in", "len_out")])
 assert PAIR_DTYPE.itemsize == C.sizeof(PbaPair) and RESULT_DTYPE.itemsize == C.sizeof(PbaResult)
 assert LOC_ROW_DTYPE.itemsize == C.sizeof(PbaLocRow) and SS_ROW_DTYPE.itemsize == C.sizeof(PbaSsRow)
 
@@ -534,6 +536,49 @@ def _overlap_strands_sharded(self, reads, mask, R, max_trial=32, overlap_min=64,
     return out, (total or [{}, {}])
 
 
+def overlap_row_pair(row, target_len: int, query_len: int) -> np.ndarray:
+    """The pair of accessors an overlap_strands row stands for (pba_overlap_row_pair; host arithmetic): one PAIR_DTYPE
+    record with a_seq = the target, b_seq = the query -- for a strand -1 row an index into the reverse-complemented set."""
+    r = np.zeros(1, STRAND_OVERLAP_DTYPE)
+    for f in STRAND_OVERLAP_DTYPE.names:
+        r[f] = row[f]
+    out = np.zeros(1, PAIR_DTYPE)
+    st = _lib.load().pba_overlap_row_pair(_ptr(r), target_len, query_len, _ptr(out))
+    if st != 0:
+        raise PbaError(st, "overlap_row_pair")
+    return out[0]
+
+
+def _correct_reads(self, reads, mask, R, max_trial=32, overlap_min=64, strands=3, weight=1, t_lo=0, t_hi=None,
+                   kernel=PBA_KERNEL_AUTO, reads_rc=None, max_boxes=0):
+    """Error-corrected reads of targets [t_lo, t_hi) (pba_correct_reads): overlaps on the strands asked for, every row voted
+    into its target's boxes, evolve.  max_boxes: a ceiling on the bases of one internal chunk of targets (0 = sized from the
+    free device memory; pba_correct_reads_budget).  Returns (SeqSet of the corrected reads, rows of CORRECT_ROW_DTYPE, [stats of the +1
+    pass, of the -1 pass])."""
+    t_hi = reads.count if t_hi is None else t_hi
+    rows = np.zeros(max(t_hi - t_lo, 1), CORRECT_ROW_DTYPE)
+    st2 = (_lib.PbaOverlapStats * 2)()
+    h = C.c_void_p()
+    rc_h = reads_rc.h if reads_rc is not None else None
+    if max_boxes:
+        st = self.lib.pba_correct_reads_budget(self.h, reads.h, rc_h, t_lo, t_hi, mask, R, max_trial, overlap_min, kernel, strands,
+                                               weight, max_boxes, C.byref(h), _ptr(rows), C.byref(st2))
+    else:
+        st = self.lib.pba_correct_reads(self.h, reads.h, rc_h, t_lo, t_hi, mask, R, max_trial, overlap_min, kernel, strands,
+                                        weight, C.byref(h), _ptr(rows), C.byref(st2))
+    self.check(st, "correct_reads")
+    return SeqSet(self, h), rows[:max(t_hi - t_lo, 0)], _stats_pair(st2)
+
+
+def _last_correct_profile(self) -> dict:
+    """HIP-event timings and counts of the most recent correct_reads on this context."""
+    pr = _lib.PbaCorrectProfile()
+    self.check(self.lib.pba_ctx_last_correct_profile(self.h, C.byref(pr)), "last_correct_profile")
+    return {n: getattr(pr, n) for n, _ in _lib.PbaCorrectProfile._fields_}
+
+
+Context.correct_reads = _correct_reads
+Context.last_correct_profile = _last_correct_profile
 Context.overlap_strands = _overlap_strands
 Context.overlap_strands_table = _overlap_strands_table
 Context.overlap_strands_sharded = _overlap_strands_sharded
@@ -693,6 +738,53 @@ class Consensus:
         n = C.c_int32()
         self.ctx.check(self.ctx.lib.pba_cons_text(self.ctx.h, self.h, buf, cap, C.byref(n)), "cons_text")
         return buf.raw[:n.value]
+
+
+class Pileup:
+    """Vote boxes of the reads [t_lo, t_hi) of a set, one segment per read, resident in HBM (pba_pileup): overlap rows vote
+    into their target's segment, evolve gives the corrected reads.  No growth."""
+
+    def __init__(self, ctx: "Context", reads: "SeqSet", t_lo: int = 0, t_hi: Optional[int] = None, weight: int = 1):
+        self.ctx, self.reads = ctx, reads
+        self.t_lo, self.t_hi = t_lo, reads.count if t_hi is None else t_hi
+        self.h = C.c_void_p()
+        ctx.check(ctx.lib.pba_pileup_create(ctx.h, reads.h, self.t_lo, self.t_hi, weight, C.byref(self.h)), "pileup_create")
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.ctx.lib.pba_pileup_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def vote(self, rows: np.ndarray, R: float, reads_rc: Optional["SeqSet"] = None) -> np.ndarray:
+        """Vote overlap_strands rows (any order, any mix of strands); returns the re-run's alignment results."""
+        rows = np.ascontiguousarray(rows, STRAND_OVERLAP_DTYPE)
+        res = np.zeros(max(rows.size, 1), RESULT_DTYPE)
+        self.ctx.check(self.ctx.lib.pba_pileup_vote(self.ctx.h, self.h, self.reads.h, reads_rc.h if reads_rc is not None else None,
+                                                    _ptr(rows), rows.size, R, _ptr(res)), "pileup_vote")
+        return res[:rows.size]
+
+    def dump(self, target: int):
+        """(sel[n, 4], sup[n, 4], tot[n]) of one target's boxes as they stand."""
+        n = C.c_int32()
+        self.ctx.check(self.ctx.lib.pba_pileup_dump(self.ctx.h, self.h, target, None, None, None, 0, C.byref(n)), "pileup_dump")
+        cap = n.value
+        sel = np.zeros((max(cap, 1), 4), np.uint16); sup = np.zeros((max(cap, 1), 4), np.uint16); tot = np.zeros(max(cap, 1), np.int32)
+        self.ctx.check(self.ctx.lib.pba_pileup_dump(self.ctx.h, self.h, target, _ptr(sel), _ptr(sup), _ptr(tot), cap, C.byref(n)),
+                       "pileup_dump")
+        return sel[:cap], sup[:cap], tot[:cap]
+
+    def evolve(self):
+        """Returns (SeqSet of the corrected reads, rows of CORRECT_ROW_DTYPE); the pile-up is spent afterwards."""
+        rows = np.zeros(max(self.t_hi - self.t_lo, 1), CORRECT_ROW_DTYPE)
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.lib.pba_pileup_evolve(self.ctx.h, self.h, C.byref(h), _ptr(rows)), "pileup_evolve")
+        return SeqSet(self.ctx, h), rows[:self.t_hi - self.t_lo]
 
 
 def script_vals(ops: np.ndarray, seg: bytes, fwd: bool = True) -> bytes:
