@@ -1434,6 +1434,86 @@ def test_overlap_later_ranges_of_a_table_skip_the_count_pass(ctx, monkeypatch):
         assert (st["cap_fill"] + st["cap_overflow"] > 0) == bool(n_cap) and (st["cap_overflow"] > 0) == bool(n_over), (pct, st)
 
 
+def _oracle_overlaps_of(oracle, texts, mask, t, nthreads=16):
+    """The oracle's locked round with read t as the reference and every read a query: the rows pba_overlap_all owes for target t."""
+    file = b"".join(eng.text2bin(x) for x in texts)
+    rec_offs = np.cumsum([0] + [4 + (len(x) + 3) // 4 for x in texts[:-1]]).astype(np.uint64)
+    rows = oracle.spaced_round(texts[t], mask, 0.30, file, rec_offs, 32, 64, buggy=False, nthreads=nthreads)
+    return [(t, int(q), int(rows["j"][q]), int(rows["dir"][q]), int(rows["ref_pos"][q]), int(rows["cost"][q]), int(rows["matlen_a"][q]),
+             int(rows["matlen_b"][q])) for q in np.nonzero(rows["found"])[0] if q != t]
+
+
+def test_overlap_wide_hook_decides_one_call_and_leaves_the_table_alone(ctx, oracle, monkeypatch):
+    """PBA_OVL_WIDE is a tuning hook of the call it is set for: one probe table, two consecutive target ranges, the hook set
+    for the first call and removed for the second -- the second call gives the rows and the counts of the same call on a fresh
+    table whose first call ran without the hook; its `wide_first` is the sampled decision again (narrow: reads 4 % apart
+    certify in the narrow window), not what the hook had said.  12 000 reads of 400 bases in ranges of 6 000 targets, so that
+    a range has more work items than the 4 096 of a sample; rows against the oracle's locked round on targets of both ranges."""
+    import torch
+    from pacbioassembly_amd import ProbeTable
+    n, rl, per = 12_000, 400, 6_000
+    g = eng.synth_genome(911, n * rl // 20)
+    reads, offs, _ = eng.synth_reads(912, g, n, rl, 0.01, 0.01, 0.01, nthreads=16)
+    mask = eng.mask_from_pattern(MASK_PAT)
+    S = ctx.seqs_from_text(reads, offs, strict_acgt=True)
+
+    def two_ranges(hook_first):
+        probes = torch.full((n * 64,), -1, dtype=torch.int64, device="cuda")
+        ctx.overlap_probes(S, 0, n, mask, 32, probes.data_ptr(), n * 64)
+        torch.cuda.synchronize()
+        table = ProbeTable(ctx, probes.data_ptr(), probes.numel(), mask, 32)
+        out = []
+        for k, (lo, hi) in enumerate(((0, per), (per, n))):
+            if k == 0 and hook_first:
+                monkeypatch.setenv("PBA_OVL_WIDE", "1")
+            else:
+                monkeypatch.delenv("PBA_OVL_WIDE", raising=False)
+            rows, st = ctx.overlap_all_table(S, table, 0.30, 64, lo, hi, PBA_KERNEL_BITVEC, per * 400)
+            out.append((rows, {k_: v for k_, v in st.items() if not k_.endswith("_ms")}))
+        table.close()
+        return out
+
+    hooked, plain = two_ranges(True), two_ranges(False)
+    assert hooked[0][1]["wide_first"] == 1 and plain[0][1]["wide_first"] == 0        # the hook did decide its own call
+    assert (hooked[0][0] == plain[0][0]).all() and hooked[0][1]["n_pairs"] == plain[0][1]["n_pairs"]
+    assert (hooked[1][0] == plain[1][0]).all() and len(plain[1][0]) > 10_000
+    assert hooked[1][1] == plain[1][1] and hooked[1][1]["wide_first"] == 0, (hooked[1][1], plain[1][1])
+    texts = [reads[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)]
+    for t in (0, per - 1, per, 9_001, n - 1):
+        exp = _oracle_overlaps_of(oracle, texts, mask, t)
+        got = hooked[t >= per][0]
+        lo, hi = np.searchsorted(got["target"], [t, t + 1])
+        assert [tuple(int(x) for x in r) for r in got[lo:hi]] == exp and len(exp) >= 1, t
+
+
+def test_overlap_room_hook_beyond_the_candidate_limit_is_ignored(ctx, oracle, monkeypatch):
+    """PBA_OVL_ROOM is held to the limit every other way of sizing the slices is held to: room x targets must stay below the
+    candidates a call can address (32-bit offsets).  The limit lowered through PBA_OVL_MAX_CANDIDATES to four times the
+    range's real candidate count, the room set so that 64 targets x room reaches it: the call sizes itself by the census as
+    if the hook were unset -- same rows (the oracle's composition), same counts, no equal-room pass (cap_fill 0)."""
+    g = eng.synth_genome(71, 9000)
+    n, rl = 64, 1300
+    reads, offs, _ = eng.synth_reads(72, g, n, rl)
+    texts = [reads[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)]
+    mask = eng.mask_from_pattern(MASK_PAT)
+    want = [r for t in range(n) for r in _oracle_overlaps_of(oracle, texts, mask, t, nthreads=8)]
+    assert len(want) > 100
+    S = ctx.seqs_from_list(texts, strict_acgt=True)
+    _, st0 = ctx.overlap_all(S, mask, 0.30, 32, 64, kernel=PBA_KERNEL_BITVEC)
+    limit = 4 * max(st0["n_candidates"], 1024)
+    monkeypatch.setenv("PBA_OVL_MAX_CANDIDATES", str(limit))
+    base, stb = ctx.overlap_all(S, mask, 0.30, 32, 64, kernel=PBA_KERNEL_BITVEC)
+    monkeypatch.setenv("PBA_OVL_ROOM", str(limit // n + 1))
+    assert (limit // n + 1) * n >= limit > st0["n_candidates"]
+    got, st = ctx.overlap_all(S, mask, 0.30, 32, 64, kernel=PBA_KERNEL_BITVEC)
+    assert [tuple(int(x) for x in r) for r in got] == want and (got == base).all()
+    for k in ("n_pairs", "n_candidates", "cap_fill", "cap_overflow"):
+        assert st[k] == stb[k] == st0[k], (k, st, stb, st0)
+    assert st["cap_fill"] == 0 and st["cap_overflow"] == 0
+    monkeypatch.setenv("PBA_OVL_ROOM", "4")                         # (a room inside the limit is still taken: here one that overflows)
+    assert ctx.overlap_all(S, mask, 0.30, 32, 64, kernel=PBA_KERNEL_BITVEC)[1]["cap_overflow"] == 1
+
+
 @pytest.mark.parametrize("pattern", ["1111111111111111", "111111111111111*", "1111111*11111111"])
 def test_overlap_all_heavy_masks_hashed_table(ctx, oracle, pattern, prekeep):
     """Masks with more than 26 care bits: the probe table is a 2^26-bucket hash with the probes' keys stored beside them
