@@ -164,7 +164,6 @@ __global__ void k_trace_walk(const pba_result *res, const uint8_t *par, const ui
     nedit[q] = (int32_t)k;
 }
 
-
 // (the attribute belongs to the current device: remembered per ctx, so a second ctx on another GPU sets it there too)
 static void tu_attrs(pba_ctx *ctx) {
     if (ctx->attr_done & 1u) return;
@@ -175,8 +174,130 @@ static void tu_attrs(pba_ctx *ctx) {
     PBA_BIG_LDS(k_align_pairs_trace);
 }
 
-extern "C" {
+// the test and tuning hooks of a call, from the environment (read per call: the tests set and unset them between calls)
+struct TraceHooks {
+    bool stream;                 // PBA_TRACE_STREAM=1: every step's parent words streamed to HBM (the round-1 form, kept for
+                                 // comparison) instead of checkpoints + recomputation
+    bool budget_set; uint64_t budget;   // PBA_TRACE_BUDGET_GB: tuning aid, HBM the parent bits / codes of one call may take
+    bool text_rowsweep;          // PBA_TEXT_ROWSWEEP=1: test hook, every text pair through the general form (both forms are cross-checked)
+};
+static TraceHooks trace_hooks_from_env() {
+    TraceHooks h{false, false, 0, false};
+    const char *e;
+    if ((e = getenv("PBA_TRACE_STREAM"))) h.stream = atoi(e) != 0;
+    if ((e = getenv("PBA_TRACE_BUDGET_GB"))) { h.budget_set = true; h.budget = (uint64_t)atoll(e) << 30; }
+    if ((e = getenv("PBA_TEXT_ROWSWEEP"))) h.text_rowsweep = atoi(e) != 0;
+    return h;
+}
 
+// Every pair inside its sequences and the engine limit (ops_off, nullable: a_len + b_len slots for each pair's script);
+// the widest band and the longest script of the batch.
+static int check_pairs(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R,
+                       const uint64_t *ops_off, int *mdmax, uint64_t *ops_max) {
+    *mdmax = 1; *ops_max = 0;
+    for (size_t q = 0; q < n; ++q) {
+        const pba_pair &p = pairs[q];
+        if (!pair_ok(A, p.a_seq, p.a_pos, p.a_len, p.flags & PBA_A_BACKWARD) ||
+            !pair_ok(B, p.b_seq, p.b_pos, p.b_len, p.flags & PBA_B_BACKWARD))
+            PBA_FAIL(PBA_E_INVALID, "pair outside its sequence (or longer than the engine limit)");
+        if (ops_off && (ops_off[q + 1] < ops_off[q] || ops_off[q + 1] - ops_off[q] < (uint64_t)p.a_len + p.b_len))
+            PBA_FAIL(PBA_E_INVALID, "ops_off must leave a_len + b_len slots per pair");
+        if (R > 0.0 && R < 1.0) *mdmax = std::max(*mdmax, max_dst_of(p.a_len, p.b_len, R));
+        *ops_max = std::max(*ops_max, (uint64_t)p.a_len + p.b_len);
+    }
+    return PBA_OK;
+}
+
+// the results of a batch to the caller's array, synchronised; redo (nullable): the pairs whose narrow pass could not certify
+// the goal row, which go round again at the reference band
+static int fetch_results(pba_ctx *ctx, const void *d_out, pba_result *out, size_t n, std::vector<uint32_t> *redo) {
+    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(pba_result) * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (size_t q = 0; redo && q < n; ++q)
+        if (out[q].rc == PBA_RC_UNCERTIFIED) redo->push_back((uint32_t)q);
+    return PBA_OK;
+}
+
+// one launch of k_align_pairs over `cnt` pairs (ids: device, nullable)
+static void launch_align_pairs(pba_ctx *ctx, const Plan &pl, int nb, const SeqSetDev &A, const SeqSetDev &B, const pba_pair *d_pairs,
+                               const uint32_t *ids, uint32_t cnt, pba_result *d_out) {
+#define PBA_PAIRS_LAUNCH(NBV)                                                                                        \
+    hipLaunchKernelGGL(k_align_pairs<NBV>, dim3(persistent_grid(ctx, cnt, Wpb<NBV>::v, pl.lds)),                      \
+                       dim3(PBA_WAVE * Wpb<NBV>::v), pl.lds * Wpb<NBV>::v, ctx->stream, A, B, d_pairs, ids, cnt, pl.cfg, \
+                       d_out, ctx->d_queue)
+    PBA_DISPATCH_NB(nb, PBA_PAIRS_LAUNCH);
+#undef PBA_PAIRS_LAUNCH
+}
+
+// ---- the traced bit-vector pass on the host: sizing and launch, shared by the batch and the one-pair text entry points
+static const uint64_t kTraceBudget = 96ull << 30;      // parent codes / bits resident for one call (and at most 80 % of free HBM)
+
+// scratch the traced bit-vector pass of one pair needs (u32 words): narrow first pass or reference band
+static uint64_t trace_words_of(int la, int lb, double R, int nb, bool full_band, bool ck) {
+    const TextClip c = text_clip(la, lb, R);
+    const int m = std::min(c.len_a, c.len_b), n = std::max(c.len_a, c.len_b);
+    if (m <= 10) return (band_matrix_cells(c) + 3) / 4;                          // the row sweep's corner: byte codes
+    const int w = full_band ? c.md : bv_pass1_w(c.md, nb);
+    return ck ? bv_ck_words(nb, m, n, w) : bv_trace_words(nb, m, n, w);
+}
+
+// One traced pass over `cnt` pairs (sub: their host indices, nullable = the first cnt), sized: the per-wavefront scratch
+// area (cap_words of parent bits for the widest pair, then ops_max + 64 goal-first ops), as many workgroups as fill the chip
+// and fit `budget`, and the ctx's scratch grown to hold them.
+struct TracePass { uint64_t cap_words, wave_words; uint32_t grid; };
+static int trace_pass_size(pba_ctx *ctx, const pba_pair *pairs, const uint32_t *sub, uint32_t cnt, double R, int nb, bool full_band,
+                           bool ck, uint64_t ops_max, size_t lds, uint64_t budget, TracePass *tp) {
+    uint64_t cap_words = 128;
+    for (uint32_t k = 0; k < cnt; ++k) {
+        const pba_pair &p = pairs[sub ? sub[k] : k];
+        cap_words = std::max(cap_words, trace_words_of(p.a_len, p.b_len, R, nb, full_band, ck));
+    }
+    tp->cap_words = (cap_words + 63) & ~63ull;
+    tp->wave_words = tp->cap_words + ((ops_max + 64 + 255) & ~255ull) / 4;
+    tp->grid = (uint32_t)std::min<uint64_t>(persistent_grid(ctx, cnt, 4, lds), budget / (tp->wave_words * 4 * 4));
+    if (tp->grid == 0) PBA_FAIL(PBA_E_NOMEM, "one wavefront's parent bits exceed the traceback budget");
+    return scratch_reserve(ctx, (size_t)tp->grid * 4 * tp->wave_words * 4);
+}
+
+// What a launch of k_trace_pairs / k_vote_pairs works on (all pointers: device).
+struct TracedLaunch {
+    SeqSetDev A, B;
+    const pba_pair *pairs;
+    pba_result *out;
+    size_t lds;                           // per wavefront
+    bool ck;                              // the checkpoint form (a pile-up's votes: that form only)
+    uint8_t *ops;                         // the sink: scripts (ops / ops_off / nedit) ...
+    const uint64_t *ops_off;
+    int32_t *nedit;
+    bool vote;                            // ... or votes, gated by overlap_min: into the boxes of one reference (C, beg, pre, post)
+    int overlap_min;
+    ConsDev C;
+    int beg, pre, post;
+    const PileView *seg;                  // ... or into the segment of each pair's own target in a pile-up's arena (C = seg->dev)
+};
+// (PBA_DISPATCH_NB without its case 0: these kernels have no row-sweep form)
+#define PBA_DISPATCH_BV_NB(nb, K) \
+    switch (nb) { case 1: K(1); break; case 2: K(2); break; case 3: K(3); break; case 4: K(4); break; case 6: K(6); break; default: K(8); break; }
+static void launch_traced(pba_ctx *ctx, const TracedLaunch &t, int nb, const AlignCfg &cfg, const uint32_t *ids, uint32_t cnt,
+                          const TracePass &tp) {
+    const dim3 grid(tp.grid), block(PBA_WAVE * 4);
+    uint32_t *const scr = (uint32_t *)ctx->d_scratch;
+#define PBA_SCRIPTS(NBV) {                                                                                            \
+        const auto k = t.ck ? k_trace_pairs<NBV, true> : k_trace_pairs<NBV, false>;                                   \
+        hipLaunchKernelGGL(k, grid, block, t.lds * 4, ctx->stream, t.A, t.B, t.pairs, ids, cnt, cfg, t.out, scr, tp.wave_words, \
+                           tp.cap_words, t.ops, t.ops_off, t.nedit, ctx->d_queue); }
+#define PBA_VOTES(NBV) {                                                                                              \
+        auto k = k_vote_pairs<NBV, true, true>;                                                                      \
+        if (!t.seg) k = t.ck ? k_vote_pairs<NBV, true, false> : k_vote_pairs<NBV, false, false>;                     \
+        hipLaunchKernelGGL(k, grid, block, t.lds * 4, ctx->stream, t.A, t.B, t.pairs, ids, cnt, cfg, t.overlap_min, t.out, scr, \
+                           tp.wave_words, tp.cap_words, t.C, t.beg, t.pre, t.post, ctx->d_queue,                     \
+                           t.seg ? t.seg->box_off : (const unsigned long long *)nullptr, t.seg ? t.seg->t_lo : 0u); }
+    if (!t.vote) { PBA_DISPATCH_BV_NB(nb, PBA_SCRIPTS); } else { PBA_DISPATCH_BV_NB(nb, PBA_VOTES); }
+#undef PBA_VOTES
+#undef PBA_SCRIPTS
+}
+
+// (the entry points below have C linkage from their declarations in pba.h / pba_host.h)
 int pba_align_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R,
                     int maxn, int maxm, int kernel, pba_result *out) {
     if (!ctx || !A || !B || (!pairs && n) || (!out && n)) return PBA_E_INVALID;
@@ -186,88 +307,29 @@ int pba_align_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pb
         PBA_FAIL(PBA_E_ALPHABET, "a sequence set holds bytes outside ACGT: the reference compares raw bytes, use pba_align_text");
     HIPCHK(hipSetDevice(ctx->device));
     tu_attrs(ctx);
-    int mdmax = 1;
-    for (size_t q = 0; q < n; ++q) {
-        const pba_pair &p = pairs[q];
-        if (!pair_ok(A, p.a_seq, p.a_pos, p.a_len, p.flags & PBA_A_BACKWARD) ||
-            !pair_ok(B, p.b_seq, p.b_pos, p.b_len, p.flags & PBA_B_BACKWARD))
-            PBA_FAIL(PBA_E_INVALID, "pair outside its sequence (or longer than the engine limit)");
-        if (R > 0.0 && R < 1.0) mdmax = std::max(mdmax, max_dst_of(p.a_len, p.b_len, R));
-    }
-    Plan pl;
-    int st = make_plan(ctx, R, maxn, maxm, kernel, mdmax, &pl);
+    int mdmax;
+    uint64_t ops_max;
+    int st = check_pairs(ctx, A, B, pairs, n, R, nullptr, &mdmax, &ops_max);
     if (st != PBA_OK) return st;
-    DevBuf d_pairs, d_out, d_ids;
+    Plan pl;
+    st = make_plan(ctx, R, maxn, maxm, kernel, mdmax, &pl);
+    if (st != PBA_OK) return st;
+    DevBuf d_pairs, d_out;
     HIPCHK(hipMalloc(&d_pairs.p, sizeof(pba_pair) * n));
     HIPCHK(hipMalloc(&d_out.p, sizeof(pba_result) * n));
     HIPCHK(hipMemcpyAsync(d_pairs.p, pairs, sizeof(pba_pair) * n, hipMemcpyHostToDevice, ctx->stream));
-#define K_PAIRS(NBV)                                                                                               \
-    (void)hipMemsetAsync(ctx->d_queue, 0, 4, ctx->stream);                                                         \
-    hipLaunchKernelGGL(k_align_pairs<NBV>, dim3(persistent_grid(ctx, cnt, Wpb<NBV>::v, pl.lds)),                    \
-                       dim3(PBA_WAVE * Wpb<NBV>::v), pl.lds * Wpb<NBV>::v, ctx->stream, A->dev(), B->dev(),         \
-                       d_pairs.as<pba_pair>(), ids, cnt, pl.cfg, d_out.as<pba_result>(), ctx->d_queue)
-    {
-        const uint32_t cnt = (uint32_t)n;
-        const uint32_t *ids = nullptr;
-        (void)hipEventRecord(ctx->ev[2], ctx->stream);
-        PBA_DISPATCH_NB(pl.nb1, K_PAIRS);
-        (void)hipEventRecord(ctx->ev[3], ctx->stream);
-        ctx->prof.nb_first = (uint32_t)pl.nb1; ctx->prof.n_first = cnt; ctx->prof.nb_redo = 0; ctx->prof.n_redo = 0;
-        ctx->prof.align_redo_ms = 0.f;
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, d_out.p, sizeof(pba_result) * n, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    // pairs whose narrow pass could not certify the goal row go round again at the reference band
-    std::vector<uint32_t> redo;
-    for (size_t q = 0; q < n; ++q)
-        if (out[q].rc == PBA_RC_UNCERTIFIED) redo.push_back((uint32_t)q);
-    if (!redo.empty()) {
-        HIPCHK(hipMalloc(&d_ids.p, sizeof(uint32_t) * redo.size()));
-        HIPCHK(hipMemcpyAsync(d_ids.p, redo.data(), sizeof(uint32_t) * redo.size(), hipMemcpyHostToDevice, ctx->stream));
-        pl.cfg.full_band = 1;
-        const uint32_t cnt = (uint32_t)redo.size();
-        const uint32_t *ids = d_ids.as<uint32_t>();
-        (void)hipEventRecord(ctx->ev[4], ctx->stream);
-        PBA_DISPATCH_NB(pl.nb2, K_PAIRS);
-        (void)hipEventRecord(ctx->ev[5], ctx->stream);
-        ctx->prof.nb_redo = (uint32_t)pl.nb2; ctx->prof.n_redo = cnt;
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(out, d_out.p, sizeof(pba_result) * n, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-    }
-#undef K_PAIRS
-    prof_finish(ctx);
-    return PBA_OK;
+    auto launch = [&](int nb, const uint32_t *ids, uint32_t cnt) {
+        launch_align_pairs(ctx, pl, nb, A->dev(), B->dev(), d_pairs.as<pba_pair>(), ids, cnt, d_out.as<pba_result>());
+    };
+    auto collect = [&](std::vector<uint32_t> &redo) { return fetch_results(ctx, d_out.p, out, n, &redo); };
+    auto finish = [&](bool redone) { return redone ? fetch_results(ctx, d_out.p, out, n, nullptr) : (int)PBA_OK; };
+    return narrow_then_redo(ctx, pl, nullptr, (uint32_t)n, launch, collect, finish);
 }
-
-// scratch the traced bit-vector pass of one pair needs (u32 words): narrow first pass or reference band
-static uint64_t trace_words_of(int la, int lb, double R, int nb, bool full_band, bool ck) {
-    const int md = max_dst_of(la, lb, R);
-    const int len_a = lb >= la ? la : std::min(la, lb + md), len_b = lb >= la ? std::min(lb, la + md) : lb;
-    const int m = std::min(len_a, len_b), n = std::max(len_a, len_b);
-    if (m <= 10) return (((uint64_t)len_a + 1) * (2ull * md + 1) + 3) / 4;       // the row sweep's corner: byte codes
-    const int w = full_band ? md : bv_pass1_w(md, nb);
-    return ck ? bv_ck_words(nb, m, n, w) : bv_trace_words(nb, m, n, w);
-}
-
 
 // ---------------------------------------------------------------------------------------------
 // One pair handed over as host text: what the compat seq_aligner<>::align (include/compat/seq_aligner.h) calls.
+// The clip of seq_aligner.h:94-102 comes first (text_clip, pba_host.h).
 // ---------------------------------------------------------------------------------------------
-static const uint64_t kTraceBudget = 96ull << 30;      // parent codes / bits resident for one call (and at most 80 % of free HBM)
-
-// What align() looks at of its two accessors.  seq_aligner.h:94-102 clips the longer one to the shorter + max_dst BEFORE
-// anything is sized, checked or read -- locator.cpp:80-81 hands it the whole rest of an 800 kb contig, ref_seq.h:282-286 the
-// whole rest of the reference -- so the engine's own limit, the size guard and the H2D copy all see the clipped lengths.
-// Same FP64 product and truncation as aln_params (dev_common.h); given (len_a, len_b) the kernels derive the same block again.
-struct TextClip { int len_a, len_b, md; };
-static inline TextClip text_clip(int la, int lb, double R) {
-    TextClip c;
-    if (lb >= la) { c.len_a = la; c.md = 1 + (int)((double)la * R); c.len_b = (int)std::min<long long>(lb, (long long)la + c.md); }
-    else          { c.len_b = lb; c.md = 1 + (int)((double)lb * R); c.len_a = (int)std::min<long long>(la, (long long)lb + c.md); }
-    return c;
-}
 // the reference's size guard (seq_aligner.h:104-107: LOG, return -1) answered on the host; 1 = *out is final, nothing to launch
 static inline int text_guard(pba_ctx *ctx, const TextClip &c, int maxn, int maxm, pba_result *out, const char *who) {
     if (maxn > 0 && ((long long)c.len_a >= (long long)maxn + maxm || c.md >= maxm)) {
@@ -281,15 +343,6 @@ static inline int text_guard(pba_ctx *ctx, const TextClip &c, int maxn, int maxm
 // elements 0 .. len-1 of an accessor in text order: element k of a backward accessor is p[-k] (dna_seq.h:211,221), so its
 // elements are the bytes [p-(len-1), p] and the accessor's origin is the last of them
 static inline const uint8_t *acc_low(const char *p, int fwd, int len) { return (const uint8_t *)((fwd || len == 0) ? p : p - (len - 1)); }
-
-static inline int scratch_reserve(pba_ctx *ctx, size_t need) {
-    if (need <= ctx->scratch_bytes) return PBA_OK;
-    if (ctx->d_scratch) { HIPCHK(hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->d_scratch); }
-    ctx->d_scratch = nullptr; ctx->scratch_bytes = 0;
-    HIPCHK(hipMalloc(&ctx->d_scratch, need));
-    ctx->scratch_bytes = need;
-    return PBA_OK;
-}
 
 // 2-bit codes (reference byte layout, dna_seq.h:147-159) and the two bit planes (dev_common.h: SeqSetDev::plane) of `len`
 // text bytes; false at the first byte outside "ACGT" (the raw-byte row sweep takes the pair then: the reference compares bytes)
@@ -333,31 +386,13 @@ static inline TextStage text_stage_layout(const TextClip &c) {
 // where the results of a staged pair land (POOL_TXT_OUT): the result, nedit, then the ops
 static const size_t kTxtOutOps = 64;
 
-static void launch_trace_pairs(pba_ctx *ctx, int nb, bool ck, uint32_t grid, size_t lds, const SeqSetDev &A, const SeqSetDev &B,
-                               const pba_pair *pairs, const uint32_t *ids, uint32_t cnt, const AlignCfg &cfg, pba_result *out,
-                               uint32_t *scr, uint64_t wave_words, uint64_t cap_words, uint8_t *ops, const uint64_t *ooff, int32_t *ne) {
-#define K_TP(NBV, CKV)                                                                                                \
-    hipLaunchKernelGGL((k_trace_pairs<NBV, CKV>), dim3(grid), dim3(PBA_WAVE * 4), lds * 4, ctx->stream, A, B, pairs, ids, cnt, \
-                       cfg, out, scr, wave_words, cap_words, ops, ooff, ne, ctx->d_queue)
-#define K_TPN(NBV) if (ck) { K_TP(NBV, true); } else { K_TP(NBV, false); }
-    switch (nb) {
-        case 1: K_TPN(1); break;
-        case 2: K_TPN(2); break;
-        case 3: K_TPN(3); break;
-        case 4: K_TPN(4); break;
-        case 6: K_TPN(6); break;
-        default: K_TPN(8); break;
-    }
-#undef K_TPN
-#undef K_TP
-}
-
 // The fast form of the three text entry points: both accessors hold ACGT only, so comparing 2-bit codes is comparing bytes
 // and the pair runs on the bit-vector array like a pair of a batch (narrow window first, the reference band if that cannot
-// certify; with `ops` the checkpoint-and-recompute traced pass, align_bvtrace.h).  One H2D copy, one or two launches on one
-// wavefront, one D2H copy; every buffer is the ctx's.  Returns 1 when the pair is not ACGT-only (nothing was launched).
+// certify; with `ops` the traced pass, align_bvtrace.h, in its checkpoint form if ck).  One H2D copy, one or two launches on
+// one wavefront, one D2H copy; every buffer is the ctx's.  Returns 1 when the pair is not ACGT-only (nothing was launched).
 static int text_pair_bitvec(pba_ctx *ctx, const char *a, int a_fwd, const char *b, int b_fwd, const TextClip &c, double R,
-                            int maxn, int maxm, pba_result *out, uint8_t *ops, int32_t ops_cap, int32_t *nedit, bool want_trace) {
+                            int maxn, int maxm, pba_result *out, uint8_t *ops, int32_t ops_cap, int32_t *nedit, bool want_trace,
+                            bool ck) {
     if (!bitvec_supports(c.md)) return 1;
     const TextStage t = text_stage_layout(c);
     const uint64_t ops_room = (uint64_t)c.len_a + c.len_b + 64;
@@ -388,39 +423,38 @@ static int text_pair_bitvec(pba_ctx *ctx, const char *a, int a_fwd, const char *
     HIPCHK(hipMemcpyAsync(d_in, h, t.bytes, hipMemcpyHostToDevice, ctx->stream));
     const SeqSetDev S{d_in + t.o_packed, (const uint64_t *)(d_in + t.o_off), (const uint32_t *)(d_in + t.o_len),
                       (const uint32_t *)(d_in + t.o_plane), (const uint64_t *)(d_in + t.o_poff)};
-    const char *e_stream = getenv("PBA_TRACE_STREAM");
-    const bool ck = !(e_stream && atoi(e_stream) != 0);
-    ctx->prof.nb_first = (uint32_t)pl.nb1; ctx->prof.n_first = 1; ctx->prof.nb_redo = 0; ctx->prof.n_redo = 0; ctx->prof.align_redo_ms = 0.f;
-    for (int pass = 0; pass < 2; ++pass) {
-        const int nb = pass ? pl.nb2 : pl.nb1;
-        pl.cfg.full_band = pass;
-        HIPCHK(hipMemsetAsync(ctx->d_queue, 0, sizeof(uint32_t), ctx->stream));
-        (void)hipEventRecord(ctx->ev[pass ? 4 : 2], ctx->stream);
-        if (want_trace) {
-            uint64_t cap_words = std::max<uint64_t>(128, trace_words_of(c.len_a, c.len_b, R, nb, pass != 0, ck));
-            cap_words = (cap_words + 63) & ~63ull;
-            const uint64_t wave_words = cap_words + ((ops_room + 255) & ~255ull) / 4;
-            st = scratch_reserve(ctx, (size_t)wave_words * 4 * 4);       // whichever of the workgroup's four wavefronts takes the pair
-            if (st != PBA_OK) return st;
-            launch_trace_pairs(ctx, nb, ck, 1, pl.lds, S, S, (const pba_pair *)(d_in + t.o_pair), nullptr, 1, pl.cfg,
-                               (pba_result *)d_res, (uint32_t *)ctx->d_scratch, wave_words, cap_words, d_res + kTxtOutOps,
-                               (const uint64_t *)(d_in + t.o_ooff), (int32_t *)(d_res + 32));
-        } else {
-#define K_ONE(NBV)                                                                                                   \
-    hipLaunchKernelGGL(k_align_pairs<NBV>, dim3(1), dim3(PBA_WAVE * Wpb<NBV>::v), pl.lds * Wpb<NBV>::v, ctx->stream, S, S, \
-                       (const pba_pair *)(d_in + t.o_pair), (const uint32_t *)nullptr, 1u, pl.cfg, (pba_result *)d_res, ctx->d_queue)
-            PBA_DISPATCH_NB(nb, K_ONE);
-#undef K_ONE
-        }
-        (void)hipEventRecord(ctx->ev[pass ? 5 : 3], ctx->stream);
-        HIPCHK(hipGetLastError());
+    TracedLaunch tl{};
+    tl.A = tl.B = S; tl.pairs = (const pba_pair *)(d_in + t.o_pair); tl.out = (pba_result *)d_res; tl.lds = pl.lds; tl.ck = ck;
+    tl.ops = d_res + kTxtOutOps; tl.ops_off = (const uint64_t *)(d_in + t.o_ooff); tl.nedit = (int32_t *)(d_res + 32);
+    TracePass tp{};
+    auto before = [&](int pass, const std::vector<uint32_t> &) {     // whichever of the workgroup's four wavefronts takes the pair
+        return want_trace ? trace_pass_size(ctx, &pr, nullptr, 1, R, pass ? pl.nb2 : pl.nb1, pass != 0, ck, ops_room - 64, pl.lds,
+                                            ~0ull, &tp) : (int)PBA_OK;
+    };
+    auto launch = [&](int nb, const uint32_t *ids, uint32_t cnt) {
+        if (want_trace) launch_traced(ctx, tl, nb, pl.cfg, ids, cnt, tp);
+        else launch_align_pairs(ctx, pl, nb, S, S, tl.pairs, ids, cnt, tl.out);
+    };
+    auto fetch = [&]() {
         HIPCHK(hipMemcpyAsync(ctx->h_stage, d_res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
         memcpy(out, ctx->h_stage, sizeof(pba_result));
-        if (pass) { ctx->prof.nb_redo = (uint32_t)nb; ctx->prof.n_redo = 1; }
-        if (out->rc != PBA_RC_UNCERTIFIED) break;
-        if (pass) PBA_FAIL(PBA_E_HIP, "reference-band pass left a pair uncertified");     // cannot happen (align_bitvec.h)
-    }
+        return (int)PBA_OK;
+    };
+    auto collect = [&](std::vector<uint32_t> &redo) {
+        const int rc = fetch();
+        if (rc == PBA_OK && out->rc == PBA_RC_UNCERTIFIED) redo.push_back(0);
+        return rc;
+    };
+    auto finish = [&](bool redone) {
+        if (!redone) return (int)PBA_OK;
+        const int rc = fetch();
+        if (rc == PBA_OK && out->rc == PBA_RC_UNCERTIFIED)
+            PBA_FAIL(PBA_E_HIP, "reference-band pass left a pair uncertified");     // cannot happen (align_bitvec.h)
+        return rc;
+    };
+    st = narrow_then_redo(ctx, pl, nullptr, 1, launch, collect, finish, before);
+    if (st != PBA_OK) return st;
     if (out->rc == -2) PBA_FAIL(PBA_E_TOOLONG, "pair outside what the launch was sized for");   // host sizes both: cannot happen
     if (want_trace) {
         int32_t ne = 0;
@@ -429,14 +463,7 @@ static int text_pair_bitvec(pba_ctx *ctx, const char *a, int a_fwd, const char *
         const int32_t ncopy = std::min(ne, ops_cap);
         if (ncopy > 0) memcpy(ops, (const uint8_t *)ctx->h_stage + kTxtOutOps, (size_t)ncopy);
     }
-    prof_finish(ctx);
     return PBA_OK;
-}
-
-// test hook: PBA_TEXT_ROWSWEEP=1 sends every pair through the general form below (the two forms are cross-checked)
-static inline bool text_force_rowsweep() {
-    const char *e = getenv("PBA_TEXT_ROWSWEEP");
-    return e && atoi(e) != 0;
 }
 
 // The general form: raw bytes (any alphabet, case-sensitive, seq_aligner.h:136) through the reference-shaped row sweep on one
@@ -456,29 +483,39 @@ static int text_pair_stage_bytes(pba_ctx *ctx, const char *a, int a_fwd, const c
     return PBA_OK;
 }
 
-int pba_align_text(pba_ctx *ctx, const char *a, int a_fwd, int la, const char *b, int b_fwd, int lb, double R,
-                   int maxn, int maxm, pba_result *out) {
+// What the three text entry points do before they launch: arguments and R, the clip, the size guard, the device, then the
+// fast form unless PBA_TEXT_ROWSWEEP forces the general one, else the row sweep's plan and the staged bytes (t->pl, da, db).
+// guarded(g) sees text_guard's answer first (g = 1: the guard hit) and fast() is the entry point's call of text_pair_bitvec.
+// Returns 0: staged for the row sweep; 1: *out is final; < 0: failed.
+struct TextCall { TextClip c; TraceHooks hooks; Plan pl; const uint8_t *da, *db; };
+template <class Guarded, class Fast>
+static int text_prologue(pba_ctx *ctx, const char *who, const char *a, int a_fwd, int la, const char *b, int b_fwd, int lb, double R,
+                         int maxn, int maxm, pba_result *out, TextCall *t, Guarded guarded, Fast fast) {
     if (!ctx || !out || la < 0 || lb < 0 || (!a && la) || (!b && lb)) return PBA_E_INVALID;
     if (!(R > 0.0) || !(R < 1.0)) PBA_FAIL(PBA_E_INVALID, "R must be in (0,1)");
-    const TextClip c = text_clip(la, lb, R);
-    int st = text_guard(ctx, c, maxn, maxm, out, "pba_align_text");
-    if (st) return st < 0 ? st : PBA_OK;
+    t->c = text_clip(la, lb, R);
+    int st = guarded(text_guard(ctx, t->c, maxn, maxm, out, who));
+    if (st) return st;
     HIPCHK(hipSetDevice(ctx->device));
     tu_attrs(ctx);
-    if (!text_force_rowsweep()) {
-        st = text_pair_bitvec(ctx, a, a_fwd, b, b_fwd, c, R, maxn, maxm, out, nullptr, 0, nullptr, false);
-        if (st != 1) return st;
-    }
-    Plan pl;
-    st = make_plan(ctx, R, maxn, maxm, PBA_KERNEL_ROWSWEEP, c.md, &pl);
+    t->hooks = trace_hooks_from_env();
+    if (!t->hooks.text_rowsweep && (st = fast()) != 1) return st == PBA_OK ? 1 : st;
+    st = make_plan(ctx, R, maxn, maxm, PBA_KERNEL_ROWSWEEP, t->c.md, &t->pl);
     if (st != PBA_OK) return st;
-    const uint8_t *da = nullptr, *db = nullptr;
-    st = text_pair_stage_bytes(ctx, a, a_fwd, b, b_fwd, c, &da, &db);
-    if (st != PBA_OK) return st;
+    return text_pair_stage_bytes(ctx, a, a_fwd, b, b_fwd, t->c, &t->da, &t->db);
+}
+
+int pba_align_text(pba_ctx *ctx, const char *a, int a_fwd, int la, const char *b, int b_fwd, int lb, double R,
+                   int maxn, int maxm, pba_result *out) {
+    TextCall t;
+    const int st = text_prologue(ctx, "pba_align_text", a, a_fwd, la, b, b_fwd, lb, R, maxn, maxm, out, &t, [](int g) { return g; }, [&] {
+        return text_pair_bitvec(ctx, a, a_fwd, b, b_fwd, t.c, R, maxn, maxm, out, nullptr, 0, nullptr, false, !t.hooks.stream);
+    });
+    if (st) return st < 0 ? st : PBA_OK;
     uint8_t *d_res = nullptr;
     POOL(POOL_TXT_OUT, kTxtOutOps, d_res);
-    hipLaunchKernelGGL(k_align_bytes, dim3(1), dim3(PBA_WAVE), pl.lds, ctx->stream, da, a_fwd ? 1 : -1, c.len_a, db,
-                       b_fwd ? 1 : -1, c.len_b, pl.cfg, (pba_result *)d_res);
+    hipLaunchKernelGGL(k_align_bytes, dim3(1), dim3(PBA_WAVE), t.pl.lds, ctx->stream, t.da, a_fwd ? 1 : -1, t.c.len_a, t.db,
+                       b_fwd ? 1 : -1, t.c.len_b, t.pl.cfg, (pba_result *)d_res);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, d_res, sizeof(pba_result), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -486,35 +523,18 @@ int pba_align_text(pba_ctx *ctx, const char *a, int a_fwd, int la, const char *b
 }
 
 // ---- traceback
-static uint64_t par_bytes_of(int la, int lb, double R) {           // (len_a + 1) * (2*max_dst + 1), seq_aligner.h:94-102
-    const int md = max_dst_of(la, lb, R);
-    const int len_a = lb >= la ? la : std::min(la, lb + md);
-    return ((uint64_t)len_a + 1) * (2ull * md + 1);
-}
-
 int pba_align_text_trace(pba_ctx *ctx, const char *a, int a_fwd, int la, const char *b, int b_fwd, int lb, double R,
                          int maxn, int maxm, pba_result *out, uint8_t *ops, int32_t ops_cap, int32_t *nedit) {
-    if (!ctx || !out || !nedit || la < 0 || lb < 0 || (!a && la) || (!b && lb) || (!ops && ops_cap) || ops_cap < 0)
-        return PBA_E_INVALID;
-    if (!(R > 0.0) || !(R < 1.0)) PBA_FAIL(PBA_E_INVALID, "R must be in (0,1)");
-    const TextClip c = text_clip(la, lb, R);
-    *nedit = 0;
-    int st = text_guard(ctx, c, maxn, maxm, out, "pba_align_text_trace");
+    if (!nedit || (!ops && ops_cap) || ops_cap < 0) return PBA_E_INVALID;
+    TextCall t;
+    const int st = text_prologue(ctx, "pba_align_text_trace", a, a_fwd, la, b, b_fwd, lb, R, maxn, maxm, out, &t,
+                                 [&](int g) { *nedit = 0; return g; }, [&] {
+        return text_pair_bitvec(ctx, a, a_fwd, b, b_fwd, t.c, R, maxn, maxm, out, ops, ops_cap, nedit, true, !t.hooks.stream);
+    });
     if (st) return st < 0 ? st : PBA_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    tu_attrs(ctx);
-    if (!text_force_rowsweep()) {
-        st = text_pair_bitvec(ctx, a, a_fwd, b, b_fwd, c, R, maxn, maxm, out, ops, ops_cap, nedit, true);
-        if (st != 1) return st;
-    }
-    Plan pl;
-    st = make_plan(ctx, R, maxn, maxm, PBA_KERNEL_ROWSWEEP, c.md, &pl);
-    if (st != PBA_OK) return st;
-    const uint64_t pb = ((uint64_t)c.len_a + 1) * (2ull * c.md + 1);
+    const TextClip &c = t.c;
+    const uint64_t pb = band_matrix_cells(c);
     if (pb > kTraceBudget) PBA_FAIL(PBA_E_NOMEM, "parent codes exceed the traceback budget");
-    const uint8_t *da = nullptr, *db = nullptr;
-    st = text_pair_stage_bytes(ctx, a, a_fwd, b, b_fwd, c, &da, &db);
-    if (st != PBA_OK) return st;
     // result, nedit and the offsets the walk reads (ops_off[0..1], par_off[0]), then the ops
     const size_t o_off = 64, o_ops = 128;
     uint8_t *d_res = nullptr, *d_par = nullptr;
@@ -522,8 +542,8 @@ int pba_align_text_trace(pba_ctx *ctx, const char *a, int a_fwd, int la, const c
     POOL(POOL_TXT_PAR, pb + 16, d_par);
     const uint64_t offs[4] = {0, (uint64_t)ops_cap, 0, 0};
     HIPCHK(hipMemcpyAsync(d_res + o_off, offs, sizeof offs, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_align_bytes_trace, dim3(1), dim3(PBA_WAVE), pl.lds, ctx->stream, da, a_fwd ? 1 : -1, c.len_a, db,
-                       b_fwd ? 1 : -1, c.len_b, pl.cfg, (pba_result *)d_res, d_par, (uint16_t *)nullptr);
+    hipLaunchKernelGGL(k_align_bytes_trace, dim3(1), dim3(PBA_WAVE), t.pl.lds, ctx->stream, t.da, a_fwd ? 1 : -1, c.len_a, t.db,
+                       b_fwd ? 1 : -1, c.len_b, t.pl.cfg, (pba_result *)d_res, d_par, (uint16_t *)nullptr);
     hipLaunchKernelGGL(k_trace_walk, dim3(1), dim3(64), 0, ctx->stream, (const pba_result *)d_res, (const uint8_t *)d_par,
                        (const uint64_t *)(d_res + o_off) + 2, d_res + o_ops, (const uint64_t *)(d_res + o_off),
                        (int32_t *)(d_res + 32), 1u);
@@ -546,36 +566,29 @@ int pba_align_text_trace(pba_ctx *ctx, const char *a, int a_fwd, int la, const c
 // the others hold cost 0xFFFF, parent 0 (the reference leaves whatever an earlier call wrote there).
 int pba_align_text_matrix(pba_ctx *ctx, const char *a, int a_fwd, int la, const char *b, int b_fwd, int lb, double R, int maxn,
                           int maxm, pba_result *out, uint16_t *cost, uint8_t *parent, uint64_t cap_cells, int32_t *rows_swept) {
-    if (!ctx || !out || la < 0 || lb < 0 || (!a && la) || (!b && lb) || ((!cost || !parent) && cap_cells)) return PBA_E_INVALID;
-    if (!(R > 0.0) || !(R < 1.0)) PBA_FAIL(PBA_E_INVALID, "R must be in (0,1)");
-    const TextClip c = text_clip(la, lb, R);
+    if ((!cost || !parent) && cap_cells) return PBA_E_INVALID;
+    TextCall t;
+    uint64_t pb = 0;                                                    // cells: (len_a + 1) * (2*max_dst + 1)
+    const int st = text_prologue(ctx, "pba_align_text_matrix", a, a_fwd, la, b, b_fwd, lb, R, maxn, maxm, out, &t, [&](int g) {
+        pb = band_matrix_cells(t.c);
+        if (rows_swept) *rows_swept = 0;
+        if (g < 0) return g;
+        if (pb * 3 > kTraceBudget) PBA_FAIL(PBA_E_NOMEM, "the matrix exceeds the traceback budget");
+        if (cap_cells < pb) PBA_FAIL(PBA_E_INVALID, "pba_align_text_matrix: cost / parent hold fewer than (len_a + 1) * (2*max_dst + 1) cells");
+        if (g == 1) { memset(cost, 0xFF, (size_t)pb * 2); memset(parent, 0, (size_t)pb); }   // the size guard: nothing is written (seq_aligner.h:104-107)
+        return g;
+    }, [] { return 1; });                                               // (the matrix is the row sweep's: no fast form)
+    if (st) return st < 0 ? st : PBA_OK;
+    const TextClip &c = t.c;
     const int md = c.md;
-    const uint64_t pb = ((uint64_t)c.len_a + 1) * (2ull * md + 1);      // cells: (len_a + 1) * (2*max_dst + 1)
-    if (rows_swept) *rows_swept = 0;
-    int st = text_guard(ctx, c, maxn, maxm, out, "pba_align_text_matrix");
-    if (st < 0) return st;
-    if (pb * 3 > kTraceBudget) PBA_FAIL(PBA_E_NOMEM, "the matrix exceeds the traceback budget");
-    if (cap_cells < pb) PBA_FAIL(PBA_E_INVALID, "pba_align_text_matrix: cost / parent hold fewer than (len_a + 1) * (2*max_dst + 1) cells");
-    if (st == 1) {                                                  // the size guard: nothing is written (seq_aligner.h:104-107)
-        memset(cost, 0xFF, (size_t)pb * 2); memset(parent, 0, (size_t)pb);
-        return PBA_OK;
-    }
-    HIPCHK(hipSetDevice(ctx->device));
-    tu_attrs(ctx);
-    Plan pl;
-    st = make_plan(ctx, R, maxn, maxm, PBA_KERNEL_ROWSWEEP, md, &pl);
-    if (st != PBA_OK) return st;
-    const uint8_t *da = nullptr, *db = nullptr;
-    st = text_pair_stage_bytes(ctx, a, a_fwd, b, b_fwd, c, &da, &db);
-    if (st != PBA_OK) return st;
     uint8_t *d_res = nullptr, *d_par = nullptr, *d_cst = nullptr;
     POOL(POOL_TXT_OUT, kTxtOutOps, d_res);
     POOL(POOL_TXT_PAR, pb + 16, d_par);
     POOL(POOL_TXT_CST, 2 * pb + 16, d_cst);
     HIPCHK(hipMemsetAsync(d_par, 0, pb, ctx->stream));
     HIPCHK(hipMemsetAsync(d_cst, 0xFF, 2 * pb, ctx->stream));
-    hipLaunchKernelGGL(k_align_bytes_trace, dim3(1), dim3(PBA_WAVE), pl.lds, ctx->stream, da, a_fwd ? 1 : -1, c.len_a, db,
-                       b_fwd ? 1 : -1, c.len_b, pl.cfg, (pba_result *)d_res, d_par, (uint16_t *)d_cst);
+    hipLaunchKernelGGL(k_align_bytes_trace, dim3(1), dim3(PBA_WAVE), t.pl.lds, ctx->stream, t.da, a_fwd ? 1 : -1, c.len_a, t.db,
+                       b_fwd ? 1 : -1, c.len_b, t.pl.cfg, (pba_result *)d_res, d_par, (uint16_t *)d_cst);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, d_res, sizeof(pba_result), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(cost, d_cst, 2 * pb, hipMemcpyDeviceToHost, ctx->stream));
@@ -594,6 +607,51 @@ int pba_align_text_matrix(pba_ctx *ctx, const char *a, int a_fwd, int la, const 
     return PBA_OK;
 }
 
+// ---- edit scripts of a batch, or their votes
+// the device side of a call of trace_batch
+struct TraceBufs { DevBuf pairs, out, ops, ooff, ne; uint64_t ops_total; };
+
+// the results of a finished call to the caller's arrays (`out` only where the last copy of it is stale), synchronised
+static int trace_results(pba_ctx *ctx, const TraceBufs &d, size_t n, bool copy_out, pba_result *out, uint8_t *ops, const uint64_t *ops_off,
+                         int32_t *nedit, bool vote) {
+    if (copy_out) HIPCHK(hipMemcpyAsync(out, d.out.p, sizeof(pba_result) * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (!vote) {
+        HIPCHK(hipMemcpyAsync(nedit, d.ne.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+        if (d.ops_total) HIPCHK(hipMemcpyAsync(ops + ops_off[0], d.ops.p, d.ops_total, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return PBA_OK;
+}
+
+// The row-sweep form: one parent byte per band cell, every pair's codes resident at once; one launch and the walk, nothing
+// to redo.
+static int trace_rowsweep(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R, const Plan &pl,
+                          uint64_t budget, const TraceBufs &d, pba_result *out, uint8_t *ops, const uint64_t *ops_off, int32_t *nedit) {
+    (void)hipEventRecord(ctx->ev[2], ctx->stream);
+    std::vector<uint64_t> par_off(n + 1, 0);
+    for (size_t q = 0; q < n; ++q)
+        par_off[q + 1] = par_off[q] + ((band_matrix_cells(text_clip(pairs[q].a_len, pairs[q].b_len, R)) + 15) & ~15ull);
+    if (par_off[n] > budget) PBA_FAIL(PBA_E_NOMEM, "parent codes of this batch exceed the traceback budget: split it");
+    DevBuf d_par, d_poff;
+    HIPCHK(hipMalloc(&d_par.p, par_off[n] + 16));
+    HIPCHK(hipMalloc(&d_poff.p, sizeof(uint64_t) * (n + 1)));
+    HIPCHK(hipMemcpyAsync(d_poff.p, par_off.data(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_align_pairs_trace, dim3((uint32_t)n), dim3(PBA_WAVE), pl.lds, ctx->stream, A->dev(), B->dev(),
+                       d.pairs.as<pba_pair>(), (uint32_t)n, pl.cfg, d.out.as<pba_result>(), d_par.as<uint8_t>(),
+                       d_poff.as<uint64_t>());
+    hipLaunchKernelGGL(k_trace_walk, dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, ctx->stream, d.out.as<pba_result>(),
+                       d_par.as<uint8_t>(), d_poff.as<uint64_t>(), d.ops.as<uint8_t>(), d.ooff.as<uint64_t>(),
+                       d.ne.as<int32_t>(), (uint32_t)n);
+    (void)hipEventRecord(ctx->ev[3], ctx->stream);
+    ctx->prof.nb_first = 0; ctx->prof.n_first = (uint32_t)n; ctx->prof.nb_redo = 0; ctx->prof.n_redo = 0;
+    ctx->prof.align_redo_ms = 0.f;
+    HIPCHK(hipGetLastError());
+    const int st = trace_results(ctx, d, n, true, out, ops, ops_off, nedit, false);
+    if (st != PBA_OK) return st;
+    prof_finish(ctx);
+    return PBA_OK;
+}
+
 // Edit scripts of a batch (vote == nullptr: ops / ops_off / nedit receive them) or their votes (vote != nullptr: the
 // paths go straight into its boxes, gated by overlap_min; ops / ops_off / nedit unused).
 int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R,
@@ -606,155 +664,55 @@ int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pa
     if (A->non_acgt || B->non_acgt) PBA_FAIL(PBA_E_ALPHABET, "a sequence set holds bytes outside ACGT: use pba_align_text_trace");
     HIPCHK(hipSetDevice(ctx->device));
     tu_attrs(ctx);
-    int mdmax = 1;
-    uint64_t ops_max = 0;
-    for (size_t q = 0; q < n; ++q) {
-        const pba_pair &p = pairs[q];
-        if (!pair_ok(A, p.a_seq, p.a_pos, p.a_len, p.flags & PBA_A_BACKWARD) ||
-            !pair_ok(B, p.b_seq, p.b_pos, p.b_len, p.flags & PBA_B_BACKWARD))
-            PBA_FAIL(PBA_E_INVALID, "pair outside its sequence (or longer than the engine limit)");
-        if (!vote && (ops_off[q + 1] < ops_off[q] || ops_off[q + 1] - ops_off[q] < (uint64_t)p.a_len + p.b_len))
-            PBA_FAIL(PBA_E_INVALID, "ops_off must leave a_len + b_len slots per pair");
-        if (R > 0.0 && R < 1.0) mdmax = std::max(mdmax, max_dst_of(p.a_len, p.b_len, R));
-        ops_max = std::max(ops_max, (uint64_t)p.a_len + p.b_len);
-    }
-    Plan pl;
-    int st = make_plan(ctx, R, maxn, maxm, kernel, mdmax, &pl);
+    int mdmax;
+    uint64_t ops_max;
+    int st = check_pairs(ctx, A, B, pairs, n, R, vote ? nullptr : ops_off, &mdmax, &ops_max);
     if (st != PBA_OK) return st;
-    ConsDev vdev = {nullptr, nullptr, nullptr, nullptr};
-    int vbeg = 0, vpre = 0, vpost = 0;
+    Plan pl;
+    st = make_plan(ctx, R, maxn, maxm, kernel, mdmax, &pl);
+    if (st != PBA_OK) return st;
+    TracedLaunch t{};
     if (vote) {
         if (pl.nb1 == 0) PBA_FAIL(PBA_E_TOOLONG, "votes from the walk need the bit-vector kernel (band too wide)");
-        if (seg) vdev = seg->dev;
-        else st = cons_vote_view(vote_cons, &vdev, &vbeg, &vpre, &vpost);
+        if (seg) t.C = seg->dev;
+        else st = cons_vote_view(vote_cons, &t.C, &t.beg, &t.pre, &t.post);
         if (st != PBA_OK) return st;
         ops_max = 0;                                             // no goal-first temporary
     }
-    const uint64_t ops_total = vote ? 0 : ops_off[n] - ops_off[0];
-    DevBuf d_pairs, d_out, d_par, d_poff, d_ops, d_ooff, d_ne;
-    HIPCHK(hipMalloc(&d_pairs.p, sizeof(pba_pair) * n));
-    HIPCHK(hipMalloc(&d_out.p, sizeof(pba_result) * n));
-    HIPCHK(hipMalloc(&d_ops.p, ops_total + 16));
-    HIPCHK(hipMalloc(&d_ooff.p, sizeof(uint64_t) * (n + 1)));
-    HIPCHK(hipMalloc(&d_ne.p, sizeof(int32_t) * n));
+    TraceBufs d;
+    d.ops_total = vote ? 0 : ops_off[n] - ops_off[0];
+    HIPCHK(hipMalloc(&d.pairs.p, sizeof(pba_pair) * n));
+    HIPCHK(hipMalloc(&d.out.p, sizeof(pba_result) * n));
+    HIPCHK(hipMalloc(&d.ops.p, d.ops_total + 16));
+    HIPCHK(hipMalloc(&d.ooff.p, sizeof(uint64_t) * (n + 1)));
+    HIPCHK(hipMalloc(&d.ne.p, sizeof(int32_t) * n));
     std::vector<uint64_t> rel(n + 1, 0);
     if (!vote) for (size_t q = 0; q <= n; ++q) rel[q] = ops_off[q] - ops_off[0];
-    HIPCHK(hipMemcpyAsync(d_pairs.p, pairs, sizeof(pba_pair) * n, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(d_ooff.p, rel.data(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(d.pairs.p, pairs, sizeof(pba_pair) * n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(d.ooff.p, rel.data(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, ctx->stream));
+    const TraceHooks hooks = trace_hooks_from_env();
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
     free_b += ctx->scratch_bytes;                            // the scratch kept from earlier calls is ours to reuse
-    uint64_t budget = std::min<uint64_t>(kTraceBudget, (uint64_t)(free_b / 10) * 8);
-    if (const char *e = getenv("PBA_TRACE_BUDGET_GB"))       // tuning aid: HBM the parent bits / codes of one call may take
-        budget = std::min<uint64_t>((uint64_t)atoll(e) << 30, (uint64_t)(free_b / 10) * 9);
-    (void)hipEventRecord(ctx->ev[2], ctx->stream);
-    if (pl.nb1 == 0) {
-        // row sweep: one parent byte per band cell, every pair's codes resident at once
-        std::vector<uint64_t> par_off(n + 1, 0);
-        for (size_t q = 0; q < n; ++q)
-            par_off[q + 1] = par_off[q] + ((par_bytes_of(pairs[q].a_len, pairs[q].b_len, R) + 15) & ~15ull);
-        if (par_off[n] > budget) PBA_FAIL(PBA_E_NOMEM, "parent codes of this batch exceed the traceback budget: split it");
-        HIPCHK(hipMalloc(&d_par.p, par_off[n] + 16));
-        HIPCHK(hipMalloc(&d_poff.p, sizeof(uint64_t) * (n + 1)));
-        HIPCHK(hipMemcpyAsync(d_poff.p, par_off.data(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_align_pairs_trace, dim3((uint32_t)n), dim3(PBA_WAVE), pl.lds, ctx->stream, A->dev(), B->dev(),
-                           d_pairs.as<pba_pair>(), (uint32_t)n, pl.cfg, d_out.as<pba_result>(), d_par.as<uint8_t>(),
-                           d_poff.as<uint64_t>());
-        hipLaunchKernelGGL(k_trace_walk, dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, ctx->stream, d_out.as<pba_result>(),
-                           d_par.as<uint8_t>(), d_poff.as<uint64_t>(), d_ops.as<uint8_t>(), d_ooff.as<uint64_t>(),
-                           d_ne.as<int32_t>(), (uint32_t)n);
-        (void)hipEventRecord(ctx->ev[3], ctx->stream);
-        ctx->prof.nb_first = 0; ctx->prof.n_first = (uint32_t)n; ctx->prof.nb_redo = 0; ctx->prof.n_redo = 0;
-        ctx->prof.align_redo_ms = 0.f;
-    } else {
-        // bit-vector array: 2 bits per processed cell in a per-wavefront scratch area, walked by the same wavefront.
-        // First launch: every pair, narrow window, scratch sized for it (so more wavefronts fit the budget); second
-        // launch: the pairs that came back uncertified, reference band.
-        ctx->prof.nb_first = (uint32_t)pl.nb1; ctx->prof.n_first = (uint32_t)n;
-        ctx->prof.nb_redo = 0; ctx->prof.n_redo = 0; ctx->prof.align_redo_ms = 0.f;
-        // checkpoints + recomputation (default) or every step's words streamed to HBM (PBA_TRACE_STREAM=1: the round-1 form,
-        // kept for comparison)
-        const char *e_stream = getenv("PBA_TRACE_STREAM");
-        const bool ck = seg || !(e_stream && atoi(e_stream) != 0);      // (a pile-up's votes: the checkpoint form only)
-        std::vector<uint32_t> redo;
-        for (int pass = 0; pass < 2; ++pass) {
-            const int nb = pass ? pl.nb2 : pl.nb1;
-            const uint32_t cnt = pass ? (uint32_t)redo.size() : (uint32_t)n;
-            uint64_t cap_words = 128;
-            for (uint32_t k = 0; k < cnt; ++k) {
-                const pba_pair &p = pairs[pass ? redo[k] : k];
-                cap_words = std::max(cap_words, trace_words_of(p.a_len, p.b_len, R, nb, pass != 0, ck));
-            }
-            cap_words = (cap_words + 63) & ~63ull;
-            const uint64_t wave_words = cap_words + ((ops_max + 64 + 255) & ~255ull) / 4;
-            uint32_t grid = persistent_grid(ctx, cnt, 4, pl.lds);
-            grid = (uint32_t)std::min<uint64_t>(grid, budget / (wave_words * 4 * 4));
-            if (grid == 0) PBA_FAIL(PBA_E_NOMEM, "one wavefront's parent bits exceed the traceback budget");
-            DevBuf d_ids;
-            const size_t need = (size_t)grid * 4 * wave_words * 4;
-            if (need > ctx->scratch_bytes) {
-                if (ctx->d_scratch) { HIPCHK(hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->d_scratch); }
-                ctx->d_scratch = nullptr; ctx->scratch_bytes = 0;
-                HIPCHK(hipMalloc(&ctx->d_scratch, need));
-                ctx->scratch_bytes = need;
-            }
-            uint32_t *const d_scr = (uint32_t *)ctx->d_scratch;
-            const uint32_t *ids = nullptr;
-            if (pass) {
-                HIPCHK(hipMalloc(&d_ids.p, sizeof(uint32_t) * cnt));
-                HIPCHK(hipMemcpyAsync(d_ids.p, redo.data(), sizeof(uint32_t) * cnt, hipMemcpyHostToDevice, ctx->stream));
-                ids = d_ids.as<uint32_t>();
-                pl.cfg.full_band = 1;
-            }
-            HIPCHK(hipMemsetAsync(ctx->d_queue, 0, sizeof(uint32_t), ctx->stream));
-            (void)hipEventRecord(ctx->ev[pass ? 4 : 2], ctx->stream);
-#define K_SEG(NBV)                                                                                                    \
-    hipLaunchKernelGGL((k_vote_pairs<NBV, true, true>), dim3(grid), dim3(PBA_WAVE * 4), pl.lds * 4, ctx->stream, A->dev(), B->dev(), \
-                       d_pairs.as<pba_pair>(), ids, cnt, pl.cfg, overlap_min, d_out.as<pba_result>(),                  \
-                       d_scr, wave_words, cap_words, vdev, 0, 0, 0, ctx->d_queue, seg->box_off, seg->t_lo)
-#define K_TRACE2(NBV, CKV)                                                                                            \
-    if (vote)                                                                                                         \
-        hipLaunchKernelGGL((k_vote_pairs<NBV, CKV>), dim3(grid), dim3(PBA_WAVE * 4), pl.lds * 4, ctx->stream, A->dev(), B->dev(), \
-                           d_pairs.as<pba_pair>(), ids, cnt, pl.cfg, overlap_min, d_out.as<pba_result>(),              \
-                           d_scr, wave_words, cap_words, vdev, vbeg, vpre, vpost, ctx->d_queue,                        \
-                           (const unsigned long long *)nullptr, 0u);                                                  \
-    else                                                                                                              \
-        hipLaunchKernelGGL((k_trace_pairs<NBV, CKV>), dim3(grid), dim3(PBA_WAVE * 4), pl.lds * 4, ctx->stream, A->dev(), B->dev(), \
-                           d_pairs.as<pba_pair>(), ids, cnt, pl.cfg, d_out.as<pba_result>(), d_scr,     \
-                           wave_words, cap_words, d_ops.as<uint8_t>(), d_ooff.as<uint64_t>(), d_ne.as<int32_t>(),      \
-                           ctx->d_queue)
-#define K_TRACE(NBV)                                                                                                  \
-    if (seg) { K_SEG(NBV); } else if (ck) { K_TRACE2(NBV, true); } else { K_TRACE2(NBV, false); }
-            switch (nb) {
-                case 1: K_TRACE(1); break;
-                case 2: K_TRACE(2); break;
-                case 3: K_TRACE(3); break;
-                case 4: K_TRACE(4); break;
-                case 6: K_TRACE(6); break;
-                default: K_TRACE(8); break;
-            }
-#undef K_TRACE
-#undef K_TRACE2
-#undef K_SEG
-            (void)hipEventRecord(ctx->ev[pass ? 5 : 3], ctx->stream);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(out, d_out.p, sizeof(pba_result) * n, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(hipStreamSynchronize(ctx->stream));           // the scratch area is freed at the end of this pass
-            if (pass) { ctx->prof.nb_redo = (uint32_t)nb; ctx->prof.n_redo = cnt; break; }
-            for (size_t q = 0; q < n; ++q)
-                if (out[q].rc == PBA_RC_UNCERTIFIED) redo.push_back((uint32_t)q);
-            if (redo.empty()) break;
-        }
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, d_out.p, sizeof(pba_result) * n, hipMemcpyDeviceToHost, ctx->stream));
-    if (!vote) {
-        HIPCHK(hipMemcpyAsync(nedit, d_ne.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
-        if (ops_total) HIPCHK(hipMemcpyAsync(ops + ops_off[0], d_ops.p, ops_total, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    prof_finish(ctx);
-    return PBA_OK;
+    const uint64_t budget = hooks.budget_set ? std::min<uint64_t>(hooks.budget, (uint64_t)(free_b / 10) * 9)
+                                             : std::min<uint64_t>(kTraceBudget, (uint64_t)(free_b / 10) * 8);
+    if (pl.nb1 == 0) return trace_rowsweep(ctx, A, B, pairs, n, R, pl, budget, d, out, ops, ops_off, nedit);
+    // bit-vector array: 2 bits per processed cell in a per-wavefront scratch area, walked by the same wavefront.
+    // First launch: every pair, narrow window, scratch sized for it (so more wavefronts fit the budget); second
+    // launch: the pairs that came back uncertified, reference band.
+    t.A = A->dev(); t.B = B->dev(); t.pairs = d.pairs.as<pba_pair>(); t.out = d.out.as<pba_result>(); t.lds = pl.lds;
+    t.ck = seg || !hooks.stream;
+    t.ops = d.ops.as<uint8_t>(); t.ops_off = d.ooff.as<uint64_t>(); t.nedit = d.ne.as<int32_t>();
+    t.vote = vote; t.overlap_min = overlap_min; t.seg = seg;
+    TracePass tp{};
+    auto before = [&](int pass, const std::vector<uint32_t> &redo) {
+        return trace_pass_size(ctx, pairs, pass ? redo.data() : nullptr, pass ? (uint32_t)redo.size() : (uint32_t)n, R,
+                               pass ? pl.nb2 : pl.nb1, pass != 0, t.ck, ops_max, pl.lds, budget, &tp);
+    };
+    auto launch = [&](int nb, const uint32_t *ids, uint32_t cnt) { launch_traced(ctx, t, nb, pl.cfg, ids, cnt, tp); };
+    auto collect = [&](std::vector<uint32_t> &redo) { return fetch_results(ctx, d.out.p, out, n, &redo); };
+    auto finish = [&](bool redone) { return trace_results(ctx, d, n, redone, out, ops, ops_off, nedit, vote); };
+    return narrow_then_redo(ctx, pl, nullptr, (uint32_t)n, launch, collect, finish, before);
 }
 
 int pba_align_batch_trace(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R,
@@ -762,5 +720,3 @@ int pba_align_batch_trace(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, co
                           int32_t *nedit) {
     return trace_batch(ctx, A, B, pairs, n, R, maxn, maxm, kernel, out, ops, ops_off, nedit, nullptr, 0);
 }
-
-}  // extern "C"

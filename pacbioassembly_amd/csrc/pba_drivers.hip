@@ -217,7 +217,6 @@ k_spaced_round(IndexDev ix, SeqSetDev Rf, uint32_t rseq_id, int ref_org, SeqSetD
     }
 }
 
-
 // (the attribute belongs to the current device: remembered per ctx, so a second ctx on another GPU sets it there too)
 static void tu_attrs(pba_ctx *ctx) {
     if (ctx->attr_done & 2u) return;
@@ -246,48 +245,33 @@ int pba_locate(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, uint32
     Plan pl;
     int st = make_plan(ctx, R, maxn, maxm, kernel, 1 + (int)(reads->max_len * R), &pl);
     if (st != PBA_OK) return st;
-    BufRef d_rows, d_aux, d_ids;                               // (pooled in the ctx: two hipMalloc / hipFree pairs were 1 ms of a 50 ms step)
+    BufRef d_rows, d_aux;                                      // (pooled in the ctx: two hipMalloc / hipFree pairs were 1 ms of a 50 ms step)
     POOL(POOL_LOC_ROWS, sizeof(pba_loc_row) * ((size_t)n + 1), d_rows.p);
     POOL(POOL_LOC_AUX, sizeof(LocAux) * ((size_t)n + 1), d_aux.p);
     std::vector<LocAux> aux(n + 1);
-#define K_LOC(NBV)                                                                                                   \
-    (void)hipMemsetAsync(ctx->d_queue, 0, 4, ctx->stream);                                                           \
+    auto launch = [&](int nb, const uint32_t *ids, uint32_t cnt) {
+#define PBA_LOC_LAUNCH(NBV)                                                                                          \
     hipLaunchKernelGGL(k_locate<NBV>, dim3(persistent_grid(ctx, cnt, Wpb<NBV>::v, pl.lds)),                           \
                        dim3(PBA_WAVE * Wpb<NBV>::v), pl.lds * Wpb<NBV>::v, ctx->stream, ix->dev(), target->dev(),     \
                        target_seq, reads->dev(), ids, cnt, trials, min_len, pl.cfg, d_rows.as<pba_loc_row>(),        \
                        d_aux.as<LocAux>(), ctx->d_queue)
-    if (n) {
-        const uint32_t cnt = n;
-        const uint32_t *ids = nullptr;
-        (void)hipEventRecord(ctx->ev[2], ctx->stream);
-        PBA_DISPATCH_NB(pl.nb1, K_LOC);
-        (void)hipEventRecord(ctx->ev[3], ctx->stream);
-        ctx->prof.nb_first = (uint32_t)pl.nb1; ctx->prof.n_first = cnt; ctx->prof.nb_redo = 0; ctx->prof.n_redo = 0;
-        ctx->prof.align_redo_ms = 0.f;
-        HIPCHK(hipGetLastError());
+        PBA_DISPATCH_NB(nb, PBA_LOC_LAUNCH);
+#undef PBA_LOC_LAUNCH
+    };
+    auto collect = [&](std::vector<uint32_t> &redo) {         // reads with an uncertified pair: walk them again at the reference band
         HIPCHK(hipMemcpyAsync(aux.data(), d_aux.p, sizeof(LocAux) * n, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        std::vector<uint32_t> redo;
         for (uint32_t r = 0; r < n; ++r)
             if (aux[r].redo) redo.push_back(r);
-        if (!redo.empty()) {      // reads with an uncertified pair: walk them again at the reference band
-            POOL(POOL_LOC_IDS, sizeof(uint32_t) * redo.size(), d_ids.p);
-            HIPCHK(hipMemcpyAsync(d_ids.p, redo.data(), sizeof(uint32_t) * redo.size(), hipMemcpyHostToDevice, ctx->stream));
-            pl.cfg.full_band = 1;
-            const uint32_t cnt = (uint32_t)redo.size();
-            const uint32_t *ids = d_ids.as<uint32_t>();
-            (void)hipEventRecord(ctx->ev[4], ctx->stream);
-            PBA_DISPATCH_NB(pl.nb2, K_LOC);
-            (void)hipEventRecord(ctx->ev[5], ctx->stream);
-            ctx->prof.nb_redo = (uint32_t)pl.nb2; ctx->prof.n_redo = cnt;
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(aux.data(), d_aux.p, sizeof(LocAux) * n, hipMemcpyDeviceToHost, ctx->stream));
-        }
+        return (int)PBA_OK;
+    };
+    auto finish = [&](bool redone) {
+        if (redone) HIPCHK(hipMemcpyAsync(aux.data(), d_aux.p, sizeof(LocAux) * n, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipMemcpyAsync(rows, d_rows.p, sizeof(pba_loc_row) * n, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
-    }
-#undef K_LOC
-    if (n) prof_finish(ctx);
+        return (int)PBA_OK;
+    };
+    if (n && (st = narrow_then_redo(ctx, pl, nullptr, n, launch, collect, finish)) != PBA_OK) return st;
     pba_loc_stats s = {0, 0, 0, 0, 0};
     int nseq = 0;
     for (uint32_t r = 0; r < n; ++r) {
@@ -325,7 +309,7 @@ int spaced_round_subset(pba_ctx *ctx, const pba_index *ix, const pba_seqs *ref, 
     // a = reference window, b = read window: the shorter side bounds max_dst (seq_aligner.h:94-102)
     int st = make_plan(ctx, R, maxn, maxm, kernel, 1 + (int)(reads->max_len * R), &pl);
     if (st != PBA_OK) return st;
-    DevBuf d_rows, d_redo, d_ids, d_sub;
+    DevBuf d_rows, d_redo, d_sub;
     HIPCHK(hipMalloc(&d_rows.p, sizeof(pba_ss_row) * (n + 1)));
     HIPCHK(hipMalloc(&d_redo.p, sizeof(int) * (n + 1)));
     HIPCHK(hipMemsetAsync(d_redo.p, 0, sizeof(int) * (n + 1), ctx->stream));
@@ -333,49 +317,36 @@ int spaced_round_subset(pba_ctx *ctx, const pba_index *ix, const pba_seqs *ref, 
         HIPCHK(hipMalloc(&d_sub.p, sizeof(uint32_t) * n_subset));
         HIPCHK(hipMemcpyAsync(d_sub.p, subset, sizeof(uint32_t) * n_subset, hipMemcpyHostToDevice, ctx->stream));
     }
-#define K_SS(NBV)                                                                                                    \
-    (void)hipMemsetAsync(ctx->d_queue, 0, 4, ctx->stream);                                                           \
+    if (!n_first) return PBA_OK;
+    std::vector<int> h_redo(n);
+    std::vector<pba_ss_row> h_rows(n);
+    auto launch = [&](int nb, const uint32_t *ids, uint32_t cnt) {
+#define PBA_SS_LAUNCH(NBV)                                                                                           \
     hipLaunchKernelGGL(k_spaced_round<NBV>, dim3(persistent_grid(ctx, cnt, Wpb<NBV>::v, pl.lds)),                     \
                        dim3(PBA_WAVE * Wpb<NBV>::v), pl.lds * Wpb<NBV>::v, ctx->stream, ix->dev(), ref->dev(),       \
                        ref_seq, ref_org, reads->dev(), ids, cnt, max_trial, overlap_min, buggy_seed_at, pl.cfg,      \
                        d_rows.as<pba_ss_row>(), d_redo.as<int>(), ctx->d_queue)
-    if (n_first) {
-        std::vector<int> h_redo(n);
-        std::vector<pba_ss_row> h_rows(n);
-        const uint32_t cnt = n_first;
-        const uint32_t *ids = subset ? d_sub.as<uint32_t>() : nullptr;
-        (void)hipEventRecord(ctx->ev[2], ctx->stream);
-        PBA_DISPATCH_NB(pl.nb1, K_SS);
-        (void)hipEventRecord(ctx->ev[3], ctx->stream);
-        ctx->prof.nb_first = (uint32_t)pl.nb1; ctx->prof.n_first = cnt; ctx->prof.nb_redo = 0; ctx->prof.n_redo = 0;
-        ctx->prof.align_redo_ms = 0.f;
-        HIPCHK(hipGetLastError());
+        PBA_DISPATCH_NB(nb, PBA_SS_LAUNCH);
+#undef PBA_SS_LAUNCH
+    };
+    auto collect = [&](std::vector<uint32_t> &redo) {
         HIPCHK(hipMemcpyAsync(h_redo.data(), d_redo.p, sizeof(int) * n, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        std::vector<uint32_t> redo;
         for (uint32_t r = 0; r < n; ++r)
             if (h_redo[r] & 1) redo.push_back(r);
-        if (!redo.empty()) {
-            HIPCHK(hipMalloc(&d_ids.p, sizeof(uint32_t) * redo.size()));
-            HIPCHK(hipMemcpyAsync(d_ids.p, redo.data(), sizeof(uint32_t) * redo.size(), hipMemcpyHostToDevice, ctx->stream));
-            pl.cfg.full_band = 1;
-            const uint32_t cnt = (uint32_t)redo.size();
-            const uint32_t *ids = d_ids.as<uint32_t>();
-            (void)hipEventRecord(ctx->ev[4], ctx->stream);
-            PBA_DISPATCH_NB(pl.nb2, K_SS);
-            (void)hipEventRecord(ctx->ev[5], ctx->stream);
-            ctx->prof.nb_redo = (uint32_t)pl.nb2; ctx->prof.n_redo = cnt;
-            HIPCHK(hipGetLastError());
-        }
+        return (int)PBA_OK;
+    };
+    auto finish = [&](bool redone) {
         HIPCHK(hipMemcpyAsync(h_rows.data(), d_rows.p, sizeof(pba_ss_row) * n, hipMemcpyDeviceToHost, ctx->stream));
-        if (touch && !redo.empty()) HIPCHK(hipMemcpyAsync(h_redo.data(), d_redo.p, sizeof(int) * n, hipMemcpyDeviceToHost, ctx->stream));
+        if (touch && redone) HIPCHK(hipMemcpyAsync(h_redo.data(), d_redo.p, sizeof(int) * n, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (touch) for (uint32_t r = 0; r < n; ++r) touch[r] = (uint8_t)((h_redo[r] >> 1) & 3);
-        if (!subset) memcpy(rows, h_rows.data(), sizeof(pba_ss_row) * n);
-        else for (uint32_t k = 0; k < n_subset; ++k) rows[subset[k]] = h_rows[subset[k]];
-        prof_finish(ctx);
-    }
-#undef K_SS
+        return (int)PBA_OK;
+    };
+    st = narrow_then_redo(ctx, pl, subset ? d_sub.as<uint32_t>() : nullptr, n_first, launch, collect, finish);
+    if (st != PBA_OK) return st;
+    if (touch) for (uint32_t r = 0; r < n; ++r) touch[r] = (uint8_t)((h_redo[r] >> 1) & 3);
+    if (!subset) memcpy(rows, h_rows.data(), sizeof(pba_ss_row) * n);
+    else for (uint32_t k = 0; k < n_subset; ++k) rows[subset[k]] = h_rows[subset[k]];
     return PBA_OK;
 }
 

@@ -2,6 +2,9 @@
 // sequence sets, seed index; pba_align.hip: explicit pairs and edit scripts; pba_drivers.hip: the reference's ordered
 // first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction).  Internal: nothing here is part of
 // the C ABI (include/pba.h).
+// Also here, once for all of them: the clip of seq_aligner.h:94-102 (text_clip), the launch plan (make_plan), and the host
+// protocol of every aligning entry point but the all-vs-all walk -- narrow window first, the uncertified items again at the
+// reference band (narrow_then_redo).
 #ifndef PBA_HOST_H
 #define PBA_HOST_H
 
@@ -110,7 +113,7 @@ static const size_t kSlack = 1024;              // readable bytes before the fir
 
 // pool slots
 enum { POOL_OVL_CAND = 0, POOL_OVL_TMP, POOL_OVL_ITEMS, POOL_OVL_REDO, POOL_OVL_REDO_IN, POOL_OVL_OUT, POOL_OVL_SMALL,
-       POOL_LOC_ROWS, POOL_LOC_AUX, POOL_LOC_IDS, POOL_IX_OFFS, POOL_IX_WORK, POOL_OVL_BLOOM, POOL_OVL_ENDS,
+       POOL_LOC_ROWS, POOL_LOC_AUX, POOL_REDO_IDS, POOL_IX_OFFS, POOL_IX_WORK, POOL_OVL_BLOOM, POOL_OVL_ENDS,
        POOL_TXT_IN, POOL_TXT_OUT, POOL_TXT_PAR, POOL_TXT_CST };
 // a buffer of at least `bytes` in pool slot `slot` (contents undefined); grows by reallocation with 1/8 headroom
 static inline int pool_reserve(pba_ctx *ctx, int slot, size_t bytes, void **out) {
@@ -185,6 +188,16 @@ static inline int stage_reserve(pba_ctx *ctx, size_t bytes) {
     return PBA_OK;
 }
 
+// the ctx's scratch of the trace / vote kernels, at least `need` bytes (contents undefined)
+static inline int scratch_reserve(pba_ctx *ctx, size_t need) {
+    if (need <= ctx->scratch_bytes) return PBA_OK;
+    if (ctx->d_scratch) { HIPCHK(hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->d_scratch); }
+    ctx->d_scratch = nullptr; ctx->scratch_bytes = 0;
+    HIPCHK(hipMalloc(&ctx->d_scratch, need));
+    ctx->scratch_bytes = need;
+    return PBA_OK;
+}
+
 // RAII for temporaries so early returns do not leak device memory
 struct DevBuf {
     void *p = nullptr;
@@ -196,9 +209,22 @@ struct DevBuf {
 // ---------------------------------------------------------------------------------------------
 // host API: alignment
 // ---------------------------------------------------------------------------------------------
-static inline int max_dst_of(int la, int lb, double R) {      // seq_aligner.h:94-102
-    return 1 + (int)((lb >= la ? la : lb) * R);
+// What align() looks at of its two accessors.  seq_aligner.h:94-102 clips the longer one to the shorter + max_dst BEFORE
+// anything is sized, checked or read -- locator.cpp:80-81 hands it the whole rest of an 800 kb contig, ref_seq.h:282-286 the
+// whole rest of the reference -- so the engine's own limit, the size guard and the H2D copy all see the clipped lengths.
+// Same FP64 product and truncation as aln_params (dev_common.h); given (len_a, len_b) the kernels derive the same block again.
+// The host's one restatement: band and scratch sizes derive from it.  (long long for the text entry points' unchecked lengths;
+// for lengths pair_ok admits the sums equal the int form's.)
+struct TextClip { int len_a, len_b, md; };
+static inline TextClip text_clip(int la, int lb, double R) {
+    TextClip c;
+    if (lb >= la) { c.len_a = la; c.md = 1 + (int)((double)la * R); c.len_b = (int)std::min<long long>(lb, (long long)la + c.md); }
+    else          { c.len_b = lb; c.md = 1 + (int)((double)lb * R); c.len_a = (int)std::min<long long>(la, (long long)lb + c.md); }
+    return c;
 }
+static inline int max_dst_of(int la, int lb, double R) { return text_clip(la, lb, R).md; }
+// cells of the reference's band matrix: (len_a + 1) * (2*max_dst + 1)
+static inline uint64_t band_matrix_cells(const TextClip &c) { return ((uint64_t)c.len_a + 1) * (2ull * c.md + 1); }
 
 // Launch plan for a batch whose widest band is max_dst_max.
 struct Plan {
@@ -242,6 +268,49 @@ static inline uint32_t persistent_grid(const pba_ctx *ctx, uint32_t n_items, int
 static inline void prof_finish(pba_ctx *ctx) {      // all launches of the call have completed (stream synchronised)
     (void)hipEventElapsedTime(&ctx->prof.align_ms, ctx->ev[2], ctx->ev[3]);
     if (ctx->prof.n_redo) (void)hipEventElapsedTime(&ctx->prof.align_redo_ms, ctx->ev[4], ctx->ev[5]);
+}
+
+// The host protocol of the aligning entry points: every item at the narrow window, then the items that came
+// back PBA_RC_UNCERTIFIED again at the reference band (cfg.full_band = 1).  Owns the queue reset, ev[2..5], the profile
+// fields of the two launches, the redo ids (one pooled slot) and prof_finish.  The caller supplies
+//   launch(nb, ids, cnt)   one launch of its kernel over `cnt` items (ids: device, nullable = items 0 .. cnt-1)
+//   collect(redo)          after the narrow launch: copy back what carries the verdicts, synchronise, list the items to redo
+//   finish(redone)         after the last launch: copy back the results (again, where a redo rewrote them) and synchronise
+//   before(pass, redo)     optional, before each launch: what depends on the pass (the trace kernels' scratch and grid)
+struct NoPassHook { int operator()(int, const std::vector<uint32_t> &) const { return PBA_OK; } };
+template <class Launch, class Collect, class Finish, class Before = NoPassHook>
+static inline int narrow_then_redo(pba_ctx *ctx, Plan &pl, const uint32_t *ids, uint32_t cnt, Launch launch, Collect collect,
+                                   Finish finish, Before before = Before()) {
+    std::vector<uint32_t> redo;
+    ctx->prof.nb_first = (uint32_t)pl.nb1; ctx->prof.n_first = cnt; ctx->prof.nb_redo = 0; ctx->prof.n_redo = 0;
+    ctx->prof.align_redo_ms = 0.f;
+    for (int pass = 0; pass < 2; ++pass) {
+        const int nb = pass ? pl.nb2 : pl.nb1;
+        if (pass) {
+            uint32_t *d_ids = nullptr;
+            cnt = (uint32_t)redo.size();
+            POOL(POOL_REDO_IDS, sizeof(uint32_t) * cnt, d_ids);
+            HIPCHK(hipMemcpyAsync(d_ids, redo.data(), sizeof(uint32_t) * cnt, hipMemcpyHostToDevice, ctx->stream));
+            ids = d_ids;
+            pl.cfg.full_band = 1;
+            ctx->prof.nb_redo = (uint32_t)nb; ctx->prof.n_redo = cnt;
+        }
+        int st = before(pass, redo);
+        if (st != PBA_OK) return st;
+        (void)hipEventRecord(ctx->ev[pass ? 4 : 2], ctx->stream);
+        HIPCHK(hipMemsetAsync(ctx->d_queue, 0, sizeof(uint32_t), ctx->stream));
+        launch(nb, ids, cnt);
+        (void)hipEventRecord(ctx->ev[pass ? 5 : 3], ctx->stream);
+        HIPCHK(hipGetLastError());
+        if (pass) break;
+        st = collect(redo);
+        if (st != PBA_OK) return st;
+        if (redo.empty()) break;
+    }
+    const int st = finish(!redo.empty());
+    if (st != PBA_OK) return st;
+    prof_finish(ctx);
+    return PBA_OK;
 }
 
 static inline bool pair_ok(const pba_seqs *S, uint32_t seq, int pos, int len, bool backward) {
