@@ -186,7 +186,8 @@ void pba_index_destroy(pba_index *ix);
 uint64_t pba_index_entries(const pba_index *ix);
 /* what get_seedmap returns (ref_seq.h:310): positions visited, not entries kept */
 uint32_t pba_index_visited(const pba_index *ix);
-/* all entries sorted by key, reference hit order within a key; returns PBA_OK and *n */
+/* all entries sorted by key, reference hit order within a key; returns PBA_OK and *n.  The partitions are merged on the
+ * host, so a dump does not witness the order the device left the entries in; pba_index_find does. */
 int pba_index_dump(pba_ctx *ctx, const pba_index *ix, uint32_t *keys, int32_t *pos, uint64_t cap, uint64_t *n);
 /* hash_table::find (locator.cpp:76, spaced_seed.cpp:265) for a batch of keys: for key q the hits are
  * hit_pos[hit_off[q] .. hit_off[q+1]) in reference list order.  hit_off has n_keys+1 slots. */

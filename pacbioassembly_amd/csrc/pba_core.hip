@@ -800,7 +800,9 @@ int pba_index_dump(pba_ctx *ctx, const pba_index *ix, uint32_t *keys, int32_t *p
         HIPCHK(hipMemcpyAsync(ent.data(), ix->d_ent, sizeof(uint64_t) * ix->n_entries, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     ent.resize(ix->n_entries);
-    std::sort(ent.begin(), ent.end());          // partitions are sorted; this only merges them by key
+    // partitions are sorted; this merges them by key -- on the host, so a dump does not witness the order the device left (a
+    // partition it left unsorted, an entry in the wrong partition, dumps the same): pba_index_find does
+    std::sort(ent.begin(), ent.end());
     for (uint64_t i = 0; i < ent.size() && i < cap; ++i) {
         const uint32_t ord = (uint32_t)ent[i];
         keys[i] = (uint32_t)(ent[i] >> 32);
