@@ -24,6 +24,17 @@ struct ConsDev {
     char *txt;
 };
 
+// Where a batch of walks votes (k_vote_pairs, pba_align.hip), and a pile-up's arena as its own kernels see it.  One
+// reference: boxes C, pair.a_pos counted from box `beg`, live range [pre, post).  box_off non-null: C is a pile-up's arena
+// (pba_pileup.hip; txt unused), one segment per pair's own a_seq -- target t owns boxes [box_off[t - t_lo], + len(t)) and
+// beg / pre / post are unused.
+struct VoteInto {
+    ConsDev C;
+    int beg, pre, post;
+    const unsigned long long *box_off;
+    uint32_t t_lo;
+};
+
 __device__ __forceinline__ int cons_c2i(int ch) { return ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : 3; }   // dna_seq.h:21
 __device__ __forceinline__ int cons_max4(unsigned long long v) {          // base_vote::max_vote, ref_seq.h:88-91
     const int a = (int)(v & 0xFFFF), b = (int)((v >> 16) & 0xFFFF), c = (int)((v >> 32) & 0xFFFF), d = (int)(v >> 48);
@@ -33,18 +44,28 @@ __device__ __forceinline__ char cons_winner(unsigned long long v) {        // ba
     const int mv = cons_max4(v);
     return mv == (int)(v & 0xFFFF) ? 'A' : (mv == (int)((v >> 16) & 0xFFFF) ? 'C' : (mv == (int)((v >> 32) & 0xFFFF) ? 'G' : 'T'));
 }
+// the sel word of vote_box(base, weight) (ref_seq.h:118: selection(c, n)); sup = 0 and total = 1 go with it
+__device__ __forceinline__ unsigned long long cons_vote_box(int code, int weight) {
+    return (unsigned long long)(unsigned)(weight & 0xFFFF) << (16 * code);
+}
+// what a box yields in evolve: bit 0 = its selection is kept, bit 1 = its suppliment splits off
+__device__ __forceinline__ int cons_yield(unsigned long long sel, unsigned long long sup, int tot) {
+    const bool S = (double)cons_max4(sup) > 0.5 * (double)tot;    // has_supply(0.5), ref_seq.h:327
+    const bool V = (double)cons_max4(sel) > 0.5 * (double)tot;    // is_valid(0.5),   ref_seq.h:336
+    return (V ? 1 : 0) | (S ? 2 : 0);
+}
 __device__ __forceinline__ void cons_bump(unsigned long long *box, int c, unsigned n) {   // counter c += n
     atomicAdd((unsigned *)box + (c >> 1), n << (16 * (c & 1)));
 }
 
-// boxes [first, first+len) <- vote_box(text[k], weight) (ref_seq.h:118: selection(c, n), total(1)); text copied too
+// boxes [first, first+len) <- vote_box(text[k], weight); text copied too
 static __global__ void __launch_bounds__(256)
 k_cons_fill(ConsDev C, int first, int len, const char *text, int weight) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= len) return;
     const char ch = text[k];
     C.txt[first + k] = ch;
-    C.sel[first + k] = (unsigned long long)(unsigned)(weight & 0xFFFF) << (16 * cons_c2i(ch));
+    C.sel[first + k] = cons_vote_box(cons_c2i(ch), weight);
     C.sup[first + k] = 0ull;
     C.tot[first + k] = 1;
 }
@@ -139,8 +160,8 @@ k_cons_evolve(ConsDev in, ConsDev out, int pre, int post, int beg, int *n_out) {
         unsigned long long sel = 0, sup = 0;
         int tot = 0;
         if (live) { sel = in.sel[i]; sup = in.sup[i]; tot = in.tot[i]; }
-        const bool S = live && (double)cons_max4(sup) > 0.5 * (double)tot;    // has_supply(0.5), ref_seq.h:327
-        const bool V = live && (double)cons_max4(sel) > 0.5 * (double)tot;    // is_valid(0.5),   ref_seq.h:336
+        const int y = cons_yield(sel, sup, tot);                // (0 beyond the list: no count exceeds half of tot = 0)
+        const bool S = (y & 2) != 0, V = (y & 1) != 0;
         const int cnt = (V ? 1 : 0) + (S ? 1 : 0);
         scan[tid] = cnt;
         __syncthreads();

@@ -101,14 +101,13 @@ k_trace_pairs(SeqSetDev A, SeqSetDev B, const pba_pair *pairs, const uint32_t *i
 // The same sweep and walk, but the path goes straight into the vote boxes of an unlocked reference (consensus.h:
 // VoteSink) -- ref_seq::try_align's align + OVERLAP_MIN gate + elect (ref_seq.h:264-267) for a batch, no script in
 // memory.  a is the reference: pair.a_pos is the position the votes start at.
-// SEG: the boxes are a pile-up's arena (pba_pileup.hip), one segment per target read: pair q votes into the window of ITS
-// a_seq -- boxes [box_off[a_seq - t_lo], + len(a_seq)), the box of a_pos at that offset + a_pos (beg / pre / post unused).
+// SEG: V is a pile-up's arena (consensus.h: VoteInto with box_off), one segment per target read: pair q votes into the
+// window of ITS a_seq, the box of a_pos at that segment's offset + a_pos.
 // The arena holds fewer than 2^31 boxes (the host refuses or chunks beyond that), so the window fits VoteSink's ints.
 template <int NB, bool CK, bool SEG = false>
 __global__ void __launch_bounds__(PBA_WAVE * 4, NB <= 4 ? (CK && NB <= 2 ? PBA_TR_OCC12 : 4) : 2)
 k_vote_pairs(SeqSetDev A, SeqSetDev B, const pba_pair *pairs, const uint32_t *ids, uint32_t n, AlignCfg cfg, int overlap_min,
-             pba_result *out, uint32_t *scratch, uint64_t wave_words, uint64_t cap_words, ConsDev C, int beg, int pre, int post,
-             uint32_t *queue, const unsigned long long *box_off, uint32_t t_lo) {
+             pba_result *out, uint32_t *scratch, uint64_t wave_words, uint64_t cap_words, VoteInto V, uint32_t *queue) {
     extern __shared__ __align__(16) uint8_t lds_all[];
     __shared__ uint2 s_tile[4][CK ? PBA_BV_TILE_WORDS(NB) : 1];
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / PBA_WAVE));
@@ -123,13 +122,13 @@ k_vote_pairs(SeqSetDev A, SeqSetDev B, const pba_pair *pairs, const uint32_t *id
         const PackedFetch fa = fetch_of(A, pr.a_seq, pr.a_pos, fwd ? 1 : -1);
         const PackedFetch fb = fetch_of(B, pr.b_seq, pr.b_pos, (pr.flags & PBA_B_BACKWARD) ? -1 : 1);
         AlnOut o;
-        int it0 = beg + pr.a_pos, w_pre = pre, w_post = post;
+        int it0 = V.beg + pr.a_pos, w_pre = V.pre, w_post = V.post;
         if constexpr (SEG) {
-            w_pre = (int)box_off[pr.a_seq - t_lo];
+            w_pre = (int)V.box_off[pr.a_seq - V.t_lo];
             w_post = w_pre + (int)A.len[pr.a_seq];
             it0 = w_pre + pr.a_pos;
         }
-        VoteSink sink{C, it0, w_pre, w_post, fwd, fb, 0, 0, 0, 0u};
+        VoteSink sink{V.C, it0, w_pre, w_post, fwd, fb, 0, 0, 0, 0u};
         if (align_bitvec_trace<NB, CK>(fa, pr.a_len, fb, pr.b_len, cfg.R, cfg.maxn, cfg.maxm, cfg.full_band != 0, (uint16_t *)lds,
                                        cfg.row_cap, mine, cap_words, overlap_min, sink, o, s_tile[wave]))
             sink.finish();
@@ -269,11 +268,8 @@ struct TracedLaunch {
     uint8_t *ops;                         // the sink: scripts (ops / ops_off / nedit) ...
     const uint64_t *ops_off;
     int32_t *nedit;
-    bool vote;                            // ... or votes, gated by overlap_min: into the boxes of one reference (C, beg, pre, post)
+    const VoteInto *vote;                 // ... or, non-null, votes gated by overlap_min (host pointer; passed by value)
     int overlap_min;
-    ConsDev C;
-    int beg, pre, post;
-    const PileView *seg;                  // ... or into the segment of each pair's own target in a pile-up's arena (C = seg->dev)
 };
 // (PBA_DISPATCH_NB without its case 0: these kernels have no row-sweep form)
 #define PBA_DISPATCH_BV_NB(nb, K) \
@@ -288,10 +284,9 @@ static void launch_traced(pba_ctx *ctx, const TracedLaunch &t, int nb, const Ali
                            tp.cap_words, t.ops, t.ops_off, t.nedit, ctx->d_queue); }
 #define PBA_VOTES(NBV) {                                                                                              \
         auto k = k_vote_pairs<NBV, true, true>;                                                                      \
-        if (!t.seg) k = t.ck ? k_vote_pairs<NBV, true, false> : k_vote_pairs<NBV, false, false>;                     \
+        if (!t.vote->box_off) k = t.ck ? k_vote_pairs<NBV, true, false> : k_vote_pairs<NBV, false, false>;           \
         hipLaunchKernelGGL(k, grid, block, t.lds * 4, ctx->stream, t.A, t.B, t.pairs, ids, cnt, cfg, t.overlap_min, t.out, scr, \
-                           tp.wave_words, tp.cap_words, t.C, t.beg, t.pre, t.post, ctx->d_queue,                     \
-                           t.seg ? t.seg->box_off : (const unsigned long long *)nullptr, t.seg ? t.seg->t_lo : 0u); }
+                           tp.wave_words, tp.cap_words, *t.vote, ctx->d_queue); }
     if (!t.vote) { PBA_DISPATCH_BV_NB(nb, PBA_SCRIPTS); } else { PBA_DISPATCH_BV_NB(nb, PBA_VOTES); }
 #undef PBA_VOTES
 #undef PBA_SCRIPTS
@@ -653,11 +648,11 @@ static int trace_rowsweep(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, co
 }
 
 // Edit scripts of a batch (vote == nullptr: ops / ops_off / nedit receive them) or their votes (vote != nullptr: the
-// paths go straight into its boxes, gated by overlap_min; ops / ops_off / nedit unused).
+// paths go straight into the boxes it names, gated by overlap_min; ops / ops_off / nedit unused).
 int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R,
                        int maxn, int maxm, int kernel, pba_result *out, uint8_t *ops, const uint64_t *ops_off,
-                       int32_t *nedit, const pba_cons *vote_cons, int overlap_min, const PileView *seg) {
-    const bool vote = vote_cons || seg;
+                       int32_t *nedit, const VoteInto *vote, int overlap_min) {
+    const bool seg = vote && vote->box_off;
     if (!ctx || !A || !B || (!pairs && n) || (!out && n) || (!vote && ((!ops_off && n) || (!nedit && n)))) return PBA_E_INVALID;
     if (n == 0) return PBA_OK;
     if (n > 0x7FFFFFFFull) PBA_FAIL(PBA_E_INVALID, "too many pairs in one batch");
@@ -674,9 +669,6 @@ int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pa
     TracedLaunch t{};
     if (vote) {
         if (pl.nb1 == 0) PBA_FAIL(PBA_E_TOOLONG, "votes from the walk need the bit-vector kernel (band too wide)");
-        if (seg) t.C = seg->dev;
-        else st = cons_vote_view(vote_cons, &t.C, &t.beg, &t.pre, &t.post);
-        if (st != PBA_OK) return st;
         ops_max = 0;                                             // no goal-first temporary
     }
     TraceBufs d;
@@ -703,7 +695,7 @@ int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pa
     t.A = A->dev(); t.B = B->dev(); t.pairs = d.pairs.as<pba_pair>(); t.out = d.out.as<pba_result>(); t.lds = pl.lds;
     t.ck = seg || !hooks.stream;
     t.ops = d.ops.as<uint8_t>(); t.ops_off = d.ooff.as<uint64_t>(); t.nedit = d.ne.as<int32_t>();
-    t.vote = vote; t.overlap_min = overlap_min; t.seg = seg;
+    t.vote = vote; t.overlap_min = overlap_min;
     TracePass tp{};
     auto before = [&](int pass, const std::vector<uint32_t> &redo) {
         return trace_pass_size(ctx, pairs, pass ? redo.data() : nullptr, pass ? (uint32_t)redo.size() : (uint32_t)n, R,
@@ -711,12 +703,12 @@ int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pa
     };
     auto launch = [&](int nb, const uint32_t *ids, uint32_t cnt) { launch_traced(ctx, t, nb, pl.cfg, ids, cnt, tp); };
     auto collect = [&](std::vector<uint32_t> &redo) { return fetch_results(ctx, d.out.p, out, n, &redo); };
-    auto finish = [&](bool redone) { return trace_results(ctx, d, n, redone, out, ops, ops_off, nedit, vote); };
+    auto finish = [&](bool redone) { return trace_results(ctx, d, n, redone, out, ops, ops_off, nedit, vote != nullptr); };
     return narrow_then_redo(ctx, pl, nullptr, (uint32_t)n, launch, collect, finish, before);
 }
 
 int pba_align_batch_trace(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R,
                           int maxn, int maxm, int kernel, pba_result *out, uint8_t *ops, const uint64_t *ops_off,
                           int32_t *nedit) {
-    return trace_batch(ctx, A, B, pairs, n, R, maxn, maxm, kernel, out, ops, ops_off, nedit, nullptr, 0);
+    return trace_batch(ctx, A, B, pairs, n, R, maxn, maxm, kernel, out, ops, ops_off, nedit);
 }

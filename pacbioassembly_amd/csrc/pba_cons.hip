@@ -12,18 +12,15 @@ struct pba_cons {
     int device;                           // (not the ctx: the object may outlive it, like pba_seqs / pba_index)
     int max_len, beg, end, pre, post;     // as in ref_seq (ref_seq.h:364-368), indices into the 3*max_len arrays
     int cur;                              // which of the two array sets is live (evolve ping-pongs)
-    ConsDev set[2];
+    VoteBoxes set[2];
     int *d_n;
-    int vote_ext;                         // votes of the running batch address the text of [pre, post) (pba_cons_round), not [beg, end)
+    const ConsDev &live() const { return set[cur].dev; }
+    // a batch of walks votes into the live boxes, pair.a_pos counted from box `origin`
+    VoteInto vote_into(int origin) const { return VoteInto{live(), origin, pre, post, nullptr, 0u}; }
 };
 
 static void cons_free_sets(pba_cons *c) {
-    for (int k = 0; k < 2; ++k) {
-        if (c->set[k].sel) (void)hipFree(c->set[k].sel);
-        if (c->set[k].sup) (void)hipFree(c->set[k].sup);
-        if (c->set[k].tot) (void)hipFree(c->set[k].tot);
-        if (c->set[k].txt) (void)hipFree(c->set[k].txt);
-    }
+    c->set[0].release(); c->set[1].release();
     if (c->d_n) (void)hipFree(c->d_n);
 }
 
@@ -32,8 +29,8 @@ static int cons_fill(pba_ctx *ctx, pba_cons *c, int first, const char *text, int
     DevBuf d_text;
     HIPCHK(hipMalloc(&d_text.p, (size_t)len));
     HIPCHK(hipMemcpyAsync(d_text.p, text, (size_t)len, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_cons_fill, dim3((uint32_t)((len + 255) / 256)), dim3(256), 0, ctx->stream, c->set[c->cur], first,
-                       len, d_text.as<char>(), weight);
+    hipLaunchKernelGGL(k_cons_fill, dim3((uint32_t)((len + 255) / 256)), dim3(256), 0, ctx->stream, c->live(), first, len,
+                       d_text.as<char>(), weight);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return PBA_OK;
@@ -50,10 +47,7 @@ int pba_cons_create(pba_ctx *ctx, const char *text, int len, int weight, int max
     c->device = ctx->device; c->max_len = max_len;
     c->beg = c->pre = max_len; c->end = c->post = max_len + len;
     const size_t cap = (size_t)3 * max_len + 64;
-    bool ok = hipMalloc((void **)&c->d_n, sizeof(int)) == hipSuccess;
-    for (int k = 0; k < 2 && ok; ++k)
-        ok = hipMalloc((void **)&c->set[k].sel, cap * 8) == hipSuccess && hipMalloc((void **)&c->set[k].sup, cap * 8) == hipSuccess &&
-             hipMalloc((void **)&c->set[k].tot, cap * 4) == hipSuccess && hipMalloc((void **)&c->set[k].txt, cap) == hipSuccess;
+    const bool ok = hipMalloc((void **)&c->d_n, sizeof(int)) == hipSuccess && c->set[0].alloc(cap, true) && c->set[1].alloc(cap, true);
     if (!ok) { cons_free_sets(c); delete c; PBA_FAIL(PBA_E_NOMEM, "pba_cons_create"); }
     int st = cons_fill(ctx, c, c->beg, text, len, weight);                    // ref_seq.h:218-225
     if (st != PBA_OK) { cons_free_sets(c); delete c; return st; }
@@ -119,17 +113,11 @@ int pba_cons_elect(pba_ctx *ctx, pba_cons *c, uint32_t n, const int32_t *pos, co
     }
     HIPCHK(hipMemcpyAsync(d_off.p, rel.data(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(d_ne.p, nedit, sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_cons_elect, dim3(n), dim3(PBA_WAVE), 0, ctx->stream, c->set[c->cur], c->beg, c->pre, c->post, n,
+    hipLaunchKernelGGL(k_cons_elect, dim3(n), dim3(PBA_WAVE), 0, ctx->stream, c->live(), c->beg, c->pre, c->post, n,
                        d_pos.as<int>(), d_fwd.as<uint8_t>(), d_ops.as<uint8_t>(), d_vals.as<char>(),
                        d_off.as<unsigned long long>(), d_ne.as<int>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    return PBA_OK;
-}
-
-int cons_vote_view(const pba_cons *c, ConsDev *dev, int *beg, int *pre, int *post) {
-    if (!c) return PBA_E_INVALID;
-    *dev = c->set[c->cur]; *beg = c->vote_ext ? c->pre : c->beg; *pre = c->pre; *post = c->post;
     return PBA_OK;
 }
 
@@ -145,7 +133,8 @@ int pba_cons_vote_pairs(pba_ctx *ctx, pba_cons *c, const pba_seqs *A, uint32_t r
         if (pairs[q].a_seq != ref_seq || ab != bb)               // try_align walks both accessors the same way (ref_seq.h:260-261)
             PBA_FAIL(PBA_E_INVALID, "pba_cons_vote_pairs: a must be the reference, both accessors in one direction");
     }
-    return trace_batch(ctx, A, B, pairs, n, R, maxn, maxm, PBA_KERNEL_BITVEC, out, nullptr, nullptr, nullptr, c, overlap_min);
+    const VoteInto into = c->vote_into(c->beg);                   // A[ref_seq] is the text of [beg, end)
+    return trace_batch(ctx, A, B, pairs, n, R, maxn, maxm, PBA_KERNEL_BITVEC, out, nullptr, nullptr, nullptr, &into, overlap_min);
 }
 
 // the text of boxes [first, first+len) as a one-sequence set (packed on the device from the object's own text array)
@@ -155,7 +144,7 @@ static int cons_text_seqs(pba_ctx *ctx, const pba_cons *c, int first, int len, p
     HIPCHK(hipMalloc(&d_offs.p, sizeof offs));
     HIPCHK(hipMemcpyAsync(d_offs.p, offs, sizeof offs, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    return pba_seqs_from_device_text(ctx, c->set[c->cur].txt + first, d_offs.p, 1, (uint64_t)len, (uint32_t)len, out);
+    return pba_seqs_from_device_text(ctx, c->live().txt + first, d_offs.p, 1, (uint64_t)len, (uint32_t)len, out);
 }
 
 // One round of spaced_seed.cpp:420-446 against an UNLOCKED reference: the reads of `pool`, in order, each stopping at its
@@ -210,30 +199,25 @@ int pba_cons_round(pba_ctx *ctx, pba_cons *c, const pba_seqs *reads, const uint3
             const pba_ss_row &w = rows[r];
             if (!w.found) continue;
             const bool fwd = w.dir == 1;
-            const int slen = (int)reads->h_len[r], s_len = slen - w.j;                  // spaced_seed.cpp:274-275, both directions
-            const int r_off = fwd ? w.ref_pos : w.ref_pos + 15;                         // spaced_seed.cpp:285
-            const int la = fwd ? post_rel - r_off : r_off - pre_rel + 1;                // get_accessor, ref_seq.h:284-285
             pba_pair pr;
             memset(&pr, 0, sizeof pr);
-            pr.a_seq = 0; pr.a_pos = r_off + org; pr.a_len = la;
-            pr.b_seq = r; pr.b_pos = fwd ? w.j : slen - w.j - 1; pr.b_len = s_len;
-            pr.flags = fwd ? 0u : (PBA_A_BACKWARD | PBA_B_BACKWARD);
+            pr.a_seq = 0; pr.b_seq = r;
+            row_accessors(w.dir, w.j, w.ref_pos, pre_rel, post_rel, org, (int)reads->h_len[r], &pr);
             vp.push_back(pr); vread.push_back(r);
             ++S.n_found;
-            if (w.matlen_a == la) {                                                     // ref_seq.h:268
+            if (w.matlen_a == pr.a_len) {                                               // ref_seq.h:268
                 grow.push_back(Growth{r, fwd, w.j, w.matlen_b});
                 if (fwd) dirty_post = true; else dirty_pre = true;
             }
         }
         if (st == PBA_OK && !vp.empty()) {                                              // elect, ref_seq.h:267
             std::vector<pba_result> out(vp.size());
-            c->vote_ext = 1;
+            const VoteInto into = c->vote_into(c->pre);                                 // ext is the text of [pre, post)
             st = trace_batch(ctx, ext, reads, vp.data(), vp.size(), R, maxn, maxm, PBA_KERNEL_BITVEC, out.data(), nullptr, nullptr,
-                             nullptr, c, overlap_min);
-            c->vote_ext = 0;
+                             nullptr, &into, overlap_min);
             for (size_t q = 0; st == PBA_OK && q < vp.size(); ++q) {
                 const pba_ss_row &w = rows[vread[q]];
-                if (out[q].rc < 0 || out[q].cost != w.cost || out[q].matlen_a != w.matlen_a || out[q].matlen_b != w.matlen_b) {
+                if (!walk_agrees(out[q], w.cost, w.matlen_a, w.matlen_b)) {
                     snprintf(ctx->err, sizeof ctx->err, "pba_cons_round: the voting walk of read %u disagrees with its round row", vread[q]);
                     st = PBA_E_HIP;
                 }
@@ -258,8 +242,8 @@ int pba_cons_round(pba_ctx *ctx, pba_cons *c, const pba_seqs *reads, const uint3
     return st;
 }
 
-// spaced_seed's main loop (spaced_seed.cpp:409-452) without -l: rounds of pba_cons_round over the reads not found yet,
-// seeds drawn as in pba_spaced_multi, evolve after every round that does not end the loop.
+// spaced_seed's main loop (spaced_seed.cpp:409-452) without -l: seed_rounds (pba_host.h) over pba_cons_round, evolve after
+// every round that does not end the loop (:450 breaks before :451).
 int pba_cons_assemble(pba_ctx *ctx, pba_cons *c, const pba_seqs *reads, double R, int max_trial, int overlap_min,
                       int buggy_seed_at, int kernel, int maxn, int maxm, const uint32_t *masks, int n_masks,
                       const uint32_t *picks, int n_picks, int max_round, pba_ss_row *rows, int32_t *found_round,
@@ -267,45 +251,24 @@ int pba_cons_assemble(pba_ctx *ctx, pba_cons *c, const pba_seqs *reads, double R
     if (!ctx || !c || !reads || !masks || n_masks < 1 || !picks || n_picks < 1 || max_round < 0 || !rows || !found_round ||
         !n_rounds || log_cap < 0 || ((!log || !ref_len_log) && log_cap))
         return PBA_E_INVALID;
-    const uint32_t n = reads->n;
-    std::vector<uint32_t> pool(n);
-    for (uint32_t r = 0; r < n; ++r) { pool[r] = r; found_round[r] = 0; memset(&rows[r], 0, sizeof rows[r]); rows[r].read = (int32_t)r; rows[r].j = -1; }
-    int nfailure = 0, draws = 0, done = 0;
-    for (int nround = 1; nround <= max_round; ++nround) {
-        const uint32_t mask = nfailure == 0 ? masks[picks[draws++ % n_picks] % (uint32_t)n_masks] : masks[nfailure - 1];   // :412
-        pba_cons_round_stats S;
-        int st = pba_cons_round(ctx, c, reads, pool.data(), (uint32_t)pool.size(), mask, R, max_trial, overlap_min, buggy_seed_at,
-                                kernel, maxn, maxm, rows, &S);
-        if (st != PBA_OK) return st;
-        std::vector<uint32_t> rest;
-        rest.reserve(pool.size());
-        for (uint32_t r : pool) {
-            if (rows[r].found) found_round[r] = nround;                                     // erased from the pool, :443
-            else rest.push_back(r);
-        }
-        if (done < log_cap) { log[done].round = nround; log[done].mask = mask; log[done].n_tried = (int32_t)pool.size(); log[done].n_found = S.n_found; }
-        pool.swap(rest);
-        bool last = false;
-        if (S.n_found != 0) nfailure = 0;                                                   // :448-449
-        else if (++nfailure == n_masks) last = true;                                        // :450: break before evolve
-        if (!last) {
-            int32_t new_len = 0;
-            st = pba_cons_evolve(ctx, c, nullptr, 0, &new_len);                             // :451
-            if (st != PBA_OK) return st;
-            if (done < log_cap) ref_len_log[done] = new_len;
-        } else if (done < log_cap) ref_len_log[done] = c->post - c->pre;
-        ++done;
-        if (last) break;
-    }
-    *n_rounds = done;
-    return PBA_OK;
+    auto round = [&](uint32_t mask, const std::vector<uint32_t> &pool) {
+        return pba_cons_round(ctx, c, reads, pool.data(), (uint32_t)pool.size(), mask, R, max_trial, overlap_min, buggy_seed_at, kernel,
+                              maxn, maxm, rows, nullptr);
+    };
+    auto after = [&](int done, bool last) {
+        int32_t new_len = c->post - c->pre;
+        const int st = last ? PBA_OK : pba_cons_evolve(ctx, c, nullptr, 0, &new_len);       // :451
+        if (st == PBA_OK && done < log_cap) ref_len_log[done] = new_len;
+        return st;
+    };
+    return seed_rounds(reads->n, masks, n_masks, picks, n_picks, max_round, rows, found_round, log, log_cap, n_rounds, round, after);
 }
 
 int pba_cons_evolve(pba_ctx *ctx, pba_cons *c, char *text_out, int cap, int32_t *new_len) {   // ref_seq.h:317-349
     if (!ctx || !c || !new_len || cap < 0 || (!text_out && cap)) return PBA_E_INVALID;
     HIPCHK(hipSetDevice(ctx->device));
     const int nxt = c->cur ^ 1;
-    hipLaunchKernelGGL(k_cons_evolve, dim3(1), dim3(1024), 0, ctx->stream, c->set[c->cur], c->set[nxt], c->pre, c->post,
+    hipLaunchKernelGGL(k_cons_evolve, dim3(1), dim3(1024), 0, ctx->stream, c->live(), c->set[nxt].dev, c->pre, c->post,
                        c->max_len, c->d_n);
     HIPCHK(hipGetLastError());
     int n = 0;
@@ -317,7 +280,7 @@ int pba_cons_evolve(pba_ctx *ctx, pba_cons *c, char *text_out, int cap, int32_t 
     *new_len = n;
     const int ncopy = std::min(n, cap);
     if (ncopy > 0) {
-        HIPCHK(hipMemcpyAsync(text_out, c->set[c->cur].txt + c->beg, (size_t)ncopy, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(text_out, c->live().txt + c->beg, (size_t)ncopy, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
     }
     return PBA_OK;
@@ -327,15 +290,7 @@ int pba_cons_dump(pba_ctx *ctx, const pba_cons *c, uint16_t *sel, uint16_t *sup,
     if (!ctx || !c || !n || cap < 0 || (cap && (!sel || !sup || !tot))) return PBA_E_INVALID;
     HIPCHK(hipSetDevice(ctx->device));
     *n = c->post - c->pre;
-    const int k = std::min(*n, cap);
-    if (k > 0) {
-        const ConsDev &d = c->set[c->cur];
-        HIPCHK(hipMemcpyAsync(sel, d.sel + c->pre, (size_t)k * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(sup, d.sup + c->pre, (size_t)k * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(tot, d.tot + c->pre, (size_t)k * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-    }
-    return PBA_OK;
+    return c->set[c->cur].to_host(ctx, (size_t)c->pre, std::min(*n, cap), sel, sup, tot);
 }
 
 int pba_cons_text(pba_ctx *ctx, const pba_cons *c, char *out, int cap, int32_t *n) {
@@ -344,11 +299,10 @@ int pba_cons_text(pba_ctx *ctx, const pba_cons *c, char *out, int cap, int32_t *
     *n = c->post - c->pre;
     const int k = std::min(*n, cap);
     if (k > 0) {
-        HIPCHK(hipMemcpyAsync(out, c->set[c->cur].txt + c->pre, (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(out, c->live().txt + c->pre, (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
     }
     return PBA_OK;
 }
-
 
 }  // extern "C"

@@ -355,9 +355,8 @@ int pba_spaced_round(pba_ctx *ctx, const pba_index *ix, const pba_seqs *ref, uin
     return spaced_round_subset(ctx, ix, ref, ref_seq, reads, R, max_trial, overlap_min, buggy_seed_at, kernel, nullptr, 0, rows);
 }
 
-// spaced_seed.cpp:409-452 for a locked reference (-l): rounds over the reads not found yet, the seed of a round drawn
-// like the reference draws it (a fresh draw after a round that found something, else the seeds in file order), stop
-// when every seed has failed in a row or after max_round.  picks[] stands in for the values rand() returns.
+// spaced_seed.cpp:409-452 for a locked reference (-l): seed_rounds (pba_host.h) over one index build and one locked round
+// per seed drawn; the loop ends right after the round in which the last seed has failed.
 int pba_spaced_multi(pba_ctx *ctx, const pba_seqs *ref, uint32_t ref_seq, const pba_seqs *reads, double R, int max_trial,
                      int overlap_min, int buggy_seed_at, int kernel, const uint32_t *masks, int n_masks,
                      const uint32_t *picks, int n_picks, int max_round, pba_ss_row *rows, int32_t *found_round,
@@ -365,34 +364,16 @@ int pba_spaced_multi(pba_ctx *ctx, const pba_seqs *ref, uint32_t ref_seq, const 
     if (!ctx || !ref || !reads || !masks || n_masks < 1 || !picks || n_picks < 1 || max_round < 0 || !rows || !found_round ||
         !n_rounds || log_cap < 0 || (!log && log_cap) || ref_seq >= ref->n)
         return PBA_E_INVALID;
-    const uint32_t n = reads->n;
-    std::vector<uint32_t> pool(n);
-    for (uint32_t r = 0; r < n; ++r) { pool[r] = r; found_round[r] = 0; memset(&rows[r], 0, sizeof rows[r]); rows[r].read = (int32_t)r; rows[r].j = -1; }
-    int nfailure = 0, draws = 0, done = 0;
-    for (int nround = 1; nround <= max_round; ++nround) {
-        const uint32_t mask = nfailure == 0 ? masks[picks[draws++ % n_picks] % (uint32_t)n_masks] : masks[nfailure - 1];   // :412
+    auto round = [&](uint32_t mask, const std::vector<uint32_t> &pool) {
         pba_index *ix = nullptr;
         int st = pba_index_build(ctx, ref, ref_seq, mask, PBA_INDEX_HEAD_TAIL, &ix);        // get_seedmap, :415
         if (st != PBA_OK) return st;
         st = spaced_round_subset(ctx, ix, ref, ref_seq, reads, R, max_trial, overlap_min, buggy_seed_at, kernel, pool.data(),
                                  (uint32_t)pool.size(), rows);
         pba_index_destroy(ix);
-        if (st != PBA_OK) return st;
-        int nmatches = 0;
-        std::vector<uint32_t> rest;
-        rest.reserve(pool.size());
-        for (uint32_t r : pool) {
-            if (rows[r].found) { found_round[r] = nround; ++nmatches; }                     // erased from the pool, :443
-            else rest.push_back(r);
-        }
-        if (done < log_cap) { log[done].round = nround; log[done].mask = mask; log[done].n_tried = (int32_t)pool.size(); log[done].n_found = nmatches; }
-        ++done;
-        pool.swap(rest);
-        if (nmatches != 0) nfailure = 0;                                                    // :448-451
-        else if (++nfailure == n_masks) break;
-    }
-    *n_rounds = done;
-    return PBA_OK;
+        return st;
+    };
+    return seed_rounds(reads->n, masks, n_masks, picks, n_picks, max_round, rows, found_round, log, log_cap, n_rounds, round);
 }
 
 }  // extern "C"

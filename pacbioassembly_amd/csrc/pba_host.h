@@ -2,9 +2,10 @@
 // sequence sets, seed index; pba_align.hip: explicit pairs and edit scripts; pba_drivers.hip: the reference's ordered
 // first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction).  Internal: nothing here is part of
 // the C ABI (include/pba.h).
-// Also here, once for all of them: the clip of seq_aligner.h:94-102 (text_clip), the launch plan (make_plan), and the host
+// Also here, once for all of them: the clip of seq_aligner.h:94-102 (text_clip), the launch plan (make_plan), the host
 // protocol of every aligning entry point but the all-vs-all walk -- narrow window first, the uncertified items again at the
-// reference band (narrow_then_redo).
+// reference band (narrow_then_redo) --, the owner of a set of vote boxes (VoteBoxes), a found row's accessors (row_accessors,
+// walk_agrees) and the seed-round loop of spaced_seed.cpp:409-452 (seed_rounds).
 #ifndef PBA_HOST_H
 #define PBA_HOST_H
 
@@ -42,7 +43,7 @@ struct pba_ctx {
     int device;
     hipStream_t own_stream, stream;
     hipDeviceProp_t prop;
-    hipEvent_t ev[6];        // index begin/end, align begin/end, redo begin/end
+    hipEvent_t ev[6];        // index begin/end, narrow launch begin/end, redo launch begin/end (narrow_then_redo, prof_finish)
     hipEvent_t ev_aux;       // "the small D2H copy queued before the last kernel has landed" (index build: sizes before the last scatter)
     uint32_t *d_queue;       // work-queue counters of the persistent aligning kernels (one per launch in flight)
     void *d_scratch;         // parent-bit scratch of the trace / vote kernels, kept between calls (tens of GB: mapping
@@ -104,6 +105,8 @@ static inline int ctx_fail(pba_ctx *ctx, int st, const char *what, hipError_t e)
         if (e__ != hipSuccess) return ctx_fail(ctx, PBA_E_HIP, #call, e__); \
     } while (0)
 #define PBA_FAIL(st, what) return ctx_fail(ctx, (st), (what), hipSuccess)
+// (for a callee that has written ctx->err itself)
+#define PBA_TRY(call) do { const int rc__ = (call); if (rc__ != PBA_OK) return rc__; } while (0)
 
 // engine limits
 static const int kMaxSeqLen = 65000;            // u16 DP costs: D(i,j) <= max(i,j) < 65535
@@ -204,6 +207,34 @@ struct DevBuf {
     ~DevBuf() { if (p) (void)hipFree(p); }
     template <class T> T *as() const { return (T *)p; }
     void reset() { if (p) (void)hipFree(p); p = nullptr; }
+};
+
+// One set of `cap` vote boxes on the device (consensus.h: sel / sup / tot, and a text byte per box where the owner keeps
+// one): two of them ping-pong in a pba_cons, one is a pba_pileup's arena.
+struct VoteBoxes {
+    ConsDev dev{};
+    void release() {
+        for (void *q : {(void *)dev.sel, (void *)dev.sup, (void *)dev.tot, (void *)dev.txt})
+            if (q) (void)hipFree(q);                        // (hipFree waits for the work that uses the buffer)
+        dev = ConsDev{nullptr, nullptr, nullptr, nullptr};
+    }
+    bool alloc(size_t cap, bool txt) {                      // all or nothing; a refused hipMalloc does not linger as the last error
+        if (hipMalloc((void **)&dev.sel, cap * 8) == hipSuccess && hipMalloc((void **)&dev.sup, cap * 8) == hipSuccess &&
+            hipMalloc((void **)&dev.tot, cap * 4) == hipSuccess && (!txt || hipMalloc((void **)&dev.txt, cap) == hipSuccess))
+            return true;
+        (void)hipGetLastError();
+        release();
+        return false;
+    }
+    // boxes [first, first + k) to the host, synchronised
+    int to_host(pba_ctx *ctx, size_t first, int k, uint16_t *sel, uint16_t *sup, int32_t *tot) const {
+        if (k <= 0) return PBA_OK;
+        HIPCHK(hipMemcpyAsync(sel, dev.sel + first, (size_t)k * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(sup, dev.sup + first, (size_t)k * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(tot, dev.tot + first, (size_t)k * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        return PBA_OK;
+    }
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -320,6 +351,61 @@ static inline bool pair_ok(const pba_seqs *S, uint32_t seq, int pos, int len, bo
     return backward ? (pos < L && pos - (len - 1) >= 0) : ((long long)pos + len <= L);
 }
 
+// The accessors a found row hands to align (spaced_seed.cpp:274-276, 285; get_accessor, ref_seq.h:282-286) against the
+// reference window [a_lo, a_hi) of index coordinates, whose text the pair addresses `org` further on; slen: the read's
+// length.  Sets a_pos, a_len, b_pos, b_len and flags of *pr.
+static inline void row_accessors(int dir, int j, int ref_pos, int a_lo, int a_hi, int org, int slen, pba_pair *pr) {
+    const bool fwd = dir == 1;
+    const int r_off = fwd ? ref_pos : ref_pos + 15;                             // spaced_seed.cpp:285
+    pr->a_pos = r_off + org;
+    pr->a_len = fwd ? a_hi - r_off : r_off - a_lo + 1;                          // get_accessor, ref_seq.h:284-285
+    pr->b_pos = fwd ? j : slen - j - 1;                                         // spaced_seed.cpp:274-276, both directions
+    pr->b_len = slen - j;
+    pr->flags = fwd ? 0u : (PBA_A_BACKWARD | PBA_B_BACKWARD);
+}
+// the voting walk of a row re-ran to the row's own cost and matlens
+static inline bool walk_agrees(const pba_result &o, int cost, int matlen_a, int matlen_b) {
+    return o.rc >= 0 && o.cost == cost && o.matlen_a == matlen_a && o.matlen_b == matlen_b;
+}
+
+// spaced_seed's main loop (spaced_seed.cpp:409-452): rounds over the reads not found yet, the seed of a round drawn like
+// the reference draws it (a fresh draw after a round that found something, else the seeds in file order; picks[] stands in
+// for the values rand() returns), stop when every seed has failed in a row or after max_round.  Owns the pool, the rows'
+// reset, found_round, the log and *n_rounds.  The caller supplies
+//   round(mask, pool)    one round over the reads of `pool`, in order, into rows[]
+//   after(done, last)    optional, once the round is logged as entry `done`; last: every seed has now failed in a row
+struct NoAfterRound { int operator()(int, bool) const { return PBA_OK; } };
+template <class Round, class After = NoAfterRound>
+static inline int seed_rounds(uint32_t n_reads, const uint32_t *masks, int n_masks, const uint32_t *picks, int n_picks, int max_round,
+                              pba_ss_row *rows, int32_t *found_round, pba_ss_round_log *log, int log_cap, int *n_rounds, Round round,
+                              After after = After()) {
+    std::vector<uint32_t> pool(n_reads), rest;
+    for (uint32_t r = 0; r < n_reads; ++r) { pool[r] = r; found_round[r] = 0; memset(&rows[r], 0, sizeof rows[r]); rows[r].read = (int32_t)r; rows[r].j = -1; }
+    int nfailure = 0, draws = 0, done = 0;
+    for (int nround = 1; nround <= max_round; ++nround) {
+        const uint32_t mask = nfailure == 0 ? masks[picks[draws++ % n_picks] % (uint32_t)n_masks] : masks[nfailure - 1];   // :412
+        int st = round(mask, pool);
+        if (st != PBA_OK) return st;
+        int nmatches = 0;
+        rest.clear();
+        for (uint32_t r : pool) {
+            if (rows[r].found) { found_round[r] = nround; ++nmatches; }                     // erased from the pool, :443
+            else rest.push_back(r);
+        }
+        if (done < log_cap) { log[done].round = nround; log[done].mask = mask; log[done].n_tried = (int32_t)pool.size(); log[done].n_found = nmatches; }
+        pool.swap(rest);
+        bool last = false;
+        if (nmatches != 0) nfailure = 0;                                                    // :448-451
+        else last = ++nfailure == n_masks;
+        st = after(done, last);
+        if (st != PBA_OK) return st;
+        ++done;
+        if (last) break;
+    }
+    *n_rounds = done;
+    return PBA_OK;
+}
+
 // the five move masks of compress(x, mask) (Hacker's Delight 7-4): gathers the bits of x under `mask` into a number
 static inline void compress_masks(uint32_t mask, uint32_t mv[5]) {
     uint32_t m = mask, mk = ~m << 1;
@@ -363,19 +449,10 @@ static inline void launch_seg_sort(pba_ctx *ctx, const uint64_t *src, uint64_t *
 extern "C" {
 // sort one oversize partition / candidate piece in global memory (pba_core.hip)
 PBA_INTERNAL int sort_partition_global(pba_ctx *ctx, uint64_t *d_part, uint32_t n);
-// edit scripts of a batch, or their votes (pba_align.hip): into the boxes of one reference (vote), or into the segment of
-// each pair's own target in a pile-up's box arena (seg; pba_pileup.hip)
-struct pba_cons;
-struct PileView {
-    ConsDev dev;                          // the arena (txt unused)
-    const unsigned long long *box_off;    // first box of target t at box_off[t - t_lo]
-    uint32_t t_lo;
-};
+// edit scripts of a batch, or (vote non-null) their votes into the boxes it names, gated by overlap_min (pba_align.hip)
 PBA_INTERNAL int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R,
                              int maxn, int maxm, int kernel, pba_result *out, uint8_t *ops, const uint64_t *ops_off,
-                             int32_t *nedit, const pba_cons *vote, int overlap_min, const PileView *seg = nullptr);
-// the vote boxes a batch of walks votes into (pba_cons.hip)
-PBA_INTERNAL int cons_vote_view(const pba_cons *c, ConsDev *dev, int *beg, int *pre, int *post);
+                             int32_t *nedit, const VoteInto *vote = nullptr, int overlap_min = 0);
 // one locked round over a subset of the reads (pba_drivers.hip)
 PBA_INTERNAL int spaced_round_subset(pba_ctx *ctx, const pba_index *ix, const pba_seqs *ref, uint32_t ref_seq, const pba_seqs *reads,
                                      double R, int max_trial, int overlap_min, int buggy_seed_at, int kernel,

@@ -24,7 +24,6 @@ static void tu_attrs(pba_ctx *ctx) {
     PBA_BIG_LDS(k_ovl_walk_rc<0>);
 }
 
-#define PBA_TRY(call) do { const int rc__ = (call); if (rc__ != PBA_OK) return rc__; } while (0)
 // a kernel template over the probe table's form (overlap.h: HASHED)
 #define PBA_PT_LAUNCH(hashed, KERNEL, grid, block, lds, stream, ...)                                  \
     do {                                                                                              \

@@ -99,3 +99,16 @@ def oracle_correct(oracle, texts, t, rows_t, weight, R=0.30):
     sel, sup, tot, _ = c.dump(len(T) + 8)
     c.evolve()
     return sel, sup, tot, c.text(2 * len(T) + 8)
+
+
+def check_dump_cap(dump, full, cap=7):
+    """dump(sel, sup, tot, cap, n_ref) -> status is a box dump of the C ABI bound to its object; full: (sel, sup, tot) of all
+    its boxes.  With room for `cap` boxes it reports the whole count, writes the first `cap` and leaves the next slot alone."""
+    import ctypes as C
+    sel = np.full((cap + 1, 4), 0xABCD, np.uint16); sup = np.full((cap + 1, 4), 0xABCD, np.uint16); tot = np.full(cap + 1, -77, np.int32)
+    n = C.c_int32()
+    assert dump(sel.ctypes.data_as(C.c_void_p), sup.ctypes.data_as(C.c_void_p), tot.ctypes.data_as(C.c_void_p), cap, C.byref(n)) == 0
+    assert n.value == len(full[2]) and n.value > cap
+    for got, want in zip((sel, sup, tot), full):
+        assert (got[:cap] == want[:cap]).all()
+    assert (sel[cap] == 0xABCD).all() and (sup[cap] == 0xABCD).all() and tot[cap] == -77

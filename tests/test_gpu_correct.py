@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import MASK_PAT, ROOT
-from correct_helpers import mixed_reads, oracle_correct, rc
+from correct_helpers import check_dump_cap, mixed_reads, oracle_correct, rc
 from pacbioassembly_amd import Pileup
 from pacbioassembly_amd import engine as eng
 from pacbioassembly_amd.engine import PAIR_DTYPE, PBA_KERNEL_BITVEC, PBA_KERNEL_ROWSWEEP, PbaError
@@ -279,6 +279,10 @@ def test_refusals(ctx, small_set):
     assert status(lambda: ctx.correct_reads(S, mask, R, weight=0)) == -1
     assert status(lambda: Pileup(ctx, S, 5, n + 1)) == -1
     assert status(lambda: pile.dump(30)) == -1 and status(lambda: pile.dump(9)) == -1
+    # a dump into fewer slots than the target has boxes: 40 boxes, room for 7
+    S40 = ctx.seqs_from_list([b"ACGTTGCAAC" * 4], strict_acgt=True)
+    p40 = Pileup(ctx, S40, weight=3)
+    check_dump_cap(lambda *a: ctx.lib.pba_pileup_dump(ctx.h, p40.h, 0, *a), p40.dump(0))
     other = ctx.seqs_from_list(texts[:-1], strict_acgt=True)                     # not the set of this pile-up
     pile_o = Pileup(ctx, other, 10, 30)
     assert status(lambda: pile_o.vote(inside[5:8], R, reads_rc=Src)) == -1

@@ -1031,6 +1031,14 @@ def test_consensus_golden_and_oracle(ctx, oracle):
     for x, y in zip(one.dump()[:3], many.dump()[:3]):
         assert (x == y).all()
     assert one.evolve() == many.evolve()
+    # a dump into fewer slots than there are boxes: 40 boxes with votes in them, room for 7
+    from correct_helpers import check_dump_cap
+    ref40 = b"ACGTTGCAAC" * 4
+    c40 = eng.Consensus(ctx, ref40, 2)
+    res, ops = ctx.align_text_trace(ref40, ref40[:3] + b"T" + ref40[3:30], 0.3, True, True)
+    assert int(res["rc"]) >= 0
+    c40.elect([0], [True], [ops], [eng.script_vals(ops, ref40[:3] + b"T" + ref40[3:30], True)])
+    check_dump_cap(lambda *a: ctx.lib.pba_cons_dump(ctx.h, c40.h, *a), c40.dump()[:3])
 
 
 def test_kernels_agree_on_drifting_paths():
