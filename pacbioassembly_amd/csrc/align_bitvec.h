@@ -270,9 +270,9 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
 
     // rare, divergent: segment finished last step / window opens now / window closed last step / diagonal enters
 #define PBA_BV_RARE(ON_EVENT)                                                         \
-    if (__builtin_amdgcn_ballot_w64(t == t_next)) {      /* wave-uniform: all lanes enabled for the shuffle */ \
+    if (const uint64_t ev_lanes = __builtin_amdgcn_ballot_w64(t == t_next)) {   /* wave-uniform: all lanes enabled for the shuffle */ \
       const int above = __shfl(score, (lane + PBA_WAVE - 1) & (PBA_WAVE - 1), PBA_WAVE); \
-      if (t == t_next) {                                                              \
+      if ((ev_lanes >> lane) & 1) {      /* from the mask: testing t == t_next again costs the step loop a second compare */ \
         if (t == t_seg + 1) segment_done(t, above);                                   \
         if (t == t_evt) {                                                             \
             /* a lane that moves on to its next superblock needs that superblock's slice of the text; a lane that \
@@ -370,7 +370,8 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
             acc[nb] = or_of_and(acc[nb], d0, dmw);
         }
         hp_last = hp; hn_last = hn;
-        dmw += dmw;                              // next row of the block (full-rate add; segment_done re-arms it every 32 rows)
+        asm("v_add_u32 %0, %1, %1" : "=v"(dmw) : "v"(dmw));   // next row of the block: a full-rate add (left to itself the compiler
+                                                               // turns dmw += dmw into the slower shift); segment_done re-arms it every 32 rows
         }
     }
     int t = t1 + 1;
