@@ -139,7 +139,8 @@ __device__ __forceinline__ uint32_t bit_mask(uint32_t x, int k) {
 // 9 full-rate ops + 3 v_addc_co (the carries are the horizontal deltas entering / leaving the block, kept as lane
 // masks in SGPR pairs), and the lane-to-lane hand-off of those deltas is a SCALAR rotate of the two masks -- no
 // DPP, no VALU.  The diagonal's D0 bits are collected with one bitop3 per block and a rotating one-hot; text
-// elements come from two 32-step bit-plane registers.  Everything rare sits behind one compare (t == t_next).
+// elements come from two 32-step bit-plane registers.  Everything rare is scheduled: the events of the sweep fall at
+// steps known in advance, kept as wave-uniform timers, and the step loop runs from one to the next without a test.
 //
 // TRACE: also store, for every step and block, the two words the traceback needs (bv_trace_walk below):
 //   word 0 = Eq | ~D0   bit r set: the cell's parent is the diagonal one (seq_aligner.h:164-166: MATCH wins ties)
@@ -187,37 +188,32 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
 
     uint32_t Pv[NB], Mv[NB], Plo[NB], Phi[NB], acc[NB];
     int s_cur = lane;
-    int t_evt;         // next step at which this lane's window opens or (after that) has just closed
-    // functions of the superblock the lane holds, recomputed where an event needs them (three registers fewer to carry
-    // through the step loop: at 64 registers per lane they were what the event handler spilled to scratch memory):
-    auto t_close1 = [&]() { return s_cur < S ? min(m, s_cur * RB + RB + w) + s_cur + 1 : INT_MAX; };          // first step after the window
-    auto t_hin_end = [&]() { return (s_cur < S && s_cur > 0) ? min(m, s_cur * RB + w) + s_cur : INT_MIN; };   // last step at which the lane above still delivers hout for this lane's column
-    auto t_diag0 = [&]() { return (s_cur < S && s_cur * RB < m) ? s_cur * RB + 1 + s_cur : INT_MAX - RB; };   // step at which this lane's first row is on the diagonal
-    int t_dstart;      // = t_diag0 until the diagonal has entered this lane's rows
-    int t_seg;         // step at which the current 32-row diagonal segment of this lane is complete
     uint32_t opened = 0;   // 0 / 1 in a VGPR (a bool would live in an SGPR pair and be re-merged with exec every step)
-
-    auto open_superblock = [&]() {              // s_cur names the superblock this lane now owns
-        const int base_row = s_cur * RB;
-        opened = 0;
-        if (s_cur < S) {
-            const int lo = max(1, base_row + 1 - wleft), hi = min(m, base_row + RB + w);
-            t_evt = lo + s_cur;
-            (void)hi;
-            if (base_row < m) {                 // the diagonal (rows 1..m) crosses this superblock
-                t_dstart = base_row + 1 + s_cur;
-                t_seg = min(t_dstart + 31, m + s_cur);
-            } else { t_dstart = INT_MAX; t_seg = INT_MAX - 1; }
+    if (s_cur < S) {
 #pragma unroll
-            for (int nb = 0; nb < NB; ++nb) load_planes32(rowsF, base_row + 32 * nb, Plo[nb], Phi[nb]);
-        } else {                                // nothing left for this lane
-            t_evt = INT_MAX; t_dstart = INT_MAX;
-            t_seg = INT_MAX - 1;
-        }
-    };
-    open_superblock();
+        for (int nb = 0; nb < NB; ++nb) load_planes32(rowsF, s_cur * RB + 32 * nb, Plo[nb], Phi[nb]);
+    }
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) { Pv[nb] = ~0u; Mv[nb] = 0u; acc[nb] = 0u; }
+
+    // The event schedule.  Nothing in it depends on the data: superblock s lives in lane s & 63, and each kind of event
+    // falls at a step that is a function of (s, m, nr, w, wleft) alone, strictly increasing in s -- at most one event of
+    // a kind per step.  So the schedule is five wave-uniform timers, each with the superblock it fires for, advanced
+    // with scalar arithmetic in the handler; no lane carries a timer and the step loop tests nothing.
+    //   open  (s): max(1, s*RB + 1 - wleft) + s             the window of superblock s opens: Pv = ~0, Mv = 0
+    //   close (s): min(m, s*RB + RB + w) + s + 1            first step after the window: the lane moves on to s + 64
+    //   hin   (s): close(s) + 1                             lane (s+1) & 63 stops taking this lane's hout: during step
+    //                                                       close(s) it still takes the one of step close(s) - 1, the
+    //                                                       last of the window.  A scalar bit operation, no lane involved
+    //   diag  (s): s*(RB+1) + 1, while s*RB < m             the diagonal enters the superblock's first row
+    //   seg      : i + s + 1 for rows i = 32, 64, .., m     the 32-row diagonal segment ending at row i (of superblock
+    //                                                       s = (i-1)/RB) was completed by the step before
+    int T_open = 1, s_op = 0;
+    int T_close = min(m, RB + w) + 1, s_cl = 0;
+    int T_hin = INT_MAX, l_hn = 0;               // (armed by each close)
+    int T_diag = 1, s_dg = 0;
+    int T_seg = min(32, m) + 1, s_sg = 0;
+    int s_next = 1;                              // the earliest of the five
 
     uint32_t wl = 0, wh = 0;                     // text bit planes: bit k = low / high bit of the element of step tb+k
     int score = 0, best = INT_MAX, fail_row = 0;
@@ -229,20 +225,19 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     fin[2 * NB * PBA_WAVE + lane] = 0xFFFFFFFFu;
     uint32_t dmw = 0;                            // one-hot: bit of the diagonal cell in its block's word (0: not in this lane)
     uint64_t hp_last = ~0ull, hn_last = 0ull;    // lane masks: delta +1 / -1 leaving each lane's last block in the previous step
-    // lanes whose first block still receives the lane above's hout (the others see "+1 per column")
-    uint64_t valid = __builtin_amdgcn_ballot_w64(1 <= t_hin_end());
-    // the one rare-event compare of the step loop
-    int t_next = min(min(t_evt, t_seg + 1), min(t_dstart, 1 <= t_hin_end() ? t_hin_end() + 1 : INT_MAX));
+    // lanes whose first block still receives the lane above's hout (the others see "+1 per column"): lane s & 63 from the
+    // step it takes superblock s (0 < s < S) up to the step before the lane above closes
+    uint64_t valid = (S >= PBA_WAVE ? ~0ull : (1ull << S) - 1ull) & ~1ull;
 
     // text planes for the 32 steps starting at the wave-uniform step tb (element of step t is t - s_cur - 1)
     auto load_text = [&](int tb) { load_planes32(colsF, tb - s_cur - 1, wl, wh); };
 
-    // A 32-row diagonal segment ended at step t-1 (row i = t-1-s_cur, or row m): check its rows against
-    // seq_aligner.h:185 and carry the diagonal score on.
-    // `above`: the score register of the lane above, fetched by the caller with all lanes enabled
-    auto segment_done = [&](int t, int above) {
-        const int rr = t - 1 - t_diag0(), i = t - 1 - s_cur, cnt = (rr & 31) + 1, i0 = i - cnt, q = rr >> 5;
-        if (q == 0) score = s_cur == 0 ? 0 : above;      // D(i0,i0): the lane above finished its rows >= 2 steps ago
+    // The 32-row diagonal segment of superblock s ending at row i (a multiple of 32, or m) is complete: check its rows
+    // against seq_aligner.h:185 and carry the diagonal score on.  Runs on lane s & 63; s and i are wave-uniform.
+    // `above`: the score of the lane above
+    auto segment_done = [&](int s, int i, int above) {
+        const int rr = i - 1 - s * RB, cnt = (rr & 31) + 1, i0 = i - cnt, q = rr >> 5;
+        if (q == 0) score = s == 0 ? 0 : above;          // D(i0,i0): the lane above finished its rows >= 2 steps ago
         uint32_t dw = 0;
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) dw = q == nb ? acc[nb] : dw;
@@ -264,43 +259,62 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) acc[nb] = 0;     // the next block's word starts clean
         if (i == m) best = score;                        // D(m,m): where the scan down the last column starts
-        if (i == m || rr == RB - 1) { t_seg = INT_MAX - 1; dmw = 0; }         // the diagonal leaves this lane's rows
-        else { t_seg = min(t_seg + 32, m + s_cur); dmw = 1u; }                // ... or enters the lane's next block at its bit 0
+        dmw = (i == m || rr == RB - 1) ? 0u : 1u;        // the diagonal leaves this lane's rows, or enters its next block at bit 0
     };
 
-    // rare, divergent: segment finished last step / window opens now / window closed last step / diagonal enters
-#define PBA_BV_RARE(ON_EVENT)                                                         \
-    if (const uint64_t ev_lanes = __builtin_amdgcn_ballot_w64(t == t_next)) {   /* wave-uniform: all lanes enabled for the shuffle */ \
-      const int above = __shfl(score, (lane + PBA_WAVE - 1) & (PBA_WAVE - 1), PBA_WAVE); \
-      if ((ev_lanes >> lane) & 1) {      /* from the mask: testing t == t_next again costs the step loop a second compare */ \
-        if (t == t_seg + 1) segment_done(t, above);                                   \
-        if (t == t_evt) {                                                             \
-            /* a lane that moves on to its next superblock needs that superblock's slice of the text; a lane that \
-               opens its first window already got its planes at the start of the chunk (no load, no wait: during  \
-               the ramp one lane opens per step, and false candidates are all ramp) */                              \
-            if (opened) {                                                             \
-                if (s_cur >= s_m) {          /* its window ended with the last column: keep that column */ \
+    // The events due at step t (== s_next), before the step runs: segment end, close / move on, open, diagonal entry.
+    // DIAG: phase 1 (the diagonal is still being swept).  Sets seg_evt when a segment was checked.
+#define PBA_BV_EVENTS(DIAG)                                                           \
+    {                                                                                 \
+        if (DIAG && t == T_seg) {                                                     \
+            const int s = s_sg, i = t - 1 - s;                                        \
+            const int above = __builtin_amdgcn_readlane(score, (s + PBA_WAVE - 1) & (PBA_WAVE - 1)); \
+            if (lane == (s & (PBA_WAVE - 1))) segment_done(s, i, above);              \
+            seg_evt = true;                                                           \
+            if (i == m) T_seg = INT_MAX;                                              \
+            else { s_sg = s + (i == s * RB + RB ? 1 : 0); T_seg = min(i + 32, m) + s_sg + 1; } \
+        }                                                                             \
+        if (t == T_hin) { valid &= ~(1ull << l_hn); T_hin = INT_MAX; }                \
+        if (t == T_close) {                                                           \
+            const int s = s_cl;                                                       \
+            if (lane == (s & (PBA_WAVE - 1))) {                                       \
+                if (s >= s_m) {              /* its window ended with the last column: keep that column */ \
                     fin[2 * NB * PBA_WAVE + lane] = (uint32_t)s_cur;                  \
                     _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) { fin[2 * nb * PBA_WAVE + lane] = Pv[nb]; fin[(2 * nb + 1) * PBA_WAVE + lane] = Mv[nb]; } \
                 }                                                                     \
-                s_cur += PBA_WAVE; open_superblock(); load_text(t - ((t - 1) & 31));  \
+                /* the lane's next superblock: its rows, and its slice of the text (a lane that opens its first window \
+                   already got its planes at the start of the chunk: no load, no wait -- during the ramp one lane opens \
+                   per step, and false candidates are all ramp) */                    \
+                s_cur += PBA_WAVE; opened = 0;                                        \
+                if (s + PBA_WAVE < S) {                                               \
+                    _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) load_planes32(rowsF, s_cur * RB + 32 * nb, Plo[nb], Phi[nb]); \
+                }                                                                     \
+                load_text(t - ((t - 1) & 31));                                        \
             }                                                                         \
-            if (t == t_evt) {                                                         \
+            /* this lane takes the lane above's hout again if it has a superblock left; the lane below stops taking this one's a step later */ \
+            T_hin = t + 1; l_hn = (s + 1) & (PBA_WAVE - 1);                           \
+            if (s + PBA_WAVE < S) valid |= 1ull << (s & (PBA_WAVE - 1)); else valid &= ~(1ull << (s & (PBA_WAVE - 1))); \
+            s_cl = s + 1;                                                             \
+            T_close = s_cl < S ? min(m, s_cl * RB + RB + w) + s_cl + 1 : INT_MAX;     \
+        }                                                                             \
+        if (t == T_open) {                                                            \
+            if (lane == (s_op & (PBA_WAVE - 1))) {                                    \
                 _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) { Pv[nb] = ~0u; Mv[nb] = 0u; } \
                 opened = 1;                                                           \
-                t_evt = t_close1();                                                   \
             }                                                                         \
+            s_op += 1;                                                                \
+            T_open = s_op < S ? max(1, s_op * RB + 1 - wleft) + s_op : INT_MAX;       \
         }                                                                             \
-        if (t == t_dstart) {                                                          \
-            dmw = 1u; t_dstart = INT_MAX;                                             \
-            _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) acc[nb] = 0;            \
+        if (DIAG && t == T_diag) {                                                    \
+            if (lane == (s_dg & (PBA_WAVE - 1))) {                                    \
+                dmw = 1u;                                                             \
+                _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) acc[nb] = 0;        \
+            }                                                                         \
+            s_dg += 1;                                                                \
+            T_diag = s_dg * RB < m ? s_dg * (RB + 1) + 1 : INT_MAX;                   \
         }                                                                             \
-        { const int he = t_hin_end();                                                 \
-          t_next = min(min(t_evt, t_seg + 1), min(t_dstart, t <= he ? he + 1 : INT_MAX)); } \
-      }                                                                               \
-      valid = __builtin_amdgcn_ballot_w64(t <= t_hin_end());   /* changes only at events: kept as a scalar mask */ \
-      if constexpr (TRACE == 1) st_on = ((__builtin_amdgcn_ballot_w64(opened != 0) >> (lane & 48)) & 0xFFFFull) != 0; \
-      ON_EVENT;                                                                       \
+        s_next = min(DIAG ? min(min(T_seg, T_diag), min(T_open, T_close)) : min(T_open, T_close), T_hin); \
+        if constexpr (TRACE == 1) st_on = ((__builtin_amdgcn_ballot_w64(opened != 0) >> (lane & 48)) & 0xFFFFull) != 0; \
     }
 
     // hin of each lane's first block: the lane above's hout of the previous step, rotated one lane up, where that
@@ -342,6 +356,9 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     // The step loop is cut into chunks of 32 steps (one pair of text planes): the scalar unit is shared by the CU's
     // four SIMDs, so every SALU instruction of the step costs four issue cycles -- the inner loop carries nothing
     // but its counter.  Everything in it is wave-uniform and stays in SGPRs.
+    // Within a chunk the steps run in stretches that end at the next scheduled event: the stretch's bound is its loop
+    // counter, and its body is the block updates, the hand-off rotate and the one-hot add -- no compare, no branch on a
+    // lane mask.
     bool failed = false;
     for (int tbv = 1; tbv <= t1; tbv += 32) {
         const int tb = __builtin_amdgcn_readfirstlane(tbv);   // (the early exit below makes the compiler treat tbv as divergent)
@@ -349,11 +366,19 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
         load_text(tb);                           // next text planes
         if (failed) break;
         int kend = min(32, t1 - tb + 1);
-        for (int k = 0; k < kend; ++k) {
+        for (int k = 0; k < kend;) {
+        if (tb + k == s_next) {
+            const int t = tb + k;
+            bool seg_evt = false;
+            PBA_BV_EVENTS(true);
+            // a segment that just ended may have failed the reference's check: leave right after this step (false
+            // candidates die on their first segment, so they cost 33 steps, not the 64 of a poll per chunk)
+            if (seg_evt && __builtin_amdgcn_ballot_w64(fail_row != 0)) { failed = true; kend = k + 1; }
+        }
+        const int kstop = min(kend, s_next - tb);
+        do {
         const int t = tb + k;
-        // a segment that just ended may have failed the reference's check: leave right after this step (false
-        // candidates die on their first segment, so they cost 33 steps, not the 64 of a poll per chunk)
-        PBA_BV_RARE(if (__builtin_amdgcn_ballot_w64(fail_row != 0)) { failed = true; kend = k; });
+        (void)t;
         const uint32_t clo = bit_mask(wl, k), chi = bit_mask(wh, k);
         PBA_BV_HIN();
 #pragma unroll
@@ -372,20 +397,19 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
         hp_last = hp; hn_last = hn;
         asm("v_add_u32 %0, %1, %1" : "=v"(dmw) : "v"(dmw));   // next row of the block: a full-rate add (left to itself the compiler
                                                                // turns dmw += dmw into the slower shift); segment_done re-arms it every 32 rows
+        } while (++k < kstop);
         }
     }
-    int t = t1 + 1;
-    if (!failed) {                               // segments that ended in the last step (the one holding row m does)
-        const int above = __shfl(score, (lane + PBA_WAVE - 1) & (PBA_WAVE - 1), PBA_WAVE);
-        if (t == t_seg + 1) segment_done(t, above);
+    if (!failed) {                               // the segment that ended in the last step: the one holding row m
+        const int above = __builtin_amdgcn_readlane(score, (s_m + PBA_WAVE - 1) & (PBA_WAVE - 1));
+        if (lane == (s_m & (PBA_WAVE - 1))) segment_done(s_m, m, above);
         failed = __builtin_amdgcn_ballot_w64(fail_row != 0) != 0;
     }
     if (failed) {
         int fr = fail_row ? fail_row : INT_MAX;  // rows fail in increasing order of step: the smallest is the first
         return wave_min_i32(fr);
     }
-    t_seg = INT_MAX - 1; t_dstart = INT_MAX;
-    t_next = min(t_evt, t <= t_hin_end() ? t_hin_end() + 1 : INT_MAX);
+    s_next = min(min(T_open, T_close), T_hin);   // the diagonal is done: what is left opens and closes windows
 
     // ------------------------------------------------------------------ phase 2: the superblocks below row m take the last column
     for (int tb = t1 + 1; tb <= t_end;) {
@@ -395,9 +419,18 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
             load_text(tb);
         }
         const int kend = min(32, k0 + (t_end - tb + 1));
-        for (int k = k0; k < kend; ++k) {
-        const int t = tb - k0 + k;
-        PBA_BV_RARE((void)0);
+        const int tc = tb - k0;                  // first step of the chunk
+        for (int k = k0; k < kend;) {
+        if (tc + k == s_next) {
+            const int t = tc + k;
+            bool seg_evt = false;
+            (void)seg_evt;
+            PBA_BV_EVENTS(false);
+        }
+        const int kstop = min(kend, s_next - tc);
+        do {
+        const int t = tc + k;
+        (void)t;
         const uint32_t clo = bit_mask(wl, k), chi = bit_mask(wh, k);
         PBA_BV_HIN();
 #pragma unroll
@@ -411,13 +444,14 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
             }
         }
         hp_last = hp; hn_last = hn;
+        } while (++k < kstop);
         }
         tb += kend - k0;
     }
 #undef PBA_BV_BLOCK
 #undef PBA_BV_TRP
 #undef PBA_BV_HIN
-#undef PBA_BV_RARE
+#undef PBA_BV_EVENTS
     // ------------------------------------------------------------------ the free end: first strict minimum down the last column
     // D(i,m) = D(m,m) + the vertical deltas of column m over rows m+1..i (seq_aligner.h:192-211 scans exactly these cells,
     // upward from the diagonal, and keeps the first strict minimum).  A lane whose window is still open holds the
