@@ -386,6 +386,68 @@ int pba_cons_assemble(pba_ctx *ctx, pba_cons *c, const pba_seqs *reads, double R
                       pba_ss_round_log *log, int32_t *ref_len_log, int log_cap, int *n_rounds);
 
 /* ------------------------------------------------------------------------ */
+/* Streamed locate: read batches that arrive step by step.  pba_locate works  */
+/* on a resident set; a caller with fresh reads every step (locator.cpp:70    */
+/* consumes them as they come) would pay pba_seqs_from_text -- allocations,   */
+/* a pageable copy, two packing kernels, several synchronisations -- in front */
+/* of every step.  A stream owns two SLOTS and a copy stream of its own:      */
+/* while the locate of batch k runs on the ctx's stream, batch k+1 is copied  */
+/* from pinned memory and packed on the copy stream.  Nothing is allocated or */
+/* freed between create and destroy.                                          */
+/*   for every batch:  pba_loc_stream_buffer  -> fill the pinned buffer       */
+/*                     pba_loc_stream_submit  -> returns at once              */
+/*                     pba_loc_stream_collect -> rows of the OLDEST batch     */
+/* Submit batch k+1 before collecting batch k to hide the upload.             */
+/* The pinned buffer of a slot must not be written between its submit and the */
+/* collect of that batch (nothing can check this).  One host thread, no graph */
+/* capture; the ctx's stream must stay the same from create to destroy.       */
+/* ------------------------------------------------------------------------ */
+typedef struct pba_loc_stream pba_loc_stream;
+enum { PBA_STREAM_TEXT = 0, PBA_STREAM_RECORDS = 1 };
+/* The locate parameters are pba_locate's, checked the same way with the same codes (ix a PBA_INDEX_ALL index of
+ * target_seq of target, target without bytes outside ACGT, R, kernel); ix and target must outlive the stream.  Each slot
+ * takes slot_bytes input bytes and slot_reads reads per batch: a pinned host buffer of slot_bytes and slot_reads + 1 u64
+ * offsets (at least 3), the device staging of the bytes, the packed arena and the bit planes with their slack, the
+ * offset / length arrays, and a pba_seqs that borrows them.  All or nothing: PBA_E_NOMEM leaves nothing behind. */
+int pba_loc_stream_create(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, uint32_t target_seq, double R, int trials,
+                          int min_len, int maxn, int maxm, int kernel, uint64_t slot_bytes, uint32_t slot_reads, int form,
+                          pba_loc_stream **out);
+/* The pinned buffers of the next free slot, to be filled in place.  PBA_STREAM_TEXT: the ASCII of the reads back to back
+ * and offsets[0..n] as for pba_seqs_from_text (offsets[0] = 0).  PBA_STREAM_RECORDS: the bytes of a binary read file as
+ * pba_seqs_from_records takes them, offsets[0] = the byte count, offsets[1] / offsets[2] = min_excl / max_excl.
+ * PBA_E_INVALID when both slots are pending. */
+int pba_loc_stream_buffer(pba_loc_stream *s, void **bytes, uint64_t **offsets);
+/* Hand the filled slot over as a batch of n reads (n == 0 is a batch; PBA_STREAM_RECORDS: n is not looked at, the batch
+ * holds the records the walk of pba_open_binary keeps).  Checked on the host: offsets not non-decreasing PBA_E_INVALID;
+ * more bytes than slot_bytes, more reads than slot_reads, or a read beyond the engine limit PBA_E_TOOLONG; a truncated
+ * record PBA_E_INVALID.  A refused batch enqueues nothing and leaves the slot free.  Otherwise the copy of the bytes and
+ * of the small arrays, the pack and an event are enqueued on the copy stream; nothing is synchronised. */
+int pba_loc_stream_submit(pba_loc_stream *s, uint32_t n);
+/* The locate of the oldest pending batch (the driver of pba_locate, on the ctx's stream, behind that batch's pack event);
+ * *n = its reads, rows[0 .. *n) and stats (nullable) as pba_locate fills them, except that rows[i].read counts from the
+ * first read ever submitted to the stream and rows[i].nseq continues the running id of locator.cpp:72,91 across batches:
+ * the rows of all batches, concatenated, are the rows of one pba_locate over the concatenated reads.  stats is per batch.
+ * A batch with a byte outside ACGT returns PBA_E_ALPHABET (as pba_locate does for such a set) before anything is launched:
+ * the batch is dropped, the slot is free, the stream stays usable, and the running `read` and `nseq` counters DO advance
+ * by what its reads would have contributed (re-submitted clean, they get new ids).  PBA_E_INVALID with nothing pending or
+ * cap below the batch size (the batch stays pending).  After any other failure the stream is spent: every later call
+ * returns PBA_E_INVALID; destroy still works. */
+int pba_loc_stream_collect(pba_loc_stream *s, pba_loc_row *rows, uint32_t cap, uint32_t *n, pba_loc_stats *stats);
+/* The set of the batch collect would run next, borrowed from its slot (valid until that collect; pba_seqs_destroy leaves
+ * it alone).  Blocks until the batch's pack has finished.  For pba_align_batch / pba_seqs_export on streamed reads. */
+int pba_loc_stream_pending(pba_loc_stream *s, const pba_seqs **set);
+/* HIP-event times of the batch collected last: the copy of its bytes, its pack, its locate, and how long the ctx's stream
+ * stood at the pack event before the locate could start (near 0 when the upload was hidden behind the batch before) */
+typedef struct {
+    float h2d_ms, pack_ms, locate_ms, stall_ms;
+    uint32_t n_reads;
+    uint64_t n_bytes;              /* input bytes copied */
+} pba_stream_profile;
+int pba_loc_stream_last_profile(const pba_loc_stream *s, pba_stream_profile *out);
+/* waits for the copy stream, then frees; legal with batches pending */
+void pba_loc_stream_destroy(pba_loc_stream *s);
+
+/* ------------------------------------------------------------------------ */
 /* All-vs-all overlap.  Not a loop the reference  */
 /* has, but built only from its pieces: every read t in [t_lo, t_hi) takes the */
 /* reference role (ref_seq::get_seedmap index of t, ref_seq.h:291-311) and     */

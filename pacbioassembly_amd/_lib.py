@@ -12,6 +12,7 @@ PBA_E_INVALID, PBA_E_NOMEM, PBA_E_HIP, PBA_E_TOOLONG, PBA_E_NODEVICE, PBA_E_ALPH
 PBA_INDEX_ALL, PBA_INDEX_HEAD_TAIL = 0, 1
 PBA_KERNEL_AUTO, PBA_KERNEL_ROWSWEEP, PBA_KERNEL_BITVEC = 0, 1, 2
 PBA_A_BACKWARD, PBA_B_BACKWARD = 1, 2
+PBA_STREAM_TEXT, PBA_STREAM_RECORDS = 0, 1
 
 
 class PbaPair(C.Structure):
@@ -47,6 +48,11 @@ class PbaProfile(C.Structure):
 class PbaCorrectProfile(C.Structure):
     _fields_ = [("overlap_ms", C.c_float), ("vote_ms", C.c_float), ("evolve_ms", C.c_float), ("n_chunks", C.c_uint32),
                 ("n_rows", C.c_uint64), ("n_bases_in", C.c_uint64), ("n_bases_out", C.c_uint64)]
+
+
+class PbaStreamProfile(C.Structure):
+    _fields_ = [("h2d_ms", C.c_float), ("pack_ms", C.c_float), ("locate_ms", C.c_float), ("stall_ms", C.c_float),
+                ("n_reads", C.c_uint32), ("n_bytes", C.c_uint64)]
 
 
 class PbaSsRow(C.Structure):
@@ -111,6 +117,14 @@ SYMBOLS = {
     "pba_align_batch_trace": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_double, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "pba_locate": (C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                              _P, _P]),
+    "pba_loc_stream_create": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64,
+                                        C.c_uint32, C.c_int, C.POINTER(_P)]),
+    "pba_loc_stream_buffer": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
+    "pba_loc_stream_submit": (C.c_int, [_P, C.c_uint32]),
+    "pba_loc_stream_collect": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(C.c_uint32), _P]),
+    "pba_loc_stream_pending": (C.c_int, [_P, C.POINTER(_P)]),
+    "pba_loc_stream_last_profile": (C.c_int, [_P, _P]),
+    "pba_loc_stream_destroy": (None, [_P]),
     "pba_spaced_round": (C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "pba_spaced_multi": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int,
                                    C.c_int, _P, _P, _P, C.c_int, C.POINTER(C.c_int)]),

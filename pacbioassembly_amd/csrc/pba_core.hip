@@ -233,8 +233,16 @@ static int seqs_planes(pba_ctx *ctx, pba_seqs *s) {
     return PBA_OK;
 }
 
+int planes_enqueue(pba_ctx *ctx, const pba_seqs *s, uint64_t words, hipStream_t stream) {
+    if (!words) return PBA_OK;
+    hipLaunchKernelGGL(k_make_planes, dim3(elem_grid(words, 256)), dim3(256), 0, stream, s->d_packed, s->d_off, s->d_len, s->d_poff,
+                       s->n, words, s->d_planes + 2 * kPlaneSlack);
+    HIPCHK(hipGetLastError());
+    return PBA_OK;
+}
+
 void pba_seqs_destroy(pba_seqs *s) {
-    if (!s) return;
+    if (!s || s->borrowed) return;      // (a stream's set: pba_loc_stream_destroy frees the slot it looks into)
     (void)hipSetDevice(s->ctx->device);
     if (s->d_planes) (void)hipFree(s->d_planes);
     if (s->d_poff) (void)hipFree(s->d_poff);

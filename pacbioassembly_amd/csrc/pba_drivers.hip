@@ -230,9 +230,12 @@ extern "C" {
 // ---------------------------------------------------------------------------------------------
 // host API: drivers
 // ---------------------------------------------------------------------------------------------
-int pba_locate(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, uint32_t target_seq, const pba_seqs *reads,
-               double R, int trials, int min_len, int maxn, int maxm, int kernel, pba_loc_row *rows,
-               pba_loc_stats *stats) {
+// The one locate driver.  pba_locate runs it on a resident set (bases 0, no event); a pba_loc_stream runs it per batch:
+// rows[i].read = read_base + i, the running id of locator.cpp:72,91 starts at nseq_base, and the ctx's stream first waits
+// for `packed` (the event behind the batch's pack on the stream's own copy stream).
+int locate_core(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, uint32_t target_seq, const pba_seqs *reads,
+                double R, int trials, int min_len, int maxn, int maxm, int kernel, pba_loc_row *rows,
+                pba_loc_stats *stats, int64_t read_base, int64_t nseq_base, hipEvent_t packed) {
     if (!ctx || !ix || !target || !reads || !rows || target_seq >= target->n || trials < 0) return PBA_E_INVALID;
     if (ix->mode != PBA_INDEX_ALL || ix->seq_len != target->h_len[target_seq])
         PBA_FAIL(PBA_E_INVALID, "pba_locate needs a PBA_INDEX_ALL index of the target sequence");
@@ -245,6 +248,7 @@ int pba_locate(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, uint32
     Plan pl;
     int st = make_plan(ctx, R, maxn, maxm, kernel, 1 + (int)(reads->max_len * R), &pl);
     if (st != PBA_OK) return st;
+    if (packed) HIPCHK(hipStreamWaitEvent(ctx->stream, packed, 0));
     BufRef d_rows, d_aux;                                      // (pooled in the ctx: two hipMalloc / hipFree pairs were 1 ms of a 50 ms step)
     POOL(POOL_LOC_ROWS, sizeof(pba_loc_row) * ((size_t)n + 1), d_rows.p);
     POOL(POOL_LOC_AUX, sizeof(LocAux) * ((size_t)n + 1), d_aux.p);
@@ -273,10 +277,10 @@ int pba_locate(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, uint32
     };
     if (n && (st = narrow_then_redo(ctx, pl, nullptr, n, launch, collect, finish)) != PBA_OK) return st;
     pba_loc_stats s = {0, 0, 0, 0, 0};
-    int nseq = 0;
+    int64_t nseq = nseq_base;
     for (uint32_t r = 0; r < n; ++r) {
-        rows[r].read = (int32_t)r;
-        rows[r].nseq = (int)reads->h_len[r] < min_len ? -1 : nseq++;      // locator.cpp:72,91
+        rows[r].read = (int32_t)(read_base + r);
+        rows[r].nseq = (int)reads->h_len[r] < min_len ? -1 : (int32_t)nseq++;      // locator.cpp:72,91
         if (rows[r].nseq >= 0) ++s.n_reads_kept;
         s.n_pairs += rows[r].n_pairs;
         s.n_located += rows[r].found;
@@ -285,6 +289,12 @@ int pba_locate(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, uint32
     }
     if (stats) *stats = s;
     return PBA_OK;
+}
+
+int pba_locate(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, uint32_t target_seq, const pba_seqs *reads,
+               double R, int trials, int min_len, int maxn, int maxm, int kernel, pba_loc_row *rows,
+               pba_loc_stats *stats) {
+    return locate_core(ctx, ix, target, target_seq, reads, R, trials, min_len, maxn, maxm, kernel, rows, stats, 0, 0, nullptr);
 }
 
 // One locked round over the reads `subset` (host ids; nullptr = every read).  rows is indexed by read id: rows of

@@ -1,6 +1,6 @@
 // pba_host.h -- host-side objects and helpers shared by the translation units of libpba.so (pba_core.hip: context,
 // sequence sets, seed index; pba_align.hip: explicit pairs and edit scripts; pba_drivers.hip: the reference's ordered
-// first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction).  Internal: nothing here is part of
+// first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction; pba_stream.hip: streamed locate).  Internal: nothing here is part of
 // the C ABI (include/pba.h).
 // Also here, once for all of them: the clip of seq_aligner.h:94-102 (text_clip), the launch plan (make_plan), the host
 // protocol of every aligning entry point but the all-vs-all walk -- narrow window first, the uncertified items again at the
@@ -79,6 +79,7 @@ struct pba_seqs {
     uint64_t plane_words;    // words of one plane incl. its slack
     std::vector<uint64_t> h_off;
     std::vector<uint32_t> h_len;
+    bool borrowed;           // the arrays belong to a pba_loc_stream slot: pba_seqs_destroy leaves the set alone, the stream frees it
     SeqSetDev dev() const { return SeqSetDev{d_packed, d_off, d_len, d_planes + 2 * kPlaneSlack, d_poff}; }
 };
 
@@ -458,6 +459,12 @@ PBA_INTERNAL int spaced_round_subset(pba_ctx *ctx, const pba_index *ix, const pb
                                      double R, int max_trial, int overlap_min, int buggy_seed_at, int kernel,
                                      const uint32_t *subset, uint32_t n_subset, pba_ss_row *rows, int ref_org = 0, int maxn = 0,
                                      int maxm = 0, uint8_t *touch = nullptr);
+// the body of pba_locate with the bases of its `read` / `nseq` columns and an event its launches wait for (pba_drivers.hip)
+PBA_INTERNAL int locate_core(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, uint32_t target_seq, const pba_seqs *reads,
+                             double R, int trials, int min_len, int maxn, int maxm, int kernel, pba_loc_row *rows,
+                             pba_loc_stats *stats, int64_t read_base, int64_t nseq_base, hipEvent_t packed);
+// k_make_planes over a set's first `words` plane words on `stream`: the arrays of `s` are on the device (pba_core.hip)
+PBA_INTERNAL int planes_enqueue(pba_ctx *ctx, const pba_seqs *s, uint64_t words, hipStream_t stream);
 }  // extern "C"
 
 #endif

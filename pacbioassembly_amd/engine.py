@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (PBA_INDEX_ALL, PBA_INDEX_HEAD_TAIL, PBA_KERNEL_AUTO, PBA_KERNEL_BITVEC, PBA_KERNEL_ROWSWEEP,
-                   PbaLocRow, PbaLocStats, PbaPair, PbaResult, PbaSsRow)
+                   PBA_STREAM_RECORDS, PBA_STREAM_TEXT, PbaLocRow, PbaLocStats, PbaPair, PbaResult, PbaSsRow)
 
 PAIR_DTYPE = np.dtype([("a_seq", "<u4"), ("a_pos", "<i4"), ("a_len", "<i4"), ("b_seq", "<u4"), ("b_pos", "<i4"),
                        ("b_len", "<i4"), ("flags", "<u4")])
@@ -589,6 +589,89 @@ Context.overlap_all_sharded = _overlap_all_sharded
 Context.overlap_all_table = _overlap_all_table
 
 
+class LocStream:
+    """Streamed locate (pba_loc_stream): two slots of pinned and device storage made once; batch k+1 is copied and packed on
+    a copy stream while the locate of batch k runs.  Per batch: fill buffer() (or submit_reads), submit, collect -- and submit
+    the next batch before collecting this one to hide its upload.  The rows of all batches, concatenated, are the rows of
+    one Context.locate over the concatenated reads."""
+
+    def __init__(self, ctx: "Context", ix, target, target_seq: int, R: float, trials: int = 50, min_len: int = 500, maxn: int = 0,
+                 maxm: int = 0, kernel: int = PBA_KERNEL_AUTO, slot_bytes: int = 1 << 20, slot_reads: int = 1024,
+                 form: int = PBA_STREAM_TEXT):
+        self.ctx, self.form, self.slot_bytes, self.slot_reads = ctx, form, int(slot_bytes), int(slot_reads)
+        self._keep = (ix, target)                       # the stream looks into both until it is closed
+        self.h = C.c_void_p()
+        ctx.check(ctx.lib.pba_loc_stream_create(ctx.h, ix.h, target.h, target_seq, R, trials, min_len, maxn, maxm, kernel,
+                                                self.slot_bytes, self.slot_reads, form, C.byref(self.h)), "loc_stream_create")
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.ctx.lib.pba_loc_stream_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def buffer(self):
+        """(bytes uint8[slot_bytes], offsets uint64[max(slot_reads + 1, 3)]): numpy views of the next free slot's pinned memory,
+        to be filled in place and left alone between submit and the collect of that batch."""
+        b, o = C.c_void_p(), C.c_void_p()
+        self.ctx.check(self.ctx.lib.pba_loc_stream_buffer(self.h, C.byref(b), C.byref(o)), "loc_stream_buffer")
+        nb, no = max(self.slot_bytes, 1), max(self.slot_reads + 1, 3)
+        return (np.ctypeslib.as_array(C.cast(b, C.POINTER(C.c_uint8)), shape=(nb,))[:self.slot_bytes],
+                np.ctypeslib.as_array(C.cast(o, C.POINTER(C.c_uint64)), shape=(no,)))
+
+    def submit(self, n: int = 0):
+        self.ctx.check(self.ctx.lib.pba_loc_stream_submit(self.h, n), "loc_stream_submit")
+
+    def submit_reads(self, reads: Sequence[bytes]):
+        """Text form: write the reads into the slot and submit them."""
+        buf, offs = self.buffer()
+        total = sum(len(r) for r in reads)
+        if total > self.slot_bytes or len(reads) > self.slot_reads:
+            raise PbaError(_lib.PBA_E_TOOLONG, "loc_stream_submit: the batch does not fit the slot")
+        offs[0] = 0
+        if reads:
+            offs[1:len(reads) + 1] = np.cumsum([len(r) for r in reads], dtype=np.uint64)
+            buf[:total] = np.frombuffer(b"".join(reads), np.uint8)
+        self.submit(len(reads))
+
+    def submit_records(self, file: bytes, min_excl: int = 500, max_excl: int = 20000):
+        """Records form: write a binary read file into the slot and submit it."""
+        buf, offs = self.buffer()
+        if len(file) > self.slot_bytes:
+            raise PbaError(_lib.PBA_E_TOOLONG, "loc_stream_submit: the batch does not fit the slot")
+        buf[:len(file)] = np.frombuffer(file, np.uint8)
+        offs[0], offs[1], offs[2] = len(file), min_excl, max_excl
+        self.submit(0)
+
+    def collect(self):
+        """(rows, stats) of the oldest pending batch."""
+        rows = np.zeros(max(self.slot_reads, 1), LOC_ROW_DTYPE)
+        stats, n = PbaLocStats(), C.c_uint32()
+        self.ctx.check(self.ctx.lib.pba_loc_stream_collect(self.h, _ptr(rows), self.slot_reads, C.byref(n), C.byref(stats)),
+                       "loc_stream_collect")
+        return rows[:n.value].copy(), {k: getattr(stats, k) for k, _ in PbaLocStats._fields_}
+
+    def pending(self) -> "SeqSet":
+        """The set of the batch collect() would run next, borrowed from its slot (valid until that collect)."""
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.lib.pba_loc_stream_pending(self.h, C.byref(h)), "loc_stream_pending")
+        return BorrowedSeqSet(self.ctx, h)
+
+    def profile(self) -> dict:
+        pr = _lib.PbaStreamProfile()
+        self.ctx.check(self.ctx.lib.pba_loc_stream_last_profile(self.h, C.byref(pr)), "loc_stream_last_profile")
+        return {k: getattr(pr, k) for k, _ in _lib.PbaStreamProfile._fields_}
+
+
+def _locate_stream(self, ix, target, target_seq, R, trials=50, min_len=500, maxn=0, maxm=0, kernel=PBA_KERNEL_AUTO,
+                   slot_bytes=1 << 20, slot_reads=1024, form=PBA_STREAM_TEXT) -> LocStream:
+    return LocStream(self, ix, target, target_seq, R, trials, min_len, maxn, maxm, kernel, slot_bytes, slot_reads, form)
+
+
+Context.locate_stream = _locate_stream
+
+
 class SeqSet:
     def __init__(self, ctx: Context, h):
         self.ctx, self.h = ctx, h
@@ -632,6 +715,16 @@ class SeqSet:
         buf = C.create_string_buffer(ln + 1)
         self.ctx.check(self.ctx.lib.pba_seqs_get_text(self.ctx.h, self.h, i, buf, ln + 1), "get_text")
         return buf.raw[:ln]
+
+
+class BorrowedSeqSet(SeqSet):
+    """A set that belongs to a LocStream slot (LocStream.pending): closing the wrapper frees nothing, and the handle must not
+    be used after the collect of its batch or the close of its stream."""
+
+    def close(self):
+        self.h = None
+
+    __del__ = close
 
 
 class Consensus:
