@@ -155,8 +155,8 @@ int pba_seqs_get_text(pba_ctx *ctx, const pba_seqs *s, uint32_t i, char *text, s
  * (16-byte aligned starts, zero pad bits), whatever layout src had (a binary read file's records included): byte for byte
  * what pba_seqs_from_text makes of the same texts.  Packed bytes and bit planes are built on the device; no base goes
  * through the host.  PBA_E_ALPHABET if src holds bytes outside ACGT (code 3 stands for N as well as T: no complement).
- * The reference never reverse-complements a read; this feeds pba_overlap_strands (and pba_locate, for a caller who
- * wants the other strand there). */
+ * The reference never reverse-complements a read; this feeds pba_overlap_strands and pba_map_reads (the locate on both
+ * strands). */
 int pba_seqs_revcomp(pba_ctx *ctx, const pba_seqs *src, const uint8_t *flip, pba_seqs **out);
 
 /* ------------------------------------------------------------------------ */
@@ -182,6 +182,17 @@ int pba_index_scan(pba_ctx *ctx, const pba_seqs *target, uint32_t seq, uint32_t 
  * all-ones are padding).  seq_len / mode / mask must be those of the scan. */
 int pba_index_from_entries(pba_ctx *ctx, const void *d_entries, uint64_t n, uint32_t mask, int mode,
                            uint32_t seq_len, pba_index **out);
+/* PBA_INDEX_ALL applied to EVERY sequence of `target`, each on its own: every position [0, len_c) of contig c is indexed, tail
+ * windows are padded with code 3 from that contig's own length (no window sees a neighbour's bases), masked key 0 is dropped.
+ * The ordinal of an entry is its GLOBAL position g = cum[c] + pos, cum = the exclusive prefix sum of the lengths; per-key hit
+ * order is ascending g: the per-contig lists of locator.cpp:62-66 concatenated in contig order.  pba_index_find /
+ * pba_index_dump on such an index return global positions; pba_index_visited the total bases.  Empty contigs and contigs
+ * shorter than 16 bases are legal; a set with bytes outside ACGT is legal here (pba_map_reads refuses it); the total must
+ * stay below 0x7FFFFFF0 bases (PBA_E_TOOLONG, decided from the lengths before anything is allocated).  One segmented scan
+ * launch whatever the number of contigs.  For pba_map_reads. */
+int pba_index_build_set(pba_ctx *ctx, const pba_seqs *target, uint32_t mask, pba_index **out);
+/* sequences the index covers: 1 for pba_index_build / pba_index_from_entries */
+uint32_t pba_index_seqs(const pba_index *ix);
 void pba_index_destroy(pba_index *ix);
 uint64_t pba_index_entries(const pba_index *ix);
 /* what get_seedmap returns (ref_seq.h:310): positions visited, not entries kept */
@@ -326,6 +337,32 @@ typedef struct {
 int pba_locate(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, uint32_t target_seq,
                const pba_seqs *reads, double R, int trials, int min_len, int maxn, int maxm, int kernel,
                pba_loc_row *rows, pba_loc_stats *stats);
+
+/* locator.cpp:70-92 against a target of MANY sequences and on BOTH strands of the reads.  ix: the pba_index_build_set index of
+ * `target` (same count, same lengths; else PBA_E_INVALID).  A read's order of trial on one strand: for j ascending, the hits
+ * of its key in ascending (contig, pos); first success, as pba_locate.  strands: 1 = the reads as given, 2 = rc(read) only,
+ * 3 = every read on +, then the reads with len >= min_len that found nothing again as rc(read) (an id list over reads_rc, no
+ * new set); the first success in that order is the row.  reads_rc: pba_seqs_revcomp(reads, NULL), or NULL to have it built
+ * inside (a set of another count or other lengths: PBA_E_INVALID).  Sets with bytes outside ACGT: PBA_E_ALPHABET.
+ * j, pos, cost, seglen, matlen_a, matlen_b, diag_cost are pba_loc_row's, in the coordinates of the text that was walked (for
+ * strand -1: of rc(read)), pos local to the contig; not found: pba_loc_row's values, strand 0, contig -1, intervals 0.
+ * Intervals (a = the read from j, b = the contig from pos): walked read [j, j + matlen_a), contig [pos, pos + matlen_b);
+ * for strand -1 the read interval is given on the read's forward strand, [len - j - matlen_a, len - j).
+ * stats->strand[0] / [1]: the + / - walk (n_reads_kept: the reads of that walk with len >= min_len); n_second_walk: reads
+ * walked on - after failing on + (strands == 3).  pba_ctx_last_profile afterwards: the two walks summed. */
+typedef struct {
+    int32_t read, nseq, found;
+    int32_t strand;                 /* +1 / -1; 0 when not found */
+    int32_t contig;                 /* -1 when not found */
+    int32_t j, pos, cost, seglen, matlen_a, matlen_b, diag_cost;   /* as pba_loc_row, in the coordinates of the text walked */
+    int32_t n_pairs;                /* pairs of the + walk plus pairs of the - walk */
+    int32_t r_beg, r_end, c_beg, c_end;   /* half-open, forward strand of the read / of the contig */
+} pba_map_row;
+typedef struct { pba_loc_stats strand[2]; uint32_t n_second_walk; } pba_map_stats;
+int pba_map_reads(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, const pba_seqs *reads,
+                  const pba_seqs *reads_rc /* nullable: built inside */, double R, int trials, int min_len,
+                  int maxn, int maxm, int kernel, int strands /* 1, 2, 3 as pba_overlap_strands */,
+                  pba_map_row *rows, pba_map_stats *stats);
 
 typedef struct {
     int32_t read, found, j, dir;   /* dir +1 forward / -1 backward (spaced_seed.cpp:426) */

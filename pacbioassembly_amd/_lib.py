@@ -33,6 +33,16 @@ class PbaLocStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_reads_kept", "n_probe_hits", "n_pairs", "n_located", "n_cells")]
 
 
+class PbaMapRow(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in
+                ("read", "nseq", "found", "strand", "contig", "j", "pos", "cost", "seglen", "matlen_a", "matlen_b", "diag_cost",
+                 "n_pairs", "r_beg", "r_end", "c_beg", "c_end")]
+
+
+class PbaMapStats(C.Structure):
+    _fields_ = [("strand", PbaLocStats * 2), ("n_second_walk", C.c_uint32)]
+
+
 class PbaOverlapStats(C.Structure):
     _fields_ = [("n_probe_entries", C.c_uint64), ("n_candidates", C.c_uint64), ("n_pairs", C.c_uint64),
                 ("n_overlaps", C.c_uint64), ("n_redo", C.c_uint64), ("scan_ms", C.c_float), ("sort_ms", C.c_float),
@@ -103,6 +113,8 @@ SYMBOLS = {
     "pba_index_scan": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, _P, C.c_uint64,
                                  C.POINTER(C.c_uint64)]),
     "pba_index_from_entries": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(_P)]),
+    "pba_index_build_set": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(_P)]),
+    "pba_index_seqs": (C.c_uint32, [_P]),
     "pba_index_destroy": (None, [_P]),
     "pba_index_entries": (C.c_uint64, [_P]),
     "pba_index_visited": (C.c_uint32, [_P]),
@@ -117,6 +129,7 @@ SYMBOLS = {
     "pba_align_batch_trace": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_double, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "pba_locate": (C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                              _P, _P]),
+    "pba_map_reads": (C.c_int, [_P, _P, _P, _P, _P, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "pba_loc_stream_create": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64,
                                         C.c_uint32, C.c_int, C.POINTER(_P)]),
     "pba_loc_stream_buffer": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),

@@ -487,6 +487,7 @@ void pba_index_destroy(pba_index *ix) {
     else if (ix->d_ent) (void)hipFree(ix->d_ent);
     if (ix->d_part_off && !ctx->ix_cache.off) { ctx->ix_cache.off = ix->d_part_off; ctx->ix_cache.off_cap = ix->off_cap; }
     else if (ix->d_part_off) (void)hipFree(ix->d_part_off);
+    if (ix->d_cum) (void)hipFree(ix->d_cum);
     delete ix;
 }
 
@@ -500,6 +501,7 @@ static int ix_alloc(pba_ctx *ctx, void **cache, size_t *cache_cap, size_t bytes,
 
 uint64_t pba_index_entries(const pba_index *ix) { return ix ? ix->n_entries : 0; }
 uint32_t pba_index_visited(const pba_index *ix) { return ix ? ix->visited : 0; }
+uint32_t pba_index_seqs(const pba_index *ix) { return ix ? ix->n_seqs : 0; }
 
 // sort one oversize partition in global memory
 int sort_partition_global(pba_ctx *ctx, uint64_t *d_part, uint32_t n) {
@@ -568,6 +570,7 @@ static pba_index *index_new(pba_ctx *ctx, uint32_t mask, uint32_t len, int mode,
     ix->tail_top = v.tail_top; ix->mode = mode; ix->n_entries = 0; ix->d_ent = nullptr; ix->d_part_off = nullptr;
     ix->ent_cap = ix->off_cap = 0;
     ix->logP = 0;
+    ix->n_seqs = 1; ix->d_cum = nullptr;
     return ix;
 }
 
@@ -794,6 +797,64 @@ int pba_index_from_entries(pba_ctx *ctx, const void *d_entries, uint64_t n, uint
     if (!ix) PBA_FAIL(PBA_E_NOMEM, "pba_index");
     int st = index_levels(ctx, ix, n, (const uint64_t *)d_entries, [](int, uint32_t *, uint32_t *, uint64_t *) {});
     if (st != PBA_OK) { pba_index_destroy(ix); return st; }
+    *out = ix;
+    return PBA_OK;
+}
+
+// PBA_INDEX_ALL over every sequence of a set: one segmented emit (k_seed_emit_set) into a flat list, then the levels and
+// the sort of the exchange form.  An entry's ordinal is its global position, so dump / find / the locate kernel read it
+// through ix_pos_of like any PBA_INDEX_ALL ordinal.
+int pba_index_build_set(pba_ctx *ctx, const pba_seqs *target, uint32_t mask, pba_index **out) {
+    if (!ctx || !target || !out) return PBA_E_INVALID;
+    *out = nullptr;
+    const uint32_t n = target->n;
+    uint64_t total = 0;
+    for (uint32_t c = 0; c < n; ++c) total += target->h_len[c];
+    if (total >= 0x7FFFFFF0ull) PBA_FAIL(PBA_E_TOOLONG, "pba_index_build_set: the set holds 2^31 bases or more");
+    HIPCHK(hipSetDevice(ctx->device));
+    VisitPlan v = visit_plan(0, PBA_INDEX_ALL);
+    v.visited = (uint32_t)total;
+    pba_index *ix = index_new(ctx, mask, (uint32_t)total, PBA_INDEX_ALL, v);
+    if (!ix) PBA_FAIL(PBA_E_NOMEM, "pba_index");
+    struct Guard { pba_index *p; ~Guard() { if (p) pba_index_destroy(p); } } guard{ix};
+    ix->n_seqs = n;
+    ix->h_cum.resize((size_t)n + 1);
+    // the tile table: (sequence, first chunk) of every PBA_IX_TILE_THREADS x PBA_IX_TILE_ITERS chunks of a sequence
+    std::vector<SetTile> tiles;
+    const uint32_t per = PBA_IX_TILE_THREADS * PBA_IX_TILE_ITERS;
+    uint32_t g = 0;
+    for (uint32_t c = 0; c < n; ++c) {
+        ix->h_cum[c] = g;
+        const uint32_t L = target->h_len[c], chunks = (uint32_t)(((uint64_t)L + 15) / 16);
+        for (uint32_t c0 = 0; c0 < chunks; c0 += per) tiles.push_back(SetTile{c, c0});
+        g += L;
+    }
+    ix->h_cum[n] = g;
+    HIPCHK(hipMalloc((void **)&ix->d_cum, sizeof(uint32_t) * ((size_t)n + 1)));
+    HIPCHK(hipMemcpyAsync(ix->d_cum, ix->h_cum.data(), sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
+    DevBuf d_tiles, d_list, counter;
+    HIPCHK(hipMalloc(&d_list.p, sizeof(uint64_t) * (total + 1)));
+    HIPCHK(hipMalloc(&counter.p, 8));
+    HIPCHK(hipMemsetAsync(counter.p, 0, 8, ctx->stream));
+    if (!tiles.empty()) {
+        HIPCHK(hipMalloc(&d_tiles.p, sizeof(SetTile) * tiles.size()));
+        HIPCHK(hipMemcpyAsync(d_tiles.p, tiles.data(), sizeof(SetTile) * tiles.size(), hipMemcpyHostToDevice, ctx->stream));
+        // (a launch's global size is a 32-bit number: at most 2^23 workgroups of 256 threads per launch)
+        for (size_t t0 = 0; t0 < tiles.size(); t0 += (size_t)1 << 23) {
+            const uint32_t grid = (uint32_t)std::min<size_t>(tiles.size() - t0, (size_t)1 << 23);
+            hipLaunchKernelGGL(k_seed_emit_set, dim3(grid), dim3(PBA_IX_TILE_THREADS), 0, ctx->stream, target->d_packed, target->d_off,
+                               target->d_len, ix->d_cum, d_tiles.as<SetTile>() + t0, mask, d_list.as<uint64_t>(),
+                               (unsigned long long)total, counter.as<unsigned long long>());
+        }
+        HIPCHK(hipGetLastError());
+    }
+    unsigned long long h_n = 0;
+    HIPCHK(hipMemcpyAsync(&h_n, counter.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));                  // (h_cum's, tiles' and h_n's copies have landed)
+    if (h_n > total) PBA_FAIL(PBA_E_HIP, "pba_index_build_set: more entries than positions");
+    const int st = index_levels(ctx, ix, h_n, d_list.as<uint64_t>(), [](int, uint32_t *, uint32_t *, uint64_t *) {});
+    if (st != PBA_OK) return st;
+    guard.p = nullptr;
     *out = ix;
     return PBA_OK;
 }

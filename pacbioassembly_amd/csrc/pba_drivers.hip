@@ -19,11 +19,30 @@ struct LocAux {
     int redo;            // 1: a pair came back PBA_RC_UNCERTIFIED, the read must be re-run at full band
 };
 
-// locator.cpp:70-92
-template <int NB>
+// The set form (pba_map_reads): ix is a pba_index_build_set index of T, a hit is a global position g = cum[c] + pos
+struct LocSet {
+    const uint32_t *cum;     // n + 1: exclusive prefix sum of the contig lengths
+    uint32_t n;              // contigs
+    int32_t *contig;         // per read: the contig of its success, -1 if none
+};
+// the contig of global position g < cum[n]: the last c with cum[c] <= g (an empty contig is never the last one)
+__device__ __forceinline__ uint32_t set_contig(const LocSet &S, uint32_t g) {
+    uint32_t lo = 0, hi = S.n;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (S.cum[mid] <= g) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// locator.cpp:70-92.  SET = false: against sequence tseq of T (`set` is not looked at).  SET = true: against every sequence of
+// T through a set index -- a hit resolves to (contig, local position) by a search of cum[], per lane in front of the
+// prefilter, wave-uniform for a survivor; the walk is otherwise the same, so a read tries, for j ascending, the hits of its
+// key in ascending (contig, pos).
+template <int NB, bool SET>
 __global__ void __launch_bounds__(PBA_WAVE * Wpb<NB>::v, Wpb<NB>::occ)
 k_locate(IndexDev ix, SeqSetDev T, uint32_t tseq, SeqSetDev Rd, const uint32_t *ids, uint32_t n, int trials,
-         int min_len, AlignCfg cfg, pba_loc_row *rows, LocAux *aux, uint32_t *queue) {
+         int min_len, AlignCfg cfg, pba_loc_row *rows, LocAux *aux, uint32_t *queue, LocSet set) {
     extern __shared__ __align__(16) uint8_t lds_all[];
     __shared__ int2 s_grp[Wpb<NB>::v][PBA_WAVE];      // the hit group in flight: position, band cells of a hit the prefilter failed
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / PBA_WAVE));   // wave-uniform on purpose: keeps the walk in SGPRs
@@ -37,11 +56,17 @@ k_locate(IndexDev ix, SeqSetDev T, uint32_t tseq, SeqSetDev Rd, const uint32_t *
     const uint32_t r = (uint32_t)__builtin_amdgcn_readfirstlane((int)(ids ? ids[slot] : slot));
     const int len = __builtin_amdgcn_readfirstlane((int)Rd.len[r]);
     int found = 0, fj = -1, fpos = -1, fcost = -1, fma = 0, fmb = 0, fdiag = -1, npairs = 0, nhit = 0, redo = 0;
+    int fctg = -1;
     long long ncell = 0;
     if (len >= min_len) {                                                   // locator.cpp:72
-        const PackedFetch rbase = fetch_of(Rd, r, 0, 1), tbase = fetch_of_uniform(T, tseq, 0, 1);
+        const PackedFetch rbase = fetch_of(Rd, r, 0, 1);
+        PackedFetch tbase = rbase;                                          // (SET: the contig's, per hit)
+        int clen = 0;
+        if constexpr (!SET) {
+            tbase = fetch_of_uniform(T, tseq, 0, 1);
+            clen = __builtin_amdgcn_readfirstlane((int)T.len[tseq]);
+        }
         const uint8_t *rseq = rbase.seq;
-        const int clen = __builtin_amdgcn_readfirstlane((int)T.len[tseq]);
         for (int j = 0; j < trials && j < len && !found && !redo; ++j) {    // locator.cpp:74
             const uint32_t key = (uint32_t)__builtin_amdgcn_readfirstlane((int)(window_key(rseq, (uint32_t)j, (uint32_t)len) & ix.mask));   // locator.cpp:75
             if (key == 0) continue;                                         // never inserted, locator.cpp:64
@@ -56,11 +81,17 @@ k_locate(IndexDev ix, SeqSetDev T, uint32_t tseq, SeqSetDev Rd, const uint32_t *
             for (uint32_t h0 = 0; h0 < cnt && !found && !redo; h0 += PBA_WAVE) {
                 const uint32_t lane = threadIdx.x & (PBA_WAVE - 1), ng = min((uint32_t)PBA_WAVE, cnt - h0);
                 const bool act = lane < ng;
-                const int mypos = act ? ix_pos_of(ix, (uint32_t)ix.ent[beg + h0 + lane]) : 0;
+                const int mypos = act ? ix_pos_of(ix, (uint32_t)ix.ent[beg + h0 + lane]) : 0;   // (SET: the global position)
                 int myfr = 0;
                 long long mycells = 0;
                 if constexpr (NB != 0) {
                     AlnOut po;
+                    if constexpr (SET) {
+                        const uint32_t myctg = set_contig(set, (uint32_t)mypos);
+                        const int lpos = mypos - (int)set.cum[myctg];
+                        myfr = prefilter32(act, rbase.at(j, 1), len - j, fetch_of(T, myctg, lpos, 1), (int)T.len[myctg] - lpos, cfg.R,
+                                           cfg.maxn, cfg.maxm, pre_t, po);
+                    } else
                     myfr = prefilter32(act, rbase.at(j, 1), len - j, tbase.at(mypos, 1), clen - mypos, cfg.R,
                                        cfg.maxn, cfg.maxm, pre_t, po);
                     mycells = myfr ? band_cells(po.len_b, po.max_dst, myfr) : 0;
@@ -90,7 +121,14 @@ k_locate(IndexDev ix, SeqSetDev T, uint32_t tseq, SeqSetDev Rd, const uint32_t *
                     surv &= surv - 1ull;
                     count_failed(hh);
                     from = hh + 1;
-                    const int pos = __builtin_amdgcn_readfirstlane(s_grp[wave][hh].x);
+                    int pos = __builtin_amdgcn_readfirstlane(s_grp[wave][hh].x);
+                    int ctg = 0;
+                    if constexpr (SET) {                                    // the survivor's contig, in scalar registers
+                        ctg = __builtin_amdgcn_readfirstlane((int)set_contig(set, (uint32_t)pos));
+                        pos -= __builtin_amdgcn_readfirstlane((int)set.cum[ctg]);
+                        tbase = fetch_of_uniform(T, (uint32_t)ctg, 0, 1);
+                        clen = __builtin_amdgcn_readfirstlane((int)T.len[ctg]);
+                    }
                     const PackedFetch fa = rbase.at(j, 1);                  // a = read from j   (locator.cpp:78)
                     const PackedFetch fb = tbase.at(pos, 1);                // b = contig from pos (locator.cpp:80)
                     AlnOut o;
@@ -100,6 +138,7 @@ k_locate(IndexDev ix, SeqSetDev T, uint32_t tseq, SeqSetDev Rd, const uint32_t *
                     ncell += pair_cells(o);
                     if (o.rc > 0) {                                         // locator.cpp:82
                         found = 1; fj = j; fpos = pos; fcost = o.cost; fma = o.matlen_a; fmb = o.matlen_b; fdiag = o.diag;
+                        fctg = ctg;
                         break;
                     }
                 }
@@ -113,6 +152,7 @@ k_locate(IndexDev ix, SeqSetDev T, uint32_t tseq, SeqSetDev Rd, const uint32_t *
         row->seglen = found ? len - fj : 0; row->matlen_a = fma; row->matlen_b = fmb; row->n_pairs = npairs;
         row->diag_cost = fdiag;
         aux[r].cells = ncell; aux[r].probe_hits = nhit; aux[r].redo = redo;
+        if constexpr (SET) set.contig[r] = found ? fctg : -1;
     }
     }
 }
@@ -221,7 +261,8 @@ k_spaced_round(IndexDev ix, SeqSetDev Rf, uint32_t rseq_id, int ref_org, SeqSetD
 static void tu_attrs(pba_ctx *ctx) {
     if (ctx->attr_done & 2u) return;
     ctx->attr_done |= 2u;
-    PBA_BIG_LDS(k_locate<0>);
+    PBA_BIG_LDS((k_locate<0, false>));
+    PBA_BIG_LDS((k_locate<0, true>));
     PBA_BIG_LDS(k_spaced_round<0>);
 }
 
@@ -230,6 +271,67 @@ extern "C" {
 // ---------------------------------------------------------------------------------------------
 // host API: drivers
 // ---------------------------------------------------------------------------------------------
+// One walk of the locate kernel: the reads `subset` (host ids; nullptr = every read) against sequence target_seq of
+// `target`, or -- contig non-null, the set form -- against every sequence of it through a pba_index_build_set index.
+// rows / aux / contig are indexed by read id and sized for every read; entries of reads outside the subset are not
+// meaningful.  The launch / collect / finish protocol both drivers share (narrow_then_redo).
+static int locate_walk(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, uint32_t target_seq, const pba_seqs *reads,
+                       const uint32_t *subset, uint32_t n_subset, double R, int trials, int min_len, int maxn, int maxm,
+                       int kernel, pba_loc_row *rows, std::vector<LocAux> &aux, int32_t *contig, hipEvent_t packed) {
+    HIPCHK(hipSetDevice(ctx->device));
+    tu_attrs(ctx);
+    const uint32_t n = reads->n, n_first = subset ? n_subset : n;
+    aux.assign((size_t)n + 1, LocAux{0, 0, 0});
+    Plan pl;
+    int st = make_plan(ctx, R, maxn, maxm, kernel, 1 + (int)(reads->max_len * R), &pl);
+    if (st != PBA_OK) return st;
+    if (packed) HIPCHK(hipStreamWaitEvent(ctx->stream, packed, 0));
+    BufRef d_rows, d_aux, d_sub, d_ctg;                        // (pooled in the ctx: two hipMalloc / hipFree pairs were 1 ms of a 50 ms step)
+    POOL(POOL_LOC_ROWS, sizeof(pba_loc_row) * ((size_t)n + 1), d_rows.p);
+    POOL(POOL_LOC_AUX, sizeof(LocAux) * ((size_t)n + 1), d_aux.p);
+    if (contig) POOL(POOL_LOC_CTG, sizeof(int32_t) * ((size_t)n + 1), d_ctg.p);
+    if (subset && n_subset) {
+        POOL(POOL_LOC_IDS, sizeof(uint32_t) * n_subset, d_sub.p);
+        HIPCHK(hipMemcpyAsync(d_sub.p, subset, sizeof(uint32_t) * n_subset, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const LocSet set = {contig ? ix->d_cum : nullptr, contig ? ix->n_seqs : 0u, d_ctg.as<int32_t>()};
+    auto launch = [&](int nb, const uint32_t *ids, uint32_t cnt) {
+#define PBA_LOC_LAUNCH_AS(NBV, SETV)                                                                                 \
+    hipLaunchKernelGGL((k_locate<NBV, SETV>), dim3(persistent_grid(ctx, cnt, Wpb<NBV>::v, pl.lds)),                   \
+                       dim3(PBA_WAVE * Wpb<NBV>::v), pl.lds * Wpb<NBV>::v, ctx->stream, ix->dev(), target->dev(),     \
+                       target_seq, reads->dev(), ids, cnt, trials, min_len, pl.cfg, d_rows.as<pba_loc_row>(),        \
+                       d_aux.as<LocAux>(), ctx->d_queue, set)
+#define PBA_LOC_LAUNCH(NBV) do { if (contig) PBA_LOC_LAUNCH_AS(NBV, true); else PBA_LOC_LAUNCH_AS(NBV, false); } while (0)
+        PBA_DISPATCH_NB(nb, PBA_LOC_LAUNCH);
+#undef PBA_LOC_LAUNCH
+#undef PBA_LOC_LAUNCH_AS
+    };
+    auto collect = [&](std::vector<uint32_t> &redo) {         // reads with an uncertified pair: walk them again at the reference band
+        HIPCHK(hipMemcpyAsync(aux.data(), d_aux.p, sizeof(LocAux) * n, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (!subset) { for (uint32_t r = 0; r < n; ++r) if (aux[r].redo) redo.push_back(r); }
+        else for (uint32_t k = 0; k < n_subset; ++k) if (aux[subset[k]].redo) redo.push_back(subset[k]);
+        return (int)PBA_OK;
+    };
+    auto finish = [&](bool redone) {
+        if (redone) HIPCHK(hipMemcpyAsync(aux.data(), d_aux.p, sizeof(LocAux) * n, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(rows, d_rows.p, sizeof(pba_loc_row) * n, hipMemcpyDeviceToHost, ctx->stream));
+        if (contig) HIPCHK(hipMemcpyAsync(contig, d_ctg.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        return (int)PBA_OK;
+    };
+    if (!n_first) return PBA_OK;
+    return narrow_then_redo(ctx, pl, subset ? d_sub.as<uint32_t>() : nullptr, n_first, launch, collect, finish);
+}
+
+// what both drivers refuse about the sets of a walk
+static int locate_sets_ok(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *reads, const char *alphabet_msg) {
+    if (reads->max_len > (uint32_t)kMaxSeqLen) PBA_FAIL(PBA_E_TOOLONG, "read longer than the engine limit");
+    if (target->non_acgt || reads->non_acgt)   // locator.cpp compares raw bytes (an 'N' only matches an 'N'); codes would match it to T
+        PBA_FAIL(PBA_E_ALPHABET, alphabet_msg);
+    return PBA_OK;
+}
+
 // The one locate driver.  pba_locate runs it on a resident set (bases 0, no event); a pba_loc_stream runs it per batch:
 // rows[i].read = read_base + i, the running id of locator.cpp:72,91 starts at nseq_base, and the ctx's stream first waits
 // for `packed` (the event behind the batch's pack on the stream's own copy stream).
@@ -239,43 +341,10 @@ int locate_core(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, uint3
     if (!ctx || !ix || !target || !reads || !rows || target_seq >= target->n || trials < 0) return PBA_E_INVALID;
     if (ix->mode != PBA_INDEX_ALL || ix->seq_len != target->h_len[target_seq])
         PBA_FAIL(PBA_E_INVALID, "pba_locate needs a PBA_INDEX_ALL index of the target sequence");
-    if (reads->max_len > (uint32_t)kMaxSeqLen) PBA_FAIL(PBA_E_TOOLONG, "read longer than the engine limit");
-    if (target->non_acgt || reads->non_acgt)   // locator.cpp compares raw bytes (an 'N' only matches an 'N'); codes would match it to T
-        PBA_FAIL(PBA_E_ALPHABET, "pba_locate: a sequence set holds bytes outside ACGT");
-    HIPCHK(hipSetDevice(ctx->device));
-    tu_attrs(ctx);
+    PBA_TRY(locate_sets_ok(ctx, target, reads, "pba_locate: a sequence set holds bytes outside ACGT"));
     const uint32_t n = reads->n;
-    Plan pl;
-    int st = make_plan(ctx, R, maxn, maxm, kernel, 1 + (int)(reads->max_len * R), &pl);
-    if (st != PBA_OK) return st;
-    if (packed) HIPCHK(hipStreamWaitEvent(ctx->stream, packed, 0));
-    BufRef d_rows, d_aux;                                      // (pooled in the ctx: two hipMalloc / hipFree pairs were 1 ms of a 50 ms step)
-    POOL(POOL_LOC_ROWS, sizeof(pba_loc_row) * ((size_t)n + 1), d_rows.p);
-    POOL(POOL_LOC_AUX, sizeof(LocAux) * ((size_t)n + 1), d_aux.p);
-    std::vector<LocAux> aux(n + 1);
-    auto launch = [&](int nb, const uint32_t *ids, uint32_t cnt) {
-#define PBA_LOC_LAUNCH(NBV)                                                                                          \
-    hipLaunchKernelGGL(k_locate<NBV>, dim3(persistent_grid(ctx, cnt, Wpb<NBV>::v, pl.lds)),                           \
-                       dim3(PBA_WAVE * Wpb<NBV>::v), pl.lds * Wpb<NBV>::v, ctx->stream, ix->dev(), target->dev(),     \
-                       target_seq, reads->dev(), ids, cnt, trials, min_len, pl.cfg, d_rows.as<pba_loc_row>(),        \
-                       d_aux.as<LocAux>(), ctx->d_queue)
-        PBA_DISPATCH_NB(nb, PBA_LOC_LAUNCH);
-#undef PBA_LOC_LAUNCH
-    };
-    auto collect = [&](std::vector<uint32_t> &redo) {         // reads with an uncertified pair: walk them again at the reference band
-        HIPCHK(hipMemcpyAsync(aux.data(), d_aux.p, sizeof(LocAux) * n, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        for (uint32_t r = 0; r < n; ++r)
-            if (aux[r].redo) redo.push_back(r);
-        return (int)PBA_OK;
-    };
-    auto finish = [&](bool redone) {
-        if (redone) HIPCHK(hipMemcpyAsync(aux.data(), d_aux.p, sizeof(LocAux) * n, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(rows, d_rows.p, sizeof(pba_loc_row) * n, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        return (int)PBA_OK;
-    };
-    if (n && (st = narrow_then_redo(ctx, pl, nullptr, n, launch, collect, finish)) != PBA_OK) return st;
+    std::vector<LocAux> aux;
+    PBA_TRY(locate_walk(ctx, ix, target, target_seq, reads, nullptr, 0, R, trials, min_len, maxn, maxm, kernel, rows, aux, nullptr, packed));
     pba_loc_stats s = {0, 0, 0, 0, 0};
     int64_t nseq = nseq_base;
     for (uint32_t r = 0; r < n; ++r) {
@@ -295,6 +364,95 @@ int pba_locate(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, uint32
                double R, int trials, int min_len, int maxn, int maxm, int kernel, pba_loc_row *rows,
                pba_loc_stats *stats) {
     return locate_core(ctx, ix, target, target_seq, reads, R, trials, min_len, maxn, maxm, kernel, rows, stats, 0, 0, nullptr);
+}
+
+// locator.cpp:70-92 against every sequence of a set and on both strands of the reads: the + walk over all reads, the - walk
+// (rc(read), an id list over the full reads_rc set) over the reads the + walk left, first success in that order.
+int pba_map_reads(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
+                  double R, int trials, int min_len, int maxn, int maxm, int kernel, int strands, pba_map_row *rows,
+                  pba_map_stats *stats) {
+    if (!ctx || !ix || !target || !reads || trials < 0 || strands < 1 || strands > 3) return PBA_E_INVALID;
+    const uint32_t n = reads->n;
+    if (!rows && n) return PBA_E_INVALID;
+    if (reads_rc && (reads_rc->n != n || reads_rc->h_len != reads->h_len))
+        PBA_FAIL(PBA_E_INVALID, "pba_map_reads: reads_rc differs from reads in count or lengths");
+    uint64_t total = 0;
+    for (uint32_t c = 0; c < target->n; ++c) total += target->h_len[c];
+    bool same = ix->mode == PBA_INDEX_ALL && ix->d_cum && ix->n_seqs == target->n && ix->seq_len == total;
+    for (uint32_t c = 0; same && c < target->n; ++c) same = ix->h_cum[c + 1] - ix->h_cum[c] == target->h_len[c];
+    if (!same)
+        PBA_FAIL(PBA_E_INVALID, "pba_map_reads needs a pba_index_build_set index of the target set");
+    PBA_TRY(locate_sets_ok(ctx, target, reads, "pba_map_reads: a sequence set holds bytes outside ACGT"));
+    if (reads_rc) PBA_TRY(locate_sets_ok(ctx, target, reads_rc, "pba_map_reads: a sequence set holds bytes outside ACGT"));
+    struct Own { pba_seqs *rc = nullptr; ~Own() { pba_seqs_destroy(rc); } } own;
+    if ((strands & 2) && !reads_rc) {
+        PBA_TRY(pba_seqs_revcomp(ctx, reads, nullptr, &own.rc));
+        reads_rc = own.rc;
+    }
+    pba_map_stats ms;
+    memset(&ms, 0, sizeof ms);
+    std::vector<pba_loc_row> lr[2];
+    std::vector<int32_t> ctg[2];
+    std::vector<LocAux> aux[2];
+    std::vector<uint32_t> second;
+    const bool have[2] = {(strands & 1) != 0, (strands & 2) != 0};
+    pba_profile prof;                                          // of the call: the two walks summed
+    memset(&prof, 0, sizeof prof);
+    for (int k = 0; k < 2; ++k) {
+        if (!have[k]) continue;
+        const bool sub = k == 1 && have[0];                    // the - walk of strands == 3: only what the + walk left
+        if (sub) {
+            for (uint32_t r = 0; r < n; ++r)
+                if ((int)reads->h_len[r] >= min_len && !lr[0][r].found) second.push_back(r);
+            ms.n_second_walk = (uint32_t)second.size();
+        }
+        lr[k].resize((size_t)n + 1); ctg[k].assign((size_t)n + 1, -1);
+        PBA_TRY(locate_walk(ctx, ix, target, 0, k ? reads_rc : reads, sub ? second.data() : nullptr, (uint32_t)second.size(), R,
+                            trials, min_len, maxn, maxm, kernel, lr[k].data(), aux[k], ctg[k].data(), nullptr));
+        if (sub ? !second.empty() : n != 0) {
+            const pba_profile &w = ctx->prof;
+            prof.align_ms += w.align_ms; prof.align_redo_ms += w.align_redo_ms; prof.n_first += w.n_first; prof.n_redo += w.n_redo;
+            prof.nb_first = std::max(prof.nb_first, w.nb_first); prof.nb_redo = std::max(prof.nb_redo, w.nb_redo);
+        }
+    }
+    prof.index_ms = ctx->prof.index_ms;
+    ctx->prof = prof;
+    std::vector<uint8_t> walked(n, 0);
+    for (uint32_t r : second) walked[r] = 1;
+    int32_t nseq = 0;
+    for (uint32_t r = 0; r < n; ++r) {
+        pba_map_row &o = rows[r];
+        const int len = (int)reads->h_len[r];
+        const bool kept = len >= min_len;
+        const pba_loc_row *win = nullptr;
+        int wk = -1;
+        int32_t npairs = 0;
+        for (int k = 0; k < 2; ++k) {
+            if (!have[k] || (k == 1 && have[0] && !walked[r])) continue;
+            const pba_loc_row &w = lr[k][r];
+            pba_loc_stats &s = ms.strand[k];
+            if (kept) ++s.n_reads_kept;
+            s.n_pairs += w.n_pairs; s.n_located += w.found; s.n_probe_hits += aux[k][r].probe_hits; s.n_cells += aux[k][r].cells;
+            npairs += w.n_pairs;
+            if (!win || (!win->found && w.found)) { win = &w; wk = k; }
+        }
+        o.read = (int32_t)r;
+        o.nseq = kept ? nseq++ : -1;                                               // locator.cpp:72,91
+        o.found = win->found;
+        o.strand = win->found ? (wk ? -1 : 1) : 0;
+        o.contig = win->found ? ctg[wk][r] : -1;
+        o.j = win->j; o.pos = win->pos; o.cost = win->cost; o.seglen = win->seglen; o.matlen_a = win->matlen_a;
+        o.matlen_b = win->matlen_b; o.diag_cost = win->diag_cost;
+        o.n_pairs = npairs;
+        o.r_beg = o.r_end = o.c_beg = o.c_end = 0;
+        if (win->found) {
+            o.r_beg = wk ? len - win->j - win->matlen_a : win->j;
+            o.r_end = wk ? len - win->j : win->j + win->matlen_a;
+            o.c_beg = win->pos; o.c_end = win->pos + win->matlen_b;
+        }
+    }
+    if (stats) *stats = ms;
+    return PBA_OK;
 }
 
 // One locked round over the reads `subset` (host ids; nullptr = every read).  rows is indexed by read id: rows of

@@ -92,6 +92,11 @@ struct pba_index {
     uint64_t n_entries;
     uint64_t *d_ent;
     uint32_t *d_part_off;
+    // pba_index_build_set: the sequences indexed and cum[0 .. n_seqs] = the exclusive prefix sum of their lengths -- an entry's
+    // ordinal is the global position cum[c] + pos.  pba_index_build: n_seqs = 1, no cum.
+    uint32_t n_seqs;
+    uint32_t *d_cum;
+    std::vector<uint32_t> h_cum;
     IndexDev dev() const { return IndexDev{d_ent, d_part_off, logP, mask, nhead, tail_top}; }
 };
 
@@ -118,7 +123,7 @@ static const size_t kSlack = 1024;              // readable bytes before the fir
 // pool slots
 enum { POOL_OVL_CAND = 0, POOL_OVL_TMP, POOL_OVL_ITEMS, POOL_OVL_REDO, POOL_OVL_REDO_IN, POOL_OVL_OUT, POOL_OVL_SMALL,
        POOL_LOC_ROWS, POOL_LOC_AUX, POOL_REDO_IDS, POOL_IX_OFFS, POOL_IX_WORK, POOL_OVL_BLOOM, POOL_OVL_ENDS,
-       POOL_TXT_IN, POOL_TXT_OUT, POOL_TXT_PAR, POOL_TXT_CST };
+       POOL_TXT_IN, POOL_TXT_OUT, POOL_TXT_PAR, POOL_TXT_CST, POOL_LOC_IDS, POOL_LOC_CTG };
 // a buffer of at least `bytes` in pool slot `slot` (contents undefined); grows by reallocation with 1/8 headroom
 static inline int pool_reserve(pba_ctx *ctx, int slot, size_t bytes, void **out) {
     if (ctx->pool[slot].cap < bytes) {

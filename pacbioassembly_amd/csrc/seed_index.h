@@ -317,6 +317,57 @@ k_seed_emit(const uint8_t *seq, uint32_t len, uint32_t mask, ScanSeg sg, uint64_
     }
 }
 
+// ... and the set form (pba_index_build_set): EVERY sequence of a set in one launch.  A workgroup takes one entry of a
+// host-built tile table -- (sequence, first chunk): PBA_IX_TILE_THREADS x PBA_IX_TILE_ITERS chunks of one sequence, so a
+// window is padded from its own sequence's length and never sees a neighbour's bases -- and an entry's ordinal is the global
+// position cum[sequence] + pos.  Chunk loop, padding rule and reservation are k_seed_emit's.
+struct SetTile { uint32_t seq, chunk0; };
+static __global__ void __launch_bounds__(PBA_IX_TILE_THREADS)
+k_seed_emit_set(const uint8_t *packed, const uint64_t *off, const uint32_t *lens, const uint32_t *cum, const SetTile *tiles,
+                uint32_t mask, uint64_t *out, unsigned long long cap, unsigned long long *counter) {
+    __shared__ uint32_t wg_count, wg_base_lo, wg_base_hi;
+    if (threadIdx.x == 0) wg_count = 0;
+    __syncthreads();
+    const SetTile t = tiles[blockIdx.x];
+    const uint8_t *seq = packed + off[t.seq];
+    const uint32_t len = lens[t.seq], g0 = cum[t.seq];
+    uint64_t be[PBA_IX_TILE_ITERS];
+    uint32_t mine = 0;
+    for (int it = 0; it < PBA_IX_TILE_ITERS; ++it) {
+        const uint32_t chunk = t.chunk0 + it * PBA_IX_TILE_THREADS + threadIdx.x;
+        be[it] = 0;
+        if ((uint64_t)chunk * 16 >= len) continue;
+        be[it] = chunk_bits(seq, chunk);
+#pragma unroll
+        for (uint32_t k = 0; k < 16; ++k) {
+            const uint32_t pos = chunk * 16 + k;
+            if (pos >= len) continue;
+            if (chunk_key(be[it], k, pos, len, mask)) ++mine;
+        }
+    }
+    uint32_t slot = mine ? atomicAdd(&wg_count, mine) : 0u;      // LDS-staged reservation: one global atomic per workgroup
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned long long b = wg_count ? atomicAdd(counter, (unsigned long long)wg_count) : 0ull;
+        wg_base_lo = (uint32_t)b; wg_base_hi = (uint32_t)(b >> 32);
+    }
+    __syncthreads();
+    unsigned long long o = ((unsigned long long)wg_base_hi << 32 | wg_base_lo) + slot;
+    for (int it = 0; it < PBA_IX_TILE_ITERS; ++it) {
+        const uint32_t chunk = t.chunk0 + it * PBA_IX_TILE_THREADS + threadIdx.x;
+        if ((uint64_t)chunk * 16 >= len) continue;
+#pragma unroll
+        for (uint32_t k = 0; k < 16; ++k) {
+            const uint32_t pos = chunk * 16 + k;
+            if (pos >= len) continue;
+            const uint32_t key = chunk_key(be[it], k, pos, len, mask);
+            if (!key) continue;
+            if (o < cap) out[o] = (uint64_t)key << 32 | (g0 + pos);
+            ++o;
+        }
+    }
+}
+
 // In-place inclusive scan of a[0 .. n) in three launches: tiles of PBA_SCAN_TILE per workgroup, the tile sums by one
 // workgroup, the carry-in added back.  (2^24 - 2^26 bucket counters, once per probe table.)
 #define PBA_SCAN_TILE 2048

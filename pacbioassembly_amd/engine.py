@@ -13,13 +13,17 @@ import numpy as np
 
 from . import _lib
 from ._lib import (PBA_INDEX_ALL, PBA_INDEX_HEAD_TAIL, PBA_KERNEL_AUTO, PBA_KERNEL_BITVEC, PBA_KERNEL_ROWSWEEP,
-                   PBA_STREAM_RECORDS, PBA_STREAM_TEXT, PbaLocRow, PbaLocStats, PbaPair, PbaResult, PbaSsRow)
+                   PBA_STREAM_RECORDS, PBA_STREAM_TEXT, PbaLocRow, PbaLocStats, PbaMapRow, PbaMapStats, PbaPair, PbaResult, PbaSsRow)
 
 PAIR_DTYPE = np.dtype([("a_seq", "<u4"), ("a_pos", "<i4"), ("a_len", "<i4"), ("b_seq", "<u4"), ("b_pos", "<i4"),
                        ("b_len", "<i4"), ("flags", "<u4")])
 RESULT_DTYPE = np.dtype([(n, "<i4") for n in ("rc", "cost", "matlen_a", "matlen_b", "len_a", "len_b", "max_dst", "diag_cost")])
 LOC_ROW_DTYPE = np.dtype([(n, "<i4") for n in
                           ("read", "nseq", "found", "j", "pos", "cost", "seglen", "matlen_a", "matlen_b", "n_pairs", "diag_cost")])
+# pba_map_row: a locate row with its strand, its contig and half-open intervals on the forward strand of read and contig
+MAP_ROW_DTYPE = np.dtype([(n, "<i4") for n in
+                          ("read", "nseq", "found", "strand", "contig", "j", "pos", "cost", "seglen", "matlen_a", "matlen_b",
+                           "diag_cost", "n_pairs", "r_beg", "r_end", "c_beg", "c_end")])
 SS_ROW_DTYPE = np.dtype([(n, "<i4") for n in
                          ("read", "found", "j", "dir", "ref_pos", "cost", "matlen_a", "matlen_b", "n_trials",
                           "n_pairs")])
@@ -31,6 +35,7 @@ STRAND_OVERLAP_DTYPE = np.dtype([(n, "<i4") for n in ("target", "query", "strand
 CORRECT_ROW_DTYPE = np.dtype([(n, "<i4") for n in ("target", "n_rows", "len_in", "len_out")])
 assert PAIR_DTYPE.itemsize == C.sizeof(PbaPair) and RESULT_DTYPE.itemsize == C.sizeof(PbaResult)
 assert LOC_ROW_DTYPE.itemsize == C.sizeof(PbaLocRow) and SS_ROW_DTYPE.itemsize == C.sizeof(PbaSsRow)
+assert MAP_ROW_DTYPE.itemsize == C.sizeof(PbaMapRow)
 
 
 class PbaError(RuntimeError):
@@ -235,6 +240,12 @@ class Context:
         self.check(self.lib.pba_index_build(self.h, target.h, seq, mask, mode, C.byref(h)), "index_build")
         return SeedIndex(self, h)
 
+    def index_build_set(self, target: "SeqSet", mask: int) -> "SeedIndex":
+        """PBA_INDEX_ALL over every sequence of `target` (pba_index_build_set): hits are global positions, for map_reads."""
+        h = C.c_void_p()
+        self.check(self.lib.pba_index_build_set(self.h, target.h, mask, C.byref(h)), "index_build_set")
+        return SeedIndex(self, h)
+
     def index_scan(self, target: "SeqSet", seq: int, mask: int, mode: int, part: int, nparts: int,
                    d_entries_ptr: int, cap: int) -> int:
         """Rank `part`'s slice of the index entries into a device buffer; returns how many were written."""
@@ -325,6 +336,19 @@ class Context:
         self.check(self.lib.pba_locate(self.h, ix.h, target.h, target_seq, reads.h, R, trials, min_len, maxn, maxm,
                                        kernel, _ptr(rows), C.byref(stats)), "locate")
         return rows[:reads.count], {n: getattr(stats, n) for n, _ in PbaLocStats._fields_}
+
+    def map_reads(self, ix: "SeedIndex", target: "SeqSet", reads: "SeqSet", R: float, trials: int = 50, min_len: int = 500,
+                  maxn: int = 0, maxm: int = 0, kernel: int = PBA_KERNEL_AUTO, strands: int = 3,
+                  reads_rc: Optional["SeqSet"] = None):
+        """Locate against every sequence of `target` (ix: index_build_set of it) on the strands asked for (pba_map_reads):
+        1 = the reads as given, 2 = their reverse complement, 3 = + first, then - for what + left.  Returns (rows of
+        MAP_ROW_DTYPE, {"strand": [stats of the + walk, of the - walk], "n_second_walk": n})."""
+        rows = np.zeros(max(reads.count, 1), MAP_ROW_DTYPE)
+        st = PbaMapStats()
+        self.check(self.lib.pba_map_reads(self.h, ix.h, target.h, reads.h, reads_rc.h if reads_rc is not None else None, R, trials,
+                                          min_len, maxn, maxm, kernel, strands, _ptr(rows), C.byref(st)), "map_reads")
+        per = [{n: getattr(st.strand[k], n) for n, _ in PbaLocStats._fields_} for k in range(2)]
+        return rows[:reads.count], {"strand": per, "n_second_walk": int(st.n_second_walk)}
 
     def spaced_round(self, ix: "SeedIndex", ref: "SeqSet", ref_seq: int, reads: "SeqSet", R: float,
                      max_trial: int = 32, overlap_min: int = 64, buggy_seed_at: bool = False,
@@ -909,6 +933,11 @@ class SeedIndex:
     @property
     def visited(self) -> int:
         return self.ctx.lib.pba_index_visited(self.h)
+
+    @property
+    def seqs(self) -> int:
+        """Sequences the index covers (pba_index_seqs): 1 unless it was made by Context.index_build_set."""
+        return self.ctx.lib.pba_index_seqs(self.h)
 
     def dump(self):
         n = self.entries
