@@ -610,7 +610,9 @@ int pba_overlap_row_pair(const pba_strand_overlap *row, uint32_t target_len, uin
  * dword: a selection counter holds weight + votes <= 65 535 (a vote beyond that would carry into the neighbouring counter
  * instead of wrapping like the reference's unsigned short), so keep weight small next to 65 535 - coverage.  Box indices are 32-bit inside the kernels: a range of 2^31 bases or more is refused with PBA_E_TOOLONG
  * (pba_correct_reads goes through such a range in chunks).  weight: the selection count of the read's own base, in
- * [1, 0xFFFF] (with 0 a read without rows would evolve to nothing). */
+ * [1, 0xFFFF] (with 0 a read without rows would evolve to nothing).  `reads` may be any set, a set of contigs included: a
+ * pile-up with a segment of more than 65 536 boxes is filled and evolved tile by tile (4 096 boxes per workgroup), byte for
+ * byte what the per-target kernels give. */
 typedef struct pba_pileup pba_pileup;
 int pba_pileup_create(pba_ctx *ctx, const pba_seqs *reads, uint32_t t_lo, uint32_t t_hi, int weight, pba_pileup **out);
 void pba_pileup_destroy(pba_pileup *p);
@@ -659,6 +661,61 @@ typedef struct {
     uint64_t n_bases_in, n_bases_out;
 } pba_correct_profile;
 int pba_ctx_last_correct_profile(const pba_ctx *ctx, pba_correct_profile *out);
+
+/* ------------------------------------------------------------------------ */
+/* Polishing a contig set from its mapped reads: the reads pba_map_reads      */
+/* places on a contig vote on that contig, evolve gives the next contig, and  */
+/* the loop repeats -- what ref_seq::try_align + evolve do for one growing    */
+/* reference (ref_seq.h:259-276, 317-349), for a whole set at once.           */
+/* ------------------------------------------------------------------------ */
+/* Host arithmetic, no ctx: the pair a found pba_map_row votes with, in try_align's roles (ref_seq.h:264: the boxes belong to
+ * a, the voted characters are b's) -- the mapper found the row with the read as a and the contig as b (locator.cpp:78-82):
+ *   a_seq = row->contig, forward from row->pos;  b_seq = row->read, forward from row->j, b_len = read_len - j
+ *   a_len = min(contig_len - pos, b_len + max_dst), max_dst = 1 + (int)(b_len * R)
+ * For a strand -1 row b indexes the set of reverse-complemented reads (j is in rc(read)'s coordinates already).  The clip of
+ * a loses nothing: align itself cuts len_a to len_b + max_dst whenever a is the longer side (seq_aligner.h:94-102), and the
+ * clipped length stays above b_len, so the same branch is taken; it is made here because an accessor is limited to 65 000
+ * elements and a contig remainder is megabases long.  PBA_E_INVALID: a NULL, found == 0, a strand other than +1 / -1, j or
+ * pos outside its sequence, R outside (0, 1).  PBA_E_TOOLONG: an accessor (the clipped a, or b) beyond the engine's limit. */
+int pba_map_row_pair(const pba_map_row *row, uint32_t contig_len, uint32_t read_len, double R, pba_pair *out);
+/* Vote n pba_map_reads rows into p = pba_pileup_create(ctx, target, c_lo, c_hi, weight): `target` is the contig set the
+ * pile-up was made from (count and lengths are checked), reads / reads_rc the sets the rows were mapped from (reads_rc may
+ * be NULL if no row has strand -1).  Rows with found == 0 are skipped (res[k] zeroed, rc = -1); every other row's contig
+ * must lie in [c_lo, c_hi).  The +1 rows and the -1 rows are two batches.  The gate is try_align's (ref_seq.h:264-265): a
+ * pair votes if and only if it aligns (rc >= 0) with matlen_a >= overlap_min.  The alignment has its roles swapped against
+ * the one the mapper ran, so it is NOT held to the row's cost or match lengths: a found row may legitimately not vote.
+ * res[k] (nullable) as pba_align_batch returns it; *n_voted (nullable) = rows that voted; the per-target n_rows that
+ * pba_pileup_evolve reports count voted rows only.  No growth (append / prepend are not applied), so votes commute.
+ * Everything the host can check -- range, sets, accessors, PBA_E_ALPHABET, PBA_E_TOOLONG -- is checked before any vote and
+ * leaves the boxes as they were; after a later failure the pile-up is spent under the rules of pba_pileup_vote. */
+int pba_pileup_vote_mapped(pba_ctx *ctx, pba_pileup *p, const pba_seqs *target, const pba_seqs *reads,
+                           const pba_seqs *reads_rc /* nullable if no row has strand -1 */, const pba_map_row *rows, uint64_t n,
+                           double R, int overlap_min, pba_result *res /* nullable */, uint64_t *n_voted /* nullable */);
+typedef struct { int32_t contig, n_rows, len_in, len_out; } pba_polish_row;      /* per contig, last round */
+typedef struct {
+    int32_t round;                 /* 1-based */
+    uint32_t n_mapped, n_voted, n_chunks;   /* found rows, rows that voted, pile-ups of the round */
+    uint64_t n_bases_in, n_bases_out;
+    float index_ms, map_ms, vote_ms, evolve_ms;   /* HIP events on the ctx's stream */
+} pba_polish_round_log;
+/* `rounds` (>= 1) times: pba_index_build_set of the current contigs, pba_map_reads of the reads on them (R, trials, min_len,
+ * maxn, maxm, kernel, strands as there), pile-ups over consecutive contig ranges (the budget of pba_correct_reads: 20 bytes
+ * per base, a quarter of the free device memory, fewer than 2^31 boxes; a range always holds at least one contig, and a
+ * single contig whose boxes do not fit is PBA_E_NOMEM), pba_pileup_vote_mapped of each range's rows, evolve, and the texts
+ * stitched into the next set on the device.  *polished: the contigs after the last round as a NEW set, contig ids
+ * unchanged: a contig that evolves to nothing stays as an empty contig, one without voted rows comes back as it was.  The
+ * caller's target is never modified.  reads_rc: pba_seqs_revcomp(reads, NULL), or NULL to have it built once inside when
+ * strands include -1.  rows_out (nullable): one entry per contig, of the last round.  log (nullable with log_cap 0): entry
+ * k describes round k + 1, up to log_cap.  The answer does not depend on how the contigs are cut into ranges. */
+int pba_polish_contigs(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc /* nullable */,
+                       uint32_t mask, double R, int trials, int min_len, int maxn, int maxm, int kernel, int strands,
+                       int overlap_min, int weight, int rounds, pba_seqs **polished, pba_polish_row *rows_out,
+                       pba_polish_round_log *log, int log_cap);
+/* The same with a ceiling on the boxes of one range (max_boxes bases; 0 = none), as pba_correct_reads_budget */
+int pba_polish_contigs_budget(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc /* nullable */,
+                              uint32_t mask, double R, int trials, int min_len, int maxn, int maxm, int kernel, int strands,
+                              int overlap_min, int weight, int rounds, uint64_t max_boxes, pba_seqs **polished,
+                              pba_polish_row *rows_out, pba_polish_round_log *log, int log_cap);
 
 const char *pba_strerror(int status);
 

@@ -55,6 +55,12 @@ class PbaProfile(C.Structure):
                 ("nb_first", C.c_uint32), ("nb_redo", C.c_uint32), ("n_first", C.c_uint32), ("n_redo", C.c_uint32)]
 
 
+class PbaPolishRoundLog(C.Structure):
+    _fields_ = [("round", C.c_int32), ("n_mapped", C.c_uint32), ("n_voted", C.c_uint32), ("n_chunks", C.c_uint32),
+                ("n_bases_in", C.c_uint64), ("n_bases_out", C.c_uint64), ("index_ms", C.c_float), ("map_ms", C.c_float),
+                ("vote_ms", C.c_float), ("evolve_ms", C.c_float)]
+
+
 class PbaCorrectProfile(C.Structure):
     _fields_ = [("overlap_ms", C.c_float), ("vote_ms", C.c_float), ("evolve_ms", C.c_float), ("n_chunks", C.c_uint32),
                 ("n_rows", C.c_uint64), ("n_bases_in", C.c_uint64), ("n_bases_out", C.c_uint64)]
@@ -180,6 +186,12 @@ SYMBOLS = {
     "pba_correct_reads_budget": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_int, C.c_int, C.c_int,
                                            C.c_int, C.c_int, C.c_uint64, C.POINTER(_P), _P, _P]),
     "pba_ctx_last_correct_profile": (C.c_int, [_P, _P]),
+    "pba_map_row_pair": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_double, _P]),
+    "pba_pileup_vote_mapped": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_double, C.c_int, _P, C.POINTER(C.c_uint64)]),
+    "pba_polish_contigs": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_int, C.c_int, C.c_int, C.POINTER(_P), _P, _P, C.c_int]),
+    "pba_polish_contigs_budget": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(_P), _P, _P, C.c_int]),
     "pba_strerror": (C.c_char_p, [C.c_int]),
 }
 

@@ -38,31 +38,25 @@ k_pile_fill(SeqSetDev S, uint32_t k0, VoteInto P, int weight) {
     }
 }
 
-// count pass: len_out[k] = characters target k evolves to
-static __global__ void __launch_bounds__(256)
-k_pile_count(VoteInto P, uint32_t k0, int *len_out) {
+// characters boxes [first, first + len) evolve to, by one workgroup of 256 threads (the sum is returned to every thread)
+static __device__ __forceinline__ int pile_block_count(const ConsDev &C, unsigned long long first, unsigned long long len) {
     __shared__ int part[4];
-    const uint32_t k = k0 + blockIdx.x;
-    const unsigned long long first = P.box_off[k], len = P.box_off[k + 1] - first;
     int mine = 0;
     for (unsigned long long i = threadIdx.x; i < len; i += 256) {
-        const int y = cons_yield(P.C.sel[first + i], P.C.sup[first + i], P.C.tot[first + i]);
+        const int y = cons_yield(C.sel[first + i], C.sup[first + i], C.tot[first + i]);
         mine += (y & 1) + (y >> 1);
     }
     const int w = wave_sum_i32(mine);                          // every lane is here: the loop has ended for all of them
     if ((threadIdx.x & (PBA_WAVE - 1)) == 0) part[threadIdx.x / PBA_WAVE] = w;
     __syncthreads();
-    if (threadIdx.x == 0) len_out[k] = part[0] + part[1] + part[2] + part[3];
+    return part[0] + part[1] + part[2] + part[3];
 }
 
-// write pass: the text of target k at text[text_off[k] ..), 256 boxes per step.  A box yields at most two characters, so the
-// offsets inside a step are two ballots and two popcounts per lane plus the totals of the wavefronts before it in LDS.
-static __global__ void __launch_bounds__(256)
-k_pile_write(VoteInto P, uint32_t k0, const unsigned long long *text_off, char *text) {
+// The text of boxes [first, first + len) at out[0 ..), by one workgroup, 256 boxes per step.  A box yields at most two
+// characters, so the offsets inside a step are two ballots and two popcounts per lane plus the totals of the wavefronts
+// before it in LDS.
+static __device__ __forceinline__ void pile_block_write(const ConsDev &C, unsigned long long first, unsigned long long len, char *out) {
     __shared__ int part[4];
-    const uint32_t k = k0 + blockIdx.x;
-    const unsigned long long first = P.box_off[k], len = P.box_off[k + 1] - first;
-    char *out = text + text_off[k];
     const int lane = threadIdx.x & (PBA_WAVE - 1), wave = threadIdx.x / PBA_WAVE;
     const unsigned long long below = (1ull << lane) - 1ull;
     unsigned long long done = 0;                               // characters written by the steps before this one
@@ -70,7 +64,7 @@ k_pile_write(VoteInto P, uint32_t k0, const unsigned long long *text_off, char *
         const unsigned long long i = base + threadIdx.x;
         unsigned long long sel = 0, sup = 0;
         int y = 0;
-        if (i < len) { sel = P.C.sel[first + i]; sup = P.C.sup[first + i]; y = cons_yield(sel, sup, P.C.tot[first + i]); }
+        if (i < len) { sel = C.sel[first + i]; sup = C.sup[first + i]; y = cons_yield(sel, sup, C.tot[first + i]); }
         const unsigned long long mv = __builtin_amdgcn_ballot_w64((y & 1) != 0), ms = __builtin_amdgcn_ballot_w64((y & 2) != 0);
         if (lane == 0) part[wave] = __builtin_popcountll(mv) + __builtin_popcountll(ms);
         __syncthreads();
@@ -85,6 +79,61 @@ k_pile_write(VoteInto P, uint32_t k0, const unsigned long long *text_off, char *
     }
 }
 
+// count pass: len_out[k] = characters target k evolves to
+static __global__ void __launch_bounds__(256)
+k_pile_count(VoteInto P, uint32_t k0, int *len_out) {
+    const uint32_t k = k0 + blockIdx.x;
+    const unsigned long long first = P.box_off[k];
+    const int n = pile_block_count(P.C, first, P.box_off[k + 1] - first);
+    if (threadIdx.x == 0) len_out[k] = n;
+}
+
+// write pass: the text of target k at text[text_off[k] ..)
+static __global__ void __launch_bounds__(256)
+k_pile_write(VoteInto P, uint32_t k0, const unsigned long long *text_off, char *text) {
+    const uint32_t k = k0 + blockIdx.x;
+    const unsigned long long first = P.box_off[k];
+    pile_block_write(P.C, first, P.box_off[k + 1] - first, text + text_off[k]);
+}
+
+// ---- long segments (a contig of megabases would keep ONE workgroup busy for tens of thousands of serial steps): the same
+// three passes with one workgroup per TILE of kPileTile boxes.  tiles[]: (segment, first box inside it), made by the host
+// (the precedent: the (contig, first chunk) table of k_seed_emit_set).  A tile's text goes to the offset the scan of the tile
+// counts gives it -- a count, not a position, so a box's two characters stay side by side wherever the tile ends.
+#define PBA_PILE_TILE 4096u
+struct PileTile { uint32_t seg, first; };
+static __device__ __forceinline__ unsigned long long pile_tile_len(const VoteInto &P, const PileTile &t) {
+    const unsigned long long rest = P.box_off[t.seg + 1] - P.box_off[t.seg] - t.first;
+    return rest < PBA_PILE_TILE ? rest : PBA_PILE_TILE;
+}
+
+static __global__ void __launch_bounds__(256)
+k_pile_fill_tiles(SeqSetDev S, const PileTile *tiles, uint32_t tile0, VoteInto P, int weight) {
+    const PileTile t = tiles[tile0 + blockIdx.x];
+    const uint8_t *seq = S.packed + S.off[P.t_lo + t.seg];
+    const unsigned long long first = P.box_off[t.seg];
+    const uint32_t end = t.first + (uint32_t)pile_tile_len(P, t);
+    for (uint32_t i = t.first + threadIdx.x; i < end; i += 256) {
+        const int code = (seq[i >> 2] >> (6 - 2 * (i & 3))) & 3;
+        P.C.sel[first + i] = cons_vote_box(code, weight);
+        P.C.sup[first + i] = 0ull;
+        P.C.tot[first + i] = 1;
+    }
+}
+
+static __global__ void __launch_bounds__(256)
+k_pile_count_tiles(VoteInto P, const PileTile *tiles, uint32_t tile0, int *tile_cnt) {
+    const PileTile t = tiles[tile0 + blockIdx.x];
+    const int n = pile_block_count(P.C, P.box_off[t.seg] + t.first, pile_tile_len(P, t));
+    if (threadIdx.x == 0) tile_cnt[tile0 + blockIdx.x] = n;
+}
+
+static __global__ void __launch_bounds__(256)
+k_pile_write_tiles(VoteInto P, const PileTile *tiles, uint32_t tile0, const unsigned long long *tile_off, char *text) {
+    const PileTile t = tiles[tile0 + blockIdx.x];
+    pile_block_write(P.C, P.box_off[t.seg] + t.first, pile_tile_len(P, t), text + tile_off[tile0 + blockIdx.x]);
+}
+
 extern "C" {
 
 struct pba_pileup {
@@ -96,6 +145,8 @@ struct pba_pileup {
     VoteBoxes boxes;                    // the arena (no txt)
     unsigned long long *d_box_off;
     std::vector<uint64_t> box_off;      // nt + 1
+    PileTile *d_tiles;                  // non-null: a segment is longer than kPileLongSeg and the tiled kernels serve (n_tiles of them)
+    uint32_t n_tiles;
     std::vector<int32_t> n_rows;        // rows voted per target
     VoteInto view() const { return VoteInto{boxes.dev, 0, 0, 0, d_box_off, t_lo}; }
 };
@@ -103,12 +154,44 @@ struct pba_pileup {
 static void pile_free_boxes(pba_pileup *p) {
     p->boxes.release();
     if (p->d_box_off) (void)hipFree(p->d_box_off);
-    p->d_box_off = nullptr;
+    if (p->d_tiles) (void)hipFree(p->d_tiles);
+    p->d_box_off = nullptr; p->d_tiles = nullptr;
 }
 
 // a launch's global size is a 32-bit number: one workgroup of 256 threads per target, at most 2^22 targets per launch
 static const uint32_t kPileSlice = 1u << 22;
 static const uint64_t kPileMaxBoxes = (1ull << 31) - 65536;
+// A pile-up whose longest segment has more boxes than this runs the tiled kernels.  Above every read the engine accepts
+// (kMaxSeqLen), so read pile-ups keep the per-target kernels.  (-DPBA_PILE_LONG_SEG=n: a tuning build, tools/build_variant.py,
+// that keeps the per-target kernels up to n boxes, to compare the two forms on one input.)
+#ifndef PBA_PILE_LONG_SEG
+#define PBA_PILE_LONG_SEG 65536
+#endif
+static const uint64_t kPileLongSeg = PBA_PILE_LONG_SEG;
+static const uint32_t kPileTile = PBA_PILE_TILE;
+static_assert(PBA_PILE_LONG_SEG >= kMaxSeqLen, "read pile-ups keep the per-target kernels");
+
+// the (segment, first box) table of a pile-up with a long segment, on the device; none (d_tiles stays null) otherwise
+static int pile_make_tiles(pba_ctx *ctx, pba_pileup *p) {
+    const uint32_t nt = p->t_hi - p->t_lo;
+    uint64_t longest = 0, n_tiles = 0;
+    for (uint32_t k = 0; k < nt; ++k) {
+        const uint64_t len = p->box_off[k + 1] - p->box_off[k];
+        longest = std::max(longest, len); n_tiles += (len + kPileTile - 1) / kPileTile;
+    }
+    if (longest <= kPileLongSeg) return PBA_OK;
+    std::vector<PileTile> tiles;
+    tiles.reserve((size_t)n_tiles);
+    for (uint32_t k = 0; k < nt; ++k)
+        for (uint64_t at = 0, len = p->box_off[k + 1] - p->box_off[k]; at < len; at += kPileTile) tiles.push_back(PileTile{k, (uint32_t)at});
+    if (hipMalloc((void **)&p->d_tiles, sizeof(PileTile) * tiles.size()) != hipSuccess) {
+        (void)hipGetLastError(); p->d_tiles = nullptr;
+        PBA_FAIL(PBA_E_NOMEM, "pba_pileup_create: tile table");
+    }
+    p->n_tiles = (uint32_t)tiles.size();
+    HIPCHK(hipMemcpy(p->d_tiles, tiles.data(), sizeof(PileTile) * tiles.size(), hipMemcpyHostToDevice));   // (tiles dies with this scope)
+    return PBA_OK;
+}
 
 int pba_overlap_row_pair(const pba_strand_overlap *row, uint32_t target_len, uint32_t query_len, pba_pair *out) {
     if (!row || !out) return PBA_E_INVALID;
@@ -134,7 +217,7 @@ int pba_pileup_create(pba_ctx *ctx, const pba_seqs *reads, uint32_t t_lo, uint32
     std::unique_ptr<pba_pileup> p(new (std::nothrow) pba_pileup());
     if (!p) PBA_FAIL(PBA_E_NOMEM, "pba_pileup");
     p->device = ctx->device; p->t_lo = t_lo; p->t_hi = t_hi; p->n_reads = reads->n; p->weight = weight; p->spent = false;
-    p->d_box_off = nullptr;
+    p->d_box_off = nullptr; p->d_tiles = nullptr; p->n_tiles = 0;
     p->box_off.assign((size_t)nt + 1, 0);
     p->n_rows.assign(nt, 0);
     for (uint32_t k = 0; k < nt; ++k) p->box_off[k + 1] = p->box_off[k] + reads->h_len[t_lo + k];
@@ -145,8 +228,15 @@ int pba_pileup_create(pba_ctx *ctx, const pba_seqs *reads, uint32_t t_lo, uint32
     if (!ok) { (void)hipGetLastError(); pile_free_boxes(p.get()); PBA_FAIL(PBA_E_NOMEM, "pba_pileup_create: vote boxes"); }
     hipError_t e = hipMemcpyAsync(p->d_box_off, p->box_off.data(), sizeof(uint64_t) * ((size_t)nt + 1), hipMemcpyHostToDevice, ctx->stream);
     const VoteInto P = p->view();
-    for (uint32_t k0 = 0; k0 < nt && e == hipSuccess; k0 += kPileSlice) {
+    const int tst = pile_make_tiles(ctx, p.get());
+    if (tst != PBA_OK) { pile_free_boxes(p.get()); return tst; }
+    for (uint32_t k0 = 0; !p->d_tiles && k0 < nt && e == hipSuccess; k0 += kPileSlice) {
         hipLaunchKernelGGL(k_pile_fill, dim3(std::min(kPileSlice, nt - k0)), dim3(256), 0, ctx->stream, reads->dev(), k0, P, weight);
+        e = hipGetLastError();
+    }
+    for (uint32_t k0 = 0; p->d_tiles && k0 < p->n_tiles && e == hipSuccess; k0 += kPileSlice) {
+        hipLaunchKernelGGL(k_pile_fill_tiles, dim3(std::min(kPileSlice, p->n_tiles - k0)), dim3(256), 0, ctx->stream, reads->dev(),
+                           p->d_tiles, k0, P, weight);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -168,6 +258,32 @@ static bool pile_same_reads(const pba_pileup *p, const pba_seqs *reads) {
     for (uint32_t k = 0; k < p->t_hi - p->t_lo; ++k)
         if (p->box_off[k + 1] - p->box_off[k] != reads->h_len[p->t_lo + k]) return false;
     return true;
+}
+
+// The votes of a call: pairs[0] against B = fwd, pairs[1] against B = rc, two batches into the boxes of p (A: the set they
+// were filled from), gated by overlap_min; after(s, results of batch s) once a batch has voted.
+extern "C++" template <class After>
+static int pile_vote_batches(pba_ctx *ctx, pba_pileup *p, const pba_seqs *A, const pba_seqs *fwd, const pba_seqs *rc,
+                             const std::vector<pba_pair> pairs[2], double R, int overlap_min, After after) {
+    HIPCHK(hipSetDevice(ctx->device));
+    const VoteInto into = p->view();
+    std::vector<pba_result> out;
+    bool voted = false;                   // a batch of this call has gone through
+    for (int s = 0; s < 2; ++s) {
+        if (pairs[s].empty()) continue;
+        out.resize(pairs[s].size());
+        const int st = trace_batch(ctx, A, s ? rc : fwd, pairs[s].data(), pairs[s].size(), R, 0, 0, PBA_KERNEL_BITVEC, out.data(), nullptr,
+                                   nullptr, nullptr, &into, overlap_min);
+        if (st != PBA_OK) {
+            // PBA_E_TOOLONG / PBA_E_INVALID come from the plan and the pair checks, before any launch.  Anything else may have
+            // left votes behind, and so has an earlier batch of this call: the boxes no longer say which rows they hold.
+            if (voted || (st != PBA_E_TOOLONG && st != PBA_E_INVALID)) p->spent = true;
+            return st;
+        }
+        voted = true;
+        PBA_TRY(after(s, out));
+    }
+    return PBA_OK;
 }
 
 int pba_pileup_vote(pba_ctx *ctx, pba_pileup *p, const pba_seqs *reads, const pba_seqs *reads_rc,
@@ -195,23 +311,8 @@ int pba_pileup_vote(pba_ctx *ctx, pba_pileup *p, const pba_seqs *reads, const pb
         const int s = r.strand == 1 ? 0 : 1;
         pairs[s].push_back(pr); which[s].push_back((uint32_t)k);
     }
-    HIPCHK(hipSetDevice(ctx->device));
-    const VoteInto into = p->view();
-    std::vector<pba_result> out;
-    bool voted = false;                   // a batch of this call has gone through
-    for (int s = 0; s < 2; ++s) {
-        if (pairs[s].empty()) continue;
-        out.resize(pairs[s].size());
-        // (the rows passed their OVERLAP_MIN gate when they were found: the walk votes whatever re-runs to success)
-        const int st = trace_batch(ctx, reads, s ? reads_rc : reads, pairs[s].data(), pairs[s].size(), R, 0, 0, PBA_KERNEL_BITVEC,
-                                   out.data(), nullptr, nullptr, nullptr, &into, 0);
-        if (st != PBA_OK) {
-            // PBA_E_TOOLONG / PBA_E_INVALID come from the plan and the pair checks, before any launch.  Anything else may have
-            // left votes behind, and so has an earlier batch of this call: the boxes no longer say which rows they hold.
-            if (voted || (st != PBA_E_TOOLONG && st != PBA_E_INVALID)) p->spent = true;
-            return st;
-        }
-        voted = true;
+    // (the rows passed their OVERLAP_MIN gate when they were found: the walk votes whatever re-runs to success)
+    return pile_vote_batches(ctx, p, reads, reads, reads_rc, pairs, R, 0, [&](int s, const std::vector<pba_result> &out) {
         for (size_t q = 0; q < out.size(); ++q) {
             const pba_strand_overlap &r = rows[which[s][q]];
             if (res) res[which[s][q]] = out[q];
@@ -226,8 +327,64 @@ int pba_pileup_vote(pba_ctx *ctx, pba_pileup *p, const pba_seqs *reads, const pb
             }
         }
         for (size_t q = 0; q < out.size(); ++q) ++p->n_rows[(uint32_t)rows[which[s][q]].target - p->t_lo];
-    }
+        return PBA_OK;
+    });
+}
+
+int pba_map_row_pair(const pba_map_row *row, uint32_t contig_len, uint32_t read_len, double R, pba_pair *out) {
+    if (!row || !out || !row->found || (row->strand != 1 && row->strand != -1)) return PBA_E_INVALID;
+    if (!(R > 0.0) || !(R < 1.0) || row->contig < 0 || row->read < 0 || row->j < 0 || row->pos < 0) return PBA_E_INVALID;
+    if (contig_len > 0x7FFFFFFFu || read_len > 0x7FFFFFFFu) return PBA_E_INVALID;
+    if ((uint32_t)row->j >= read_len || (uint32_t)row->pos >= contig_len) return PBA_E_INVALID;
+    // align cuts a to b + max_dst itself whenever a is the longer side (seq_aligner.h:94-102): the same cut, made here
+    const TextClip c = text_clip((int)(contig_len - (uint32_t)row->pos), (int)(read_len - (uint32_t)row->j), R);
+    if (c.len_a > kMaxSeqLen || read_len - (uint32_t)row->j > (uint32_t)kMaxSeqLen) return PBA_E_TOOLONG;
+    memset(out, 0, sizeof *out);
+    out->a_seq = (uint32_t)row->contig; out->a_pos = row->pos; out->a_len = c.len_a;
+    out->b_seq = (uint32_t)row->read; out->b_pos = row->j; out->b_len = (int32_t)(read_len - (uint32_t)row->j);
     return PBA_OK;
+}
+
+int pba_pileup_vote_mapped(pba_ctx *ctx, pba_pileup *p, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
+                           const pba_map_row *rows, uint64_t n, double R, int overlap_min, pba_result *res, uint64_t *n_voted) {
+    if (!ctx || !p || !target || !reads || (!rows && n)) return PBA_E_INVALID;
+    if (n_voted) *n_voted = 0;
+    if (p->spent) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_mapped: the pile-up is spent");
+    if (!(R > 0.0) || !(R < 1.0)) PBA_FAIL(PBA_E_INVALID, "R must be in (0,1)");
+    if (!pile_same_reads(p, target)) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_mapped: target is not the set of this pile-up");
+    if (reads_rc && (reads_rc->n != reads->n || reads_rc->h_len != reads->h_len))
+        PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_mapped: reads_rc differs from reads in count or lengths");
+    if (target->non_acgt || reads->non_acgt || (reads_rc && reads_rc->non_acgt))
+        PBA_FAIL(PBA_E_ALPHABET, "pba_pileup_vote_mapped: a set holds bytes outside ACGT");
+    if (n > 0x7FFFFFFFull) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_mapped: too many rows in one call");
+    std::vector<pba_pair> pairs[2];       // strand +1 (B = reads), strand -1 (B = reads_rc)
+    std::vector<uint32_t> which[2];
+    for (uint64_t k = 0; k < n; ++k) {
+        const pba_map_row &r = rows[k];
+        if (!r.found) continue;
+        if (r.contig < 0 || (uint32_t)r.contig < p->t_lo || (uint32_t)r.contig >= p->t_hi)
+            PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_mapped: a row's contig is outside the pile-up's range");
+        if (r.read < 0 || (uint32_t)r.read >= reads->n) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_mapped: a row's read is not a read of the set");
+        if (r.strand == -1 && !reads_rc) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_mapped: a strand -1 row needs reads_rc");
+        pba_pair pr;
+        const int st = pba_map_row_pair(&r, target->h_len[r.contig], reads->h_len[r.read], R, &pr);
+        if (st == PBA_E_TOOLONG) PBA_FAIL(PBA_E_TOOLONG, "pba_pileup_vote_mapped: a row's accessor is longer than the engine limit");
+        if (st != PBA_OK) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_mapped: a row's strand or accessors are not valid for its sequences");
+        const int s = r.strand == 1 ? 0 : 1;
+        pairs[s].push_back(pr); which[s].push_back((uint32_t)k);
+    }
+    for (uint64_t k = 0; res && k < n; ++k)
+        if (!rows[k].found) { memset(&res[k], 0, sizeof res[k]); res[k].rc = -1; }
+    // try_align's gate (ref_seq.h:264-265).  No re-run check: the roles are swapped against the walk that found the row.
+    return pile_vote_batches(ctx, p, target, reads, reads_rc, pairs, R, overlap_min, [&](int s, const std::vector<pba_result> &out) {
+        for (size_t q = 0; q < out.size(); ++q) {
+            if (res) res[which[s][q]] = out[q];
+            if (out[q].rc < 0 || out[q].matlen_a < overlap_min) continue;
+            ++p->n_rows[(uint32_t)rows[which[s][q]].contig - p->t_lo];
+            if (n_voted) ++*n_voted;
+        }
+        return PBA_OK;
+    });
 }
 
 int pba_pileup_dump(pba_ctx *ctx, const pba_pileup *p, uint32_t target, uint16_t *sel, uint16_t *sup, int32_t *tot, int cap,
@@ -243,30 +400,71 @@ int pba_pileup_dump(pba_ctx *ctx, const pba_pileup *p, uint32_t target, uint16_t
 // a pile-up evolved to one contiguous device text: target k at text[off[k] .. off[k+1]); d_off: off on the device (nt + 1 u64)
 struct PileText { DevBuf text, d_off; std::vector<uint64_t> off; };
 
+// count pass: len_out[k] of every target; tiled form: also tile_off[i], where tile i's text starts inside the one text
+// (the scan runs on the host, which needs the lengths anyway: 2^31 boxes are 524 288 tiles)
+static int pile_count(pba_ctx *ctx, const pba_pileup *p, std::vector<int32_t> *len_out, std::vector<uint64_t> *tile_off) {
+    const uint32_t nt = p->t_hi - p->t_lo, n = p->d_tiles ? p->n_tiles : nt;
+    const VoteInto P = p->view();
+    DevBuf d_cnt;
+    std::vector<int32_t> cnt(n, 0);
+    HIPCHK(hipMalloc(&d_cnt.p, sizeof(int32_t) * ((size_t)n + 1)));
+    for (uint32_t k0 = 0; k0 < n; k0 += kPileSlice) {
+        const dim3 grid(std::min(kPileSlice, n - k0));
+        if (p->d_tiles) hipLaunchKernelGGL(k_pile_count_tiles, grid, dim3(256), 0, ctx->stream, P, p->d_tiles, k0, d_cnt.as<int>());
+        else hipLaunchKernelGGL(k_pile_count, grid, dim3(256), 0, ctx->stream, P, k0, d_cnt.as<int>());
+    }
+    HIPCHK(hipGetLastError());
+    if (n) HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (!p->d_tiles) { len_out->swap(cnt); return PBA_OK; }
+    len_out->assign(nt, 0);
+    tile_off->assign((size_t)n + 1, 0);
+    uint32_t i = 0;                                            // the tiles lie in segment order, a segment's in box order
+    for (uint32_t k = 0; k < nt; ++k)
+        for (uint64_t at = 0, len = p->box_off[k + 1] - p->box_off[k]; at < len; at += kPileTile, ++i) {
+            if ((uint64_t)(*len_out)[k] + (uint64_t)cnt[i] > 0x7FFFFFFFull) PBA_FAIL(PBA_E_TOOLONG, "pba_pileup_evolve: a segment evolves to 2^31 characters or more");
+            (*len_out)[k] += cnt[i];
+            (*tile_off)[i + 1] = (*tile_off)[i] + (uint64_t)cnt[i];
+        }
+    return PBA_OK;
+}
+
+// write pass: every target's text at T->off (already on the device as T->d_off), tile by tile at tile_off in the tiled form
+static int pile_write(pba_ctx *ctx, const pba_pileup *p, const PileText *T, const std::vector<uint64_t> &tile_off) {
+    const uint32_t nt = p->t_hi - p->t_lo, n = p->d_tiles ? p->n_tiles : nt;
+    const VoteInto P = p->view();
+    DevBuf d_toff;
+    if (p->d_tiles) {
+        HIPCHK(hipMalloc(&d_toff.p, sizeof(uint64_t) * tile_off.size()));
+        HIPCHK(hipMemcpyAsync(d_toff.p, tile_off.data(), sizeof(uint64_t) * tile_off.size(), hipMemcpyHostToDevice, ctx->stream));
+    }
+    for (uint32_t k0 = 0; k0 < n; k0 += kPileSlice) {
+        const dim3 grid(std::min(kPileSlice, n - k0));
+        if (p->d_tiles)
+            hipLaunchKernelGGL(k_pile_write_tiles, grid, dim3(256), 0, ctx->stream, P, p->d_tiles, k0, d_toff.as<unsigned long long>(),
+                               T->text.as<char>());
+        else
+            hipLaunchKernelGGL(k_pile_write, grid, dim3(256), 0, ctx->stream, P, k0, T->d_off.as<unsigned long long>(), T->text.as<char>());
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return PBA_OK;
+}
+
 // evolve to *T; the boxes are released
 static int pile_evolve_text(pba_ctx *ctx, pba_pileup *p, PileText *T, pba_correct_row *rows_out) {
     if (p->spent) PBA_FAIL(PBA_E_INVALID, "pba_pileup_evolve: the pile-up is spent");
     HIPCHK(hipSetDevice(ctx->device));
     const uint32_t nt = p->t_hi - p->t_lo;
-    const VoteInto P = p->view();
-    DevBuf d_len;
-    std::vector<int32_t> len_out(nt, 0);
-    HIPCHK(hipMalloc(&d_len.p, sizeof(int32_t) * ((size_t)nt + 1)));
-    for (uint32_t k0 = 0; k0 < nt; k0 += kPileSlice)
-        hipLaunchKernelGGL(k_pile_count, dim3(std::min(kPileSlice, nt - k0)), dim3(256), 0, ctx->stream, P, k0, d_len.as<int>());
-    HIPCHK(hipGetLastError());
-    if (nt) HIPCHK(hipMemcpyAsync(len_out.data(), d_len.p, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    std::vector<int32_t> len_out;
+    std::vector<uint64_t> tile_off;
+    PBA_TRY(pile_count(ctx, p, &len_out, &tile_off));
     T->off.assign((size_t)nt + 1, 0);
     for (uint32_t k = 0; k < nt; ++k) T->off[k + 1] = T->off[k] + (uint64_t)len_out[k];
     HIPCHK(hipMalloc(&T->text.p, T->off[nt] + kSlack));
     HIPCHK(hipMalloc(&T->d_off.p, sizeof(uint64_t) * ((size_t)nt + 1)));
     HIPCHK(hipMemcpyAsync(T->d_off.p, T->off.data(), sizeof(uint64_t) * ((size_t)nt + 1), hipMemcpyHostToDevice, ctx->stream));
-    for (uint32_t k0 = 0; k0 < nt; k0 += kPileSlice)
-        hipLaunchKernelGGL(k_pile_write, dim3(std::min(kPileSlice, nt - k0)), dim3(256), 0, ctx->stream, P, k0,
-                           T->d_off.as<unsigned long long>(), T->text.as<char>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    PBA_TRY(pile_write(ctx, p, T, tile_off));
     for (uint32_t k = 0; rows_out && k < nt; ++k) {
         rows_out[k].target = (int32_t)(p->t_lo + k); rows_out[k].n_rows = p->n_rows[k];
         rows_out[k].len_in = (int32_t)(p->box_off[k + 1] - p->box_off[k]); rows_out[k].len_out = len_out[k];
@@ -435,36 +633,38 @@ static int correct_evolve(CorrectRun &c, uint32_t lo) {
     return PBA_OK;
 }
 
-// The chunks' texts as one packed set.  One chunk: its text and device offsets as they are, no copy.  Otherwise (none: an
-// empty range) the texts side by side in one buffer under offsets that run through.
-static int correct_stitch(CorrectRun &c, pba_seqs **corrected) {
-    pba_ctx *ctx = c.ctx;
-    const auto timed = c.clk.time(ctx->stream, &c.prof.evolve_ms);
-    const uint32_t nt = c.t_hi - c.t_lo;
-    if (c.chunks.size() == 1) {
-        const PileText &T = c.chunks[0];
-        c.prof.n_bases_out = T.off.back();
-        return pba_seqs_from_device_text(ctx, T.text.p, T.d_off.p, nt, T.off.back(), 0, corrected);
+// The chunks' texts as one packed set of nt sequences.  One chunk: its text and device offsets as they are, no copy.
+// Otherwise (none: an empty range) the texts side by side in one buffer under offsets that run through.
+static int stitch_chunks(pba_ctx *ctx, std::deque<PileText> &chunks, uint32_t nt, uint64_t *n_bases_out, pba_seqs **out) {
+    if (chunks.size() == 1) {
+        const PileText &T = chunks[0];
+        *n_bases_out = T.off.back();
+        return pba_seqs_from_device_text(ctx, T.text.p, T.d_off.p, nt, T.off.back(), 0, out);
     }
     std::vector<uint64_t> all_off(1, 0);
-    for (const PileText &T : c.chunks) {
+    for (const PileText &T : chunks) {
         const uint64_t base = all_off.back();
         for (size_t k = 1; k < T.off.size(); ++k) all_off.push_back(base + T.off[k]);
     }
     DevBuf all, d_off;
     HIPCHK(hipMalloc(&all.p, all_off.back() + kSlack));
     uint64_t at = 0;
-    for (const PileText &T : c.chunks) {
+    for (const PileText &T : chunks) {
         if (T.off.back()) HIPCHK(copy_d2d((uint8_t *)all.p + at, T.text.p, T.off.back(), ctx->stream));
         at += T.off.back();
     }
-    if (!c.chunks.empty()) c.chunks.back().d_off.reset();
+    if (!chunks.empty()) chunks.back().d_off.reset();
     HIPCHK(hipMalloc(&d_off.p, sizeof(uint64_t) * all_off.size()));
     HIPCHK(hipMemcpyAsync(d_off.p, all_off.data(), sizeof(uint64_t) * all_off.size(), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    c.chunks.clear();
-    c.prof.n_bases_out = all_off.back();
-    return pba_seqs_from_device_text(ctx, all.p, d_off.p, nt, all_off.back(), 0, corrected);
+    chunks.clear();
+    *n_bases_out = all_off.back();
+    return pba_seqs_from_device_text(ctx, all.p, d_off.p, nt, all_off.back(), 0, out);
+}
+
+static int correct_stitch(CorrectRun &c, pba_seqs **corrected) {
+    const auto timed = c.clk.time(c.ctx->stream, &c.prof.evolve_ms);
+    return stitch_chunks(c.ctx, c.chunks, c.t_hi - c.t_lo, &c.prof.n_bases_out, corrected);
 }
 
 int pba_correct_reads(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t t_lo, uint32_t t_hi,
@@ -503,6 +703,164 @@ int pba_correct_reads_budget(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs
     PBA_TRY(correct_stitch(c, corrected));
     ctx->cprof = c.prof;
     if (stats) { stats[0] = c.tot[0]; stats[1] = c.tot[1]; }
+    return PBA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// pba_polish_contigs: index -> map -> vote -> evolve over a contig set, round after round
+// ---------------------------------------------------------------------------------------------
+// what lives across one call of pba_polish_contigs
+struct PolishRun {
+    pba_ctx *ctx;
+    const pba_seqs *reads, *reads_rc;            // reads_rc: the caller's, or `rc`
+    uint32_t mask;
+    double R;
+    int trials, min_len, maxn, maxm, kernel, strands, overlap_min, weight;
+    uint64_t max_boxes;
+    const pba_seqs *cur;                         // the round's contigs: the caller's target, then `own`
+    pba_seqs *rc = nullptr, *own = nullptr;      // owned: the reverse complement, the set the last round made, the index, the pile-up
+    pba_index *ix = nullptr;
+    pba_pileup *pile = nullptr;
+    StageClock clk;
+    pba_polish_round_log lg;                     // the round in progress
+    std::vector<pba_map_row> rows;               // the round's rows, then its found rows ordered by contig
+    std::vector<uint64_t> first;                 // found rows of contig c: rows[first[c] .. first[c + 1])
+    std::vector<pba_correct_row> crows;          // per contig, this round
+    std::deque<PileText> chunks;
+    ~PolishRun() { pba_pileup_destroy(pile); pba_index_destroy(ix); if (own) pba_seqs_destroy(own); if (rc) pba_seqs_destroy(rc); }
+};
+
+static int polish_check(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc, int strands, int weight,
+                        int rounds) {
+    if (rounds < 1) PBA_FAIL(PBA_E_INVALID, "pba_polish_contigs: rounds must be at least 1");
+    if (weight < 1 || weight > 0xFFFF) PBA_FAIL(PBA_E_INVALID, "pba_polish_contigs: weight must be in [1, 65535]");
+    if (strands < 1 || strands > 3) PBA_FAIL(PBA_E_INVALID, "pba_polish_contigs: strands must be 1 (+1), 2 (-1) or 3 (both)");
+    if (reads_rc && (reads_rc->n != reads->n || reads_rc->h_len != reads->h_len))
+        PBA_FAIL(PBA_E_INVALID, "pba_polish_contigs: reads_rc differs from reads in count or lengths");
+    if (target->non_acgt || reads->non_acgt || (reads_rc && reads_rc->non_acgt))
+        PBA_FAIL(PBA_E_ALPHABET, "pba_polish_contigs: a set holds bytes outside ACGT");
+    return PBA_OK;
+}
+
+// the round's index and its rows; the found ones ordered by contig (stable: by read inside a contig)
+static int polish_map(PolishRun &c) {
+    pba_ctx *ctx = c.ctx;
+    {
+        const auto timed = c.clk.time(ctx->stream, &c.lg.index_ms);
+        PBA_TRY(pba_index_build_set(ctx, c.cur, c.mask, &c.ix));
+    }
+    {
+        const auto timed = c.clk.time(ctx->stream, &c.lg.map_ms);
+        c.rows.assign(std::max<size_t>(c.reads->n, 1), pba_map_row{});
+        PBA_TRY(pba_map_reads(ctx, c.ix, c.cur, c.reads, c.reads_rc, c.R, c.trials, c.min_len, c.maxn, c.maxm, c.kernel, c.strands,
+                              c.rows.data(), nullptr));
+    }
+    pba_index_destroy(c.ix); c.ix = nullptr;
+    c.first.assign((size_t)c.cur->n + 1, 0);
+    for (uint32_t r = 0; r < c.reads->n; ++r)
+        if (c.rows[r].found) ++c.first[(size_t)c.rows[r].contig + 1];
+    for (uint32_t k = 0; k < c.cur->n; ++k) c.first[k + 1] += c.first[k];
+    std::vector<pba_map_row> by(c.first.back());
+    std::vector<uint64_t> at(c.first.begin(), c.first.end() - 1);
+    for (uint32_t r = 0; r < c.reads->n; ++r)
+        if (c.rows[r].found) by[at[c.rows[r].contig]++] = c.rows[r];
+    c.rows.swap(by);
+    c.lg.n_mapped = (uint32_t)c.rows.size();
+    return PBA_OK;
+}
+
+// The next chunk of contigs [lo, *hi): as many as fit the budget of correct_next_chunk (a quarter of the free memory at 20
+// bytes a box, fewer than kPileMaxBoxes) and max_boxes, where set; one contig at least, whatever max_boxes says -- but a
+// single contig beyond what the card can hold is PBA_E_NOMEM.
+static int polish_next_chunk(const PolishRun &c, uint32_t lo, uint32_t *hi) {
+    pba_ctx *ctx = c.ctx;
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const uint64_t room = std::min<uint64_t>(kPileMaxBoxes - 1, (uint64_t)(free_b / 4) / 20);
+    const uint64_t budget = c.max_boxes ? std::min(room, c.max_boxes) : room;
+    uint64_t boxes = 0;
+    *hi = lo;
+    while (*hi < c.cur->n && (*hi == lo || boxes + c.cur->h_len[*hi] <= budget)) boxes += c.cur->h_len[(*hi)++];
+    if (boxes > room) PBA_FAIL(PBA_E_NOMEM, "pba_polish_contigs: the vote boxes of one contig do not fit the device");
+    return PBA_OK;
+}
+
+// the chunk's boxes and the votes of the rows mapped to its contigs
+static int polish_vote(PolishRun &c, uint32_t lo, uint32_t hi) {
+    const auto timed = c.clk.time(c.ctx->stream, &c.lg.vote_ms);
+    uint64_t voted = 0;
+    PBA_TRY(pba_pileup_create(c.ctx, c.cur, lo, hi, c.weight, &c.pile));
+    PBA_TRY(pba_pileup_vote_mapped(c.ctx, c.pile, c.cur, c.reads, c.reads_rc, c.rows.data() + c.first[lo], c.first[hi] - c.first[lo], c.R,
+                                   c.overlap_min, nullptr, &voted));
+    c.lg.n_voted += (uint32_t)voted;
+    return PBA_OK;
+}
+
+// the chunk's boxes to its text (and its rows of crows); the pile-up is gone after it
+static int polish_evolve(PolishRun &c, uint32_t lo) {
+    if (!c.chunks.empty()) c.chunks.back().d_off.reset();    // only the last chunk's offsets are used again (stitch_chunks)
+    {
+        const auto timed = c.clk.time(c.ctx->stream, &c.lg.evolve_ms);
+        c.chunks.emplace_back();
+        PBA_TRY(pile_evolve_text(c.ctx, c.pile, &c.chunks.back(), c.crows.data() + lo));
+    }
+    pba_pileup_destroy(c.pile); c.pile = nullptr;
+    return PBA_OK;
+}
+
+// one round: c.cur -> c.own (the set of the round before, if it was ours, is dropped)
+static int polish_round(PolishRun &c) {
+    PBA_TRY(polish_map(c));
+    const uint32_t nt = c.cur->n;
+    c.crows.assign(std::max<uint32_t>(nt, 1), pba_correct_row{});
+    for (uint32_t lo = 0, hi = 0; lo < nt; lo = hi) {
+        PBA_TRY(polish_next_chunk(c, lo, &hi));
+        PBA_TRY(polish_vote(c, lo, hi));
+        PBA_TRY(polish_evolve(c, lo));
+        ++c.lg.n_chunks;
+    }
+    for (uint32_t k = 0; k < nt; ++k) c.lg.n_bases_in += c.cur->h_len[k];
+    pba_seqs *next = nullptr;
+    {
+        const auto timed = c.clk.time(c.ctx->stream, &c.lg.evolve_ms);
+        PBA_TRY(stitch_chunks(c.ctx, c.chunks, nt, &c.lg.n_bases_out, &next));
+    }
+    c.chunks.clear();
+    if (c.own) pba_seqs_destroy(c.own);
+    c.own = next; c.cur = next;
+    return PBA_OK;
+}
+
+int pba_polish_contigs(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t mask, double R,
+                       int trials, int min_len, int maxn, int maxm, int kernel, int strands, int overlap_min, int weight, int rounds,
+                       pba_seqs **polished, pba_polish_row *rows_out, pba_polish_round_log *log, int log_cap) {
+    return pba_polish_contigs_budget(ctx, target, reads, reads_rc, mask, R, trials, min_len, maxn, maxm, kernel, strands, overlap_min,
+                                     weight, rounds, 0, polished, rows_out, log, log_cap);
+}
+
+int pba_polish_contigs_budget(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t mask,
+                              double R, int trials, int min_len, int maxn, int maxm, int kernel, int strands, int overlap_min, int weight,
+                              int rounds, uint64_t max_boxes, pba_seqs **polished, pba_polish_row *rows_out,
+                              pba_polish_round_log *log, int log_cap) {
+    if (!ctx || !target || !reads || !polished || (log_cap > 0 && !log)) return PBA_E_INVALID;
+    *polished = nullptr;
+    PBA_TRY(polish_check(ctx, target, reads, reads_rc, strands, weight, rounds));
+    HIPCHK(hipSetDevice(ctx->device));
+    PolishRun c{ctx, reads, reads_rc, mask, R, trials, min_len, maxn, maxm, kernel, strands, overlap_min, weight, max_boxes, target};
+    if (!c.clk.init()) PBA_FAIL(PBA_E_HIP, "pba_polish_contigs: events");
+    if ((strands & 2) && !c.reads_rc) {
+        PBA_TRY(pba_seqs_revcomp(ctx, reads, nullptr, &c.rc));
+        c.reads_rc = c.rc;
+    }
+    for (int round = 0; round < rounds; ++round) {
+        memset(&c.lg, 0, sizeof c.lg);
+        c.lg.round = round + 1;
+        PBA_TRY(polish_round(c));
+        if (round < log_cap) log[round] = c.lg;
+    }
+    for (uint32_t k = 0; rows_out && k < c.cur->n; ++k)
+        rows_out[k] = pba_polish_row{c.crows[k].target, c.crows[k].n_rows, c.crows[k].len_in, c.crows[k].len_out};
+    *polished = c.own; c.own = nullptr;
     return PBA_OK;
 }
 

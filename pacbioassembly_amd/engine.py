@@ -33,9 +33,13 @@ STRAND_OVERLAP_DTYPE = np.dtype([(n, "<i4") for n in ("target", "query", "strand
                                                      "matlen_b", "t_beg", "t_end", "q_beg", "q_end")])
 # pba_correct_row: one per target of a corrected range
 CORRECT_ROW_DTYPE = np.dtype([(n, "<i4") for n in ("target", "n_rows", "len_in", "len_out")])
+POLISH_ROW_DTYPE = np.dtype([(n, "<i4") for n in ("contig", "n_rows", "len_in", "len_out")])
+POLISH_LOG_DTYPE = np.dtype([("round", "<i4"), ("n_mapped", "<u4"), ("n_voted", "<u4"), ("n_chunks", "<u4"), ("n_bases_in", "<u8"),
+                             ("n_bases_out", "<u8"), ("index_ms", "<f4"), ("map_ms", "<f4"), ("vote_ms", "<f4"), ("evolve_ms", "<f4")])
 assert PAIR_DTYPE.itemsize == C.sizeof(PbaPair) and RESULT_DTYPE.itemsize == C.sizeof(PbaResult)
 assert LOC_ROW_DTYPE.itemsize == C.sizeof(PbaLocRow) and SS_ROW_DTYPE.itemsize == C.sizeof(PbaSsRow)
 assert MAP_ROW_DTYPE.itemsize == C.sizeof(PbaMapRow)
+assert POLISH_LOG_DTYPE.itemsize == C.sizeof(_lib.PbaPolishRoundLog)
 
 
 class PbaError(RuntimeError):
@@ -573,6 +577,35 @@ def overlap_row_pair(row, target_len: int, query_len: int) -> np.ndarray:
     return out[0]
 
 
+def map_row_pair(row, contig_len: int, read_len: int, R: float) -> np.ndarray:
+    """The pair a found map_reads row votes with (pba_map_row_pair; host arithmetic): one PAIR_DTYPE record with a = the
+    contig from pos, clipped to b_len + max_dst, b = the read from j -- for a strand -1 row an index into the
+    reverse-complemented set."""
+    r = np.zeros(1, MAP_ROW_DTYPE)
+    for f in ("read", "found", "strand", "contig", "j", "pos"):          # what the pair is made of
+        r[f] = row[f]
+    out = np.zeros(1, PAIR_DTYPE)
+    st = _lib.load().pba_map_row_pair(_ptr(r), contig_len, read_len, R, _ptr(out))
+    if st != 0:
+        raise PbaError(st, "map_row_pair")
+    return out[0]
+
+
+def _polish_contigs(self, target, reads, mask, R, trials=50, min_len=500, maxn=0, maxm=0, kernel=PBA_KERNEL_AUTO, strands=3,
+                    overlap_min=64, weight=1, rounds=1, reads_rc=None, max_boxes=0):
+    """`rounds` rounds of index -> map_reads -> vote -> evolve over the contigs of `target` (pba_polish_contigs).  max_boxes: a
+    ceiling on the bases of one internal range of contigs (0 = sized from the free device memory; pba_polish_contigs_budget).
+    Returns (SeqSet of the polished contigs, rows of POLISH_ROW_DTYPE for the last round, log of POLISH_LOG_DTYPE per round)."""
+    rows = np.zeros(max(target.count, 1), POLISH_ROW_DTYPE)
+    log = np.zeros(max(rounds, 1), POLISH_LOG_DTYPE)
+    h = C.c_void_p()
+    rc_h = reads_rc.h if reads_rc is not None else None
+    st = self.lib.pba_polish_contigs_budget(self.h, target.h, reads.h, rc_h, mask, R, trials, min_len, maxn, maxm, kernel, strands,
+                                            overlap_min, weight, rounds, max_boxes, C.byref(h), _ptr(rows), _ptr(log), log.size)
+    self.check(st, "polish_contigs")
+    return SeqSet(self, h), rows[:target.count], log[:max(rounds, 0)]
+
+
 def _correct_reads(self, reads, mask, R, max_trial=32, overlap_min=64, strands=3, weight=1, t_lo=0, t_hi=None,
                    kernel=PBA_KERNEL_AUTO, reads_rc=None, max_boxes=0):
     """Error-corrected reads of targets [t_lo, t_hi) (pba_correct_reads): overlaps on the strands asked for, every row voted
@@ -602,6 +635,7 @@ def _last_correct_profile(self) -> dict:
 
 
 Context.correct_reads = _correct_reads
+Context.polish_contigs = _polish_contigs
 Context.last_correct_profile = _last_correct_profile
 Context.overlap_strands = _overlap_strands
 Context.overlap_strands_table = _overlap_strands_table
@@ -885,6 +919,17 @@ class Pileup:
         self.ctx.check(self.ctx.lib.pba_pileup_vote(self.ctx.h, self.h, self.reads.h, reads_rc.h if reads_rc is not None else None,
                                                     _ptr(rows), rows.size, R, _ptr(res)), "pileup_vote")
         return res[:rows.size]
+
+    def vote_mapped(self, reads: "SeqSet", rows: np.ndarray, R: float, overlap_min: int = 64, reads_rc: Optional["SeqSet"] = None):
+        """Vote map_reads rows of `reads` against the set this pile-up was made from (pba_pileup_vote_mapped): a found row
+        votes if its contig-as-a alignment succeeds with matlen_a >= overlap_min.  Returns (results row by row, rows voted)."""
+        rows = np.ascontiguousarray(rows, MAP_ROW_DTYPE)
+        res = np.zeros(max(rows.size, 1), RESULT_DTYPE)
+        n_voted = C.c_uint64()
+        self.ctx.check(self.ctx.lib.pba_pileup_vote_mapped(self.ctx.h, self.h, self.reads.h, reads.h,
+                                                           reads_rc.h if reads_rc is not None else None, _ptr(rows), rows.size, R,
+                                                           overlap_min, _ptr(res), C.byref(n_voted)), "pileup_vote_mapped")
+        return res[:rows.size], int(n_voted.value)
 
     def dump(self, target: int):
         """(sel[n, 4], sup[n, 4], tot[n]) of one target's boxes as they stand."""
