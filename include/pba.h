@@ -717,6 +717,60 @@ int pba_polish_contigs_budget(pba_ctx *ctx, const pba_seqs *target, const pba_se
                               int overlap_min, int weight, int rounds, uint64_t max_boxes, pba_seqs **polished,
                               pba_polish_row *rows_out, pba_polish_round_log *log, int log_cap);
 
+/* ------------------------------------------------------------------------ */
+/* Layout: reads into contigs from their overlap rows (overlap -> LAYOUT ->   */
+/* consensus).  Not a step the reference has -- it grows one reference, read  */
+/* by read (spaced_seed.cpp:409-452) -- but built on the rows its walk gives: */
+/* every pba_strand_overlap row is a semi-global alignment from a probe near  */
+/* one end of the query to the end of one of the two reads                    */
+/* (spaced_seed.cpp:420-437, seq_aligner.h:94-102), so it is a containment or */
+/* a dovetail.  A best-overlap graph: one winning dovetail per read end,      */
+/* mutual winners are mates, chains of mates are contigs.  DESIGN §5.6 has    */
+/* the semantics in full; tests/layout_ref.py restates them.                  */
+/* ------------------------------------------------------------------------ */
+typedef struct pba_layout pba_layout;
+enum { PBA_LAY_UNPLACED = 0, PBA_LAY_PLACED = 1, PBA_LAY_CONTAINED = 2 };
+typedef struct {
+    int32_t read, state;
+    int32_t contig, rank, orient;   /* PLACED: contig id, position in its chain, 0 = as given / 1 = reverse-complemented */
+    int32_t offset, skip, adv;      /* PLACED: first contig base it supplies, bases of the walked read skipped, bases supplied */
+    int32_t container;              /* CONTAINED: the read that contains it; else -1 */
+} pba_layout_row;                   /* not PLACED: contig -1, rank / orient / offset / skip / adv 0 */
+typedef struct {
+    /* n_rows = n_internal + n_contain (accepted) + n_contain_refused + n_dovetail; n_dovetail_dropped of the dovetails touch a contained read */
+    uint64_t n_rows, n_internal, n_contain, n_contain_refused, n_dovetail, n_dovetail_dropped;
+    /* n_mated_ends: read ends with a mate before the cycles are cut; n_cycles: cycles cut (each once, not once per direction) */
+    uint32_t n_contained, n_mated_ends, n_cycles, n_contigs, n_placed, n_unplaced;
+    uint64_t n_bases;               /* bases of all contigs */
+    float classify_ms, chain_ms, stitch_ms;   /* HIP events on the ctx's stream; stitch_ms is filled by pba_layout_stitch */
+} pba_layout_stats;
+/* The layout of `reads` from n_rows overlap rows (host array, any order; only target, query, strand, cost and the four
+ * interval ends are read).  hang: the largest overhang a row may leave on the shorter side of either end and still count
+ * (beyond it the row is internal and ignored); min_reads: chains of fewer reads stay PBA_LAY_UNPLACED.  The rows go to the
+ * device once; classification, the best edge of every read end (u64 atomicMax of length, cost, row index: the longest
+ * interval, then the lowest cost -- taken within [0, 65535] --, then the lowest row index), mates, chains (pointer jumping
+ * over the 2 * n states (read, orientation)), cycle cuts and the per-read table all run there; the host scans the head flags
+ * into contig ids (ascending head read).  Checked on the host before anything is uploaded: PBA_E_INVALID for target == query, an id
+ * outside the set, an interval empty or outside its read, a strand other than +1 / -1, hang < 0, min_reads < 1;
+ * PBA_E_TOOLONG for 2^32 rows or more (a key holds 32 bits of row index), 2^28 reads or more, a read of more than 65 535
+ * bases (16 bits of length), or a contig of 0x7FFFFFF0 bases or more.  No reads and no rows are legal: no contigs. */
+int pba_layout_create(pba_ctx *ctx, const pba_seqs *reads, const pba_strand_overlap *rows, uint64_t n_rows, int hang,
+                      int min_reads, pba_layout **out, pba_layout_stats *stats /* nullable */);
+/* the per-read table, out[r] for read r; cap below the number of reads: PBA_E_INVALID */
+int pba_layout_rows(pba_ctx *ctx, const pba_layout *lay, pba_layout_row *out /* one per read */, uint32_t cap);
+uint32_t pba_layout_contigs(const pba_layout *lay);
+/* per contig (any array nullable): the read its canonical traversal starts at, its reads, its bases; cap below the number
+ * of contigs: PBA_E_INVALID */
+int pba_layout_contig_info(const pba_layout *lay, int32_t *head_read, int32_t *n_reads, int32_t *length, uint32_t cap);
+/* The contigs as a NEW set: contig base offset + p of a PLACED read is base skip + p of the read, or of its reverse
+ * complement where orient == 1 (reversed, code ^ 3), for p in [0, adv).  ASCII is written on the device from the packed
+ * arena and packed by pba_seqs_from_device_text: byte for byte what pba_seqs_from_text makes of the same texts.  `reads` must
+ * be the set the layout was made from (another count or other lengths: PBA_E_INVALID); PBA_E_ALPHABET for a set with bytes
+ * outside ACGT (no complement, as pba_seqs_revcomp). */
+int pba_layout_stitch(pba_ctx *ctx, const pba_layout *lay, const pba_seqs *reads, pba_seqs **contigs);
+int pba_layout_last_stats(const pba_layout *lay, pba_layout_stats *out);
+void pba_layout_destroy(pba_layout *lay);
+
 const char *pba_strerror(int status);
 
 #ifdef __cplusplus

@@ -71,6 +71,12 @@ class PbaStreamProfile(C.Structure):
                 ("n_reads", C.c_uint32), ("n_bytes", C.c_uint64)]
 
 
+class PbaLayoutStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_rows", "n_internal", "n_contain", "n_contain_refused", "n_dovetail", "n_dovetail_dropped")] + \
+               [(n, C.c_uint32) for n in ("n_contained", "n_mated_ends", "n_cycles", "n_contigs", "n_placed", "n_unplaced")] + \
+               [("n_bases", C.c_uint64), ("classify_ms", C.c_float), ("chain_ms", C.c_float), ("stitch_ms", C.c_float)]
+
+
 class PbaSsRow(C.Structure):
     _fields_ = [(n, C.c_int32) for n in
                 ("read", "found", "j", "dir", "ref_pos", "cost", "matlen_a", "matlen_b", "n_trials", "n_pairs")]
@@ -192,6 +198,13 @@ SYMBOLS = {
                                      C.c_int, C.c_int, C.c_int, C.POINTER(_P), _P, _P, C.c_int]),
     "pba_polish_contigs_budget": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(_P), _P, _P, C.c_int]),
+    "pba_layout_create": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, C.c_int, C.POINTER(_P), _P]),
+    "pba_layout_rows": (C.c_int, [_P, _P, _P, C.c_uint32]),
+    "pba_layout_contigs": (C.c_uint32, [_P]),
+    "pba_layout_contig_info": (C.c_int, [_P, _P, _P, _P, C.c_uint32]),
+    "pba_layout_stitch": (C.c_int, [_P, _P, _P, C.POINTER(_P)]),
+    "pba_layout_last_stats": (C.c_int, [_P, _P]),
+    "pba_layout_destroy": (None, [_P]),
     "pba_strerror": (C.c_char_p, [C.c_int]),
 }
 

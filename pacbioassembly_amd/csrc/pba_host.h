@@ -1,6 +1,6 @@
 // pba_host.h -- host-side objects and helpers shared by the translation units of libpba.so (pba_core.hip: context,
 // sequence sets, seed index; pba_align.hip: explicit pairs and edit scripts; pba_drivers.hip: the reference's ordered
-// first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction; pba_stream.hip: streamed locate).  Internal: nothing here is part of
+// first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction; pba_stream.hip: streamed locate; pba_layout.hip: layout).  Internal: nothing here is part of
 // the C ABI (include/pba.h).
 // Also here, once for all of them: the clip of seq_aligner.h:94-102 (text_clip), the launch plan (make_plan), the host
 // protocol of every aligning entry point but the all-vs-all walk -- narrow window first, the uncertified items again at the
@@ -123,7 +123,7 @@ static const size_t kSlack = 1024;              // readable bytes before the fir
 // pool slots
 enum { POOL_OVL_CAND = 0, POOL_OVL_TMP, POOL_OVL_ITEMS, POOL_OVL_REDO, POOL_OVL_REDO_IN, POOL_OVL_OUT, POOL_OVL_SMALL,
        POOL_LOC_ROWS, POOL_LOC_AUX, POOL_REDO_IDS, POOL_IX_OFFS, POOL_IX_WORK, POOL_OVL_BLOOM, POOL_OVL_ENDS,
-       POOL_TXT_IN, POOL_TXT_OUT, POOL_TXT_PAR, POOL_TXT_CST, POOL_LOC_IDS, POOL_LOC_CTG };
+       POOL_TXT_IN, POOL_TXT_OUT, POOL_TXT_PAR, POOL_TXT_CST, POOL_LOC_IDS, POOL_LOC_CTG, POOL_LAY_WORK, POOL_LAY_ROWS };
 // a buffer of at least `bytes` in pool slot `slot` (contents undefined); grows by reallocation with 1/8 headroom
 static inline int pool_reserve(pba_ctx *ctx, int slot, size_t bytes, void **out) {
     if (ctx->pool[slot].cap < bytes) {
@@ -213,6 +213,23 @@ struct DevBuf {
     ~DevBuf() { if (p) (void)hipFree(p); }
     template <class T> T *as() const { return (T *)p; }
     void reset() { if (p) (void)hipFree(p); p = nullptr; }
+};
+
+// The time of a stage between two events on the ctx's stream, added to *acc when the scope ends (every stage ends
+// synchronised): a stage times itself, whichever way it returns.
+struct StageClock {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~StageClock() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    bool init() { return hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess; }
+    struct Scope {
+        const StageClock &c; hipStream_t s; float *acc;
+        ~Scope() {
+            float ms = 0.f;
+            (void)hipEventRecord(c.e1, s);
+            if (hipEventSynchronize(c.e1) == hipSuccess && hipEventElapsedTime(&ms, c.e0, c.e1) == hipSuccess) *acc += ms;
+        }
+    };
+    Scope time(hipStream_t s, float *acc) const { (void)hipEventRecord(e0, s); return Scope{*this, s, acc}; }
 };
 
 // One set of `cap` vote boxes on the device (consensus.h: sel / sup / tot, and a text byte per box where the owner keeps

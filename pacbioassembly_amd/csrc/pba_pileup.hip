@@ -491,23 +491,6 @@ int pba_ctx_last_correct_profile(const pba_ctx *ctx, pba_correct_profile *out) {
 // ---------------------------------------------------------------------------------------------
 // pba_correct_reads: overlap -> vote -> evolve over a read set, in chunks of targets whose boxes fit the card
 // ---------------------------------------------------------------------------------------------
-// The time of a stage between two events on the ctx's stream, added to *acc when the scope ends (every stage ends
-// synchronised): a stage times itself, whichever way it returns.
-struct StageClock {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~StageClock() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-    bool init() { return hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess; }
-    struct Scope {
-        const StageClock &c; hipStream_t s; float *acc;
-        ~Scope() {
-            float ms = 0.f;
-            (void)hipEventRecord(c.e1, s);
-            if (hipEventSynchronize(c.e1) == hipSuccess && hipEventElapsedTime(&ms, c.e0, c.e1) == hipSuccess) *acc += ms;
-        }
-    };
-    Scope time(hipStream_t s, float *acc) const { (void)hipEventRecord(e0, s); return Scope{*this, s, acc}; }
-};
-
 static void stats_add(pba_overlap_stats &a, const pba_overlap_stats &b, bool first) {
     if (first) { a = b; return; }
     a.n_candidates += b.n_candidates; a.n_pairs += b.n_pairs; a.n_overlaps += b.n_overlaps; a.n_redo += b.n_redo;

@@ -36,6 +36,10 @@ CORRECT_ROW_DTYPE = np.dtype([(n, "<i4") for n in ("target", "n_rows", "len_in",
 POLISH_ROW_DTYPE = np.dtype([(n, "<i4") for n in ("contig", "n_rows", "len_in", "len_out")])
 POLISH_LOG_DTYPE = np.dtype([("round", "<i4"), ("n_mapped", "<u4"), ("n_voted", "<u4"), ("n_chunks", "<u4"), ("n_bases_in", "<u8"),
                              ("n_bases_out", "<u8"), ("index_ms", "<f4"), ("map_ms", "<f4"), ("vote_ms", "<f4"), ("evolve_ms", "<f4")])
+# pba_layout_row: one per read of a layout
+LAYOUT_ROW_DTYPE = np.dtype([(n, "<i4") for n in ("read", "state", "contig", "rank", "orient", "offset", "skip", "adv", "container")])
+LAYOUT_CONTIG_DTYPE = np.dtype([(n, "<i4") for n in ("head_read", "n_reads", "length")])
+PBA_LAY_UNPLACED, PBA_LAY_PLACED, PBA_LAY_CONTAINED = 0, 1, 2
 assert PAIR_DTYPE.itemsize == C.sizeof(PbaPair) and RESULT_DTYPE.itemsize == C.sizeof(PbaResult)
 assert LOC_ROW_DTYPE.itemsize == C.sizeof(PbaLocRow) and SS_ROW_DTYPE.itemsize == C.sizeof(PbaSsRow)
 assert MAP_ROW_DTYPE.itemsize == C.sizeof(PbaMapRow)
@@ -459,6 +463,7 @@ def _overlap_all_sharded(self, reads, mask, R, max_trial=32, overlap_min=64, tar
     if own:
         slots = n * 2 * max_trial
         probes = torch.full((max(slots, 1),), -1, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()      # the fill runs on torch's stream, the emit on the ctx's: without this it can land on top of the entries
         self.overlap_probes(reads, 0, n, mask, max_trial, probes.data_ptr(), slots)
         torch.cuda.synchronize()
         table = ProbeTable(self, probes.data_ptr(), probes.numel(), mask, max_trial)
@@ -536,6 +541,7 @@ def _overlap_strands_sharded(self, reads, mask, R, max_trial=32, overlap_min=64,
                 continue
             slots = n * 2 * max_trial
             probes = torch.full((max(slots, 1),), -1, dtype=torch.int64, device="cuda")
+            torch.cuda.synchronize()  # the fill runs on torch's stream, the emit on the ctx's: without this it can land on top of the entries
             self.overlap_probes(S, 0, n, mask, max_trial, probes.data_ptr(), slots)
             torch.cuda.synchronize()
             tables.append(ProbeTable(self, probes.data_ptr(), probes.numel(), mask, max_trial))
@@ -947,6 +953,76 @@ class Pileup:
         h = C.c_void_p()
         self.ctx.check(self.ctx.lib.pba_pileup_evolve(self.ctx.h, self.h, C.byref(h), _ptr(rows)), "pileup_evolve")
         return SeqSet(self.ctx, h), rows[:self.t_hi - self.t_lo]
+
+
+class Layout:
+    """The layout of a read set from its overlap rows (pba_layout): containments, the best dovetail at every read end,
+    chains of mutual best edges as contigs.  rows(): the per-read table; contigs(): head read, reads and bases per contig;
+    stitch(reads): the contigs as a new SeqSet, written on the device."""
+
+    def __init__(self, ctx: "Context", reads: "SeqSet", rows: np.ndarray, hang: int = 64, min_reads: int = 2):
+        self.ctx, self.n = ctx, reads.count
+        rows = np.ascontiguousarray(rows, STRAND_OVERLAP_DTYPE)
+        self.h = C.c_void_p()
+        st = _lib.PbaLayoutStats()
+        ctx.check(ctx.lib.pba_layout_create(ctx.h, reads.h, _ptr(rows), rows.size, hang, min_reads, C.byref(self.h), C.byref(st)),
+                  "layout_create")
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.ctx.lib.pba_layout_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def stats(self) -> dict:
+        st = _lib.PbaLayoutStats()
+        self.ctx.check(self.ctx.lib.pba_layout_last_stats(self.h, C.byref(st)), "layout_last_stats")
+        return {n: getattr(st, n) for n, _ in _lib.PbaLayoutStats._fields_}
+
+    def rows(self) -> np.ndarray:
+        """One LAYOUT_ROW_DTYPE record per read."""
+        out = np.zeros(max(self.n, 1), LAYOUT_ROW_DTYPE)
+        self.ctx.check(self.ctx.lib.pba_layout_rows(self.ctx.h, self.h, _ptr(out), self.n), "layout_rows")
+        return out[:self.n]
+
+    def contigs(self) -> np.ndarray:
+        """One LAYOUT_CONTIG_DTYPE record per contig, by ascending head read."""
+        nc = int(self.ctx.lib.pba_layout_contigs(self.h))
+        head, cnt, length = (np.zeros(max(nc, 1), np.int32) for _ in range(3))
+        self.ctx.check(self.ctx.lib.pba_layout_contig_info(self.h, _ptr(head), _ptr(cnt), _ptr(length), nc), "layout_contig_info")
+        out = np.zeros(nc, LAYOUT_CONTIG_DTYPE)
+        out["head_read"], out["n_reads"], out["length"] = head[:nc], cnt[:nc], length[:nc]
+        return out
+
+    def stitch(self, reads: "SeqSet") -> "SeqSet":
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.lib.pba_layout_stitch(self.ctx.h, self.h, reads.h, C.byref(h)), "layout_stitch")
+        return SeqSet(self.ctx, h)
+
+
+def _layout(self, reads, rows, hang=64, min_reads=2) -> "Layout":
+    """Lay `reads` out into contigs from overlap_strands rows (pba_layout_create)."""
+    return Layout(self, reads, rows, hang, min_reads)
+
+
+def _layout_reads(self, reads, mask, R, max_trial=32, overlap_min=64, hang=64, min_reads=2, strands=3, targets_per_call=10000,
+                  kernel=PBA_KERNEL_AUTO, reads_rc=None):
+    """overlap_strands_sharded -> layout -> stitch.  Returns (SeqSet of the contigs, the Layout, the overlap rows, [stats of
+    the +1 pass, of the -1 pass])."""
+    rows, st2 = self.overlap_strands_sharded(reads, mask, R, max_trial, overlap_min, targets_per_call, kernel, strands=strands,
+                                             reads_rc=reads_rc)
+    lay = self.layout(reads, rows, hang, min_reads)
+    return lay.stitch(reads), lay, rows, st2
+
+
+Context.layout = _layout
+Context.layout_reads = _layout_reads
 
 
 def script_vals(ops: np.ndarray, seg: bytes, fwd: bool = True) -> bytes:
