@@ -216,7 +216,9 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     int s_next = 1;                              // the earliest of the five
 
     uint32_t wl = 0, wh = 0;                     // text bit planes: bit k = low / high bit of the element of step tb+k
-    int score = 0, best = INT_MAX, fail_row = 0;
+    // wave-uniform, in scalar registers: the running D(i,i) at the end of the last segment judged (segments end in row
+    // order, so it simply carries on from lane to lane) and the first failing row (0: none so far)
+    int score = 0, fail_row = 0;
     // the vertical deltas of the LAST column as this lane's last superblock at or below row m left them (a lane keeps
     // stepping on garbage after its window has closed, so they are put aside at the close); fin_s: that superblock, or -1
     // They live in LDS (fin: PBA_BV_FIN_WORDS(NB) u32 of this wavefront's own: [2*nb][lane] Pv, [2*nb+1][lane] Mv, [2*NB][lane]
@@ -233,44 +235,50 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     auto load_text = [&](int tb) { load_planes32(colsF, tb - s_cur - 1, wl, wh); };
 
     // The 32-row diagonal segment of superblock s ending at row i (a multiple of 32, or m) is complete: check its rows
-    // against seq_aligner.h:185 and carry the diagonal score on.  Runs on lane s & 63; s and i are wave-uniform.
-    // `above`: the score of the lane above
-    auto segment_done = [&](int s, int i, int above) {
+    // against seq_aligner.h:185 and carry the diagonal score on.  Judged on the scalar side: s, i, the running score and
+    // the verdict are wave-uniform, and the one datum a lane holds -- the segment's word, acc[q] of lane s & 63 -- comes
+    // over with one v_readlane.  The FP64 comparisons run on uniform operands (the scalar unit has no FP64) and their
+    // result is a scalar condition.  What is left for the lane: its acc[] cleared and its one-hot re-armed.
+    // Returns 0, or the first failing row (PBA_BV_BAIL: the sweep is given up); a sweep ends at its first failure, so
+    // no segment is judged after one.
+    auto segment_done = [&](int s, int i) -> int {
         const int rr = i - 1 - s * RB, cnt = (rr & 31) + 1, i0 = i - cnt, q = rr >> 5;
-        if (q == 0) score = s == 0 ? 0 : above;          // D(i0,i0): the lane above finished its rows >= 2 steps ago
+        const int L = s & (PBA_WAVE - 1);
         uint32_t dw = 0;
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) dw = q == nb ? acc[nb] : dw;
+        for (int nb = 0; nb < NB; ++nb) if (q == nb) dw = __builtin_amdgcn_readlane(acc[nb], L);
         dw &= 0xFFFFFFFFu >> (32 - cnt);
         // D(i0+k, i0+k) = score + k - popcount(low k bits of dw); non-decreasing in k
         const int end = score + cnt - __builtin_popcount(dw);
         const int ifirst = max(i0 + 1, 11);                                   // rows <= 10 are never checked
-        if (i >= ifirst && (double)end > (double)ifirst * R && fail_row == 0) {
+        int fr = 0;
+        if (i >= ifirst && (double)end > (double)ifirst * R) {
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)     // (rare, and it ends within a few rows)
             for (int k = ifirst - i0; k <= cnt; ++k) {                        // row by row
                 const int d = score + k - __builtin_popcount(dw & (0xFFFFFFFFu >> (32 - k)));
-                if ((double)d > (double)(i0 + k) * R) { fail_row = i0 + k; break; }
+                if ((double)d > (double)(i0 + k) * R) { fr = i0 + k; break; }
             }
         }
         if constexpr (BAIL) {
-            if (bail_w > 0 && i >= 1024 && fail_row == 0 &&
-                ((float)end - 4.0f * __builtin_sqrtf((float)end)) * (float)m > (float)i * (float)bail_w) fail_row = PBA_BV_BAIL;
+            if (bail_w > 0 && i >= 1024 && fr == 0 &&
+                ((float)end - 4.0f * __builtin_sqrtf((float)end)) * (float)m > (float)i * (float)bail_w) fr = PBA_BV_BAIL;
         }
-        score = end;
+        score = end;                                     // D(i,i): the next segment starts from it, in whichever lane
+        if (lane == L) {
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) acc[nb] = 0;     // the next block's word starts clean
-        if (i == m) best = score;                        // D(m,m): where the scan down the last column starts
-        dmw = (i == m || rr == RB - 1) ? 0u : 1u;        // the diagonal leaves this lane's rows, or enters its next block at bit 0
+            for (int nb = 0; nb < NB; ++nb) acc[nb] = 0; // the next block's word starts clean
+            dmw = (i == m || rr == RB - 1) ? 0u : 1u;    // the diagonal leaves this lane's rows, or enters its next block at bit 0
+        }
+        return fr;
     };
 
     // The events due at step t (== s_next), before the step runs: segment end, close / move on, open, diagonal entry.
-    // DIAG: phase 1 (the diagonal is still being swept).  Sets seg_evt when a segment was checked.
+    // DIAG: phase 1 (the diagonal is still being swept).  Sets seg_fail when a segment's check failed.
 #define PBA_BV_EVENTS(DIAG)                                                           \
     {                                                                                 \
         if (DIAG && t == T_seg) {                                                     \
             const int s = s_sg, i = t - 1 - s;                                        \
-            const int above = __builtin_amdgcn_readlane(score, (s + PBA_WAVE - 1) & (PBA_WAVE - 1)); \
-            if (lane == (s & (PBA_WAVE - 1))) segment_done(s, i, above);              \
-            seg_evt = true;                                                           \
+            seg_fail = segment_done(s, i);                                            \
             if (i == m) T_seg = INT_MAX;                                              \
             else { s_sg = s + (i == s * RB + RB ? 1 : 0); T_seg = min(i + 32, m) + s_sg + 1; } \
         }                                                                             \
@@ -359,21 +367,20 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     // Within a chunk the steps run in stretches that end at the next scheduled event: the stretch's bound is its loop
     // counter, and its body is the block updates, the hand-off rotate and the one-hot add -- no compare, no branch on a
     // lane mask.
-    bool failed = false;
     for (int tbv = 1; tbv <= t1; tbv += 32) {
         const int tb = __builtin_amdgcn_readfirstlane(tbv);   // (the early exit below makes the compiler treat tbv as divergent)
         if constexpr (TRACE == 2) bv_ckpt_store<NB>(tr, tb, lane, Pv, Mv, s_cur, opened, hp_last, hn_last);
         load_text(tb);                           // next text planes
-        if (failed) break;
+        if (fail_row) break;
         int kend = min(32, t1 - tb + 1);
         for (int k = 0; k < kend;) {
         if (tb + k == s_next) {
             const int t = tb + k;
-            bool seg_evt = false;
+            int seg_fail = 0;
             PBA_BV_EVENTS(true);
             // a segment that just ended may have failed the reference's check: leave right after this step (false
             // candidates die on their first segment, so they cost 33 steps, not the 64 of a poll per chunk)
-            if (seg_evt && __builtin_amdgcn_ballot_w64(fail_row != 0)) { failed = true; kend = k + 1; }
+            if (seg_fail) { fail_row = seg_fail; kend = k + 1; }
         }
         const int kstop = min(kend, s_next - tb);
         do {
@@ -400,15 +407,8 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
         } while (++k < kstop);
         }
     }
-    if (!failed) {                               // the segment that ended in the last step: the one holding row m
-        const int above = __builtin_amdgcn_readlane(score, (s_m + PBA_WAVE - 1) & (PBA_WAVE - 1));
-        if (lane == (s_m & (PBA_WAVE - 1))) segment_done(s_m, m, above);
-        failed = __builtin_amdgcn_ballot_w64(fail_row != 0) != 0;
-    }
-    if (failed) {
-        int fr = fail_row ? fail_row : INT_MAX;  // rows fail in increasing order of step: the smallest is the first
-        return wave_min_i32(fr);
-    }
+    if (fail_row == 0) fail_row = segment_done(s_m, m);   // the segment that ended in the last step: the one holding row m
+    if (fail_row) return __builtin_amdgcn_readfirstlane(fail_row);
     s_next = min(min(T_open, T_close), T_hin);   // the diagonal is done: what is left opens and closes windows
 
     // ------------------------------------------------------------------ phase 2: the superblocks below row m take the last column
@@ -423,8 +423,8 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
         for (int k = k0; k < kend;) {
         if (tc + k == s_next) {
             const int t = tc + k;
-            bool seg_evt = false;
-            (void)seg_evt;
+            int seg_fail = 0;
+            (void)seg_fail;
             PBA_BV_EVENTS(false);
         }
         const int kstop = min(kend, s_next - tc);
@@ -480,7 +480,7 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     // v_readlane: the results are wave-uniform and the compiler must know it, or every loop that depends on
     // them (the callers' candidate walks, and through their lengths this function's own step loop) is treated
     // as divergent and its counters and bounds move from SGPRs into VGPRs
-    int gbest = __builtin_amdgcn_readlane(best, s_m & (PBA_WAVE - 1)), gi = m, run = gbest;   // D(m,m)
+    int gbest = __builtin_amdgcn_readfirstlane(score), gi = m, run = gbest;   // D(m,m): where the scan down the last column starts
     diag_out = gbest;
     for (int sb = s_m; sb < S; ++sb) {
         const int L = sb & (PBA_WAVE - 1);
