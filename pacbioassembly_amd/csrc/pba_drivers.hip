@@ -8,7 +8,9 @@
 // kernels: drivers.  One wavefront per read walks the reference's ordered candidate loop and
 // stops at the first success, so the pairs it aligns are exactly the pairs the reference aligns.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ long long pair_cells(const AlnOut &o) {
+__device__ __forceinline__ long long pair_cells(const AlnOut &o, const AlignCfg &cfg) {
+    // a pair the size guard refuses (seq_aligner.h:104-107) returns before init_cell: no cell of it is ever evaluated
+    if (cfg.maxn > 0 && (o.len_a >= cfg.maxn + cfg.maxm || o.max_dst >= cfg.maxm)) return 0;
     return band_cells(o.len_b, o.max_dst, o.fail_row ? o.fail_row : o.len_a);
 }
 
@@ -135,7 +137,7 @@ k_locate(IndexDev ix, SeqSetDev T, uint32_t tseq, SeqSetDev Rd, const uint32_t *
                     align_dispatch<NB>(fa, len - j, fb, clen - pos, cfg, lds, o, true);
                     if (o.rc == PBA_RC_UNCERTIFIED) { redo = 1; break; }
                     ++npairs;
-                    ncell += pair_cells(o);
+                    ncell += pair_cells(o, cfg);
                     if (o.rc > 0) {                                         // locator.cpp:82
                         found = 1; fj = j; fpos = pos; fcost = o.cost; fma = o.matlen_a; fmb = o.matlen_b; fdiag = o.diag;
                         fctg = ctg;

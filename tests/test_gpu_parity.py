@@ -295,13 +295,14 @@ def test_locate_golden(ctx, name, kernel):
         assert st[k] == v, (name, k, st)
 
 
-def test_locate_cells_match_oracle(ctx, oracle):
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_locate_cells_match_oracle(ctx, oracle, kernel):
     meta = {m["name"]: m for m in gold_json("locator.json")}["cfg1_pacbio"]
     g, reads, offs = locator_inputs(meta)
     T = ctx.seqs_from_list([g.tobytes()])
     Rd = ctx.seqs_from_text(reads, offs)
     ix = ctx.index_build(T, 0, meta["mask"], PBA_INDEX_ALL)
-    _, st = ctx.locate(ix, T, 0, Rd, meta["R"], meta["trials"], meta["min_len"], kernel=PBA_KERNEL_ROWSWEEP)
+    _, st = ctx.locate(ix, T, 0, Rd, meta["R"], meta["trials"], meta["min_len"], kernel=kernel)
     _, so = oracle.locator(g, meta["mask"], meta["R"], reads, offs, meta["trials"], meta["min_len"], nthreads=4)
     assert st == so
 

@@ -30,6 +30,7 @@ def exported(ctx, S):
     """The packed arena of a set (pba_seqs_export) and its offsets, on the host."""
     import torch
     buf = torch.zeros(max(S.packed_bytes, 1), dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()                  # the fill runs on torch's stream, the export on the engine's
     offs = S.export(buf.data_ptr(), buf.numel())
     torch.cuda.synchronize()
     return buf.cpu().numpy()[:S.packed_bytes].tobytes(), offs.tolist()

@@ -52,6 +52,7 @@ def export_bytes(S):
     import torch
     cap = max(int(S.packed_bytes), 16)
     d = torch.full((cap,), 0xA5, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()                  # the fill runs on torch's stream, the export on the engine's
     offs = S.export(d.data_ptr(), cap)
     return d.cpu().numpy()[:int(S.packed_bytes)].copy(), offs.copy(), S.lengths().copy()
 
