@@ -326,8 +326,6 @@ struct OvlCfg {
     int overlap_min;
     int row_cap;      // u16 cells of LDS per wavefront
     uint32_t t2;
-    uint32_t chunk;   // work items a wavefront of the walk takes at a time when there are >= 2^20 of them (0: PBA_OVL_CHUNK)
-    int fused;        // the lists hold survivors of the scan's first 32 rows only (k_ovl_scan); pairs are counted by the scan and k_ovl_after
 };
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -543,9 +541,7 @@ k_ovl_items(const uint32_t *item_pre, const uint32_t *cand_off, uint32_t n_targe
 #ifndef PBA_OVL_OCC34
 #define PBA_OVL_OCC34 8
 #endif
-#define PBA_OVL_CHUNK 16          // work items a wavefront takes at a time (big inputs)
-#define PBA_OVL_S2_CAP 256        // survivors of the first prefilter stage a chunk can hand to the second
-
+#define PBA_OVL_CHUNK 16          // work items a wavefront of the row-sweep walk takes at a time (big inputs)
 
 // One candidate of target `ref` (length ref_len, visiting order ht) set up like spaced_seed.cpp:274-286 /
 // ref_seq.h:282-286.  ok = false: skipped before the aligner (segment shorter than OVERLAP_MIN).
@@ -594,8 +590,15 @@ __device__ __forceinline__ void ovl_emit(pba_overlap *out, unsigned long long ca
 // the end: a target costs as much as its few true overlaps, which vary a lot.)
 // A candidate the narrow window cannot certify parks its (target, query): the rest of that query's candidates are
 // skipped and (target - t_lo, candidate index) goes to redo_out.
-// Second launch (redo_in != nullptr, full_band): one parked (target, query) per work item, resumed at the parked
-// candidate with the reference band until the first success or the end of the query's candidates.
+// Later launches (redo_in != nullptr; full_band in the last): one parked (target, query) per work item, resumed at the
+// parked candidate in a wider ring until the first success or the end of the query's candidates.
+// The ring kind fixes the form at compile time, because the host sizes the lists by it (pba_overlap.hip):
+//   NB != 0 : the list holds the survivors of the scan's first 32 rows (k_ovl_scan), one item at a time.  The lanes of a
+//             first launch put their item's own 64 candidates through rows 33..64 (prefilter64) before the array gets
+//             any; a continuation past the item's end and a resumed run go to the array as they are.  Nothing is counted:
+//             pairs = the scan's candidates past the gate - what k_ovl_after finds behind the successes.
+//   NB == 0 : the list holds every candidate (k_ovl_count / k_ovl_fill), no prefilter, up to PBA_OVL_CHUNK items at a
+//             time; every alignment that was decided is a pair and goes to n_pairs.
 // Rd: the targets (and every length); Q: the queries' bases -- Rd itself (k_ovl_walk, the forward entry points: it has the
 // signature and, the body being inlined with Q = Rd, the code it had before there was a Q; one kernel for both made the
 // forward walk 1 % slower at 200 k reads, 447.5 -> 452.7 ms) or the reads' reverse complement (k_ovl_walk_rc).
@@ -612,93 +615,23 @@ __device__ __forceinline__ void ovl_walk(const SeqSetDev &Rd, const SeqSetDev &Q
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / PBA_WAVE));
     uint16_t *lds = (uint16_t *)(lds_all + (size_t)wave * cfg.row_cap * 2);
     const bool l0 = (threadIdx.x & (PBA_WAVE - 1)) == 0;
-    const uint32_t lane_id = threadIdx.x & (PBA_WAVE - 1);
-    const PreThresholds pre_t(cfg.R);
-    // A million reads make hundreds of millions of light items (a group of 64 mostly false candidates): one atomic on
-    // the queue and one on the pair counter per item is then what the walk waits for (every wavefront on the same two
-    // addresses).  Items are taken up to 16 at a time and the pairs are added up per wavefront.
+    constexpr bool BV = NB != 0;
+    // Row-sweep form: a million reads make hundreds of millions of light items (a group of 64 mostly false candidates):
+    // one atomic on the queue and one on the pair counter per item is then what the walk waits for (every wavefront on
+    // the same two addresses).  Items are taken up to 16 at a time and the pairs are added up per wavefront.
     // (below a million items chunks cost more in load balance at the end of the launch than they save: an item with a true
     // overlap is ~500 x a group of false candidates)
-    // (after the pre-sort prefilter stage an item is 64 candidates of runs that hold a survivor -- a true overlap in every
-    // fourth: the host then asks for single items, cfg.chunk = 1)
-    const uint32_t chunk = (redo_in || n_items < (1u << 20)) ? 1u : (cfg.chunk ? min(cfg.chunk, (uint32_t)PBA_OVL_CHUNK) : (uint32_t)PBA_OVL_CHUNK);
-    // Two-stage prefilter over a chunk (first launch, bit-vector kernels): the first 32 rows of every candidate of the
-    // chunk's groups (one candidate per lane, prefilter32), the survivors of ALL its groups listed in LDS and put
-    // through rows 33..64 together (prefilter64, one survivor per lane) -- and only what passes both reaches the
-    // wavefront-wide array.  fail[k]: lanes of group k that failed in either stage.
+    // Bit-vector form: an item is 64 candidates of runs that hold a survivor of 32 rows -- a true overlap in every fourth:
+    // single items.
+    const uint32_t chunk = (BV || redo_in || n_items < (1u << 20)) ? 1u : (uint32_t)PBA_OVL_CHUNK;
     constexpr int WPB = NB ? 4 : 1;
-    __shared__ uint32_t s2_fail[WPB][PBA_OVL_CHUNK][2];
-    __shared__ uint16_t s2_list[WPB][PBA_OVL_S2_CAP];
     __shared__ uint64_t s_cd[WPB][PBA_WAVE];           // the group in flight: kept here, not in registers, while the array has the wavefront
-    // cfg.fused: every listed candidate has passed its first 32 rows in the scan (k_ovl_scan), which also counted the pairs;
-    // a chunk then goes through rows 33..64 directly (no first stage, no survivor list) and nothing is counted here
-    const bool fused = NB != 0 && cfg.fused != 0;
-    const bool two_stage = NB != 0 && !redo_in && !fused;
-    unsigned long long pairs = 0;
+    [[maybe_unused]] unsigned long long pairs = 0;     // (row-sweep form)
     for (;;) {
         const uint32_t base = (uint32_t)__builtin_amdgcn_readfirstlane(
             (int)atomicAdd(queue, l0 ? chunk : 0u));                    // see next_slot() in pba_device.hip
         if (base >= n_items) break;
         const uint32_t item_end = min(n_items, base + chunk);
-        if constexpr (NB != 0) {
-          if (fused && !redo_in) {
-            for (uint32_t k = 0; k < item_end - base; ++k) {
-                const uint2 it = items[base + k];
-                const uint32_t c_end_k = cand_off[it.x] + cand_cnt[it.x];
-                const bool act = lane_id < min((uint32_t)PBA_WAVE, c_end_k - it.y);
-                const uint64_t cd = act ? cand[it.y + lane_id] : 0ull;
-                const uint32_t t = t_lo + it.x;
-                const int ref_len = (int)Rd.len[t];
-                const HeadTail ht(ref_len);
-                const OvlCand m = ovl_decode(Rd, ref_len, ht, cd, cfg);
-                const bool fail2 = prefilter64(act && m.ok, fetch_of(Rd, t, m.r_off, m.fwd ? 1 : -1), m.r_len,
-                                               fetch_of(Q, act ? m.q : 0u, m.s_off, m.fwd ? 1 : -1), m.s_len, cfg.R);
-                const uint64_t f2 = __builtin_amdgcn_ballot_w64(fail2);
-                if (l0) { s2_fail[wave][k][0] = (uint32_t)f2; s2_fail[wave][k][1] = (uint32_t)(f2 >> 32); }
-            }
-            __builtin_amdgcn_wave_barrier();
-          }
-          if (two_stage) {
-            uint32_t ns = 0;                                            // survivors of stage 1 listed so far (wave-uniform)
-            for (uint32_t k = 0; k < item_end - base; ++k) {
-                const uint2 it = items[base + k];
-                const uint32_t c_end_k = cand_off[it.x] + cand_cnt[it.x];
-                const bool act = lane_id < min((uint32_t)PBA_WAVE, c_end_k - it.y);
-                const uint64_t cd = act ? cand[it.y + lane_id] : 0ull;
-                const uint32_t t = t_lo + it.x;
-                const int ref_len = (int)Rd.len[t];
-                const HeadTail ht(ref_len);
-                const OvlCand m = ovl_decode(Rd, ref_len, ht, cd, cfg);
-                AlnOut po;
-                const int fr = prefilter32(act && m.ok, fetch_of(Rd, t, m.r_off, m.fwd ? 1 : -1), m.r_len,
-                                           fetch_of(Q, act ? m.q : 0u, m.s_off, m.fwd ? 1 : -1), m.s_len, cfg.R, 0, 0, pre_t, po);
-                const uint64_t f1 = __builtin_amdgcn_ballot_w64(fr != 0);
-                const uint64_t s1 = __builtin_amdgcn_ballot_w64(act && m.ok && fr == 0);
-                if (l0) { s2_fail[wave][k][0] = (uint32_t)f1; s2_fail[wave][k][1] = (uint32_t)(f1 >> 32); }
-                if (s1) {
-                    const uint32_t at = ns + (uint32_t)__builtin_popcountll(s1 & ((1ull << lane_id) - 1ull));
-                    if (((s1 >> lane_id) & 1ull) && at < PBA_OVL_S2_CAP) s2_list[wave][at] = (uint16_t)(k << 6 | lane_id);
-                    ns += (uint32_t)__builtin_popcountll(s1);
-                }
-            }
-            ns = min(ns, (uint32_t)PBA_OVL_S2_CAP);                     // (survivors beyond the list go to the array untested: still exact)
-            __builtin_amdgcn_wave_barrier();
-            for (uint32_t b0 = 0; b0 < ns; b0 += PBA_WAVE) {
-                const bool have = b0 + lane_id < ns;
-                const uint32_t e = have ? s2_list[wave][b0 + lane_id] : 0u, k = e >> 6, ln = e & 63u;
-                const uint2 it = items[base + (have ? k : 0u)];
-                const uint64_t cd = have ? cand[it.y + ln] : 0ull;
-                const uint32_t t = t_lo + it.x;
-                const int ref_len = (int)Rd.len[t];
-                const HeadTail ht(ref_len);
-                const OvlCand m = ovl_decode(Rd, ref_len, ht, cd, cfg);
-                const bool fail2 = prefilter64(have, fetch_of(Rd, t, m.r_off, m.fwd ? 1 : -1), m.r_len,
-                                               fetch_of(Q, have ? m.q : 0u, m.s_off, m.fwd ? 1 : -1), m.s_len, cfg.R);
-                if (fail2) atomicOr(&s2_fail[wave][k][ln >> 5], 1u << (ln & 31u));
-            }
-            __builtin_amdgcn_wave_barrier();
-          }
-        }
         for (uint32_t item = base; item < item_end; ++item) {
         const uint32_t NONE = 0xFFFFFFFFu;
         uint32_t tl, c_begin, c_end, own_end, skip_q = NONE, only_q = NONE;
@@ -718,8 +651,8 @@ __device__ __forceinline__ void ovl_walk(const SeqSetDev &Rd, const SeqSetDev &Q
         const HeadTail ht(ref_len);
         uint32_t done_q = NONE, last_q = NONE;
         bool stop = false;
-        // 64 candidates at a time: every lane decodes its candidate and runs its first 32 rows (prefilter.h); then the
-        // group is walked in order and only the candidates that survived get the wavefront
+        // 64 candidates at a time: every lane decodes its candidate; then the group is walked in order and only the
+        // candidates still standing get the wavefront
         for (uint32_t c0 = c_begin; c0 < c_end && !stop; c0 += PBA_WAVE) {
             if (c0 >= own_end) {                                            // past the own group: only to finish its last run
                 const uint32_t nq = uni((uint32_t)(cand[c0] >> PBA_OVL_Q_SHIFT));
@@ -730,21 +663,16 @@ __device__ __forceinline__ void ovl_walk(const SeqSetDev &Rd, const SeqSetDev &Q
             const uint64_t mycd = act ? cand[c0 + lane] : 0ull;
             const uint32_t myq = (uint32_t)(mycd >> PBA_OVL_Q_SHIFT);
             const OvlCand m = ovl_decode(Rd, ref_len, ht, mycd, cfg);
-            int myfr = 0;
-            if constexpr (NB != 0) {
-                if ((two_stage || (fused && !redo_in)) && c0 == c_begin) {   // the stage(s) ran on this group with the rest of the chunk
-                    const uint32_t w32 = s2_fail[wave][item - base][lane >> 5];
-                    myfr = (int)((w32 >> (lane & 31u)) & 1u);
-                } else if (fused) {
-                    myfr = 0;                                            // passed its first 32 rows in the scan: the array decides
-                } else {
-                    AlnOut po;
-                    myfr = prefilter32(act && m.ok, ref.at(m.r_off, m.fwd ? 1 : -1), m.r_len,
-                                       fetch_of(Q, act ? myq : 0u, m.s_off, m.fwd ? 1 : -1), m.s_len, cfg.R, 0, 0, pre_t, po);
-                }
+            // rows 33..64 of the item's own candidates, one per lane; what follows a run past the item's end, or resumes
+            // one, has passed its first 32 rows in the scan and goes to the array
+            bool fail64 = false;
+            if constexpr (BV) {
+                if (!redo_in && c0 == c_begin)
+                    fail64 = prefilter64(act && m.ok, ref.at(m.r_off, m.fwd ? 1 : -1), m.r_len,
+                                         fetch_of(Q, act ? myq : 0u, m.s_off, m.fwd ? 1 : -1), m.s_len, cfg.R);
             }
-            // Nearly every candidate has failed by now, so the group is not walked lane by lane: lane masks say where the
-            // walk of this group ends, which failed candidates count as pairs, and only the survivors are visited.
+            // The group is not walked lane by lane: lane masks say where the walk of this group ends, and only the
+            // survivors are visited.
             const uint32_t up_q = (uint32_t)__shfl_up((int)myq, 1, PBA_WAVE);
             __builtin_amdgcn_wave_barrier();                                    // (the previous group's reads are done)
             s_cd[wave][lane] = mycd;
@@ -756,22 +684,10 @@ __device__ __forceinline__ void ovl_walk(const SeqSetDev &Rd, const SeqSetDev &Q
             const uint32_t lim = brk ? (uint32_t)__builtin_ctzll(brk) : ng;
             const uint64_t in = lim >= PBA_WAVE ? ~0ull : (1ull << lim) - 1ull;
             const uint64_t live = __builtin_amdgcn_ballot_w64(act && myq != skip_q) & in;   // (a leading run of the previous group is not ours)
-            const uint64_t failed = __builtin_amdgcn_ballot_w64(myfr != 0) & live;          // failed within their first 32 rows
-            uint64_t surv = __builtin_amdgcn_ballot_w64(myfr == 0 && m.ok) & live;
-            uint32_t from = 0;
-            // failed candidates of lanes [from, to): pairs the reference aligned, unless their query was done already
-            auto count_failed = [&](uint32_t to) {
-                if (to > from) {
-                    const uint64_t f = failed & (to >= PBA_WAVE ? ~0ull : (1ull << to) - 1ull) & ~((1ull << from) - 1ull);
-                    if (f) pairs += (unsigned long long)__builtin_popcountll(
-                               f & __builtin_amdgcn_ballot_w64((uint32_t)(s_cd[wave][lane] >> PBA_OVL_Q_SHIFT) != done_q));
-                }
-            };
+            uint64_t surv = __builtin_amdgcn_ballot_w64(!fail64 && m.ok) & live;
             while (surv) {
                 const uint32_t k = (uint32_t)__builtin_ctzll(surv);
                 surv &= surv - 1ull;
-                count_failed(k);
-                from = k + 1;
                 const uint32_t c = c0 + k;
                 const uint64_t cd = uniform_u64(s_cd[wave][k]);
                 const uint32_t q = (uint32_t)(cd >> PBA_OVL_Q_SHIFT);
@@ -788,18 +704,17 @@ __device__ __forceinline__ void ovl_walk(const SeqSetDev &Rd, const SeqSetDev &Q
                     if (l0 && slot < redo_cap) redo_out[slot] = make_uint2(tl, c);
                     continue;
                 }
-                ++pairs;
+                if constexpr (!BV) ++pairs;
                 if (o.rc < 0 || o.matlen_a < cfg.overlap_min) continue;     // ref_seq.h:264-265
                 done_q = q;
                 ovl_emit(out, cap, n_out, t, q, mk.j, mk.fwd, mk.hit, o);
             }
-            count_failed(lim);
             if (lim) last_q = uni((uint32_t)(s_cd[wave][lim - 1] >> PBA_OVL_Q_SHIFT));
             if (brk) stop = true;
         }
         }
     }
-    atomicAdd(n_pairs, l0 ? pairs : 0ull);
+    if constexpr (!BV) atomicAdd(n_pairs, l0 ? pairs : 0ull);
 }
 #define PBA_OVL_WALK_BOUNDS __launch_bounds__(PBA_WAVE * (NB ? 4 : 1), NB == 0 ? 1 : (NB <= 2 ? PBA_OVL_OCC12 : (NB <= 4 ? PBA_OVL_OCC34 : 3)))
 template <int NB>

@@ -646,7 +646,6 @@ static int overlap_table(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *qs
     PBA_TRY(make_plan(ctx, R, 0, 0, kernel, 1 + (int)(reads->max_len * R), &c.pl));
     c.fused = c.pl.nb1 != 0;
     c.ocfg.R = R; c.ocfg.overlap_min = overlap_min; c.ocfg.row_cap = c.pl.cfg.row_cap; c.ocfg.t2 = tab->t2;
-    c.ocfg.chunk = c.fused ? 1u : 0u; c.ocfg.fused = c.fused ? 1 : 0;
     HIPCHK(hipMalloc(&c.d_cnt.p, 8 * CNT_SLOTS));
     HIPCHK(c.cnt_clear(CNT_OVERLAPS, CNT_SLOTS));
     uint32_t *d_small = nullptr;                             // room for five arrays of nt + 1, four in use

@@ -162,7 +162,7 @@ __device__ __forceinline__ int prefilter32(bool active, const PackedFetch &fa, i
 // About one random pair in seventy survives its first 32 rows; nearly all of those fail before row 64.  Handing each
 // of them to the wavefront-wide array costs ~2 500 instructions a piece (one pair in flight, the array mostly in its
 // ramp); the same 64 rows as a two-block Myers column sweep in ONE lane cost about as much for up to 64 survivors at
-// once.  Callers collect the survivors of many groups and run this on them together.  Same exactness argument as
+// once.  The all-vs-all walk runs it on the 64 listed candidates of a work item (overlap.h).  Same exactness argument as
 // above: cell (i,i), i <= 64, depends on the square [1..i] x [1..i] only.
 #define PBA_PRE2_ROWS 64
 // true: some row 11..64 fails the reference's check (seq_aligner.h:185); false: all pass, or the stage does not apply

@@ -17,6 +17,8 @@ them one side over A / C, the other over G / T, so that no path with an indel is
 Two consequences the CPU test asserts: rows 13 .. 16 are out of reach of a forward MASK_PAT pair at any R (ALT_PAT, a mask with
 its wildcards there, reaches them through the locator), and at R = 0.9 no row of 11 .. 64 is in reach of any seeded pair
 (the dearest one costs i - 12 at row i, below 0.9 i until row 121): what R = 0.9 can show is that nothing fails falsely."""
+import functools
+
 import numpy as np
 
 import align_rings as ar
@@ -431,12 +433,13 @@ def _overlap_case(R: float, pat: str, attempt: int):
     return texts, designed, nq, nq + W
 
 
-def overlap_candidates(texts, pat: str, overlap_min: int = OVL_MIN):
+def overlap_candidates(texts, pat: str, overlap_min: int = OVL_MIN, qtexts=None):
     """Every candidate of an all-vs-all call with one trial, by enumeration: [(target, query, forward, hit, a, b)] -- the
     query's head window (forward) or tail window (backward) found at a visited position of another read (0 .. len - 17 at these
-    lengths: ref_seq's get_seedmap), past the OVERLAP_MIN gate; a, b: the two accessors' elements."""
+    lengths: ref_seq's get_seedmap), past the OVERLAP_MIN gate; a, b: the two accessors' elements.  qtexts: the queries' bases
+    where they are not the targets' (the reverse-complement pass of pba_overlap_strands), read for read."""
     out, n_match = [], 0
-    for q, qt in enumerate(texts):
+    for q, qt in enumerate(texts if qtexts is None else qtexts):
         if len(qt) < 16:
             continue
         for fwd in (True, False):
@@ -452,3 +455,152 @@ def overlap_candidates(texts, pat: str, overlap_min: int = OVL_MIN):
                     if len(qt) >= overlap_min:
                         out.append((t, q, fwd, p, tt[p:] if fwd else tt[:p + 16][::-1], qt if fwd else qt[::-1]))
     return out, n_match
+
+
+# ----------------------------------------------------------------------------- the walk's group edges
+# The walk takes a target's sorted survivors 64 at a time (overlap.h: ovl_walk); a (target, query) run belongs to the group it
+# starts in.  One target per situation, each run as (forward failures, forward success, backward success, backward failures):
+# within a run the forward candidates come first, by position -- so the success at the target's tail is the last of them -- and
+# the backward ones behind, the success at the target's head first.  FILL = a run of 16 that fails.
+STRADDLE_FILL = (8, False, False, 8)
+STRADDLE_RUNS = {
+    # slots 48 .. 72: the run crosses 63 | 64, fails 24 times -- eight of them in the second group -- and succeeds at slot 72
+    "a": (STRADDLE_FILL,) * 3 + ((24, True, False, 0), (10, False, True, 4)),
+    # slots 48 .. 76: the first success at slot 63, another one at slot 64 that nobody may report
+    "b": (STRADDLE_FILL,) * 3 + ((15, True, True, 12), STRADDLE_FILL),
+    # slots 64 .. 74: the run starts with the second group
+    "c": (STRADDLE_FILL,) * 4 + ((10, True, False, 0), (6, False, True, 5)),
+}
+STRADDLE_PLACE = 68      # elements of a failing place: the 64 rows and a few more
+
+
+def _comp(x: bytes) -> bytes:
+    return x.translate(bytes.maketrans(b"ACGT", b"TGCA"))[::-1]
+
+
+@functools.lru_cache(maxsize=None)
+def straddle_case(R: float, pat: str = MASK_PAT):
+    """_straddle_case from the first seed at which the three targets hold the designed candidates only"""
+    for attempt in range(8):
+        texts, designed, nq = _straddle_case(R, pat, attempt)
+        found = {c[:4] for c in overlap_candidates(texts, pat)[0] if c[0] >= nq}
+        if found == set(designed):
+            return texts, designed, nq
+    raise RuntimeError("no seed without a chance hit")
+
+
+def _straddle_case(R: float, pat: str, attempt: int):
+    """(texts, designed, n_queries): the queries (a head and a tail of 96 bases whose windows hit planted places only), then one
+    target per entry of STRADDLE_RUNS, its runs in query order.  designed = {(target, query, forward, hit position)}.  Every
+    failing place fails first at a reachable row of 33 .. 64 (it is listed by the scan, rows 33 .. 64 or the array fail it);
+    a success is a tightrope that reaches the target's end."""
+    rng = np.random.RandomState(9700 + int(R * 100) + 10000 * attempt)
+    m = OVL_M
+    big = {d: [f for f in reachable(R, pat, d) if f > 32] for d in (True, False)}
+    queries, plans = [], []
+    for name in sorted(STRADDLE_RUNS):
+        plan = []
+        for run in STRADDLE_RUNS[name]:
+            xh, xt = base_side(rng, m), base_side(rng, m)
+            plan.append((len(queries), xh, xt, run))
+            queries.append(xh + ar.rand_seq(rng, 30) + xt[::-1])
+        plans.append(plan)
+    nq = len(queries)
+    texts, designed, k = list(queries), [], 0
+    for t, plan in enumerate(plans):
+        head, tail, mids = None, None, []
+        for q, xh, xt, (nf, f_ok, b_ok, nb) in plan:
+            for d, x, n in ((True, xh, nf), (False, xt, nb)):
+                for _ in range(n):
+                    k += 1
+                    mids.append((q, d, fail_first_at(rng, big[d][k % len(big[d])], R, pat, d, m, x=x)[1][:STRADDLE_PLACE]))
+            if f_ok:
+                assert tail is None
+                tail = (q, tightrope(rng, R, m, pat, True, x=xh)[1])
+            if b_ok:
+                assert head is None
+                head = (q, tightrope(rng, R, m, pat, False, x=xt)[1])
+        buf = bytearray()
+        if head:
+            buf += head[1][::-1]
+            designed.append((nq + t, head[0], False, len(buf) - 16))
+        for q, d, y in mids:
+            buf += ar.rand_seq(rng, int(rng.randint(8, 16)))
+            designed.append((nq + t, q, d, len(buf) if d else len(buf) + len(y) - 16))
+            buf += y if d else y[::-1]
+        buf += ar.rand_seq(rng, int(rng.randint(8, 16)))
+        if tail:
+            designed.append((nq + t, tail[0], True, len(buf)))
+            buf += tail[1]
+        texts.append(bytes(buf))
+    return texts, designed, nq
+
+
+def straddle_views(R: float, NB: int = 1):
+    """The two ways the case is run, as {name: (texts, qtexts)}: "forward" (pba_overlap_all: queries and targets from one set)
+    and "rc" (the reverse-complement pass of pba_overlap_strands over the set whose QUERY reads were flipped: its queries' bases
+    are the designed ones again).  NB = 2: behind an unrelated long read that sizes the plan."""
+    texts, _, nq = straddle_case(R)
+    if NB == 2:
+        texts = texts + [ar.pilot(ar.row_of(2, 2)[0], R, seed=3)[0]]
+    mixed = [_comp(x) if i < nq else x for i, x in enumerate(texts)]
+    return {"forward": (texts, texts), "rc": (mixed, [_comp(x) for x in mixed])}, nq
+
+
+def walk_composition(oracle, texts, qtexts, R: float, pat: str = MASK_PAT, overlap_min: int = OVL_MIN):
+    """What the all-vs-all walk has to do, from the enumeration and the oracle's verdict per candidate alone.  Returns
+    dict(slices = {target: its listed candidates in the order of the sorted slice, each with its verdict x}, n_match, n_pre,
+    n_listed, rows = [(target, query, dir, ref_pos, cost, matlen_a, matlen_b)] and pairs of a plain walk of every candidate
+    in that order: a run is tried until its first success, ref_seq.h:264-265)."""
+    cands, n_match = overlap_candidates(texts, pat, overlap_min, qtexts)
+    cands.sort(key=lambda c: (c[0], c[1], not c[2], c[3]))
+    slices, rows, pairs, n_pre, done = {}, [], 0, 0, None
+    for t, q, fwd, p, a, b in cands:
+        x = oracle.align(a, b, R)
+        ok = x["rc"] > 0 and x["matlen_a"] >= overlap_min
+        if x["rc"] == -1 and 11 <= x["fail_row"] <= 32 and x["len_a"] >= 32 and x["len_b"] >= 32:
+            n_pre += 1                                                    # settled by the scan's 32 rows: counted, never listed
+        else:
+            slices.setdefault(t, []).append(dict(q=q, fwd=fwd, p=p, x=x, ok=ok))
+        if done == (t, q):
+            continue
+        pairs += 1
+        if ok:
+            done = (t, q)
+            rows.append((t, q, 1 if fwd else -1, p, x["cost"], x["matlen_a"], x["matlen_b"]))
+    return dict(slices=slices, n_match=n_match, n_pre=n_pre, n_listed=sum(len(v) for v in slices.values()), rows=rows, pairs=pairs)
+
+
+def straddle_situations(slices):
+    """which of the three situations each target of 65 .. 192 listed candidates shows at slots 63 | 64: {target: "a" / "b" / "c"}"""
+    out = {}
+    for t, L in slices.items():
+        if not 65 <= len(L) <= 192:
+            continue
+        if L[63]["q"] != L[64]["q"]:
+            out[t] = "c"                                                  # a run starts exactly at slot 64
+            continue
+        run = [i for i, c in enumerate(L) if c["q"] == L[63]["q"]]
+        wins = [i for i in run if L[i]["ok"]]
+        if wins and wins[0] >= 64 and any(L[i]["x"]["rc"] == -1 and 33 <= L[i]["x"]["fail_row"] <= 64 for i in range(64, wins[0])):
+            out[t] = "a"                                                  # followed past the group's end, the array fails what lies before the success
+        elif wins and wins[0] <= 63 and any(i >= 64 for i in wins):
+            out[t] = "b"                                                  # done in the first group; a success behind the edge that must be skipped
+    return out
+
+
+def oracle_composition(oracle, texts, qtexts, R: float, pat: str = MASK_PAT, overlap_min: int = OVL_MIN):
+    """(rows, pairs) of the oracle's locked spaced_seed round of every target against the file of the queries, one trial, the
+    target's own read left out: rows as walk_composition's"""
+    from pacbioassembly_amd import engine as eng
+    file = b"".join(eng.text2bin(t) for t in qtexts)
+    offs = np.cumsum([0] + [4 + (len(t) + 3) // 4 for t in qtexts[:-1]]).astype(np.uint64)
+    mask = eng.mask_from_pattern(pat)
+    want, pairs = [], 0
+    for t in range(len(texts)):
+        r = oracle.spaced_round(texts[t], mask, R, file, offs, 1, overlap_min, buggy=False, nthreads=8)
+        pairs += int(r["n_pairs"].sum()) - int(r["n_pairs"][t])
+        assert not r["j"][r["found"] == 1].any()
+        want += [(t, q, int(r["dir"][q]), int(r["ref_pos"][q]), int(r["cost"][q]), int(r["matlen_a"][q]), int(r["matlen_b"][q]))
+                 for q in range(len(texts)) if q != t and r["found"][q]]
+    return want, pairs

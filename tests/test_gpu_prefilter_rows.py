@@ -9,11 +9,12 @@ and 64 on either side, and the thresholds of six R.  Every input's identity is p
   prefilter64         ovl_walk, the form the all-vs-all entry points take (every listed candidate has been through the scan's 32
                       rows, the walk runs rows 33 .. 64 on the first group of an item): rows and n_pairs.
 
+                      test_walk_group_edges: the groups behind the first -- a run followed past its item's end, a run that
+                      the next item must skip, a run that starts with the second group -- where nothing is prefiltered.
+
 What this cannot show.  A candidate that passes rows 33 .. 64 falsely goes to the wavefront-wide aligner, which fails it at the
 same row: no output row and no counter differs, so for prefilter64 only a false FAIL (a tightrope that goes unreported) and a
-miscount are pinned.  And the walk's other form -- prefilter32 and prefilter64 over a survivor list in LDS -- is taken only when
-the lists were NOT made by the scan, which no entry point asks for any more (pba_overlap.hip: fused = nb1 != 0, and nb1 == 0 is
-the row-sweep walk, which has no prefilter): there is no hook that reaches it, and none is added here.
+miscount are pinned.
 Needs a real MI355X (-m gpu)."""
 import numpy as np
 import pytest
@@ -23,7 +24,7 @@ import map_ref
 import prefilter_inputs as pi
 from conftest import MASK_PAT
 from pacbioassembly_amd import engine as eng
-from pacbioassembly_amd.engine import PBA_INDEX_ALL, PBA_INDEX_HEAD_TAIL, PBA_KERNEL_BITVEC
+from pacbioassembly_amd.engine import PBA_INDEX_ALL, PBA_INDEX_HEAD_TAIL, PBA_KERNEL_BITVEC, PBA_KERNEL_ROWSWEEP
 from test_gpu_parity import prekeep  # noqa: F401  (the three ways the scan sizes the survivors' slices)
 
 pytestmark = pytest.mark.gpu
@@ -240,6 +241,53 @@ def test_prefilter_rows_scan_and_walk(ctx, oracle, prekeep, R, pat, NB):
     assert st["n_pairs"] == E["pairs"] and st["n_candidates"] == E["n_match"]
     assert (st["n_prefiltered"], st["n_listed"]) == (E["n_pre"], E["n_listed"]), st
     assert st["wide_first"] == 0 and st["cap_overflow"] == (prekeep == "equal_room_overflows")
+
+
+def straddle_expected(oracle, R, NB):
+    """both views of the case, what each is, and the oracle's answer -- once per session"""
+    key = ("straddle", R, NB)
+    if key in _CACHE:
+        return _CACHE[key]
+    views, nq = pi.straddle_views(R, NB)
+    out = {}
+    for name, (texts, qtexts) in views.items():
+        assert ar.nb1(1 + int(max(len(t) for t in texts) * R)) == NB and max(len(t) for t in texts) < 20000
+        W = pi.walk_composition(oracle, texts, qtexts, R)
+        assert pi.straddle_situations(W["slices"]) == {nq: "a", nq + 1: "b", nq + 2: "c"}
+        want, pairs = pi.oracle_composition(oracle, texts, qtexts, R)
+        assert (W["rows"], W["pairs"]) == (want, pairs) and len(want) >= 10
+        out[name] = dict(texts=texts, want=want, pairs=pairs, n_match=W["n_match"], n_pre=W["n_pre"], n_listed=W["n_listed"])
+    _CACHE[key] = out
+    return out
+
+
+@pytest.mark.parametrize("NB", [1, 2])
+@pytest.mark.parametrize("R", [0.30, 0.15])
+def test_walk_group_edges(ctx, oracle, R, NB):
+    """ovl_walk<NB> behind an item's first group, through k_ovl_walk (pba_overlap_all) and k_ovl_walk_rc (the reverse-complement
+    pass of pba_overlap_strands over the set with its queries flipped).  Three targets of 87 .. 93 listed candidates
+    (prefilter_inputs.straddle_case; test_prefilter_inputs_cpu.py says what they are, and so does straddle_expected): a run
+    that crosses slots 63 | 64, fails eight times behind the edge at rows 33 .. 64 -- the array's to find: nothing is prefiltered
+    there -- and then succeeds; a run that succeeds at slot 63 and would again at slot 64, which its own item must not reach and
+    the next one must skip; a run that starts at slot 64.  Rows equal to the oracle's composition, the counters to the
+    enumeration's, and the row-sweep walk agrees."""
+    E = straddle_expected(oracle, R, NB)
+    mask = eng.mask_from_pattern(MASK_PAT)
+    rows_of = lambda got: [tuple(int(r[c]) for c in ("target", "query", "dir", "ref_pos", "cost", "matlen_a", "matlen_b")) for r in got]
+    for name, e in E.items():
+        S = ctx.seqs_from_list(e["texts"], strict_acgt=True)
+        for kernel in (PBA_KERNEL_BITVEC, PBA_KERNEL_ROWSWEEP):
+            if name == "forward":
+                got, st = ctx.overlap_all(S, mask, R, 1, pi.OVL_MIN, kernel=kernel)
+            else:
+                got, sts = ctx.overlap_strands(S, mask, R, 1, pi.OVL_MIN, strands=2, kernel=kernel)
+                st = sts[1]
+                assert (got["strand"] == -1).all()
+            print(name, kernel, {k: st[k] for k in ("n_candidates", "n_pairs", "n_overlaps", "n_listed", "n_prefiltered", "n_redo")})
+            assert not got["j"].any() and rows_of(got) == e["want"], (name, kernel)
+            assert st["n_pairs"] == e["pairs"] and st["n_overlaps"] == len(e["want"]), (name, kernel, st)
+            if kernel == PBA_KERNEL_BITVEC:
+                assert (st["n_candidates"], st["n_listed"], st["n_prefiltered"]) == (e["n_match"], e["n_listed"], e["n_pre"]), (name, st)
 
 
 @pytest.mark.parametrize("R", [0.15, 0.30])

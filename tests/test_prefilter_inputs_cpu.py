@@ -165,3 +165,28 @@ def test_overlap_case_candidates_agree_in_both_references(oracle, R):
             assert R < 0.15 or fo == 0
             assert max(pi.plain_diag(a, b)[25:33]) == 2 < sum(x != y for x, y in zip(a[:32], b[:32]))      # the diagonal alone counts more
     assert n_indel == 2 * len(pi.OVL_INDEL_ROWS)
+
+
+@pytest.mark.parametrize("view", ["forward", "rc"])
+@pytest.mark.parametrize("R", [0.15, 0.30])
+def test_straddle_case_shows_the_walks_group_edges(oracle, R, view):
+    """The three targets of straddle_case, as enumeration and the oracle see them (both ways the GPU test runs them): each
+    has 65 .. 192 listed candidates and shows its situation at slots 63 | 64 of the sorted slice -- (a) a run that crosses the
+    edge, fails in the second group at rows 33 .. 64 and succeeds behind that; (b) a run that crosses it with its first success
+    before and another success behind; (c) a run that starts at slot 64.  And a plain walk of the enumeration in slice order
+    gives the oracle's rows and pair count: the order is the one the reference tries candidates in."""
+    views, nq = pi.straddle_views(R)
+    texts, qtexts = views[view]
+    W = pi.walk_composition(oracle, texts, qtexts, R)
+    assert pi.straddle_situations(W["slices"]) == {nq: "a", nq + 1: "b", nq + 2: "c"}
+    for t in range(nq, nq + 3):
+        L = W["slices"][t]
+        assert [c["q"] for c in L] == sorted(c["q"] for c in L)
+        runs = [sum(c["q"] == q for c in L) for q in sorted({c["q"] for c in L})]
+        assert min(runs) >= 10 and max(runs) <= 30 and {c["fwd"] for c in L} == {True, False}
+        assert all(c["ok"] or (c["x"]["rc"] == -1 and 33 <= c["x"]["fail_row"] <= 64) for c in L)       # nothing the scan would stop
+    assert W["n_pre"] == 0
+    want, pairs = pi.oracle_composition(oracle, texts, qtexts, R)
+    assert (W["rows"], W["pairs"]) == (want, pairs)
+    hit = {(t, q) for t, q, *_ in want}
+    assert len({(t, q) for t, q in hit if t >= nq}) == 5 and len(want) >= 10             # (b)'s two successes are one row; and the mirrors
