@@ -282,6 +282,25 @@ int ref_cons_try(int pos, char *seg_origin, int seg_len, int fwd, double R, int3
 
 void ref_cons_evolve(void) { g_cons->evolve(); }
 
+/* ref_seq::elect on a script given as plain arrays (ops: MATCH 1 / INSERT 2 / DELETE 3, vals: edits[k].val).  The caller
+ * keeps every vote inside [pre, post) and gives no forward INSERT on the first box: the list iterators of apply_edits
+ * (ref_seq.h:25-41) are undefined beyond that. */
+void ref_cons_elect(int pos, int fwd, const uint8_t *ops, const char *vals, int nedit) {
+    std::vector<edit> ed(nedit > 0 ? nedit : 1);
+    for (int k = 0; k < nedit; ++k) { ed[k].op = (enum OP)ops[k]; ed[k].val = vals[k]; }
+    g_cons->elect(pos, &ed[0], nedit, fwd != 0);
+}
+
+/* growth without an alignment (ref_seq.h:227-242), so that a state can have pre < beg and post > end */
+void ref_cons_append(const char *seg, int len) {
+    std::vector<char> s(seg, seg + len);
+    if (len > 0) g_cons->append(&s[0], len);
+}
+void ref_cons_prepend(const char *seg, int len) {
+    std::vector<char> s(seg, seg + len);
+    if (len > 0) g_cons->prepend(&s[0], len);
+}
+
 /* one UNLOCKED round of spaced_seed.cpp:420-446 on g_cons: get_seedmap, then every read of the pool in order through
  * try_align (spaced_seed.cpp:262-298) with the reference's own ref_seq::try_align (votes, growth) on the stock
  * t_aligner, OVERLAP_MIN = 64 and the reference's seed_at.  rows[k] <-> pool[k], 10 ints as ref_spaced_round.

@@ -299,6 +299,21 @@ class RefCons(_ConsBase):
     def evolve(self):
         self.lib.ref_cons_evolve()
 
+    def elect(self, pos: int, fwd: bool, ops: np.ndarray, vals: bytes):
+        """ref_seq::elect itself.  Every vote of the script must fall inside [pre, post), and a forward script must not
+        begin with an INSERT on the first box: the reference's list iterators are undefined beyond that."""
+        ops = np.ascontiguousarray(ops, np.uint8)
+        self.lib.ref_cons_elect.argtypes = [C.c_int, C.c_int, _P, C.c_char_p, C.c_int]
+        self.lib.ref_cons_elect(pos, int(fwd), _ptr(ops), vals, ops.size)
+
+    def append(self, seg: bytes):
+        self.lib.ref_cons_append.argtypes = [C.c_char_p, C.c_int]
+        self.lib.ref_cons_append(seg, len(seg))
+
+    def prepend(self, seg: bytes):
+        self.lib.ref_cons_prepend.argtypes = [C.c_char_p, C.c_int]
+        self.lib.ref_cons_prepend(seg, len(seg))
+
     def round(self, mask, R, max_trial, file: bytes, rec_offs, pool, buggy=True):
         assert buggy, "the reference only has its own seed_at"
         buf = np.frombuffer(file + b"\0" * 65536, np.uint8).copy()
@@ -350,6 +365,11 @@ class Ref:
 
     def consensus(self, text: bytes, weight: int = 1):
         return RefCons(self, text, weight)
+
+    def has(self, symbol: str) -> bool:
+        """Whether the library at hand was built from a harness that has this entry point (a prebuilt oracle/_ref that the
+        checkout could not rebuild may be older than oracle/ref_harness.cpp)."""
+        return hasattr(self.lib, symbol)
 
     def encode(self, t: bytes) -> int:
         return self.lib.ref_encode(t)

@@ -169,6 +169,22 @@ def test_consensus_golden(oracle):
         assert sum(t[4] for r in want["rounds"] for t in r["tries"]) >= 12
 
 
+def test_votebox_golden(oracle):
+    """The hand-built vote-box states (tests/votebox_inputs.py) as the reference itself elected and evolved them, twice in a
+    row (tests/golden/votebox.json: every state the reference is defined on): extent, vote boxes and text of the oracle at
+    every stage."""
+    import votebox_inputs as vb
+    gold = gold_json("votebox.json")["states"]
+    assert set(gold) == {st.name for st in vb.all_states() if st.ref_safe}
+    assert {st.name for st in vb.evolve_states()} <= set(gold)
+    for st in vb.all_states():
+        if st.name not in gold:
+            continue
+        c = vb.build(oracle.consensus, st)
+        vb.elect_loop(c, st)
+        assert vb.record(vb.stages(c, st)) == gold[st.name], st.name
+
+
 def test_spaced_multi_golden(oracle):
     """spaced_seed's main loop for a locked reference (seed rotation, pool erasure, stop rule; spaced_seed.cpp:409-452):
     the oracle's locked rounds chained by the same loop reproduce the reference's chain."""
