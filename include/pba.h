@@ -771,6 +771,77 @@ int pba_layout_stitch(pba_ctx *ctx, const pba_layout *lay, const pba_seqs *reads
 int pba_layout_last_stats(const pba_layout *lay, pba_layout_stats *out);
 void pba_layout_destroy(pba_layout *lay);
 
+/* ------------------------------------------------------------------------ */
+/* Placement and consensus of a layout (overlap -> layout -> PLACE -> VOTE   */
+/* -> evolve; DESIGN §5.7, tests/place_ref.py restates the rule).  An overlap */
+/* row ties its query to its target at an exact base: the first pair of      */
+/* elements its alignment compared (pba_overlap_row_pair).  Where the target */
+/* is PLACED and SUPPLIES that base to its contig, the base has a contig     */
+/* coordinate, and the query -- contained reads included -- can vote on the  */
+/* contig from there with try_align's gate, with no index and no mapper.     */
+/* ------------------------------------------------------------------------ */
+typedef struct {
+    int32_t read, found;          /* found 0: no eligible row; every other field 0, contig -1 */
+    uint32_t row;                 /* index of the winning row */
+    int32_t contig, pos, dir;     /* anchor base on the contig; +1 forward / -1 backward (both accessors) */
+    int32_t strand, j;            /* b = the read (+1) or its reverse complement (-1), anchor index in that text */
+} pba_place_row;
+typedef struct {
+    /* n_rows = n_target_not_placed + n_outside (the anchor is not a base the target supplies) + n_eligible */
+    uint64_t n_rows, n_target_not_placed, n_outside, n_eligible;
+    /* reads with a placement, and of those the PLACED / CONTAINED / UNPLACED reads of the layout */
+    uint32_t n_found, n_found_placed, n_found_contained, n_found_unplaced;
+    float place_ms;               /* HIP events on the ctx's stream */
+} pba_place_stats;
+/* One placement per read from n_rows overlap rows (host array, any order, not necessarily the rows the layout was made
+ * from; target, query, strand, dir, cost and the four interval ends are read).  With lt / lq the lengths of target t and
+ * query q and T the layout's row of t:
+ *   walked query interval  strand +1: [qb, qe) = [q_beg, q_end);  strand -1: [lq - q_end, lq - q_beg)
+ *   anchor                 dir +1: xa = t_beg, yb = qb;           dir -1: xa = t_end - 1, yb = qe - 1
+ *   eligible               T.state == PBA_LAY_PLACED and T.skip <= at < T.skip + T.adv, at = xa (T.orient 0) / lt - 1 - xa (1)
+ *   on the contig          contig = T.contig, pos = T.offset + at - T.skip;
+ *                          orient 0: dir, strand, j = yb;  orient 1 (the contig holds rc(t)): -dir, -strand, j = lq - 1 - yb
+ * Among the eligible rows of a query the largest (q_end - q_beg, -cost within [0, 65535], -row index) wins: the key of the
+ * layout's best edges.  The query may be in any state.  The rows go to the device once (the ctx's pooled row buffer); a lane
+ * per row decides eligibility and does a u64 atomicMax into its query's slot, a lane per read writes its row; the work
+ * arrays are pooled, nothing is allocated in a repeated call.  `reads` must be the set the layout was made from.  Checked on
+ * the host before anything is uploaded, as pba_layout_create checks its rows; also PBA_E_INVALID: a dir other than +1 / -1,
+ * a set of another count or other lengths, cap below the number of reads.  No rows and no reads are legal. */
+int pba_layout_place(pba_ctx *ctx, const pba_layout *lay, const pba_seqs *reads, const pba_strand_overlap *rows, uint64_t n_rows,
+                     pba_place_row *out /* one per read */, uint32_t cap, pba_place_stats *stats /* nullable */);
+/* Host arithmetic, no ctx: the pair a found placement votes with, in try_align's roles (a = the contig, b = the read):
+ *   dir +1: a forward from pos,  remainder contig_len - pos;  b forward from j,  b_len = read_len - j
+ *   dir -1: a backward from pos, remainder pos + 1;           b backward from j, b_len = j + 1 (PBA_A_BACKWARD | PBA_B_BACKWARD)
+ *   a_len = min(remainder, b_len + max_dst), max_dst = 1 + (int)(b_len * R): the clip of pba_map_row_pair
+ * For strand -1 b indexes the set of reverse-complemented reads.  PBA_E_INVALID: a NULL, found == 0, a dir or strand other
+ * than +1 / -1, pos or j outside its sequence, R outside (0, 1).  PBA_E_TOOLONG: an accessor beyond the engine's limit. */
+int pba_place_row_pair(const pba_place_row *row, uint32_t contig_len, uint32_t read_len, double R, pba_pair *out);
+/* The twin of pba_pileup_vote_mapped for placement rows: p = pba_pileup_create(ctx, contigs, c_lo, c_hi, weight), any contig
+ * set and any placement rows (not only a layout's).  Rows with found == 0 are skipped (res[k] zeroed, rc = -1); every other
+ * row's contig must lie in [c_lo, c_hi).  The +1 rows and the -1 rows are two batches; a pair votes if and only if it aligns
+ * (rc >= 0) with matlen_a >= overlap_min.  Checks, *n_voted, res and the rules of a spent pile-up as there. */
+int pba_pileup_vote_placed(pba_ctx *ctx, pba_pileup *p, const pba_seqs *contigs, const pba_seqs *reads,
+                           const pba_seqs *reads_rc /* nullable if no row has strand -1 */, const pba_place_row *rows, uint64_t n,
+                           double R, int overlap_min, pba_result *res /* nullable */, uint64_t *n_voted /* nullable */);
+typedef struct {
+    pba_place_stats place;         /* of the one pba_layout_place (place.place_ms: its time) */
+    uint64_t n_voted;              /* placements that voted */
+    uint64_t n_bases_in, n_bases_out;
+    uint32_t n_chunks, n_contigs;
+    float stitch_ms, vote_ms, evolve_ms;   /* HIP events on the ctx's stream */
+} pba_layout_cons_stats;
+/* The consensus of a layout's contigs: pba_layout_stitch, pba_layout_place of `rows`, then pile-ups over consecutive contig
+ * ranges (the budget of pba_polish_contigs: 20 bytes per base, a quarter of the free device memory, fewer than 2^31 boxes,
+ * max_boxes where it is not 0; a range always holds at least one contig, and a single contig whose boxes do not fit is
+ * PBA_E_NOMEM), pba_pileup_vote_placed of each range's placements, evolve, and the texts stitched into *consensus on the
+ * device.  ONE round: a placement addresses the stitched text and evolve moves the coordinates; further rounds are
+ * pba_polish_contigs'.  Contig ids are unchanged, a contig without votes comes back as it was, and the answer does not
+ * depend on the cut.  reads_rc: pba_seqs_revcomp(reads, NULL), or NULL to have it built inside when a placement needs it.
+ * rows_out (nullable): one entry per contig. */
+int pba_layout_consensus(pba_ctx *ctx, const pba_layout *lay, const pba_seqs *reads, const pba_seqs *reads_rc /* nullable */,
+                         const pba_strand_overlap *rows, uint64_t n_rows, double R, int overlap_min, int weight, uint64_t max_boxes,
+                         pba_seqs **consensus, pba_polish_row *rows_out /* nullable */, pba_layout_cons_stats *stats /* nullable */);
+
 const char *pba_strerror(int status);
 
 #ifdef __cplusplus

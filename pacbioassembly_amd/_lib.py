@@ -77,6 +77,17 @@ class PbaLayoutStats(C.Structure):
                [("n_bases", C.c_uint64), ("classify_ms", C.c_float), ("chain_ms", C.c_float), ("stitch_ms", C.c_float)]
 
 
+class PbaPlaceStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_rows", "n_target_not_placed", "n_outside", "n_eligible")] + \
+               [(n, C.c_uint32) for n in ("n_found", "n_found_placed", "n_found_contained", "n_found_unplaced")] + [("place_ms", C.c_float)]
+
+
+class PbaLayoutConsStats(C.Structure):
+    _fields_ = [("place", PbaPlaceStats), ("n_voted", C.c_uint64), ("n_bases_in", C.c_uint64), ("n_bases_out", C.c_uint64),
+                ("n_chunks", C.c_uint32), ("n_contigs", C.c_uint32), ("stitch_ms", C.c_float), ("vote_ms", C.c_float),
+                ("evolve_ms", C.c_float)]
+
+
 class PbaSsRow(C.Structure):
     _fields_ = [(n, C.c_int32) for n in
                 ("read", "found", "j", "dir", "ref_pos", "cost", "matlen_a", "matlen_b", "n_trials", "n_pairs")]
@@ -205,6 +216,10 @@ SYMBOLS = {
     "pba_layout_stitch": (C.c_int, [_P, _P, _P, C.POINTER(_P)]),
     "pba_layout_last_stats": (C.c_int, [_P, _P]),
     "pba_layout_destroy": (None, [_P]),
+    "pba_layout_place": (C.c_int, [_P, _P, _P, _P, C.c_uint64, _P, C.c_uint32, _P]),
+    "pba_place_row_pair": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_double, _P]),
+    "pba_pileup_vote_placed": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_double, C.c_int, _P, C.POINTER(C.c_uint64)]),
+    "pba_layout_consensus": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.c_double, C.c_int, C.c_int, C.c_uint64, C.POINTER(_P), _P, _P]),
     "pba_strerror": (C.c_char_p, [C.c_int]),
 }
 

@@ -20,6 +20,9 @@
 //   k_lay_table      a lane per read: its pba_layout_row, and its slot in the (contig, rank) order (a counting sort whose
 //                    counts are the chains' read counts: slot = first slot of the contig + rank)
 //   k_lay_stitch     a lane per 16 output bases: the supplying read by bisection over the slots' text offsets
+// Placement (pba_layout_place), over any rows against a finished layout:
+//   k_lay_pick       a lane per row: the anchor's contig coordinate (lay_anchor); u64 atomicMax of the best-edge key at the query
+//   k_lay_emit       a lane per read: the winning row back out of the key, its anchor again, one pba_place_row
 // Plain loads, vector stores and global atomics only; no LDS (nothing is shared inside a workgroup but the counters' sums).
 #include "pba_host.h"
 
@@ -261,6 +264,62 @@ k_lay_stitch(SeqSetDev S, const pba_layout_row *table, const int *slot_read, con
     }
 }
 
+// ---- placement: where a row's anchor -- the first pair of elements its alignment compared -- lies on the target's contig
+enum { PC_NOT_PLACED = 0, PC_OUTSIDE, PC_ELIGIBLE, PC_FOUND_PLACED, PC_FOUND_CONTAINED, PC_FOUND_UNPLACED, PC_COUNT };
+struct LayAnchor { int kind, contig, pos, dir, strand, j; };  // kind: PC_NOT_PLACED / PC_OUTSIDE / PC_ELIGIBLE (then the rest)
+
+// The one geometry of both placement kernels.  The anchor base must be one the target SUPPLIES: only there is
+// contig[offset + p] == walked(t)[skip + p] an identity; the bases before skip were supplied by the predecessor's text.
+static __device__ __forceinline__ LayAnchor lay_anchor(const pba_strand_overlap &r, const uint32_t *len, const pba_layout_row *table) {
+    const pba_layout_row T = table[r.target];
+    LayAnchor a{PC_NOT_PLACED, -1, 0, 0, 0, 0};
+    if (T.state != PBA_LAY_PLACED) return a;
+    const int lt = (int)len[r.target], lq = (int)len[r.query];
+    const int qb = r.strand == 1 ? r.q_beg : lq - r.q_end, qe = r.strand == 1 ? r.q_end : lq - r.q_beg;   // of the walked text
+    const int xa = r.dir == 1 ? r.t_beg : r.t_end - 1, yb = r.dir == 1 ? qb : qe - 1;
+    const int at = T.orient ? lt - 1 - xa : xa;               // the anchor in the text the contig holds of t
+    a.kind = PC_OUTSIDE;
+    if (at < T.skip || at >= T.skip + T.adv) return a;
+    a.kind = PC_ELIGIBLE; a.contig = T.contig; a.pos = T.offset + at - T.skip;
+    a.dir = T.orient ? -r.dir : r.dir; a.strand = T.orient ? -r.strand : r.strand;   // the contig holds rc(t): all turns round
+    a.j = T.orient ? lq - 1 - yb : yb;
+    return a;
+}
+
+static __global__ void __launch_bounds__(256)
+k_lay_pick(const pba_strand_overlap *rows, uint64_t n_rows, const uint32_t *len, const pba_layout_row *table, unsigned long long *pick,
+           unsigned long long *counters) {
+    int c[3] = {0, 0, 0};
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n_rows; k += (uint64_t)gridDim.x * blockDim.x) {
+        const pba_strand_overlap r = rows[k];
+        const LayAnchor a = lay_anchor(r, len, table);
+        ++c[a.kind];
+        if (a.kind == PC_ELIGIBLE) atomicMax(&pick[r.query], lay_key(r.q_end - r.q_beg, r.cost, k));
+    }
+    lay_count(counters, PC_NOT_PLACED, c[PC_NOT_PLACED]); lay_count(counters, PC_OUTSIDE, c[PC_OUTSIDE]);
+    lay_count(counters, PC_ELIGIBLE, c[PC_ELIGIBLE]);
+}
+
+static __global__ void __launch_bounds__(256)
+k_lay_emit(const pba_strand_overlap *rows, const uint32_t *len, const pba_layout_row *table, const unsigned long long *pick,
+           pba_place_row *out, uint32_t n, unsigned long long *counters) {
+    int c[3] = {0, 0, 0};                                     // found reads by layout state: UNPLACED, PLACED, CONTAINED
+    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x) {
+        pba_place_row o;
+        o.read = (int32_t)r; o.found = 0; o.row = 0u; o.contig = -1; o.pos = o.dir = o.strand = o.j = 0;
+        const unsigned long long key = pick[r];
+        if (key != 0ull) {                                    // (a key holds a length >= 1: never 0)
+            const uint32_t k = lay_key_row(key);
+            const LayAnchor a = lay_anchor(rows[k], len, table);   // eligible: it was picked
+            o.found = 1; o.row = k; o.contig = a.contig; o.pos = a.pos; o.dir = a.dir; o.strand = a.strand; o.j = a.j;
+            ++c[table[r].state];
+        }
+        out[r] = o;
+    }
+    lay_count(counters, PC_FOUND_PLACED, c[PBA_LAY_PLACED]); lay_count(counters, PC_FOUND_CONTAINED, c[PBA_LAY_CONTAINED]);
+    lay_count(counters, PC_FOUND_UNPLACED, c[PBA_LAY_UNPLACED]);
+}
+
 extern "C" {
 
 struct pba_layout {
@@ -278,23 +337,30 @@ struct pba_layout {
 
 static const uint64_t kLayMaxContig = 0x7FFFFFF0ull;
 
-static int lay_check(pba_ctx *ctx, const pba_seqs *reads, const pba_strand_overlap *rows, uint64_t n_rows, int hang, int min_reads) {
-    if (hang < 0) PBA_FAIL(PBA_E_INVALID, "pba_layout_create: hang must be >= 0");
-    if (min_reads < 1) PBA_FAIL(PBA_E_INVALID, "pba_layout_create: min_reads must be >= 1");
-    if (n_rows >= (1ull << 32)) PBA_FAIL(PBA_E_TOOLONG, "pba_layout_create: 2^32 rows or more (a key holds 32 bits of row index)");
-    if (reads->n >= (1u << 28)) PBA_FAIL(PBA_E_TOOLONG, "pba_layout_create: 2^28 reads or more");
-    if (reads->max_len > 0xFFFFu) PBA_FAIL(PBA_E_TOOLONG, "pba_layout_create: a read of more than 65 535 bases (a key holds 16 bits of length)");
+// what every entry point that takes rows checks of them (who: its name, in front of the message); want_dir: dir is read too
+#define LAY_FAIL(st, what) do { char m__[192]; snprintf(m__, sizeof m__, "%s: %s", who, (what)); return ctx_fail(ctx, (st), m__, hipSuccess); } while (0)
+static int lay_check_rows(pba_ctx *ctx, const char *who, const pba_seqs *reads, const pba_strand_overlap *rows, uint64_t n_rows, bool want_dir) {
+    if (n_rows >= (1ull << 32)) LAY_FAIL(PBA_E_TOOLONG, "2^32 rows or more (a key holds 32 bits of row index)");
+    if (reads->n >= (1u << 28)) LAY_FAIL(PBA_E_TOOLONG, "2^28 reads or more");
+    if (reads->max_len > 0xFFFFu) LAY_FAIL(PBA_E_TOOLONG, "a read of more than 65 535 bases (a key holds 16 bits of length)");
     const int64_t n = reads->n;
     for (uint64_t k = 0; k < n_rows; ++k) {
         const pba_strand_overlap &r = rows[k];
-        if (r.target < 0 || r.target >= n || r.query < 0 || r.query >= n) PBA_FAIL(PBA_E_INVALID, "pba_layout_create: a row names a read outside the set");
-        if (r.target == r.query) PBA_FAIL(PBA_E_INVALID, "pba_layout_create: a row pairs a read with itself");
-        if (r.strand != 1 && r.strand != -1) PBA_FAIL(PBA_E_INVALID, "pba_layout_create: a row's strand is neither +1 nor -1");
+        if (r.target < 0 || r.target >= n || r.query < 0 || r.query >= n) LAY_FAIL(PBA_E_INVALID, "a row names a read outside the set");
+        if (r.target == r.query) LAY_FAIL(PBA_E_INVALID, "a row pairs a read with itself");
+        if (r.strand != 1 && r.strand != -1) LAY_FAIL(PBA_E_INVALID, "a row's strand is neither +1 nor -1");
+        if (want_dir && r.dir != 1 && r.dir != -1) LAY_FAIL(PBA_E_INVALID, "a row's dir is neither +1 nor -1");
         const int64_t lt = reads->h_len[r.target], lq = reads->h_len[r.query];
         if (r.t_beg < 0 || r.t_beg >= r.t_end || r.t_end > lt || r.q_beg < 0 || r.q_beg >= r.q_end || r.q_end > lq)
-            PBA_FAIL(PBA_E_INVALID, "pba_layout_create: a row's interval is empty or outside its read");
+            LAY_FAIL(PBA_E_INVALID, "a row's interval is empty or outside its read");
     }
     return PBA_OK;
+}
+
+static int lay_check(pba_ctx *ctx, const pba_seqs *reads, const pba_strand_overlap *rows, uint64_t n_rows, int hang, int min_reads) {
+    if (hang < 0) PBA_FAIL(PBA_E_INVALID, "pba_layout_create: hang must be >= 0");
+    if (min_reads < 1) PBA_FAIL(PBA_E_INVALID, "pba_layout_create: min_reads must be >= 1");
+    return lay_check_rows(ctx, "pba_layout_create", reads, rows, n_rows, false);
 }
 
 static inline dim3 lay_grid(uint64_t n) { return dim3(elem_grid(n, 256)); }
@@ -475,6 +541,56 @@ int pba_layout_stitch(pba_ctx *ctx, const pba_layout *lay, const pba_seqs *reads
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return pba_seqs_from_device_text(ctx, text.p, d_off.p, nc, total, 0, contigs);
+}
+
+int pba_layout_place(pba_ctx *ctx, const pba_layout *lay, const pba_seqs *reads, const pba_strand_overlap *rows, uint64_t n_rows,
+                     pba_place_row *out, uint32_t cap, pba_place_stats *stats) {
+    if (!ctx || !lay || !reads || (!rows && n_rows)) return PBA_E_INVALID;
+    if (reads->n != lay->n || !std::equal(lay->h_len.begin(), lay->h_len.end(), reads->h_len.begin()))
+        PBA_FAIL(PBA_E_INVALID, "pba_layout_place: the set differs from the layout's in count or lengths");
+    if (cap < lay->n || (!out && lay->n)) PBA_FAIL(PBA_E_INVALID, "pba_layout_place: room for fewer rows than the layout has reads");
+    PBA_TRY(lay_check_rows(ctx, "pba_layout_place", reads, rows, n_rows, true));
+    HIPCHK(hipSetDevice(ctx->device));
+    StageClock clk;
+    if (!clk.init()) PBA_FAIL(PBA_E_HIP, "pba_layout_place: hipEventCreate");
+    const uint32_t n = lay->n;
+    const size_t N = std::max<size_t>(n, 1);
+    size_t carve = 0;
+    auto take = [&carve](size_t bytes) { const size_t at = carve; carve += (bytes + 255) & ~(size_t)255; return at; };
+    const size_t o_pick = take(8 * N), o_cnt = take(8 * PC_COUNT), o_out = take(sizeof(pba_place_row) * N);
+    uint8_t *work = nullptr, *d_rows = nullptr;
+    POOL(POOL_LAY_WORK, carve, work);
+    POOL(POOL_LAY_ROWS, std::max<size_t>(1, sizeof(pba_strand_overlap) * n_rows), d_rows);
+    const pba_strand_overlap *R = (const pba_strand_overlap *)d_rows;
+    unsigned long long *pick = (unsigned long long *)(work + o_pick), *cnt = (unsigned long long *)(work + o_cnt);
+    pba_place_row *d_out = (pba_place_row *)(work + o_out);
+    unsigned long long h_cnt[PC_COUNT];
+    memset(h_cnt, 0, sizeof h_cnt);
+    pba_place_stats s;
+    memset(&s, 0, sizeof s);
+    s.n_rows = n_rows;
+    hipStream_t st = ctx->stream;
+    {   // rows up once; the pick and the emit
+        const auto timed = clk.time(st, &s.place_ms);
+        if (n_rows) HIPCHK(hipMemcpyAsync(d_rows, rows, sizeof(pba_strand_overlap) * n_rows, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(pick, 0, 8 * N, st));
+        HIPCHK(hipMemsetAsync(cnt, 0, 8 * PC_COUNT, st));
+        if (n_rows) hipLaunchKernelGGL(k_lay_pick, lay_grid(n_rows), dim3(256), 0, st, R, n_rows, reads->d_len, lay->table, pick, cnt);
+        if (n) {
+            hipLaunchKernelGGL(k_lay_emit, lay_grid(n), dim3(256), 0, st, R, reads->d_len, lay->table, pick, d_out, n, cnt);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(out, d_out, sizeof(pba_place_row) * (size_t)n, hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h_cnt, cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    s.n_target_not_placed = h_cnt[PC_NOT_PLACED]; s.n_outside = h_cnt[PC_OUTSIDE]; s.n_eligible = h_cnt[PC_ELIGIBLE];
+    s.n_found_placed = (uint32_t)h_cnt[PC_FOUND_PLACED]; s.n_found_contained = (uint32_t)h_cnt[PC_FOUND_CONTAINED];
+    s.n_found_unplaced = (uint32_t)h_cnt[PC_FOUND_UNPLACED];
+    s.n_found = s.n_found_placed + s.n_found_contained + s.n_found_unplaced;
+    if (stats) *stats = s;
+    return PBA_OK;
 }
 
 int pba_layout_last_stats(const pba_layout *lay, pba_layout_stats *out) {

@@ -1,6 +1,8 @@
 // pba_pileup.hip -- read correction from overlap pile-ups: the vote boxes of MANY references at once (every read of a
 // target range is one, csrc/consensus.h has the single-reference form), the segmented vote and evolve, and the driver
-// that chains overlap -> vote -> evolve over a read set.  Host side and kernels.
+// that chains overlap -> vote -> evolve over a read set.  Host side and kernels.  The same boxes serve contigs: the
+// drivers that polish a contig set from its mapped reads and that vote a layout's reads onto its contigs from their
+// placements (pba_layout_consensus) are here too.
 // One process per GPU, one pba_ctx per process, one HIP stream per ctx.  Everything here fails loudly
 // (PBA_E_NODEVICE / PBA_E_HIP): there is no CPU path behind these entry points.
 //
@@ -377,6 +379,66 @@ int pba_pileup_vote_mapped(pba_ctx *ctx, pba_pileup *p, const pba_seqs *target, 
         if (!rows[k].found) { memset(&res[k], 0, sizeof res[k]); res[k].rc = -1; }
     // try_align's gate (ref_seq.h:264-265).  No re-run check: the roles are swapped against the walk that found the row.
     return pile_vote_batches(ctx, p, target, reads, reads_rc, pairs, R, overlap_min, [&](int s, const std::vector<pba_result> &out) {
+        for (size_t q = 0; q < out.size(); ++q) {
+            if (res) res[which[s][q]] = out[q];
+            if (out[q].rc < 0 || out[q].matlen_a < overlap_min) continue;
+            ++p->n_rows[(uint32_t)rows[which[s][q]].contig - p->t_lo];
+            if (n_voted) ++*n_voted;
+        }
+        return PBA_OK;
+    });
+}
+
+int pba_place_row_pair(const pba_place_row *row, uint32_t contig_len, uint32_t read_len, double R, pba_pair *out) {
+    if (!row || !out || !row->found || (row->strand != 1 && row->strand != -1) || (row->dir != 1 && row->dir != -1)) return PBA_E_INVALID;
+    if (!(R > 0.0) || !(R < 1.0) || row->contig < 0 || row->read < 0 || row->j < 0 || row->pos < 0) return PBA_E_INVALID;
+    if (contig_len > 0x7FFFFFFFu || read_len > 0x7FFFFFFFu) return PBA_E_INVALID;
+    if ((uint32_t)row->j >= read_len || (uint32_t)row->pos >= contig_len) return PBA_E_INVALID;
+    const bool fwd = row->dir == 1;
+    const int rem_a = fwd ? (int)(contig_len - (uint32_t)row->pos) : row->pos + 1;
+    const int b_len = fwd ? (int)(read_len - (uint32_t)row->j) : row->j + 1;
+    const TextClip c = text_clip(rem_a, b_len, R);            // the cut align makes itself, as in pba_map_row_pair
+    if (c.len_a > kMaxSeqLen || b_len > kMaxSeqLen) return PBA_E_TOOLONG;
+    memset(out, 0, sizeof *out);
+    out->a_seq = (uint32_t)row->contig; out->a_pos = row->pos; out->a_len = c.len_a;
+    out->b_seq = (uint32_t)row->read; out->b_pos = row->j; out->b_len = b_len;
+    out->flags = fwd ? 0u : (PBA_A_BACKWARD | PBA_B_BACKWARD);
+    return PBA_OK;
+}
+
+int pba_pileup_vote_placed(pba_ctx *ctx, pba_pileup *p, const pba_seqs *contigs, const pba_seqs *reads, const pba_seqs *reads_rc,
+                           const pba_place_row *rows, uint64_t n, double R, int overlap_min, pba_result *res, uint64_t *n_voted) {
+    if (!ctx || !p || !contigs || !reads || (!rows && n)) return PBA_E_INVALID;
+    if (n_voted) *n_voted = 0;
+    if (p->spent) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_placed: the pile-up is spent");
+    if (!(R > 0.0) || !(R < 1.0)) PBA_FAIL(PBA_E_INVALID, "R must be in (0,1)");
+    if (!pile_same_reads(p, contigs)) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_placed: contigs is not the set of this pile-up");
+    if (reads_rc && (reads_rc->n != reads->n || reads_rc->h_len != reads->h_len))
+        PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_placed: reads_rc differs from reads in count or lengths");
+    if (contigs->non_acgt || reads->non_acgt || (reads_rc && reads_rc->non_acgt))
+        PBA_FAIL(PBA_E_ALPHABET, "pba_pileup_vote_placed: a set holds bytes outside ACGT");
+    if (n > 0x7FFFFFFFull) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_placed: too many rows in one call");
+    std::vector<pba_pair> pairs[2];       // strand +1 (B = reads), strand -1 (B = reads_rc)
+    std::vector<uint32_t> which[2];
+    for (uint64_t k = 0; k < n; ++k) {
+        const pba_place_row &r = rows[k];
+        if (!r.found) continue;
+        if (r.contig < 0 || (uint32_t)r.contig < p->t_lo || (uint32_t)r.contig >= p->t_hi)
+            PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_placed: a row's contig is outside the pile-up's range");
+        if (r.read < 0 || (uint32_t)r.read >= reads->n) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_placed: a row's read is not a read of the set");
+        if (r.strand == -1 && !reads_rc) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_placed: a strand -1 row needs reads_rc");
+        pba_pair pr;
+        const int st = pba_place_row_pair(&r, contigs->h_len[r.contig], reads->h_len[r.read], R, &pr);
+        if (st == PBA_E_TOOLONG) PBA_FAIL(PBA_E_TOOLONG, "pba_pileup_vote_placed: a row's accessor is longer than the engine limit");
+        if (st != PBA_OK) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_placed: a row's dir, strand or anchor is not valid for its sequences");
+        const int s = r.strand == 1 ? 0 : 1;
+        pairs[s].push_back(pr); which[s].push_back((uint32_t)k);
+    }
+    for (uint64_t k = 0; res && k < n; ++k)
+        if (!rows[k].found) { memset(&res[k], 0, sizeof res[k]); res[k].rc = -1; }
+    // try_align's gate (ref_seq.h:264-265).  No re-run check: this alignment starts at the row's anchor but has the contig,
+    // not the target read, as a, and runs to the end of the read.
+    return pile_vote_batches(ctx, p, contigs, reads, reads_rc, pairs, R, overlap_min, [&](int s, const std::vector<pba_result> &out) {
         for (size_t q = 0; q < out.size(); ++q) {
             if (res) res[which[s][q]] = out[q];
             if (out[q].rc < 0 || out[q].matlen_a < overlap_min) continue;
@@ -844,6 +906,126 @@ int pba_polish_contigs_budget(pba_ctx *ctx, const pba_seqs *target, const pba_se
     for (uint32_t k = 0; rows_out && k < c.cur->n; ++k)
         rows_out[k] = pba_polish_row{c.crows[k].target, c.crows[k].n_rows, c.crows[k].len_in, c.crows[k].len_out};
     *polished = c.own; c.own = nullptr;
+    return PBA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// pba_layout_consensus: stitch -> place -> vote -> evolve over a layout's contigs, one round
+// ---------------------------------------------------------------------------------------------
+// what lives across one call of pba_layout_consensus
+struct LayConsRun {
+    pba_ctx *ctx;
+    const pba_seqs *reads, *reads_rc;            // reads_rc: the caller's, or `rc`
+    double R;
+    int overlap_min, weight;
+    uint64_t max_boxes;
+    pba_seqs *rc = nullptr, *contigs = nullptr;  // owned: the reverse complement, the stitched set, the range's pile-up
+    pba_pileup *pile = nullptr;
+    StageClock clk;
+    pba_layout_cons_stats st;
+    std::vector<pba_place_row> places;           // one per read, then the found ones ordered by contig
+    std::vector<uint64_t> first;                 // found placements of contig c: places[first[c] .. first[c + 1])
+    std::vector<pba_correct_row> crows;          // per contig
+    std::deque<PileText> chunks;
+    ~LayConsRun() { pba_pileup_destroy(pile); if (contigs) pba_seqs_destroy(contigs); if (rc) pba_seqs_destroy(rc); }
+};
+
+// the placements; the found ones ordered by contig (stable: by read inside a contig); the reverse complement if one needs it
+static int laycons_place(LayConsRun &c, const pba_layout *lay, const pba_strand_overlap *rows, uint64_t n_rows) {
+    pba_ctx *ctx = c.ctx;
+    c.places.assign(std::max<size_t>(c.reads->n, 1), pba_place_row{});
+    PBA_TRY(pba_layout_place(ctx, lay, c.reads, rows, n_rows, c.places.data(), c.reads->n, &c.st.place));
+    c.first.assign((size_t)c.contigs->n + 1, 0);
+    bool minus = false;
+    for (uint32_t r = 0; r < c.reads->n; ++r)
+        if (c.places[r].found) { ++c.first[(size_t)c.places[r].contig + 1]; minus |= c.places[r].strand == -1; }
+    for (uint32_t k = 0; k < c.contigs->n; ++k) c.first[k + 1] += c.first[k];
+    std::vector<pba_place_row> by(c.first.back());
+    std::vector<uint64_t> at(c.first.begin(), c.first.end() - 1);
+    for (uint32_t r = 0; r < c.reads->n; ++r)
+        if (c.places[r].found) by[at[c.places[r].contig]++] = c.places[r];
+    c.places.swap(by);
+    if (minus && !c.reads_rc) {
+        PBA_TRY(pba_seqs_revcomp(ctx, c.reads, nullptr, &c.rc));
+        c.reads_rc = c.rc;
+    }
+    return PBA_OK;
+}
+
+// the next range of contigs [lo, *hi): the budget rule of polish_next_chunk
+static int laycons_next_chunk(const LayConsRun &c, uint32_t lo, uint32_t *hi) {
+    pba_ctx *ctx = c.ctx;
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const uint64_t room = std::min<uint64_t>(kPileMaxBoxes - 1, (uint64_t)(free_b / 4) / 20);
+    const uint64_t budget = c.max_boxes ? std::min(room, c.max_boxes) : room;
+    uint64_t boxes = 0;
+    *hi = lo;
+    while (*hi < c.contigs->n && (*hi == lo || boxes + c.contigs->h_len[*hi] <= budget)) boxes += c.contigs->h_len[(*hi)++];
+    if (boxes > room) PBA_FAIL(PBA_E_NOMEM, "pba_layout_consensus: the vote boxes of one contig do not fit the device");
+    return PBA_OK;
+}
+
+// the range's boxes and the votes of the reads placed on its contigs
+static int laycons_vote(LayConsRun &c, uint32_t lo, uint32_t hi) {
+    const auto timed = c.clk.time(c.ctx->stream, &c.st.vote_ms);
+    uint64_t voted = 0;
+    PBA_TRY(pba_pileup_create(c.ctx, c.contigs, lo, hi, c.weight, &c.pile));
+    PBA_TRY(pba_pileup_vote_placed(c.ctx, c.pile, c.contigs, c.reads, c.reads_rc, c.places.data() + c.first[lo], c.first[hi] - c.first[lo],
+                                   c.R, c.overlap_min, nullptr, &voted));
+    c.st.n_voted += voted;
+    return PBA_OK;
+}
+
+// the range's boxes to its text (and its rows of crows); the pile-up is gone after it
+static int laycons_evolve(LayConsRun &c, uint32_t lo) {
+    if (!c.chunks.empty()) c.chunks.back().d_off.reset();    // only the last chunk's offsets are used again (stitch_chunks)
+    {
+        const auto timed = c.clk.time(c.ctx->stream, &c.st.evolve_ms);
+        c.chunks.emplace_back();
+        PBA_TRY(pile_evolve_text(c.ctx, c.pile, &c.chunks.back(), c.crows.data() + lo));
+    }
+    pba_pileup_destroy(c.pile); c.pile = nullptr;
+    return PBA_OK;
+}
+
+int pba_layout_consensus(pba_ctx *ctx, const pba_layout *lay, const pba_seqs *reads, const pba_seqs *reads_rc,
+                         const pba_strand_overlap *rows, uint64_t n_rows, double R, int overlap_min, int weight, uint64_t max_boxes,
+                         pba_seqs **consensus, pba_polish_row *rows_out, pba_layout_cons_stats *stats) {
+    if (!ctx || !lay || !reads || !consensus || (!rows && n_rows)) return PBA_E_INVALID;
+    *consensus = nullptr;
+    if (weight < 1 || weight > 0xFFFF) PBA_FAIL(PBA_E_INVALID, "pba_layout_consensus: weight must be in [1, 65535]");
+    if (!(R > 0.0) || !(R < 1.0)) PBA_FAIL(PBA_E_INVALID, "R must be in (0,1)");
+    if (reads_rc && (reads_rc->n != reads->n || reads_rc->h_len != reads->h_len))
+        PBA_FAIL(PBA_E_INVALID, "pba_layout_consensus: reads_rc differs from reads in count or lengths");
+    if (reads->non_acgt || (reads_rc && reads_rc->non_acgt)) PBA_FAIL(PBA_E_ALPHABET, "pba_layout_consensus: a set holds bytes outside ACGT");
+    HIPCHK(hipSetDevice(ctx->device));
+    LayConsRun c{ctx, reads, reads_rc, R, overlap_min, weight, max_boxes};
+    if (!c.clk.init()) PBA_FAIL(PBA_E_HIP, "pba_layout_consensus: events");
+    memset(&c.st, 0, sizeof c.st);
+    {
+        const auto timed = c.clk.time(ctx->stream, &c.st.stitch_ms);
+        PBA_TRY(pba_layout_stitch(ctx, lay, reads, &c.contigs));
+    }
+    PBA_TRY(laycons_place(c, lay, rows, n_rows));
+    const uint32_t nt = c.contigs->n;
+    c.st.n_contigs = nt;
+    c.crows.assign(std::max<uint32_t>(nt, 1), pba_correct_row{});
+    for (uint32_t lo = 0, hi = 0; lo < nt; lo = hi) {
+        PBA_TRY(laycons_next_chunk(c, lo, &hi));
+        PBA_TRY(laycons_vote(c, lo, hi));
+        PBA_TRY(laycons_evolve(c, lo));
+        ++c.st.n_chunks;
+    }
+    for (uint32_t k = 0; k < nt; ++k) c.st.n_bases_in += c.contigs->h_len[k];
+    {
+        const auto timed = c.clk.time(ctx->stream, &c.st.evolve_ms);
+        PBA_TRY(stitch_chunks(ctx, c.chunks, nt, &c.st.n_bases_out, consensus));
+    }
+    c.chunks.clear();
+    for (uint32_t k = 0; rows_out && k < nt; ++k)
+        rows_out[k] = pba_polish_row{c.crows[k].target, c.crows[k].n_rows, c.crows[k].len_in, c.crows[k].len_out};
+    if (stats) *stats = c.st;
     return PBA_OK;
 }
 

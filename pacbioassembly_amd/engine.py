@@ -40,10 +40,14 @@ POLISH_LOG_DTYPE = np.dtype([("round", "<i4"), ("n_mapped", "<u4"), ("n_voted", 
 LAYOUT_ROW_DTYPE = np.dtype([(n, "<i4") for n in ("read", "state", "contig", "rank", "orient", "offset", "skip", "adv", "container")])
 LAYOUT_CONTIG_DTYPE = np.dtype([(n, "<i4") for n in ("head_read", "n_reads", "length")])
 PBA_LAY_UNPLACED, PBA_LAY_PLACED, PBA_LAY_CONTAINED = 0, 1, 2
+# pba_place_row: one per read, where it votes on its layout's contigs
+PLACE_ROW_DTYPE = np.dtype([("read", "<i4"), ("found", "<i4"), ("row", "<u4"), ("contig", "<i4"), ("pos", "<i4"), ("dir", "<i4"),
+                            ("strand", "<i4"), ("j", "<i4")])
 assert PAIR_DTYPE.itemsize == C.sizeof(PbaPair) and RESULT_DTYPE.itemsize == C.sizeof(PbaResult)
 assert LOC_ROW_DTYPE.itemsize == C.sizeof(PbaLocRow) and SS_ROW_DTYPE.itemsize == C.sizeof(PbaSsRow)
 assert MAP_ROW_DTYPE.itemsize == C.sizeof(PbaMapRow)
 assert POLISH_LOG_DTYPE.itemsize == C.sizeof(_lib.PbaPolishRoundLog)
+assert PLACE_ROW_DTYPE.itemsize == 32
 
 
 class PbaError(RuntimeError):
@@ -597,6 +601,20 @@ def map_row_pair(row, contig_len: int, read_len: int, R: float) -> np.ndarray:
     return out[0]
 
 
+def place_row_pair(row, contig_len: int, read_len: int, R: float) -> np.ndarray:
+    """The pair a found placement votes with (pba_place_row_pair; host arithmetic): one PAIR_DTYPE record with a = the contig
+    from pos, clipped to b_len + max_dst, b = the read from j, both backward for dir -1 -- for a strand -1 row b indexes the
+    reverse-complemented set."""
+    r = np.zeros(1, PLACE_ROW_DTYPE)
+    for f in PLACE_ROW_DTYPE.names:
+        r[f] = row[f]
+    out = np.zeros(1, PAIR_DTYPE)
+    st = _lib.load().pba_place_row_pair(_ptr(r), contig_len, read_len, R, _ptr(out))
+    if st != 0:
+        raise PbaError(st, "place_row_pair")
+    return out[0]
+
+
 def _polish_contigs(self, target, reads, mask, R, trials=50, min_len=500, maxn=0, maxm=0, kernel=PBA_KERNEL_AUTO, strands=3,
                     overlap_min=64, weight=1, rounds=1, reads_rc=None, max_boxes=0):
     """`rounds` rounds of index -> map_reads -> vote -> evolve over the contigs of `target` (pba_polish_contigs).  max_boxes: a
@@ -937,6 +955,18 @@ class Pileup:
                                                            overlap_min, _ptr(res), C.byref(n_voted)), "pileup_vote_mapped")
         return res[:rows.size], int(n_voted.value)
 
+    def vote_placed(self, reads: "SeqSet", rows: np.ndarray, R: float, overlap_min: int = 64, reads_rc: Optional["SeqSet"] = None):
+        """Vote placement rows (Layout.place, or any PLACE_ROW_DTYPE rows) of `reads` onto the contig set this pile-up was made
+        from (pba_pileup_vote_placed): a found row votes if its alignment from the anchor succeeds with matlen_a >=
+        overlap_min.  Returns (results row by row, rows voted)."""
+        rows = np.ascontiguousarray(rows, PLACE_ROW_DTYPE)
+        res = np.zeros(max(rows.size, 1), RESULT_DTYPE)
+        n_voted = C.c_uint64()
+        self.ctx.check(self.ctx.lib.pba_pileup_vote_placed(self.ctx.h, self.h, self.reads.h, reads.h,
+                                                           reads_rc.h if reads_rc is not None else None, _ptr(rows), rows.size, R,
+                                                           overlap_min, _ptr(res), C.byref(n_voted)), "pileup_vote_placed")
+        return res[:rows.size], int(n_voted.value)
+
     def dump(self, target: int):
         """(sel[n, 4], sup[n, 4], tot[n]) of one target's boxes as they stand."""
         n = C.c_int32()
@@ -1005,6 +1035,17 @@ class Layout:
         self.ctx.check(self.ctx.lib.pba_layout_stitch(self.ctx.h, self.h, reads.h, C.byref(h)), "layout_stitch")
         return SeqSet(self.ctx, h)
 
+    def place(self, reads: "SeqSet", rows: np.ndarray) -> np.ndarray:
+        """One PLACE_ROW_DTYPE record per read: where overlap_strands `rows` (any rows over `reads`, dir included) anchor it
+        on this layout's contigs (pba_layout_place).  The counters of the call are kept in place_stats."""
+        rows = np.ascontiguousarray(rows, STRAND_OVERLAP_DTYPE)
+        out = np.zeros(max(self.n, 1), PLACE_ROW_DTYPE)
+        st = _lib.PbaPlaceStats()
+        self.ctx.check(self.ctx.lib.pba_layout_place(self.ctx.h, self.h, reads.h, _ptr(rows), rows.size, _ptr(out), self.n, C.byref(st)),
+                       "layout_place")
+        self.place_stats = {n: getattr(st, n) for n, _ in _lib.PbaPlaceStats._fields_}
+        return out[:self.n]
+
 
 def _layout(self, reads, rows, hang=64, min_reads=2) -> "Layout":
     """Lay `reads` out into contigs from overlap_strands rows (pba_layout_create)."""
@@ -1021,8 +1062,27 @@ def _layout_reads(self, reads, mask, R, max_trial=32, overlap_min=64, hang=64, m
     return lay.stitch(reads), lay, rows, st2
 
 
+def _layout_consensus(self, lay, reads, rows, R, overlap_min=64, weight=1, max_boxes=0, reads_rc=None):
+    """The consensus of a layout's contigs from the reads its overlap rows place on them (pba_layout_consensus): stitch ->
+    place -> vote -> evolve, one round.  max_boxes: a ceiling on the bases of one internal range of contigs (0 = sized from the
+    free device memory).  Returns (SeqSet of the contigs, rows of POLISH_ROW_DTYPE per contig, stats: the place counters,
+    n_voted, n_chunks, n_contigs, bases in and out and the stage times)."""
+    rows = np.ascontiguousarray(rows, STRAND_OVERLAP_DTYPE)
+    nc = int(self.lib.pba_layout_contigs(lay.h))
+    rows_out = np.zeros(max(nc, 1), POLISH_ROW_DTYPE)
+    st = _lib.PbaLayoutConsStats()
+    h = C.c_void_p()
+    rc_h = reads_rc.h if reads_rc is not None else None
+    self.check(self.lib.pba_layout_consensus(self.h, lay.h, reads.h, rc_h, _ptr(rows), rows.size, R, overlap_min, weight, max_boxes,
+                                             C.byref(h), _ptr(rows_out), C.byref(st)), "layout_consensus")
+    stats = {n: getattr(st.place, n) for n, _ in _lib.PbaPlaceStats._fields_}
+    stats.update({n: getattr(st, n) for n, _ in _lib.PbaLayoutConsStats._fields_ if n != "place"})
+    return SeqSet(self, h), rows_out[:nc], stats
+
+
 Context.layout = _layout
 Context.layout_reads = _layout_reads
+Context.layout_consensus = _layout_consensus
 
 
 def script_vals(ops: np.ndarray, seg: bytes, fwd: bool = True) -> bytes:

@@ -4,7 +4,13 @@
 per-stage HIP-event times (overlap scan / sort / walk of both strands, layout classify / chain / stitch, the polish round's
 stages), the layout's counters, contig count and N50, and the mean edit distance of sampled contig windows to the genome
 before and after polishing.  The expectation to check: layout and stitch cost far less than the overlap call that feeds them.
-A measured line belongs in profiles/layout_line.json."""
+A measured line belongs in profiles/layout_line.json.
+--consensus (opt-in; the defaults are unchanged) adds a leg next to the polish leg: pba_layout_consensus of the same layout
+and rows (stitch -> place -> vote -> evolve, one round, no index and no mapper), its stage times and counters, and the
+distance of the same sampled windows as stitched, after layout_consensus and after the one polish round; the line is also
+written to profiles/layout_consensus_line.json.  The expectation to record: place costs a few row-sized launches, vote costs
+what polish's vote stage costs for the same number of voting reads.  Compare times against the polish leg of the same run at
+the parent commit's code, never against itself."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -23,6 +29,7 @@ ap.add_argument("--min-reads", type=int, default=2)
 ap.add_argument("--targets-per-call", type=int, default=10_000)
 ap.add_argument("--sample", type=int, default=40, help="contig windows of --window bases whose distance to the genome is measured")
 ap.add_argument("--window", type=int, default=2000)
+ap.add_argument("--consensus", action="store_true", help="also run pba_layout_consensus on the layout and report it next to the polish leg")
 a = ap.parse_args()
 _COMP = bytes.maketrans(b"ACGT", b"TGCA")
 
@@ -83,6 +90,12 @@ lens = np.sort(info["length"].astype(np.int64))[::-1]
 n50 = int(lens[np.searchsorted(np.cumsum(lens), lens.sum() / 2)]) if lens.size else 0
 polished, prow, plog = ctx.polish_contigs(contigs, Rd, mask, a.R, 50, 500, strands=3, rounds=1, reads_rc=Rc)
 t3 = time.perf_counter()
+cons = None
+if a.consensus:
+    ctx.layout_consensus(lay, Rd, rows, a.R, a.overlap_min, reads_rc=Rc)[0].close()      # warm-up, as for the layout
+    t4 = time.perf_counter()
+    cons, crow, cst = ctx.layout_consensus(lay, Rd, rows, a.R, a.overlap_min, reads_rc=Rc)
+    t5 = time.perf_counter()
 
 
 def windows(S):
@@ -104,7 +117,7 @@ def windows(S):
 
 
 ovl_ms = sum(s.get(k, 0.0) for s in ost for k in ("scan_ms", "sort_ms", "walk_ms"))
-print(json.dumps({
+line = {
     "workload": f"layout of {a.reads} x {a.read_len} reads @15% of a {a.genome} genome, {int(flip.sum())} reverse-complemented, R={a.R}, "
                 f"max_trial={a.max_trial}, overlap_min={a.overlap_min}, hang={a.hang}, min_reads={a.min_reads}",
     "overlap_rows": int(len(rows)), "overlap_event_ms": round(ovl_ms, 2), "overlap_wall_s": round(t_ovl - t0, 3),
@@ -116,4 +129,13 @@ print(json.dumps({
     "polish_rows_voted": int(plog["n_voted"].sum()),
     "truth_sample": {"windows": int(min(a.sample, len(info))), "window": a.window, "mean_distance_before": windows(contigs),
                      "mean_distance_after": windows(polished)},
-}))
+}
+if cons is not None:
+    line["consensus"] = {k: round(float(cst[k]), 3) for k in ("stitch_ms", "place_ms", "vote_ms", "evolve_ms")}
+    line["consensus_wall_s"] = round(t5 - t4, 3)
+    line["consensus_counters"] = {k: int(v) for k, v in cst.items() if not k.endswith("_ms")}
+    line["truth_sample"].update(mean_distance_stitched=line["truth_sample"]["mean_distance_before"],
+                                mean_distance_after_consensus=windows(cons), mean_distance_after_polish=line["truth_sample"]["mean_distance_after"])
+    with open(os.path.join(ROOT, "profiles", "layout_consensus_line.json"), "w") as f:
+        f.write(json.dumps(line) + "\n")
+print(json.dumps(line))
