@@ -111,6 +111,12 @@ static inline int ctx_fail(pba_ctx *ctx, int st, const char *what, hipError_t e)
         if (e__ != hipSuccess) return ctx_fail(ctx, PBA_E_HIP, #call, e__); \
     } while (0)
 #define PBA_FAIL(st, what) return ctx_fail(ctx, (st), (what), hipSuccess)
+// "who: what" where code shared by several entry points fails: who is the public function that was called
+static inline int ctx_fail_as(pba_ctx *ctx, int st, const char *who, const char *what) {
+    char msg[256];
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return ctx_fail(ctx, st, msg, hipSuccess);
+}
 // (for a callee that has written ctx->err itself)
 #define PBA_TRY(call) do { const int rc__ = (call); if (rc__ != PBA_OK) return rc__; } while (0)
 

@@ -2,7 +2,9 @@
 // target range is one, csrc/consensus.h has the single-reference form), the segmented vote and evolve, and the driver
 // that chains overlap -> vote -> evolve over a read set.  Host side and kernels.  The same boxes serve contigs: the
 // drivers that polish a contig set from its mapped reads and that vote a layout's reads onto its contigs from their
-// placements (pba_layout_consensus) are here too.
+// placements (pba_layout_consensus) are here too.  Mapped rows and placements vote through one gated vote
+// (pile_vote_gated) and one anchor -> pair function; the three drivers share their run state (PileRun), the budget of a
+// range and its greedy take, and the two contig drivers one round over the ranges of a contig set (contig_round).
 // One process per GPU, one pba_ctx per process, one HIP stream per ctx.  Everything here fails loudly
 // (PBA_E_NODEVICE / PBA_E_HIP): there is no CPU path behind these entry points.
 //
@@ -262,6 +264,21 @@ static bool pile_same_reads(const pba_pileup *p, const pba_seqs *reads) {
     return true;
 }
 
+// What every vote call checks before it looks at a row, in the order include/pba.h gives.  who: the public function that
+// was called; target: the set the boxes were filled from (under pba_pileup_vote the reads themselves).
+static int pile_vote_check(pba_ctx *ctx, const pba_pileup *p, const char *who, const pba_seqs *target, const pba_seqs *reads,
+                           const pba_seqs *reads_rc, uint64_t n, double R) {
+    if (p->spent) return ctx_fail_as(ctx, PBA_E_INVALID, who, "the pile-up is spent");
+    if (!(R > 0.0) || !(R < 1.0)) PBA_FAIL(PBA_E_INVALID, "R must be in (0,1)");
+    if (!pile_same_reads(p, target)) return ctx_fail_as(ctx, PBA_E_INVALID, who, "the target set is not the set of this pile-up");
+    if (reads_rc && (reads_rc->n != reads->n || reads_rc->h_len != reads->h_len))
+        return ctx_fail_as(ctx, PBA_E_INVALID, who, "reads_rc differs from reads in count or lengths");
+    if (target->non_acgt || reads->non_acgt || (reads_rc && reads_rc->non_acgt))
+        return ctx_fail_as(ctx, PBA_E_ALPHABET, who, "a set holds bytes outside ACGT");
+    if (n > 0x7FFFFFFFull) return ctx_fail_as(ctx, PBA_E_INVALID, who, "too many rows in one call");
+    return PBA_OK;
+}
+
 // The votes of a call: pairs[0] against B = fwd, pairs[1] against B = rc, two batches into the boxes of p (A: the set they
 // were filled from), gated by overlap_min; after(s, results of batch s) once a batch has voted.
 extern "C++" template <class After>
@@ -291,14 +308,8 @@ static int pile_vote_batches(pba_ctx *ctx, pba_pileup *p, const pba_seqs *A, con
 int pba_pileup_vote(pba_ctx *ctx, pba_pileup *p, const pba_seqs *reads, const pba_seqs *reads_rc,
                     const pba_strand_overlap *rows, uint64_t n, double R, pba_result *res) {
     if (!ctx || !p || !reads || (!rows && n)) return PBA_E_INVALID;
-    if (p->spent) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote: the pile-up is spent");
-    if (!(R > 0.0) || !(R < 1.0)) PBA_FAIL(PBA_E_INVALID, "R must be in (0,1)");
-    if (!pile_same_reads(p, reads)) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote: reads is not the set of this pile-up");
-    if (reads_rc && (reads_rc->n != reads->n || reads_rc->h_len != reads->h_len))
-        PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote: reads_rc differs from reads in count or lengths");
-    if (reads->non_acgt || (reads_rc && reads_rc->non_acgt)) PBA_FAIL(PBA_E_ALPHABET, "pba_pileup_vote: the read set holds bytes outside ACGT");
+    PBA_TRY(pile_vote_check(ctx, p, "pba_pileup_vote", reads, reads, reads_rc, n, R));
     if (n == 0) return PBA_OK;
-    if (n > 0x7FFFFFFFull) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote: too many rows in one call");
     std::vector<pba_pair> pairs[2];       // strand +1 (B = reads), strand -1 (B = reads_rc)
     std::vector<uint32_t> which[2];
     for (uint64_t k = 0; k < n; ++k) {
@@ -333,51 +344,69 @@ int pba_pileup_vote(pba_ctx *ctx, pba_pileup *p, const pba_seqs *reads, const pb
     });
 }
 
+// The pair of a read that votes from an anchor: base `pos` of the contig against base `j` of the read's text, from there
+// onwards (dir +1) or backwards (dir -1, both accessors) to the end of the read.  The callers have checked the anchor
+// against the lengths.
+static int anchored_pair(int32_t contig, int32_t pos, int32_t read, int32_t j, int dir, uint32_t contig_len, uint32_t read_len,
+                         double R, pba_pair *out) {
+    const bool fwd = dir == 1;
+    const int rem_a = fwd ? (int)(contig_len - (uint32_t)pos) : pos + 1;
+    const int b_len = fwd ? (int)(read_len - (uint32_t)j) : j + 1;
+    // align cuts a to b + max_dst itself whenever a is the longer side (seq_aligner.h:94-102): the same cut, made here
+    const TextClip c = text_clip(rem_a, b_len, R);
+    if (c.len_a > kMaxSeqLen || b_len > kMaxSeqLen) return PBA_E_TOOLONG;
+    memset(out, 0, sizeof *out);
+    out->a_seq = (uint32_t)contig; out->a_pos = pos; out->a_len = c.len_a;
+    out->b_seq = (uint32_t)read; out->b_pos = j; out->b_len = b_len;
+    out->flags = fwd ? 0u : (PBA_A_BACKWARD | PBA_B_BACKWARD);
+    return PBA_OK;
+}
+
 int pba_map_row_pair(const pba_map_row *row, uint32_t contig_len, uint32_t read_len, double R, pba_pair *out) {
     if (!row || !out || !row->found || (row->strand != 1 && row->strand != -1)) return PBA_E_INVALID;
     if (!(R > 0.0) || !(R < 1.0) || row->contig < 0 || row->read < 0 || row->j < 0 || row->pos < 0) return PBA_E_INVALID;
     if (contig_len > 0x7FFFFFFFu || read_len > 0x7FFFFFFFu) return PBA_E_INVALID;
     if ((uint32_t)row->j >= read_len || (uint32_t)row->pos >= contig_len) return PBA_E_INVALID;
-    // align cuts a to b + max_dst itself whenever a is the longer side (seq_aligner.h:94-102): the same cut, made here
-    const TextClip c = text_clip((int)(contig_len - (uint32_t)row->pos), (int)(read_len - (uint32_t)row->j), R);
-    if (c.len_a > kMaxSeqLen || read_len - (uint32_t)row->j > (uint32_t)kMaxSeqLen) return PBA_E_TOOLONG;
-    memset(out, 0, sizeof *out);
-    out->a_seq = (uint32_t)row->contig; out->a_pos = row->pos; out->a_len = c.len_a;
-    out->b_seq = (uint32_t)row->read; out->b_pos = row->j; out->b_len = (int32_t)(read_len - (uint32_t)row->j);
-    return PBA_OK;
+    return anchored_pair(row->contig, row->pos, row->read, row->j, 1, contig_len, read_len, R, out);
 }
 
-int pba_pileup_vote_mapped(pba_ctx *ctx, pba_pileup *p, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
-                           const pba_map_row *rows, uint64_t n, double R, int overlap_min, pba_result *res, uint64_t *n_voted) {
+int pba_place_row_pair(const pba_place_row *row, uint32_t contig_len, uint32_t read_len, double R, pba_pair *out) {
+    if (!row || !out || !row->found || (row->strand != 1 && row->strand != -1) || (row->dir != 1 && row->dir != -1)) return PBA_E_INVALID;
+    if (!(R > 0.0) || !(R < 1.0) || row->contig < 0 || row->read < 0 || row->j < 0 || row->pos < 0) return PBA_E_INVALID;
+    if (contig_len > 0x7FFFFFFFu || read_len > 0x7FFFFFFFu) return PBA_E_INVALID;
+    if ((uint32_t)row->j >= read_len || (uint32_t)row->pos >= contig_len) return PBA_E_INVALID;
+    return anchored_pair(row->contig, row->pos, row->read, row->j, row->dir, contig_len, read_len, R, out);
+}
+
+// Rows of reads anchored on the targets of p (pba_map_row, pba_place_row: the fields read here have one name in both), each
+// through the pair make_pair gives it, under try_align's gate.  who: the public function that was called.
+extern "C++" template <class Row>
+static int pile_vote_gated(pba_ctx *ctx, pba_pileup *p, const char *who, const pba_seqs *target, const pba_seqs *reads,
+                           const pba_seqs *reads_rc, const Row *rows, uint64_t n, double R, int overlap_min, pba_result *res,
+                           uint64_t *n_voted, int (*make_pair)(const Row *, uint32_t, uint32_t, double, pba_pair *)) {
     if (!ctx || !p || !target || !reads || (!rows && n)) return PBA_E_INVALID;
     if (n_voted) *n_voted = 0;
-    if (p->spent) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_mapped: the pile-up is spent");
-    if (!(R > 0.0) || !(R < 1.0)) PBA_FAIL(PBA_E_INVALID, "R must be in (0,1)");
-    if (!pile_same_reads(p, target)) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_mapped: target is not the set of this pile-up");
-    if (reads_rc && (reads_rc->n != reads->n || reads_rc->h_len != reads->h_len))
-        PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_mapped: reads_rc differs from reads in count or lengths");
-    if (target->non_acgt || reads->non_acgt || (reads_rc && reads_rc->non_acgt))
-        PBA_FAIL(PBA_E_ALPHABET, "pba_pileup_vote_mapped: a set holds bytes outside ACGT");
-    if (n > 0x7FFFFFFFull) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_mapped: too many rows in one call");
+    PBA_TRY(pile_vote_check(ctx, p, who, target, reads, reads_rc, n, R));
     std::vector<pba_pair> pairs[2];       // strand +1 (B = reads), strand -1 (B = reads_rc)
     std::vector<uint32_t> which[2];
     for (uint64_t k = 0; k < n; ++k) {
-        const pba_map_row &r = rows[k];
+        const Row &r = rows[k];
         if (!r.found) continue;
         if (r.contig < 0 || (uint32_t)r.contig < p->t_lo || (uint32_t)r.contig >= p->t_hi)
-            PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_mapped: a row's contig is outside the pile-up's range");
-        if (r.read < 0 || (uint32_t)r.read >= reads->n) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_mapped: a row's read is not a read of the set");
-        if (r.strand == -1 && !reads_rc) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_mapped: a strand -1 row needs reads_rc");
+            return ctx_fail_as(ctx, PBA_E_INVALID, who, "a row's contig is outside the pile-up's range");
+        if (r.read < 0 || (uint32_t)r.read >= reads->n) return ctx_fail_as(ctx, PBA_E_INVALID, who, "a row's read is not a read of the set");
+        if (r.strand == -1 && !reads_rc) return ctx_fail_as(ctx, PBA_E_INVALID, who, "a strand -1 row needs reads_rc");
         pba_pair pr;
-        const int st = pba_map_row_pair(&r, target->h_len[r.contig], reads->h_len[r.read], R, &pr);
-        if (st == PBA_E_TOOLONG) PBA_FAIL(PBA_E_TOOLONG, "pba_pileup_vote_mapped: a row's accessor is longer than the engine limit");
-        if (st != PBA_OK) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_mapped: a row's strand or accessors are not valid for its sequences");
+        const int st = make_pair(&r, target->h_len[r.contig], reads->h_len[r.read], R, &pr);
+        if (st == PBA_E_TOOLONG) return ctx_fail_as(ctx, PBA_E_TOOLONG, who, "a row's accessor is longer than the engine limit");
+        if (st != PBA_OK) return ctx_fail_as(ctx, PBA_E_INVALID, who, "a row's strand or anchor is not valid for its sequences");
         const int s = r.strand == 1 ? 0 : 1;
         pairs[s].push_back(pr); which[s].push_back((uint32_t)k);
     }
     for (uint64_t k = 0; res && k < n; ++k)
         if (!rows[k].found) { memset(&res[k], 0, sizeof res[k]); res[k].rc = -1; }
-    // try_align's gate (ref_seq.h:264-265).  No re-run check: the roles are swapped against the walk that found the row.
+    // try_align's gate (ref_seq.h:264-265).  No re-run check: this alignment has the contig as a, where the walk that
+    // found the row had the read (a mapped row) or the target read (a placement), and runs to the end of the read.
     return pile_vote_batches(ctx, p, target, reads, reads_rc, pairs, R, overlap_min, [&](int s, const std::vector<pba_result> &out) {
         for (size_t q = 0; q < out.size(); ++q) {
             if (res) res[which[s][q]] = out[q];
@@ -389,64 +418,14 @@ int pba_pileup_vote_mapped(pba_ctx *ctx, pba_pileup *p, const pba_seqs *target, 
     });
 }
 
-int pba_place_row_pair(const pba_place_row *row, uint32_t contig_len, uint32_t read_len, double R, pba_pair *out) {
-    if (!row || !out || !row->found || (row->strand != 1 && row->strand != -1) || (row->dir != 1 && row->dir != -1)) return PBA_E_INVALID;
-    if (!(R > 0.0) || !(R < 1.0) || row->contig < 0 || row->read < 0 || row->j < 0 || row->pos < 0) return PBA_E_INVALID;
-    if (contig_len > 0x7FFFFFFFu || read_len > 0x7FFFFFFFu) return PBA_E_INVALID;
-    if ((uint32_t)row->j >= read_len || (uint32_t)row->pos >= contig_len) return PBA_E_INVALID;
-    const bool fwd = row->dir == 1;
-    const int rem_a = fwd ? (int)(contig_len - (uint32_t)row->pos) : row->pos + 1;
-    const int b_len = fwd ? (int)(read_len - (uint32_t)row->j) : row->j + 1;
-    const TextClip c = text_clip(rem_a, b_len, R);            // the cut align makes itself, as in pba_map_row_pair
-    if (c.len_a > kMaxSeqLen || b_len > kMaxSeqLen) return PBA_E_TOOLONG;
-    memset(out, 0, sizeof *out);
-    out->a_seq = (uint32_t)row->contig; out->a_pos = row->pos; out->a_len = c.len_a;
-    out->b_seq = (uint32_t)row->read; out->b_pos = row->j; out->b_len = b_len;
-    out->flags = fwd ? 0u : (PBA_A_BACKWARD | PBA_B_BACKWARD);
-    return PBA_OK;
+int pba_pileup_vote_mapped(pba_ctx *ctx, pba_pileup *p, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
+                           const pba_map_row *rows, uint64_t n, double R, int overlap_min, pba_result *res, uint64_t *n_voted) {
+    return pile_vote_gated(ctx, p, "pba_pileup_vote_mapped", target, reads, reads_rc, rows, n, R, overlap_min, res, n_voted, pba_map_row_pair);
 }
 
 int pba_pileup_vote_placed(pba_ctx *ctx, pba_pileup *p, const pba_seqs *contigs, const pba_seqs *reads, const pba_seqs *reads_rc,
                            const pba_place_row *rows, uint64_t n, double R, int overlap_min, pba_result *res, uint64_t *n_voted) {
-    if (!ctx || !p || !contigs || !reads || (!rows && n)) return PBA_E_INVALID;
-    if (n_voted) *n_voted = 0;
-    if (p->spent) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_placed: the pile-up is spent");
-    if (!(R > 0.0) || !(R < 1.0)) PBA_FAIL(PBA_E_INVALID, "R must be in (0,1)");
-    if (!pile_same_reads(p, contigs)) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_placed: contigs is not the set of this pile-up");
-    if (reads_rc && (reads_rc->n != reads->n || reads_rc->h_len != reads->h_len))
-        PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_placed: reads_rc differs from reads in count or lengths");
-    if (contigs->non_acgt || reads->non_acgt || (reads_rc && reads_rc->non_acgt))
-        PBA_FAIL(PBA_E_ALPHABET, "pba_pileup_vote_placed: a set holds bytes outside ACGT");
-    if (n > 0x7FFFFFFFull) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_placed: too many rows in one call");
-    std::vector<pba_pair> pairs[2];       // strand +1 (B = reads), strand -1 (B = reads_rc)
-    std::vector<uint32_t> which[2];
-    for (uint64_t k = 0; k < n; ++k) {
-        const pba_place_row &r = rows[k];
-        if (!r.found) continue;
-        if (r.contig < 0 || (uint32_t)r.contig < p->t_lo || (uint32_t)r.contig >= p->t_hi)
-            PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_placed: a row's contig is outside the pile-up's range");
-        if (r.read < 0 || (uint32_t)r.read >= reads->n) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_placed: a row's read is not a read of the set");
-        if (r.strand == -1 && !reads_rc) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_placed: a strand -1 row needs reads_rc");
-        pba_pair pr;
-        const int st = pba_place_row_pair(&r, contigs->h_len[r.contig], reads->h_len[r.read], R, &pr);
-        if (st == PBA_E_TOOLONG) PBA_FAIL(PBA_E_TOOLONG, "pba_pileup_vote_placed: a row's accessor is longer than the engine limit");
-        if (st != PBA_OK) PBA_FAIL(PBA_E_INVALID, "pba_pileup_vote_placed: a row's dir, strand or anchor is not valid for its sequences");
-        const int s = r.strand == 1 ? 0 : 1;
-        pairs[s].push_back(pr); which[s].push_back((uint32_t)k);
-    }
-    for (uint64_t k = 0; res && k < n; ++k)
-        if (!rows[k].found) { memset(&res[k], 0, sizeof res[k]); res[k].rc = -1; }
-    // try_align's gate (ref_seq.h:264-265).  No re-run check: this alignment starts at the row's anchor but has the contig,
-    // not the target read, as a, and runs to the end of the read.
-    return pile_vote_batches(ctx, p, contigs, reads, reads_rc, pairs, R, overlap_min, [&](int s, const std::vector<pba_result> &out) {
-        for (size_t q = 0; q < out.size(); ++q) {
-            if (res) res[which[s][q]] = out[q];
-            if (out[q].rc < 0 || out[q].matlen_a < overlap_min) continue;
-            ++p->n_rows[(uint32_t)rows[which[s][q]].contig - p->t_lo];
-            if (n_voted) ++*n_voted;
-        }
-        return PBA_OK;
-    });
+    return pile_vote_gated(ctx, p, "pba_pileup_vote_placed", contigs, reads, reads_rc, rows, n, R, overlap_min, res, n_voted, pba_place_row_pair);
 }
 
 int pba_pileup_dump(pba_ctx *ctx, const pba_pileup *p, uint32_t target, uint16_t *sel, uint16_t *sup, int32_t *tot, int cap,
@@ -561,25 +540,64 @@ static void stats_add(pba_overlap_stats &a, const pba_overlap_stats &b, bool fir
     a.wide_first = std::max(a.wide_first, b.wide_first);
 }
 
-// what lives across one call of pba_correct_reads
-struct CorrectRun {
+// what every driver below keeps across one call: the read sets, the pile-up of the range in hand, the texts evolved so far
+struct PileRun {
     pba_ctx *ctx;
     const pba_seqs *reads, *reads_rc;            // reads_rc: the caller's, or `rc`
+    pba_seqs *rc = nullptr;                      // owned: the reverse complement, the range's pile-up
+    pba_pileup *pile = nullptr;
+    StageClock clk;
+    std::deque<PileText> chunks;                 // the evolved text of every range so far
+    std::vector<pba_correct_row> crows;          // per contig (the contig drivers)
+    ~PileRun() { pba_pileup_destroy(pile); if (rc) pba_seqs_destroy(rc); }
+    // the reverse complement of the reads, made once where the caller gave none
+    int need_rc() {
+        if (reads_rc) return PBA_OK;
+        PBA_TRY(pba_seqs_revcomp(ctx, reads, nullptr, &rc));
+        reads_rc = rc;
+        return PBA_OK;
+    }
+    // the pile-up's boxes to the next text of `chunks` (and its rows of rows_out), timed into *ms; the pile-up is gone after it
+    int evolve_chunk(float *ms, pba_correct_row *rows_out) {
+        if (!chunks.empty()) chunks.back().d_off.reset();    // only the last chunk's offsets are used again (stitch_chunks)
+        {
+            const auto timed = clk.time(ctx->stream, ms);
+            chunks.emplace_back();
+            PBA_TRY(pile_evolve_text(ctx, pile, &chunks.back(), rows_out));
+        }
+        pba_pileup_destroy(pile); pile = nullptr;            // (host memory only by now: not part of the stage's time)
+        return PBA_OK;
+    }
+};
+
+// The boxes of one pile-up.  room: a quarter of the free memory at 20 bytes a box, fewer than kPileMaxBoxes; budget: room
+// under max_boxes, where set, halved `shrink` times, one box at least.
+struct PileBudget { uint64_t room, budget; };
+static int pile_budget(pba_ctx *ctx, uint64_t max_boxes, uint32_t shrink, PileBudget *b) {
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    b->room = std::min<uint64_t>(kPileMaxBoxes - 1, (uint64_t)(free_b / 4) / 20);
+    b->budget = std::max<uint64_t>(1, (max_boxes ? std::min(b->room, max_boxes) : b->room) >> shrink);
+    return PBA_OK;
+}
+
+// sequences [lo, *hi) of S, below `end`, and their *boxes: consecutive ones while they fit the budget, one at least
+static void pile_take(const pba_seqs *S, uint32_t lo, uint32_t end, uint64_t budget, uint32_t *hi, uint64_t *boxes) {
+    *hi = lo; *boxes = 0;
+    while (*hi < end && (*hi == lo || *boxes + S->h_len[*hi] <= budget)) *boxes += S->h_len[(*hi)++];
+}
+
+// what lives across one call of pba_correct_reads
+struct CorrectRun : PileRun {
     uint32_t t_lo, t_hi;
     double R;
     int overlap_min, kernel, strands, weight;
-    uint64_t max_boxes;
-    pba_correct_row *rows_out;
-    pba_seqs *rc = nullptr;                      // owned: the reverse complement, the probe tables, the chunk's pile-up
-    pba_probe_table *tab[2] = {nullptr, nullptr};
-    pba_pileup *pile = nullptr;
-    StageClock clk;
+    pba_probe_table *tab[2] = {nullptr, nullptr};   // owned
     pba_correct_profile prof;
     pba_overlap_stats tot[2];                    // summed over the chunks
     std::vector<pba_strand_overlap> rows;        // the chunk's overlaps (n_rows of them); grows to what a call reports
     uint64_t n_rows = 0;
-    std::deque<PileText> chunks;                 // the evolved text of every chunk so far
-    ~CorrectRun() { pba_pileup_destroy(pile); pba_probe_table_destroy(tab[0]); pba_probe_table_destroy(tab[1]); if (rc) pba_seqs_destroy(rc); }
+    ~CorrectRun() { pba_probe_table_destroy(tab[0]); pba_probe_table_destroy(tab[1]); }
 };
 
 static int correct_check(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, int max_trial, int strands, int weight) {
@@ -596,10 +614,7 @@ static int correct_check(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *re
 static int correct_prepare(CorrectRun &c, uint32_t mask, int max_trial) {
     pba_ctx *ctx = c.ctx;
     const auto timed = c.clk.time(ctx->stream, &c.prof.overlap_ms);
-    if ((c.strands & 2) && !c.reads_rc) {
-        PBA_TRY(pba_seqs_revcomp(ctx, c.reads, nullptr, &c.rc));
-        c.reads_rc = c.rc;
-    }
+    if (c.strands & 2) PBA_TRY(c.need_rc());
     const pba_seqs *sets[2] = {c.reads, c.reads_rc};
     for (int s = 0; s < 2; ++s) {
         if (!(c.strands & (1 << s))) continue;
@@ -610,20 +625,6 @@ static int correct_prepare(CorrectRun &c, uint32_t mask, int max_trial) {
         PBA_TRY(pba_overlap_probes(ctx, sets[s], 0, c.reads->n, mask, max_trial, d_pent.p, pcap, &n_pent));
         PBA_TRY(pba_probe_table_create(ctx, d_pent.p, n_pent, mask, max_trial, &c.tab[s]));
     }
-    return PBA_OK;
-}
-
-// The next chunk of targets [lo, *hi) and its *boxes: as many as fit a quarter of the free memory at 20 bytes a box (and
-// max_boxes, where set), that budget halved `shrink` times; one target at least.
-static int correct_next_chunk(const CorrectRun &c, uint32_t lo, uint32_t shrink, uint32_t *hi, uint64_t *boxes) {
-    pba_ctx *ctx = c.ctx;
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    uint64_t budget = std::min<uint64_t>(kPileMaxBoxes - 1, (uint64_t)(free_b / 4) / 20);
-    if (c.max_boxes) budget = std::min(budget, c.max_boxes);
-    budget = std::max<uint64_t>(1, budget >> shrink);
-    *hi = lo; *boxes = 0;
-    while (*hi < c.t_hi && (*hi == lo || *boxes + c.reads->h_len[*hi] <= budget)) *boxes += c.reads->h_len[(*hi)++];
     return PBA_OK;
 }
 
@@ -664,18 +665,6 @@ static int correct_vote(CorrectRun &c, uint32_t lo, uint32_t hi) {
         return PBA_E_HIP;
     }
     return st;
-}
-
-// the chunk's boxes to its text (and its rows of rows_out); the pile-up is gone after it
-static int correct_evolve(CorrectRun &c, uint32_t lo) {
-    if (!c.chunks.empty()) c.chunks.back().d_off.reset();    // only the last chunk's offsets are used again (correct_stitch)
-    {
-        const auto timed = c.clk.time(c.ctx->stream, &c.prof.evolve_ms);
-        c.chunks.emplace_back();
-        PBA_TRY(pile_evolve_text(c.ctx, c.pile, &c.chunks.back(), c.rows_out ? c.rows_out + (lo - c.t_lo) : nullptr));
-    }
-    pba_pileup_destroy(c.pile); c.pile = nullptr;            // (host memory only by now: not part of the stage's time)
-    return PBA_OK;
 }
 
 // The chunks' texts as one packed set of nt sequences.  One chunk: its text and device offsets as they are, no copy.
@@ -726,7 +715,7 @@ int pba_correct_reads_budget(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs
     *corrected = nullptr;
     PBA_TRY(correct_check(ctx, reads, reads_rc, max_trial, strands, weight));
     HIPCHK(hipSetDevice(ctx->device));
-    CorrectRun c{ctx, reads, reads_rc, t_lo, t_hi, R, overlap_min, kernel, strands, weight, max_boxes, rows_out};
+    CorrectRun c{{ctx, reads, reads_rc}, t_lo, t_hi, R, overlap_min, kernel, strands, weight};
     if (!c.clk.init()) PBA_FAIL(PBA_E_HIP, "pba_correct_reads: events");
     memset(&c.prof, 0, sizeof c.prof);
     memset(c.tot, 0, sizeof c.tot);
@@ -736,12 +725,14 @@ int pba_correct_reads_budget(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs
         uint32_t hi = lo;
         uint64_t boxes = 0;
         bool halve = false;
-        PBA_TRY(correct_next_chunk(c, lo, shrink, &hi, &boxes));
+        PileBudget b;
+        PBA_TRY(pile_budget(ctx, max_boxes, shrink, &b));
+        pile_take(reads, lo, t_hi, b.budget, &hi, &boxes);   // (a read beyond b.room is left to pba_pileup_create)
         const int st = correct_overlaps(c, lo, hi, &halve);
         if (halve) { ++shrink; continue; }
         if (st != PBA_OK) return st;
         PBA_TRY(correct_vote(c, lo, hi));
-        PBA_TRY(correct_evolve(c, lo));
+        PBA_TRY(c.evolve_chunk(&c.prof.evolve_ms, rows_out ? rows_out + (lo - t_lo) : nullptr));
         c.prof.n_rows += c.n_rows; c.prof.n_bases_in += boxes; ++c.prof.n_chunks;
         lo = hi;
     }
@@ -752,27 +743,82 @@ int pba_correct_reads_budget(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs
 }
 
 // ---------------------------------------------------------------------------------------------
+// what the two contig drivers share: found rows by contig, and one round of ranges over a contig set
+// ---------------------------------------------------------------------------------------------
+// rows <- its found rows ordered by contig (stable: by read inside a contig); those of contig c: rows[first[c] .. first[c + 1])
+extern "C++" template <class Row>
+static void bucket_by_contig(std::vector<Row> &rows, uint32_t n_contigs, std::vector<uint64_t> &first) {
+    first.assign((size_t)n_contigs + 1, 0);
+    for (const Row &r : rows)
+        if (r.found) ++first[(size_t)r.contig + 1];
+    for (uint32_t k = 0; k < n_contigs; ++k) first[k + 1] += first[k];
+    std::vector<Row> by(first.back());
+    std::vector<uint64_t> at(first.begin(), first.end() - 1);
+    for (const Row &r : rows)
+        if (r.found) by[at[r.contig]++] = r;
+    rows.swap(by);
+}
+
+struct RoundResult { uint64_t n_voted, n_bases_in, n_bases_out; uint32_t n_chunks; float vote_ms, evolve_ms; };
+
+// One round over a contig set: pile-ups over consecutive ranges [lo, hi) under the budget (one contig at least, whatever
+// max_boxes says -- but a single contig beyond what the card can hold is PBA_E_NOMEM), each created and voted with
+// vote(first[lo], first[hi] - first[lo], &voted) -- the bucketed rows of its contigs -- then evolved into c.crows; the texts
+// stitched into *out.  vote_ms: create + vote; evolve_ms: evolve + stitch.  who: the public function that was called.
+extern "C++" template <class Vote>
+static int contig_round(PileRun &c, const char *who, const pba_seqs *contigs, int weight, uint64_t max_boxes,
+                        const std::vector<uint64_t> &first, Vote vote, RoundResult *r, pba_seqs **out) {
+    pba_ctx *ctx = c.ctx;
+    const uint32_t nt = contigs->n;
+    *r = RoundResult{};
+    c.crows.assign(std::max<uint32_t>(nt, 1), pba_correct_row{});
+    for (uint32_t lo = 0, hi = 0; lo < nt; lo = hi) {
+        PileBudget b;
+        uint64_t boxes = 0;
+        PBA_TRY(pile_budget(ctx, max_boxes, 0, &b));
+        pile_take(contigs, lo, nt, b.budget, &hi, &boxes);
+        if (boxes > b.room) return ctx_fail_as(ctx, PBA_E_NOMEM, who, "the vote boxes of one contig do not fit the device");
+        {
+            const auto timed = c.clk.time(ctx->stream, &r->vote_ms);
+            uint64_t voted = 0;
+            PBA_TRY(pba_pileup_create(ctx, contigs, lo, hi, weight, &c.pile));
+            PBA_TRY(vote(first[lo], first[hi] - first[lo], &voted));
+            r->n_voted += voted;
+        }
+        PBA_TRY(c.evolve_chunk(&r->evolve_ms, c.crows.data() + lo));
+        ++r->n_chunks;
+    }
+    for (uint32_t k = 0; k < nt; ++k) r->n_bases_in += contigs->h_len[k];
+    {
+        const auto timed = c.clk.time(ctx->stream, &r->evolve_ms);
+        PBA_TRY(stitch_chunks(ctx, c.chunks, nt, &r->n_bases_out, out));
+    }
+    c.chunks.clear();
+    return PBA_OK;
+}
+
+// the per-contig rows of the last round as the contig drivers report them
+static void polish_rows_out(const std::vector<pba_correct_row> &crows, uint32_t n, pba_polish_row *rows_out) {
+    for (uint32_t k = 0; rows_out && k < n; ++k)
+        rows_out[k] = pba_polish_row{crows[k].target, crows[k].n_rows, crows[k].len_in, crows[k].len_out};
+}
+
+// ---------------------------------------------------------------------------------------------
 // pba_polish_contigs: index -> map -> vote -> evolve over a contig set, round after round
 // ---------------------------------------------------------------------------------------------
 // what lives across one call of pba_polish_contigs
-struct PolishRun {
-    pba_ctx *ctx;
-    const pba_seqs *reads, *reads_rc;            // reads_rc: the caller's, or `rc`
+struct PolishRun : PileRun {
     uint32_t mask;
     double R;
     int trials, min_len, maxn, maxm, kernel, strands, overlap_min, weight;
     uint64_t max_boxes;
     const pba_seqs *cur;                         // the round's contigs: the caller's target, then `own`
-    pba_seqs *rc = nullptr, *own = nullptr;      // owned: the reverse complement, the set the last round made, the index, the pile-up
+    pba_seqs *own = nullptr;                     // owned: the set the last round made, the index
     pba_index *ix = nullptr;
-    pba_pileup *pile = nullptr;
-    StageClock clk;
     pba_polish_round_log lg;                     // the round in progress
     std::vector<pba_map_row> rows;               // the round's rows, then its found rows ordered by contig
     std::vector<uint64_t> first;                 // found rows of contig c: rows[first[c] .. first[c + 1])
-    std::vector<pba_correct_row> crows;          // per contig, this round
-    std::deque<PileText> chunks;
-    ~PolishRun() { pba_pileup_destroy(pile); pba_index_destroy(ix); if (own) pba_seqs_destroy(own); if (rc) pba_seqs_destroy(rc); }
+    ~PolishRun() { pba_index_destroy(ix); if (own) pba_seqs_destroy(own); }
 };
 
 static int polish_check(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc, int strands, int weight,
@@ -787,7 +833,7 @@ static int polish_check(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *re
     return PBA_OK;
 }
 
-// the round's index and its rows; the found ones ordered by contig (stable: by read inside a contig)
+// the round's index and its rows; the found ones ordered by contig
 static int polish_map(PolishRun &c) {
     pba_ctx *ctx = c.ctx;
     {
@@ -801,76 +847,21 @@ static int polish_map(PolishRun &c) {
                               c.rows.data(), nullptr));
     }
     pba_index_destroy(c.ix); c.ix = nullptr;
-    c.first.assign((size_t)c.cur->n + 1, 0);
-    for (uint32_t r = 0; r < c.reads->n; ++r)
-        if (c.rows[r].found) ++c.first[(size_t)c.rows[r].contig + 1];
-    for (uint32_t k = 0; k < c.cur->n; ++k) c.first[k + 1] += c.first[k];
-    std::vector<pba_map_row> by(c.first.back());
-    std::vector<uint64_t> at(c.first.begin(), c.first.end() - 1);
-    for (uint32_t r = 0; r < c.reads->n; ++r)
-        if (c.rows[r].found) by[at[c.rows[r].contig]++] = c.rows[r];
-    c.rows.swap(by);
+    bucket_by_contig(c.rows, c.cur->n, c.first);
     c.lg.n_mapped = (uint32_t)c.rows.size();
-    return PBA_OK;
-}
-
-// The next chunk of contigs [lo, *hi): as many as fit the budget of correct_next_chunk (a quarter of the free memory at 20
-// bytes a box, fewer than kPileMaxBoxes) and max_boxes, where set; one contig at least, whatever max_boxes says -- but a
-// single contig beyond what the card can hold is PBA_E_NOMEM.
-static int polish_next_chunk(const PolishRun &c, uint32_t lo, uint32_t *hi) {
-    pba_ctx *ctx = c.ctx;
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    const uint64_t room = std::min<uint64_t>(kPileMaxBoxes - 1, (uint64_t)(free_b / 4) / 20);
-    const uint64_t budget = c.max_boxes ? std::min(room, c.max_boxes) : room;
-    uint64_t boxes = 0;
-    *hi = lo;
-    while (*hi < c.cur->n && (*hi == lo || boxes + c.cur->h_len[*hi] <= budget)) boxes += c.cur->h_len[(*hi)++];
-    if (boxes > room) PBA_FAIL(PBA_E_NOMEM, "pba_polish_contigs: the vote boxes of one contig do not fit the device");
-    return PBA_OK;
-}
-
-// the chunk's boxes and the votes of the rows mapped to its contigs
-static int polish_vote(PolishRun &c, uint32_t lo, uint32_t hi) {
-    const auto timed = c.clk.time(c.ctx->stream, &c.lg.vote_ms);
-    uint64_t voted = 0;
-    PBA_TRY(pba_pileup_create(c.ctx, c.cur, lo, hi, c.weight, &c.pile));
-    PBA_TRY(pba_pileup_vote_mapped(c.ctx, c.pile, c.cur, c.reads, c.reads_rc, c.rows.data() + c.first[lo], c.first[hi] - c.first[lo], c.R,
-                                   c.overlap_min, nullptr, &voted));
-    c.lg.n_voted += (uint32_t)voted;
-    return PBA_OK;
-}
-
-// the chunk's boxes to its text (and its rows of crows); the pile-up is gone after it
-static int polish_evolve(PolishRun &c, uint32_t lo) {
-    if (!c.chunks.empty()) c.chunks.back().d_off.reset();    // only the last chunk's offsets are used again (stitch_chunks)
-    {
-        const auto timed = c.clk.time(c.ctx->stream, &c.lg.evolve_ms);
-        c.chunks.emplace_back();
-        PBA_TRY(pile_evolve_text(c.ctx, c.pile, &c.chunks.back(), c.crows.data() + lo));
-    }
-    pba_pileup_destroy(c.pile); c.pile = nullptr;
     return PBA_OK;
 }
 
 // one round: c.cur -> c.own (the set of the round before, if it was ours, is dropped)
 static int polish_round(PolishRun &c) {
     PBA_TRY(polish_map(c));
-    const uint32_t nt = c.cur->n;
-    c.crows.assign(std::max<uint32_t>(nt, 1), pba_correct_row{});
-    for (uint32_t lo = 0, hi = 0; lo < nt; lo = hi) {
-        PBA_TRY(polish_next_chunk(c, lo, &hi));
-        PBA_TRY(polish_vote(c, lo, hi));
-        PBA_TRY(polish_evolve(c, lo));
-        ++c.lg.n_chunks;
-    }
-    for (uint32_t k = 0; k < nt; ++k) c.lg.n_bases_in += c.cur->h_len[k];
+    RoundResult r;
     pba_seqs *next = nullptr;
-    {
-        const auto timed = c.clk.time(c.ctx->stream, &c.lg.evolve_ms);
-        PBA_TRY(stitch_chunks(c.ctx, c.chunks, nt, &c.lg.n_bases_out, &next));
-    }
-    c.chunks.clear();
+    PBA_TRY(contig_round(c, "pba_polish_contigs", c.cur, c.weight, c.max_boxes, c.first, [&](uint64_t at, uint64_t n, uint64_t *voted) {
+        return pba_pileup_vote_mapped(c.ctx, c.pile, c.cur, c.reads, c.reads_rc, c.rows.data() + at, n, c.R, c.overlap_min, nullptr, voted);
+    }, &r, &next));
+    c.lg.n_voted = (uint32_t)r.n_voted; c.lg.n_chunks = r.n_chunks; c.lg.n_bases_in = r.n_bases_in; c.lg.n_bases_out = r.n_bases_out;
+    c.lg.vote_ms = r.vote_ms; c.lg.evolve_ms = r.evolve_ms;
     if (c.own) pba_seqs_destroy(c.own);
     c.own = next; c.cur = next;
     return PBA_OK;
@@ -891,20 +882,16 @@ int pba_polish_contigs_budget(pba_ctx *ctx, const pba_seqs *target, const pba_se
     *polished = nullptr;
     PBA_TRY(polish_check(ctx, target, reads, reads_rc, strands, weight, rounds));
     HIPCHK(hipSetDevice(ctx->device));
-    PolishRun c{ctx, reads, reads_rc, mask, R, trials, min_len, maxn, maxm, kernel, strands, overlap_min, weight, max_boxes, target};
+    PolishRun c{{ctx, reads, reads_rc}, mask, R, trials, min_len, maxn, maxm, kernel, strands, overlap_min, weight, max_boxes, target};
     if (!c.clk.init()) PBA_FAIL(PBA_E_HIP, "pba_polish_contigs: events");
-    if ((strands & 2) && !c.reads_rc) {
-        PBA_TRY(pba_seqs_revcomp(ctx, reads, nullptr, &c.rc));
-        c.reads_rc = c.rc;
-    }
+    if (strands & 2) PBA_TRY(c.need_rc());
     for (int round = 0; round < rounds; ++round) {
         memset(&c.lg, 0, sizeof c.lg);
         c.lg.round = round + 1;
         PBA_TRY(polish_round(c));
         if (round < log_cap) log[round] = c.lg;
     }
-    for (uint32_t k = 0; rows_out && k < c.cur->n; ++k)
-        rows_out[k] = pba_polish_row{c.crows[k].target, c.crows[k].n_rows, c.crows[k].len_in, c.crows[k].len_out};
+    polish_rows_out(c.crows, c.cur->n, rows_out);
     *polished = c.own; c.own = nullptr;
     return PBA_OK;
 }
@@ -913,79 +900,21 @@ int pba_polish_contigs_budget(pba_ctx *ctx, const pba_seqs *target, const pba_se
 // pba_layout_consensus: stitch -> place -> vote -> evolve over a layout's contigs, one round
 // ---------------------------------------------------------------------------------------------
 // what lives across one call of pba_layout_consensus
-struct LayConsRun {
-    pba_ctx *ctx;
-    const pba_seqs *reads, *reads_rc;            // reads_rc: the caller's, or `rc`
-    double R;
-    int overlap_min, weight;
-    uint64_t max_boxes;
-    pba_seqs *rc = nullptr, *contigs = nullptr;  // owned: the reverse complement, the stitched set, the range's pile-up
-    pba_pileup *pile = nullptr;
-    StageClock clk;
+struct LayConsRun : PileRun {
+    pba_seqs *contigs = nullptr;                 // owned: the stitched set
     pba_layout_cons_stats st;
     std::vector<pba_place_row> places;           // one per read, then the found ones ordered by contig
     std::vector<uint64_t> first;                 // found placements of contig c: places[first[c] .. first[c + 1])
-    std::vector<pba_correct_row> crows;          // per contig
-    std::deque<PileText> chunks;
-    ~LayConsRun() { pba_pileup_destroy(pile); if (contigs) pba_seqs_destroy(contigs); if (rc) pba_seqs_destroy(rc); }
+    ~LayConsRun() { if (contigs) pba_seqs_destroy(contigs); }
 };
 
-// the placements; the found ones ordered by contig (stable: by read inside a contig); the reverse complement if one needs it
+// the placements, the found ones ordered by contig; the reverse complement if one of them needs it
 static int laycons_place(LayConsRun &c, const pba_layout *lay, const pba_strand_overlap *rows, uint64_t n_rows) {
-    pba_ctx *ctx = c.ctx;
     c.places.assign(std::max<size_t>(c.reads->n, 1), pba_place_row{});
-    PBA_TRY(pba_layout_place(ctx, lay, c.reads, rows, n_rows, c.places.data(), c.reads->n, &c.st.place));
-    c.first.assign((size_t)c.contigs->n + 1, 0);
-    bool minus = false;
-    for (uint32_t r = 0; r < c.reads->n; ++r)
-        if (c.places[r].found) { ++c.first[(size_t)c.places[r].contig + 1]; minus |= c.places[r].strand == -1; }
-    for (uint32_t k = 0; k < c.contigs->n; ++k) c.first[k + 1] += c.first[k];
-    std::vector<pba_place_row> by(c.first.back());
-    std::vector<uint64_t> at(c.first.begin(), c.first.end() - 1);
-    for (uint32_t r = 0; r < c.reads->n; ++r)
-        if (c.places[r].found) by[at[c.places[r].contig]++] = c.places[r];
-    c.places.swap(by);
-    if (minus && !c.reads_rc) {
-        PBA_TRY(pba_seqs_revcomp(ctx, c.reads, nullptr, &c.rc));
-        c.reads_rc = c.rc;
-    }
-    return PBA_OK;
-}
-
-// the next range of contigs [lo, *hi): the budget rule of polish_next_chunk
-static int laycons_next_chunk(const LayConsRun &c, uint32_t lo, uint32_t *hi) {
-    pba_ctx *ctx = c.ctx;
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    const uint64_t room = std::min<uint64_t>(kPileMaxBoxes - 1, (uint64_t)(free_b / 4) / 20);
-    const uint64_t budget = c.max_boxes ? std::min(room, c.max_boxes) : room;
-    uint64_t boxes = 0;
-    *hi = lo;
-    while (*hi < c.contigs->n && (*hi == lo || boxes + c.contigs->h_len[*hi] <= budget)) boxes += c.contigs->h_len[(*hi)++];
-    if (boxes > room) PBA_FAIL(PBA_E_NOMEM, "pba_layout_consensus: the vote boxes of one contig do not fit the device");
-    return PBA_OK;
-}
-
-// the range's boxes and the votes of the reads placed on its contigs
-static int laycons_vote(LayConsRun &c, uint32_t lo, uint32_t hi) {
-    const auto timed = c.clk.time(c.ctx->stream, &c.st.vote_ms);
-    uint64_t voted = 0;
-    PBA_TRY(pba_pileup_create(c.ctx, c.contigs, lo, hi, c.weight, &c.pile));
-    PBA_TRY(pba_pileup_vote_placed(c.ctx, c.pile, c.contigs, c.reads, c.reads_rc, c.places.data() + c.first[lo], c.first[hi] - c.first[lo],
-                                   c.R, c.overlap_min, nullptr, &voted));
-    c.st.n_voted += voted;
-    return PBA_OK;
-}
-
-// the range's boxes to its text (and its rows of crows); the pile-up is gone after it
-static int laycons_evolve(LayConsRun &c, uint32_t lo) {
-    if (!c.chunks.empty()) c.chunks.back().d_off.reset();    // only the last chunk's offsets are used again (stitch_chunks)
-    {
-        const auto timed = c.clk.time(c.ctx->stream, &c.st.evolve_ms);
-        c.chunks.emplace_back();
-        PBA_TRY(pile_evolve_text(c.ctx, c.pile, &c.chunks.back(), c.crows.data() + lo));
-    }
-    pba_pileup_destroy(c.pile); c.pile = nullptr;
+    PBA_TRY(pba_layout_place(c.ctx, lay, c.reads, rows, n_rows, c.places.data(), c.reads->n, &c.st.place));
+    bucket_by_contig(c.places, c.contigs->n, c.first);
+    for (const pba_place_row &r : c.places)
+        if (r.strand == -1) return c.need_rc();
     return PBA_OK;
 }
 
@@ -1000,7 +929,7 @@ int pba_layout_consensus(pba_ctx *ctx, const pba_layout *lay, const pba_seqs *re
         PBA_FAIL(PBA_E_INVALID, "pba_layout_consensus: reads_rc differs from reads in count or lengths");
     if (reads->non_acgt || (reads_rc && reads_rc->non_acgt)) PBA_FAIL(PBA_E_ALPHABET, "pba_layout_consensus: a set holds bytes outside ACGT");
     HIPCHK(hipSetDevice(ctx->device));
-    LayConsRun c{ctx, reads, reads_rc, R, overlap_min, weight, max_boxes};
+    LayConsRun c{{ctx, reads, reads_rc}};
     if (!c.clk.init()) PBA_FAIL(PBA_E_HIP, "pba_layout_consensus: events");
     memset(&c.st, 0, sizeof c.st);
     {
@@ -1008,23 +937,14 @@ int pba_layout_consensus(pba_ctx *ctx, const pba_layout *lay, const pba_seqs *re
         PBA_TRY(pba_layout_stitch(ctx, lay, reads, &c.contigs));
     }
     PBA_TRY(laycons_place(c, lay, rows, n_rows));
-    const uint32_t nt = c.contigs->n;
-    c.st.n_contigs = nt;
-    c.crows.assign(std::max<uint32_t>(nt, 1), pba_correct_row{});
-    for (uint32_t lo = 0, hi = 0; lo < nt; lo = hi) {
-        PBA_TRY(laycons_next_chunk(c, lo, &hi));
-        PBA_TRY(laycons_vote(c, lo, hi));
-        PBA_TRY(laycons_evolve(c, lo));
-        ++c.st.n_chunks;
-    }
-    for (uint32_t k = 0; k < nt; ++k) c.st.n_bases_in += c.contigs->h_len[k];
-    {
-        const auto timed = c.clk.time(ctx->stream, &c.st.evolve_ms);
-        PBA_TRY(stitch_chunks(ctx, c.chunks, nt, &c.st.n_bases_out, consensus));
-    }
-    c.chunks.clear();
-    for (uint32_t k = 0; rows_out && k < nt; ++k)
-        rows_out[k] = pba_polish_row{c.crows[k].target, c.crows[k].n_rows, c.crows[k].len_in, c.crows[k].len_out};
+    RoundResult r;
+    PBA_TRY(contig_round(c, "pba_layout_consensus", c.contigs, weight, max_boxes, c.first, [&](uint64_t at, uint64_t n, uint64_t *voted) {
+        return pba_pileup_vote_placed(ctx, c.pile, c.contigs, reads, c.reads_rc, c.places.data() + at, n, R, overlap_min, nullptr, voted);
+    }, &r, consensus));
+    c.st.n_contigs = c.contigs->n;
+    c.st.n_voted = r.n_voted; c.st.n_chunks = r.n_chunks; c.st.n_bases_in = r.n_bases_in; c.st.n_bases_out = r.n_bases_out;
+    c.st.vote_ms = r.vote_ms; c.st.evolve_ms = r.evolve_ms;
+    polish_rows_out(c.crows, c.contigs->n, rows_out);
     if (stats) *stats = c.st;
     return PBA_OK;
 }

@@ -164,6 +164,13 @@ def yields(sel, sup, tot):
     return (sel.max(axis=1) > 0.5 * tot).astype(int) + (sup.max(axis=1) > 0.5 * tot).astype(int)
 
 
+class PileupAs:
+    """A pile-up handle presented with another set as its own (what a caller that mixes up its sets passes)."""
+
+    def __init__(self, pile, reads):
+        self.ctx, self.h, self.reads = pile.ctx, pile.h, reads
+
+
 if __name__ == "__main__":
     import sys
     from oraclelib import Oracle

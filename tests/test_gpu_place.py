@@ -16,6 +16,7 @@ from pacbioassembly_amd.engine import PLACE_ROW_DTYPE, PbaError
 from place_ref import (EDGE_LEN, HAND_LAY_ROWS, HAND_LENS, HAND_PLACE, HAND_TABLE, NOISY_SEED, OVERLAP_MIN, PLACE_COUNTERS, PLACE_FIELDS,
                        R, check_result, edge_case, fuzz_rows, hand_placements, hand_texts, make_place_rows, noisy_reads,
                        oracle_boxes, oracle_consensus, oracle_evolve, oracle_vote_placed, place_ref, place_tilings)
+from polish_helpers import PileupAs
 
 pytestmark = pytest.mark.gpu
 
@@ -258,7 +259,7 @@ def test_refusals(ctx, hand, noisy):
     bad["dir"][1] = 0
     assert status(lambda: pile.vote_placed(Rd, bad, R, OVERLAP_MIN, reads_rc=Rc)) == -1
     other = ctx.seqs_from_list([c + b"A" for c in noisy["ctexts"]], strict_acgt=True)
-    assert status(lambda: Pileup.vote_placed(_As(pile, other), Rd, inside[:3], R, OVERLAP_MIN, reads_rc=Rc)) == -1   # not the pile-up's set
+    assert status(lambda: Pileup.vote_placed(PileupAs(pile, other), Rd, inside[:3], R, OVERLAP_MIN, reads_rc=Rc)) == -1   # not the pile-up's set
     loose = ctx.seqs_from_list([r[:50] + b"N" + r[51:] for r in noisy["texts"]], strict_acgt=False)
     assert status(lambda: pile.vote_placed(loose, inside[:3], R, OVERLAP_MIN, reads_rc=Rc)) == -6         # bytes outside ACGT
     for x, y in zip(before, pile.dump(1)):
@@ -267,10 +268,3 @@ def test_refusals(ctx, hand, noisy):
     assert status(lambda: ctx.layout_consensus(noisy["lay"], Rd, noisy["rows"], R, weight=0)) == -1
     pile.evolve()
     assert status(lambda: pile.vote_placed(Rd, inside[:3], R, OVERLAP_MIN, reads_rc=Rc)) == -1            # spent
-
-
-class _As:
-    """A pile-up handle presented with another set as its own (what a caller that mixes up its sets passes)."""
-
-    def __init__(self, pile, reads):
-        self.ctx, self.h, self.reads = pile.ctx, pile.h, reads

@@ -9,8 +9,8 @@ from conftest import MASK_PAT
 from map_ref import rand_text
 from pacbioassembly_amd import Pileup
 from pacbioassembly_amd import engine as eng
-from pacbioassembly_amd.engine import PbaError
-from polish_helpers import (EDGE_DEL, EDGE_INS, OVERLAP_MIN, POLISH_LENS, R, TILE, check_result, edge_case, oracle_boxes,
+from pacbioassembly_amd.engine import PLACE_ROW_DTYPE, PbaError
+from polish_helpers import (EDGE_DEL, EDGE_INS, OVERLAP_MIN, POLISH_LENS, R, TILE, PileupAs, check_result, edge_case, oracle_boxes,
                             oracle_evolve, oracle_polish_round, oracle_vote, polish_case, yields)
 
 pytestmark = pytest.mark.gpu
@@ -72,6 +72,28 @@ def test_votes_vs_oracle(ctx, case, round1):
     assert n_voted == voted[1] + voted[-1] == sum(w[2] for w in round1 if w)
     _, crows = pile.evolve()
     assert [int(x) for x in crows["n_rows"]] == [w[2] if w else 0 for w in round1]
+
+
+def test_placements_vote_as_the_mapped_rows_they_restate(ctx, case):
+    """The case's rows as placement rows (same read, found, contig, pos, strand and j; dir = +1; row = k) through vote_placed,
+    against the rows themselves through vote_mapped on a second pile-up: results row by row (unfound rows included), rows
+    voted, every contig's boxes, the evolved texts and the per-contig rows are identical."""
+    rows = case["rows"]
+    places = np.zeros(rows.size, PLACE_ROW_DTYPE)
+    for f in ("read", "found", "contig", "pos", "strand", "j"):
+        places[f] = rows[f]
+    places["dir"] = 1
+    places["row"] = np.arange(rows.size)
+    mapped, placed = Pileup(ctx, case["T"]), Pileup(ctx, case["T"])
+    res_m, voted_m = mapped.vote_mapped(case["Rd"], rows, R, OVERLAP_MIN, reads_rc=case["Rc"])
+    res_p, voted_p = placed.vote_placed(case["Rd"], places, R, OVERLAP_MIN, reads_rc=case["Rc"])
+    assert (rows["found"] == 0).any() and 0 < voted_m < int(rows["found"].sum())
+    assert res_m.dtype == res_p.dtype and res_m.tobytes() == res_p.tobytes() and voted_m == voted_p
+    for c in range(len(POLISH_LENS)):
+        for x, y, name in zip(mapped.dump(c), placed.dump(c), ("sel", "sup", "tot")):
+            assert x.shape == y.shape and (x == y).all(), (c, name)
+    (out_m, crows_m), (out_p, crows_p) = mapped.evolve(), placed.evolve()
+    assert texts_of(out_m) == texts_of(out_p) and crows_m.tobytes() == crows_p.tobytes() and crows_m["n_rows"].sum() == voted_m
 
 
 @pytest.mark.parametrize("long_len", [65536, 65537, 70001, 200000])
@@ -169,7 +191,7 @@ def test_refusals(ctx, case):
     assert status(lambda: pile.vote_mapped(Rd, outside, R, OVERLAP_MIN, reads_rc=Rc)) == -1
     assert status(lambda: pile.vote_mapped(Rd, minus[:3], R, OVERLAP_MIN)) == -1                       # strand -1 without reads_rc
     other = ctx.seqs_from_list([c + b"A" for c in case["contigs"]], strict_acgt=True)
-    assert status(lambda: Pileup.vote_mapped(_As(pile, other), Rd, found[:3], R, OVERLAP_MIN, reads_rc=Rc)) == -1   # not the pile-up's set
+    assert status(lambda: Pileup.vote_mapped(PileupAs(pile, other), Rd, found[:3], R, OVERLAP_MIN, reads_rc=Rc)) == -1   # not the pile-up's set
     loose = ctx.seqs_from_list([r[:50] + b"N" + r[51:] for r in case["reads"]], strict_acgt=False)
     assert status(lambda: pile.vote_mapped(loose, found[:3], R, OVERLAP_MIN, reads_rc=Rc)) == -6      # bytes outside ACGT
     after = pile.dump(LONG)
@@ -179,10 +201,3 @@ def test_refusals(ctx, case):
     assert status(lambda: ctx.polish_contigs(T, Rd, mask, R, rounds=0)) == -1
     pile.evolve()
     assert status(lambda: pile.vote_mapped(Rd, found[:3], R, OVERLAP_MIN, reads_rc=Rc)) == -1          # spent
-
-
-class _As:
-    """A pile-up handle presented with another set as its own (what a caller that mixes up its sets passes)."""
-
-    def __init__(self, pile, reads):
-        self.ctx, self.h, self.reads = pile.ctx, pile.h, reads

@@ -135,6 +135,42 @@ def test_place_row_pair_through_the_library(lib):
     assert lib.pba_place_row_pair(C.c_void_p(r.ctypes.data), 2000, 1000, 0.3, C.c_void_p(out.ctypes.data)) == 0
 
 
+def test_a_forward_placement_makes_the_pair_of_its_map_row(lib):
+    """pba_map_row_pair and pba_place_row_pair with dir = +1 on the same anchor: equal in every field of the pair, flags 0,
+    at the first, second and last base of the contig, the first and last of the read, both strands, a contig shorter and
+    longer than the read and the 200 000 / 40 000 clip case of test_polish_cpu.py; and the same status for the same bad input."""
+    def both(pos, j, cl, rl, R, strand=1, found=1):
+        """("ok", pair) or ("refused", status) from each of the two functions"""
+        anchor = dict(read=5, found=found, contig=2, pos=pos, strand=strand, j=j)
+        got = []
+        for fn, row in ((eng.map_row_pair, anchor), (eng.place_row_pair, dict(anchor, row=9, dir=1))):
+            try:
+                pair = fn(row, cl, rl, R)
+                got.append(("ok", tuple(int(pair[k]) for k in PAIR_DTYPE.names)))
+            except PbaError as e:
+                got.append(("refused", e.status))
+        return got
+
+    n = 0
+    for cl, rl in ((1, 1), (2000, 1000), (1000, 2000), (200000, 40000)):
+        for R in (0.05, 0.30):
+            for strand in (1, -1):
+                for pos in sorted({p for p in (0, 1, cl - 1) if p < cl}):
+                    for j in sorted({0, rl - 1}):
+                        m, p = both(pos, j, cl, rl, R, strand)
+                        assert m[0] == "ok" and m == p and m[1][-1] == 0, (cl, rl, R, strand, pos, j, m, p)
+                        assert m[1][:2] == (2, pos) and m[1][3:6] == (5, j, rl - j), m
+                        n += 1
+    assert n == 2 * 2 * (1 + 3 * 2 * 3)
+    # the clip itself: 40 000 read bases from the contig's first base take 40 000 + 1 + 12 000 of its 200 000
+    assert both(0, 0, 200000, 40000, 0.30)[0] == ("ok", (2, 0, 52001, 5, 0, 40000, 0))
+    for bad, want in ((dict(pos=2000, j=10), -1), (dict(pos=100, j=1000), -1), (dict(pos=100, j=10, R=0.0), -1),
+                      (dict(pos=100, j=10, R=1.0), -1), (dict(pos=100, j=10, found=0), -1),
+                      (dict(pos=0, j=0, cl=200000, rl=65001), -4)):
+        args = dict(dict(cl=2000, rl=1000, R=0.30), **bad)
+        assert both(**args) == [("refused", want)] * 2, bad
+
+
 def test_edge_case_is_exact_and_meets_its_conditions(lib, oracle):
     """The hand-made placements of the 70 001-base contig (place_ref.EDGE_PLACES): every one is exact, and the oracle votes
     all but the two that leave the contig 41 bases."""
