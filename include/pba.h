@@ -485,6 +485,45 @@ int pba_loc_stream_last_profile(const pba_loc_stream *s, pba_stream_profile *out
 void pba_loc_stream_destroy(pba_loc_stream *s);
 
 /* ------------------------------------------------------------------------ */
+/* Streamed mapping: pba_map_reads (many contigs, both strands) on read       */
+/* batches that arrive step by step.  The slots, the copy stream and the      */
+/* buffer / submit / collect protocol are pba_loc_stream's; with strands & 2  */
+/* a slot also holds rc(batch) -- a second packed arena, a second set of bit  */
+/* planes and a second borrowed pba_seqs -- written on the copy stream behind */
+/* the forward pack: from the same staged ASCII (PBA_STREAM_TEXT) or from the */
+/* uploaded file (PBA_STREAM_RECORDS).  No pba_seqs_revcomp, no allocation    */
+/* between create and destroy.                                                */
+/* ------------------------------------------------------------------------ */
+typedef struct pba_map_stream pba_map_stream;
+/* The mapping parameters are pba_map_reads', checked the same way with the same codes at the door: ix the
+ * pba_index_build_set index of target (same count, same lengths), strands in 1..3, R, kernel; a target with bytes outside
+ * ACGT: PBA_E_ALPHABET.  ix and target must outlive the stream.  slot_bytes, slot_reads, form and what a slot holds are
+ * pba_loc_stream_create's; with strands == 1 nothing is allocated for the reverse complement.  All or nothing:
+ * PBA_E_NOMEM leaves nothing behind. */
+int pba_map_stream_create(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, double R, int trials, int min_len,
+                          int maxn, int maxm, int kernel, int strands, uint64_t slot_bytes, uint32_t slot_reads, int form,
+                          pba_map_stream **out);
+/* as pba_loc_stream_buffer */
+int pba_map_stream_buffer(pba_map_stream *s, void **bytes, uint64_t **offsets);
+/* as pba_loc_stream_submit: the same host checks with the same codes, a refused batch enqueues nothing; behind the forward
+ * pack the pack of rc(batch) is enqueued (strands & 2), and one event behind both */
+int pba_map_stream_submit(pba_map_stream *s, uint32_t n);
+/* pba_map_reads of the oldest pending batch (both walks on the ctx's stream, behind that batch's pack event); *n = its
+ * reads, rows[0 .. *n) and stats (nullable, per batch) as pba_map_reads fills them, except that rows[i].read counts from the
+ * first read ever submitted and rows[i].nseq continues the running id across batches: the rows of all batches,
+ * concatenated, are the rows of one pba_map_reads over the concatenated reads, and every field of stats, summed over the
+ * batches, is that call's (strands == 3: the second walk is over the reads this batch's + walk left).  A batch with a byte
+ * outside ACGT, the cap, nothing pending and a spent stream: as pba_loc_stream_collect. */
+int pba_map_stream_collect(pba_map_stream *s, pba_map_row *rows, uint32_t cap, uint32_t *n, pba_map_stats *stats);
+/* Both sets of the batch collect would run next, borrowed from its slot (valid until that collect): *fwd the reads, *rc their
+ * reverse complement in pba_seqs_revcomp's layout, NULL with strands == 1.  Blocks until both packs have finished. */
+int pba_map_stream_pending(pba_map_stream *s, const pba_seqs **fwd, const pba_seqs **rc);
+/* as pba_loc_stream_last_profile: pack_ms covers the packs of both strands, locate_ms both walks */
+int pba_map_stream_last_profile(const pba_map_stream *s, pba_stream_profile *out);
+/* waits for the copy stream, then frees; legal with batches pending */
+void pba_map_stream_destroy(pba_map_stream *s);
+
+/* ------------------------------------------------------------------------ */
 /* All-vs-all overlap.  Not a loop the reference  */
 /* has, but built only from its pieces: every read t in [t_lo, t_hi) takes the */
 /* reference role (ref_seq::get_seedmap index of t, ref_seq.h:291-311) and     */

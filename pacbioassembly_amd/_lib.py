@@ -161,6 +161,14 @@ SYMBOLS = {
     "pba_loc_stream_pending": (C.c_int, [_P, C.POINTER(_P)]),
     "pba_loc_stream_last_profile": (C.c_int, [_P, _P]),
     "pba_loc_stream_destroy": (None, [_P]),
+    "pba_map_stream_create": (C.c_int, [_P, _P, _P, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64,
+                                        C.c_uint32, C.c_int, C.POINTER(_P)]),
+    "pba_map_stream_buffer": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
+    "pba_map_stream_submit": (C.c_int, [_P, C.c_uint32]),
+    "pba_map_stream_collect": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(C.c_uint32), _P]),
+    "pba_map_stream_pending": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
+    "pba_map_stream_last_profile": (C.c_int, [_P, _P]),
+    "pba_map_stream_destroy": (None, [_P]),
     "pba_spaced_round": (C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "pba_spaced_multi": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int,
                                    C.c_int, _P, _P, _P, C.c_int, C.POINTER(C.c_int)]),

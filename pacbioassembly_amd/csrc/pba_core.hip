@@ -409,6 +409,15 @@ int pba_seqs_from_device_packed(pba_ctx *ctx, const void *d_packed, uint64_t n_b
     return PBA_OK;
 }
 
+int revcomp_enqueue(pba_ctx *ctx, const pba_seqs *src, const pba_seqs *dst, const uint8_t *d_flip, hipStream_t stream) {
+    const uint64_t total_dwords = dst->h_off[dst->n] / 4;
+    if (!total_dwords) return PBA_OK;
+    hipLaunchKernelGGL(k_revcomp, dim3(elem_grid(total_dwords, 256)), dim3(256), 0, stream, src->d_packed, src->d_off, dst->d_off,
+                       dst->d_len, d_flip, dst->n, total_dwords, dst->d_packed);
+    HIPCHK(hipGetLastError());
+    return PBA_OK;
+}
+
 int pba_seqs_revcomp(pba_ctx *ctx, const pba_seqs *src, const uint8_t *flip, pba_seqs **out) {
     if (!ctx || !src || !out) return PBA_E_INVALID;
     *out = nullptr;
@@ -435,12 +444,8 @@ int pba_seqs_revcomp(pba_ctx *ctx, const pba_seqs *src, const uint8_t *flip, pba
         HIPCHK(hipMalloc(&d_flip.p, n));
         HIPCHK(hipMemcpyAsync(d_flip.p, flip, n, hipMemcpyHostToDevice, ctx->stream));
     }
-    const uint64_t total_dwords = pk / 4;
-    if (total_dwords) {
-        hipLaunchKernelGGL(k_revcomp, dim3(elem_grid(total_dwords, 256)), dim3(256), 0, ctx->stream, src->d_packed, src->d_off, s->d_off,
-                           s->d_len, flip ? d_flip.as<uint8_t>() : nullptr, n, total_dwords, s->d_packed);
-        HIPCHK(hipGetLastError());
-    }
+    st = revcomp_enqueue(ctx, src, s, flip ? d_flip.as<uint8_t>() : nullptr, ctx->stream);
+    if (st != PBA_OK) return st;
     st = seqs_planes(ctx, s);                                 // (synchronises: d_flip and the host offsets outlive their copies)
     if (st != PBA_OK) return st;
     guard.p = nullptr;

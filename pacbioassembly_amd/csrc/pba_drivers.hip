@@ -368,22 +368,31 @@ int pba_locate(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, uint32
     return locate_core(ctx, ix, target, target_seq, reads, R, trials, min_len, maxn, maxm, kernel, rows, stats, 0, 0, nullptr);
 }
 
-// locator.cpp:70-92 against every sequence of a set and on both strands of the reads: the + walk over all reads, the - walk
-// (rc(read), an id list over the full reads_rc set) over the reads the + walk left, first success in that order.
-int pba_map_reads(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
-                  double R, int trials, int min_len, int maxn, int maxm, int kernel, int strands, pba_map_row *rows,
-                  pba_map_stats *stats) {
-    if (!ctx || !ix || !target || !reads || trials < 0 || strands < 1 || strands > 3) return PBA_E_INVALID;
-    const uint32_t n = reads->n;
-    if (!rows && n) return PBA_E_INVALID;
-    if (reads_rc && (reads_rc->n != n || reads_rc->h_len != reads->h_len))
-        PBA_FAIL(PBA_E_INVALID, "pba_map_reads: reads_rc differs from reads in count or lengths");
+// what pba_map_reads asks of its index: the pba_index_build_set index of the target set
+int map_target_ok(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target) {
     uint64_t total = 0;
     for (uint32_t c = 0; c < target->n; ++c) total += target->h_len[c];
     bool same = ix->mode == PBA_INDEX_ALL && ix->d_cum && ix->n_seqs == target->n && ix->seq_len == total;
     for (uint32_t c = 0; same && c < target->n; ++c) same = ix->h_cum[c + 1] - ix->h_cum[c] == target->h_len[c];
     if (!same)
         PBA_FAIL(PBA_E_INVALID, "pba_map_reads needs a pba_index_build_set index of the target set");
+    return PBA_OK;
+}
+
+// locator.cpp:70-92 against every sequence of a set and on both strands of the reads: the + walk over all reads, the - walk
+// (rc(read), an id list over the full reads_rc set) over the reads the + walk left, first success in that order.
+// The one mapping driver.  pba_map_reads runs it on a resident set (bases 0, no event); a pba_map_stream runs it per batch, as
+// a pba_loc_stream runs locate_core: rows[i].read = read_base + i, the running id starts at nseq_base, and both walks wait for
+// `packed` (one event behind the packs of both strands).
+int map_core(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
+             double R, int trials, int min_len, int maxn, int maxm, int kernel, int strands, pba_map_row *rows,
+             pba_map_stats *stats, int64_t read_base, int64_t nseq_base, hipEvent_t packed) {
+    if (!ctx || !ix || !target || !reads || trials < 0 || strands < 1 || strands > 3) return PBA_E_INVALID;
+    const uint32_t n = reads->n;
+    if (!rows && n) return PBA_E_INVALID;
+    if (reads_rc && (reads_rc->n != n || reads_rc->h_len != reads->h_len))
+        PBA_FAIL(PBA_E_INVALID, "pba_map_reads: reads_rc differs from reads in count or lengths");
+    PBA_TRY(map_target_ok(ctx, ix, target));
     PBA_TRY(locate_sets_ok(ctx, target, reads, "pba_map_reads: a sequence set holds bytes outside ACGT"));
     if (reads_rc) PBA_TRY(locate_sets_ok(ctx, target, reads_rc, "pba_map_reads: a sequence set holds bytes outside ACGT"));
     struct Own { pba_seqs *rc = nullptr; ~Own() { pba_seqs_destroy(rc); } } own;
@@ -410,7 +419,7 @@ int pba_map_reads(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, con
         }
         lr[k].resize((size_t)n + 1); ctg[k].assign((size_t)n + 1, -1);
         PBA_TRY(locate_walk(ctx, ix, target, 0, k ? reads_rc : reads, sub ? second.data() : nullptr, (uint32_t)second.size(), R,
-                            trials, min_len, maxn, maxm, kernel, lr[k].data(), aux[k], ctg[k].data(), nullptr));
+                            trials, min_len, maxn, maxm, kernel, lr[k].data(), aux[k], ctg[k].data(), packed));
         if (sub ? !second.empty() : n != 0) {
             const pba_profile &w = ctx->prof;
             prof.align_ms += w.align_ms; prof.align_redo_ms += w.align_redo_ms; prof.n_first += w.n_first; prof.n_redo += w.n_redo;
@@ -421,7 +430,7 @@ int pba_map_reads(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, con
     ctx->prof = prof;
     std::vector<uint8_t> walked(n, 0);
     for (uint32_t r : second) walked[r] = 1;
-    int32_t nseq = 0;
+    int64_t nseq = nseq_base;
     for (uint32_t r = 0; r < n; ++r) {
         pba_map_row &o = rows[r];
         const int len = (int)reads->h_len[r];
@@ -438,8 +447,8 @@ int pba_map_reads(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, con
             npairs += w.n_pairs;
             if (!win || (!win->found && w.found)) { win = &w; wk = k; }
         }
-        o.read = (int32_t)r;
-        o.nseq = kept ? nseq++ : -1;                                               // locator.cpp:72,91
+        o.read = (int32_t)(read_base + r);
+        o.nseq = kept ? (int32_t)nseq++ : -1;                                      // locator.cpp:72,91
         o.found = win->found;
         o.strand = win->found ? (wk ? -1 : 1) : 0;
         o.contig = win->found ? ctg[wk][r] : -1;
@@ -455,6 +464,12 @@ int pba_map_reads(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, con
     }
     if (stats) *stats = ms;
     return PBA_OK;
+}
+
+int pba_map_reads(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
+                  double R, int trials, int min_len, int maxn, int maxm, int kernel, int strands, pba_map_row *rows,
+                  pba_map_stats *stats) {
+    return map_core(ctx, ix, target, reads, reads_rc, R, trials, min_len, maxn, maxm, kernel, strands, rows, stats, 0, 0, nullptr);
 }
 
 // One locked round over the reads `subset` (host ids; nullptr = every read).  rows is indexed by read id: rows of

@@ -1,6 +1,6 @@
 // pba_host.h -- host-side objects and helpers shared by the translation units of libpba.so (pba_core.hip: context,
 // sequence sets, seed index; pba_align.hip: explicit pairs and edit scripts; pba_drivers.hip: the reference's ordered
-// first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction; pba_stream.hip: streamed locate; pba_layout.hip: layout).  Internal: nothing here is part of
+// first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction; pba_stream.hip: streamed locate and mapping; pba_layout.hip: layout).  Internal: nothing here is part of
 // the C ABI (include/pba.h).
 // Also here, once for all of them: the clip of seq_aligner.h:94-102 (text_clip), the launch plan (make_plan), the host
 // protocol of every aligning entry point but the all-vs-all walk -- narrow window first, the uncertified items again at the
@@ -79,7 +79,7 @@ struct pba_seqs {
     uint64_t plane_words;    // words of one plane incl. its slack
     std::vector<uint64_t> h_off;
     std::vector<uint32_t> h_len;
-    bool borrowed;           // the arrays belong to a pba_loc_stream slot: pba_seqs_destroy leaves the set alone, the stream frees it
+    bool borrowed;           // the arrays belong to a stream's slot (pba_stream.hip): pba_seqs_destroy leaves the set alone, the stream frees it
     SeqSetDev dev() const { return SeqSetDev{d_packed, d_off, d_len, d_planes + 2 * kPlaneSlack, d_poff}; }
 };
 
@@ -493,6 +493,15 @@ PBA_INTERNAL int locate_core(pba_ctx *ctx, const pba_index *ix, const pba_seqs *
                              pba_loc_stats *stats, int64_t read_base, int64_t nseq_base, hipEvent_t packed);
 // k_make_planes over a set's first `words` plane words on `stream`: the arrays of `s` are on the device (pba_core.hip)
 PBA_INTERNAL int planes_enqueue(pba_ctx *ctx, const pba_seqs *s, uint64_t words, hipStream_t stream);
+// k_revcomp of `src` into `dst` on `stream`: dst has pba_seqs_from_text's layout of src's lengths (h_off[0 .. n] on the host,
+// d_off[0 .. n] and d_len on the device); d_flip: device, nullable = every sequence.  Alignment padding is not written (pba_core.hip)
+PBA_INTERNAL int revcomp_enqueue(pba_ctx *ctx, const pba_seqs *src, const pba_seqs *dst, const uint8_t *d_flip, hipStream_t stream);
+// the body of pba_map_reads with the bases of its `read` / `nseq` columns and an event both walks wait for (pba_drivers.hip)
+PBA_INTERNAL int map_core(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
+                          double R, int trials, int min_len, int maxn, int maxm, int kernel, int strands, pba_map_row *rows,
+                          pba_map_stats *stats, int64_t read_base, int64_t nseq_base, hipEvent_t packed);
+// pba_map_reads' checks of its index and target (pba_drivers.hip)
+PBA_INTERNAL int map_target_ok(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target);
 }  // extern "C"
 
 #endif

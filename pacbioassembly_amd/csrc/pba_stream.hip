@@ -1,6 +1,7 @@
-// pba_stream.hip -- streamed locate (include/pba.h: pba_loc_stream): two slots of reused storage, a copy stream of its own,
-// a one-pass pack.  While the locate of batch k runs on the ctx's stream, batch k+1 is copied from pinned memory and packed
-// on the copy stream.  Nothing is allocated or freed between create and destroy.  DESIGN.md 4.7.
+// pba_stream.hip -- streamed locate and streamed mapping (include/pba.h: pba_loc_stream, pba_map_stream): two slots of reused
+// storage, a copy stream of its own, a one-pass pack.  While the walk of batch k runs on the ctx's stream, batch k+1 is copied
+// from pinned memory and packed on the copy stream -- for a pba_map_stream with strands & 2 on both strands.  Nothing is
+// allocated or freed between create and destroy.  DESIGN.md 4.7, 4.9.
 #include "pba_host.h"
 #include "pba_internal.h"
 
@@ -13,7 +14,11 @@
 // (k_pack_text / k_make_planes bisect once per dword).  The last work item zeroes the slack behind the last sequence.
 // The slot is reused: every dword of the used extent is written -- alignment padding and pad bits as zero, plane bits
 // masked at the sequence's length -- so that nothing of an earlier batch stays where a sweep can read it.
+// RC = true writes rc(s) in the same layout (what pba_seqs_revcomp gives of the forward set) from the same text: the 32 OUTPUT
+// bases 32u .. 32u + 31 of a thread are the complements of text bytes L - 1 - 32u downwards, so its window ends at L - 32u
+// and, in the sequence's last unit, begins before the sequence's first byte -- the bytes there fall under the masks.
 #define PBA_PP_BASES 2048          // bases per work item: 64 lanes x 32
+template <bool RC>
 __global__ void __launch_bounds__(256)
 k_pack_planes(const uint8_t *__restrict__ text, const uint64_t *__restrict__ text_off, const uint64_t *__restrict__ pk_off,
               const uint64_t *__restrict__ poff, const uint32_t *__restrict__ len, const uint32_t *__restrict__ item, uint32_t n,
@@ -40,10 +45,19 @@ k_pack_planes(const uint8_t *__restrict__ text, const uint64_t *__restrict__ tex
         const int64_t left = (int64_t)L - (int64_t)u * 32;                 // bases of the sequence from this thread's first on
         const int valid = left < 32 ? (int)left : 32;
         uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (valid > 0) {                   // (may run up to 31 bytes past the sequence: the neighbour's text or the staging slack)
-            const uint8_t *src = text + text_off[s] + (uint64_t)u * 32;
-            __builtin_memcpy(w, src, 16);
-            __builtin_memcpy(w + 4, src + 16, 16);
+        if (valid > 0) {
+            if constexpr (RC) {            // (may begin up to 31 bytes before the sequence: the neighbour's text or the staging's front slack)
+                const uint8_t *src = text + ((int64_t)text_off[s] + (int64_t)L - 32 - (int64_t)u * 32);
+                uint32_t v[8];
+                __builtin_memcpy(v, src, 16);
+                __builtin_memcpy(v + 4, src + 16, 16);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) w[j] = __builtin_bswap32(v[7 - j]);   // byte order reversed within and across the two loads
+            } else {                       // (may run up to 31 bytes past the sequence: the neighbour's text or the staging slack)
+                const uint8_t *src = text + text_off[s] + (uint64_t)u * 32;
+                __builtin_memcpy(w, src, 16);
+                __builtin_memcpy(w + 4, src + 16, 16);
+            }
         }
         // Four characters at a time, no branches.  x = ch ^ 'A' is 0x00 / 0x02 / 0x06 / 0x15 for A / C / G / T; t = bits 2:1 of x is
         // 0 / 1 / 3 / 2, so t ^ (t >> 1) is the code of C2I (dna_seq.h:21) on ACGT.  Any other byte differs from the x its own t
@@ -57,7 +71,7 @@ k_pack_planes(const uint8_t *__restrict__ text, const uint64_t *__restrict__ tex
             const uint32_t t0 = t & 0x01010101u, t1 = (t >> 1) & 0x01010101u, tt = t1 & ~t0;
             const uint32_t d = x ^ ((t0 << 1) | ((t0 & t1) << 2) | (tt * 0x15u));          // non-zero bytes: not ACGT
             const uint32_t nz = ((((d & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | d) >> 7) & 0x01010101u;
-            const uint32_t code = (t ^ t1) | (nz * 3u);
+            const uint32_t code = ((t ^ t1) | (nz * 3u)) ^ (RC ? 0x03030303u : 0u);         // (RC: the complement is code ^ 3)
             be[j >> 2] |= ((code * 0x40100401u) & 0xFF000000u) >> (8 * (j & 3));             // byte = c0<<6 | c1<<4 | c2<<2 | c3
             plo |= (((code & 0x01010101u) * 0x01020408u) >> 24) << (4 * j);
             phi |= ((((code >> 1) & 0x01010101u) * 0x01020408u) >> 24) << (4 * j);
@@ -79,35 +93,37 @@ k_pack_planes(const uint8_t *__restrict__ text, const uint64_t *__restrict__ tex
 }
 
 // ---------------------------------------------------------------------------------------------
-// host side
+// host side: the slots, under both kinds of stream
 // ---------------------------------------------------------------------------------------------
 static const uint64_t kRecordSlack = 65536;      // zero bytes behind a binary read file (pba_seqs_from_records)
+static const size_t kTextFront = 64;             // staging bytes in front of the text: k_pack_planes<true> begins up to 31 bytes early
 
 struct StreamSlot {
     uint8_t *h_bytes;        // pinned: the caller's input bytes
     uint64_t *h_offs;        // pinned: the caller's offsets
     uint64_t *h_off, *h_poff;   // pinned: packed byte offset / plane word offset of every sequence
+    uint64_t *h_roff;        // pinned: packed byte offset inside the rc arena (records form; the text form's is h_off)
     uint32_t *h_len, *h_item, *h_bad;
-    uint8_t *d_text;         // staging of the ASCII (text form)
+    uint8_t *d_text_alloc;   // staging of the ASCII (text form); d_text = d_text_alloc + kTextFront
+    uint8_t *d_text;
     uint64_t *d_toff;
     uint32_t *d_item, *d_bad;
     pba_seqs *set;           // borrows the arena, the planes and off / len / poff of this slot
+    pba_seqs *rc;            // rc(batch): its own arena, planes and off; len / poff are the forward set's
     hipEvent_t ev_begin, ev_h2d, ev_pack;
     uint32_t n;
     uint64_t n_bytes;
 };
 
-struct pba_loc_stream {
+struct StreamCore {
     pba_ctx *ctx;
-    const pba_index *ix;
-    const pba_seqs *target;
-    uint32_t target_seq;
-    double R;
-    int trials, min_len, maxn, maxm, kernel, form;
-    uint64_t slot_bytes, pk_cap, plane_cap;      // plane_cap: word pairs between the slacks
+    const char *name;        // "pba_loc_stream" / "pba_map_stream": who a failure is reported as
+    int form, min_len;
+    bool rc;                 // a slot holds rc(batch) as well
+    uint64_t slot_bytes, pk_cap, rc_cap, plane_cap;      // plane_cap: word pairs between the slacks
     uint32_t slot_reads;
     hipStream_t copy;
-    hipEvent_t ev_loc0, ev_loc1;                 // the locate of a batch, on the ctx's stream
+    hipEvent_t ev_loc0, ev_loc1;                 // the walk(s) of a batch, on the ctx's stream
     bool have_loc1, spent;
     StreamSlot slot[2];
     int head, npend;
@@ -115,16 +131,45 @@ struct pba_loc_stream {
     pba_stream_profile prof;
 };
 
-static void stream_free(pba_loc_stream *s) {
-    (void)hipSetDevice(s->ctx->device);
-    if (s->copy) (void)hipStreamSynchronize(s->copy);
-    (void)hipStreamSynchronize(s->ctx->stream);
-    for (StreamSlot &sl : s->slot) {
-        for (void *h : {(void *)sl.h_bytes, (void *)sl.h_offs, (void *)sl.h_off, (void *)sl.h_poff, (void *)sl.h_len, (void *)sl.h_item,
-                        (void *)sl.h_bad})
+struct pba_loc_stream {
+    StreamCore c;
+    const pba_index *ix;
+    const pba_seqs *target;
+    uint32_t target_seq;
+    double R;
+    int trials, maxn, maxm, kernel;
+};
+
+struct pba_map_stream {
+    StreamCore c;
+    const pba_index *ix;
+    const pba_seqs *target;
+    double R;
+    int trials, maxn, maxm, kernel, strands;
+};
+
+static int core_fail(StreamCore &c, int st, const char *fn, const char *what) {
+    char who[64];
+    snprintf(who, sizeof who, "%s_%s", c.name, fn);
+    return ctx_fail_as(c.ctx, st, who, what);
+}
+
+static void core_free(StreamCore &c) {
+    (void)hipSetDevice(c.ctx->device);
+    if (c.copy) (void)hipStreamSynchronize(c.copy);
+    (void)hipStreamSynchronize(c.ctx->stream);
+    for (StreamSlot &sl : c.slot) {
+        for (void *h : {(void *)sl.h_bytes, (void *)sl.h_offs, (void *)sl.h_off, (void *)sl.h_poff, (void *)sl.h_roff, (void *)sl.h_len,
+                        (void *)sl.h_item, (void *)sl.h_bad})
             if (h) (void)hipHostFree(h);
-        for (void *d : {(void *)sl.d_text, (void *)sl.d_toff, (void *)sl.d_item, (void *)sl.d_bad})
+        for (void *d : {(void *)sl.d_text_alloc, (void *)sl.d_toff, (void *)sl.d_item, (void *)sl.d_bad})
             if (d) (void)hipFree(d);
+        if (sl.rc) {                           // (len / poff belong to the forward set)
+            pba_seqs *q = sl.rc;
+            for (void *d : {(void *)q->d_alloc, (void *)q->d_planes, (void *)q->d_off})
+                if (d) (void)hipFree(d);
+            delete q;
+        }
         if (sl.set) {
             pba_seqs *q = sl.set;
             for (void *d : {(void *)q->d_alloc, (void *)q->d_planes, (void *)q->d_off, (void *)q->d_len, (void *)q->d_poff})
@@ -134,10 +179,9 @@ static void stream_free(pba_loc_stream *s) {
         for (hipEvent_t e : {sl.ev_begin, sl.ev_h2d, sl.ev_pack})
             if (e) (void)hipEventDestroy(e);
     }
-    for (hipEvent_t e : {s->ev_loc0, s->ev_loc1})
+    for (hipEvent_t e : {c.ev_loc0, c.ev_loc1})
         if (e) (void)hipEventDestroy(e);
-    if (s->copy) (void)hipStreamDestroy(s->copy);
-    delete s;
+    if (c.copy) (void)hipStreamDestroy(c.copy);
 }
 
 template <class T> static bool pinned(T **p, size_t count) {
@@ -147,44 +191,78 @@ template <class T> static bool device(T **p, size_t count) {
     return hipMalloc((void **)p, std::max<size_t>(1, count) * sizeof(T)) == hipSuccess;
 }
 
-static bool slot_alloc(pba_loc_stream *s, StreamSlot &sl) {
-    const size_t nr = (size_t)s->slot_reads + 1, trail = s->form == PBA_STREAM_RECORDS ? kRecordSlack + kSlack : kSlack;
-    const bool text = s->form == PBA_STREAM_TEXT;
-    if (!pinned(&sl.h_bytes, s->slot_bytes) || !pinned(&sl.h_offs, std::max<size_t>(nr, 3)) || !pinned(&sl.h_off, nr) ||
+// a borrowed set over an arena of `arena` bytes and the slot's planes, both zeroed once (the slack in front of the arena and
+// of the planes is never written again)
+static pba_seqs *set_alloc(StreamCore &c, pba_seqs **at, size_t arena, size_t nr) {
+    pba_seqs *q = new (std::nothrow) pba_seqs();
+    if (!q) return nullptr;
+    *at = q;
+    q->ctx = c.ctx; q->borrowed = true;
+    q->h_off.reserve(nr); q->h_len.reserve(nr);
+    const size_t planes = (c.plane_cap + 2 * kPlaneSlack) * 2 * sizeof(uint32_t);
+    if (!device(&q->d_alloc, arena) || !device(&q->d_planes, planes / sizeof(uint32_t)) || !device(&q->d_off, nr)) return nullptr;
+    q->d_packed = q->d_alloc + kSlack;
+    if (memset_big(q->d_alloc, 0, arena, c.copy) != hipSuccess || memset_big(q->d_planes, 0, planes, c.copy) != hipSuccess) return nullptr;
+    return q;
+}
+
+static bool slot_alloc(StreamCore &c, StreamSlot &sl) {
+    const size_t nr = (size_t)c.slot_reads + 1, trail = c.form == PBA_STREAM_RECORDS ? kRecordSlack + kSlack : kSlack;
+    const bool text = c.form == PBA_STREAM_TEXT;
+    if (!pinned(&sl.h_bytes, c.slot_bytes) || !pinned(&sl.h_offs, std::max<size_t>(nr, 3)) || !pinned(&sl.h_off, nr) ||
         !pinned(&sl.h_poff, nr) || !pinned(&sl.h_len, nr) || !pinned(&sl.h_item, nr) || !pinned(&sl.h_bad, 1))
         return false;
-    if (text && (!device(&sl.d_text, s->slot_bytes + 64) || !device(&sl.d_toff, nr) || !device(&sl.d_item, nr))) return false;
+    if (c.rc && !text && !pinned(&sl.h_roff, nr)) return false;
+    if (text && (!device(&sl.d_text_alloc, kTextFront + c.slot_bytes + 64) || !device(&sl.d_toff, nr) || !device(&sl.d_item, nr))) return false;
     if (!device(&sl.d_bad, 1)) return false;
-    pba_seqs *q = new (std::nothrow) pba_seqs();
-    if (!q) return false;
-    sl.set = q;
-    q->ctx = s->ctx; q->borrowed = true;
-    q->h_off.reserve(nr); q->h_len.reserve(nr);
-    const size_t arena = kSlack + s->pk_cap + trail, planes = (s->plane_cap + 2 * kPlaneSlack) * 2 * sizeof(uint32_t);
-    if (!device(&q->d_alloc, arena) || !device(&q->d_planes, planes / sizeof(uint32_t)) || !device(&q->d_off, nr) ||
-        !device(&q->d_len, nr) || !device(&q->d_poff, nr))
-        return false;
-    q->d_packed = q->d_alloc + kSlack;
-    // (the slack in front of the arena and of the planes is zeroed here, once, and never written again)
-    if (memset_big(q->d_alloc, 0, arena, s->copy) != hipSuccess || memset_big(q->d_planes, 0, planes, s->copy) != hipSuccess) return false;
-    if (text && hipMemsetAsync(sl.d_text, 0, s->slot_bytes + 64, s->copy) != hipSuccess) return false;
+    pba_seqs *q = set_alloc(c, &sl.set, kSlack + c.pk_cap + trail, nr);
+    if (!q || !device(&q->d_len, nr) || !device(&q->d_poff, nr)) return false;
+    if (c.rc) {
+        pba_seqs *r = set_alloc(c, &sl.rc, kSlack + c.rc_cap + kSlack, nr);
+        if (!r) return false;
+        r->d_len = q->d_len; r->d_poff = q->d_poff;
+    }
+    if (text) {
+        if (hipMemsetAsync(sl.d_text_alloc, 0, kTextFront + c.slot_bytes + 64, c.copy) != hipSuccess) return false;
+        sl.d_text = sl.d_text_alloc + kTextFront;
+    }
     return hipEventCreate(&sl.ev_begin) == hipSuccess && hipEventCreate(&sl.ev_h2d) == hipSuccess &&
            hipEventCreate(&sl.ev_pack) == hipSuccess;
 }
 
+// what both creates do once their own checks are through; on failure the caller frees the core
+static int core_create(StreamCore &c, pba_ctx *ctx, const char *name, int form, int min_len, bool rc, uint64_t slot_bytes,
+                       uint32_t slot_reads) {
+    c.ctx = ctx; c.name = name; c.form = form; c.min_len = min_len; c.rc = rc; c.slot_bytes = slot_bytes; c.slot_reads = slot_reads;
+    if (form == PBA_STREAM_TEXT) {         // every read rounds up to 16 packed bytes and to one plane word
+        c.pk_cap = ((slot_bytes + 3) / 4 + 16ull * slot_reads + 15) & ~15ull;
+        c.rc_cap = c.pk_cap;
+        c.plane_cap = slot_bytes / 32 + slot_reads + 1;
+    } else {                               // the file is the arena; four bases per payload byte
+        c.pk_cap = (slot_bytes + 15) & ~15ull;
+        c.rc_cap = (slot_bytes + 16ull * slot_reads + 15) & ~15ull;      // (rc: every payload rounds up to 16 bytes)
+        c.plane_cap = slot_bytes / 8 + slot_reads + 1;
+    }
+    bool ok = hipStreamCreateWithFlags(&c.copy, hipStreamNonBlocking) == hipSuccess;
+    ok = ok && hipEventCreate(&c.ev_loc0) == hipSuccess && hipEventCreate(&c.ev_loc1) == hipSuccess;
+    ok = ok && slot_alloc(c, c.slot[0]) && slot_alloc(c, c.slot[1]);
+    ok = ok && hipStreamSynchronize(c.copy) == hipSuccess;
+    if (!ok) (void)hipGetLastError();
+    return ok ? PBA_OK : PBA_E_NOMEM;
+}
+
 // the host half of a text batch: layout of pba_seqs_from_text (seqs_pack) plus the work-item prefix of k_pack_planes
-static int plan_text(pba_loc_stream *s, StreamSlot &sl, uint32_t n, uint64_t *pk_total, uint64_t *words, uint32_t *items) {
-    pba_ctx *ctx = s->ctx;
-    if (n > s->slot_reads) PBA_FAIL(PBA_E_TOOLONG, "pba_loc_stream_submit: more reads than slot_reads");
+static int plan_text(StreamCore &c, StreamSlot &sl, uint32_t n, uint64_t *pk_total, uint64_t *words, uint32_t *items) {
+    if (n > c.slot_reads) return core_fail(c, PBA_E_TOOLONG, "submit", "more reads than slot_reads");
     const uint64_t *to = sl.h_offs;
     for (uint32_t i = 0; i < n; ++i)
-        if (to[i + 1] < to[i]) PBA_FAIL(PBA_E_INVALID, "pba_loc_stream_submit: offsets must be non-decreasing");
-    if (to[n] > s->slot_bytes) PBA_FAIL(PBA_E_TOOLONG, "pba_loc_stream_submit: more bytes than slot_bytes");
+        if (to[i + 1] < to[i]) return core_fail(c, PBA_E_INVALID, "submit", "offsets must be non-decreasing");
+    if (to[n] > c.slot_bytes) return core_fail(c, PBA_E_TOOLONG, "submit", "more bytes than slot_bytes");
     uint64_t pk = 0, w = 0, it = 0;
     uint32_t max_len = 0;
     for (uint32_t i = 0; i < n; ++i) {
         const uint64_t L = to[i + 1] - to[i];
-        if (L > (uint64_t)kMaxSeqLen) PBA_FAIL(PBA_E_TOOLONG, "pba_loc_stream_submit: read longer than the engine limit");
+        if (L > (uint64_t)kMaxSeqLen) return core_fail(c, PBA_E_TOOLONG, "submit", "read longer than the engine limit");
         sl.h_off[i] = pk; sl.h_poff[i] = w; sl.h_len[i] = (uint32_t)L; sl.h_item[i] = (uint32_t)it;
         max_len = std::max(max_len, (uint32_t)L);
         pk += ((L + 3) / 4 + 15) & ~15ull;
@@ -197,68 +275,201 @@ static int plan_text(pba_loc_stream *s, StreamSlot &sl, uint32_t n, uint64_t *pk
     return PBA_OK;
 }
 
-// ... of a binary read file: pba_seqs_from_records' walk; the file is the arena
-static int plan_records(pba_loc_stream *s, StreamSlot &sl, uint32_t *n_out, uint64_t *pk_total, uint64_t *words) {
-    pba_ctx *ctx = s->ctx;
+// ... of a binary read file: pba_seqs_from_records' walk; the file is the arena (rc: pba_seqs_revcomp's layout beside it)
+static int plan_records(StreamCore &c, StreamSlot &sl, uint32_t *n_out, uint64_t *pk_total, uint64_t *rc_total, uint64_t *words) {
     const uint64_t file_len = sl.h_offs[0];
-    if (file_len > s->slot_bytes) PBA_FAIL(PBA_E_TOOLONG, "pba_loc_stream_submit: more bytes than slot_bytes");
+    if (file_len > c.slot_bytes) return core_fail(c, PBA_E_TOOLONG, "submit", "more bytes than slot_bytes");
     const uint32_t min_excl = (uint32_t)sl.h_offs[1], max_excl = (uint32_t)sl.h_offs[2];
-    const size_t kept = pba_open_binary(sl.h_bytes, file_len, min_excl, max_excl, sl.h_off, s->slot_reads, nullptr);
-    if (kept > s->slot_reads) PBA_FAIL(PBA_E_TOOLONG, "pba_loc_stream_submit: more reads than slot_reads");
-    uint64_t w = 0;
+    const size_t kept = pba_open_binary(sl.h_bytes, file_len, min_excl, max_excl, sl.h_off, c.slot_reads, nullptr);
+    if (kept > c.slot_reads) return core_fail(c, PBA_E_TOOLONG, "submit", "more reads than slot_reads");
+    uint64_t w = 0, rpk = 0;
     uint32_t max_len = 0;
     for (size_t i = 0; i < kept; ++i) {
         const uint64_t rec = sl.h_off[i];
         uint32_t L;
         memcpy(&L, sl.h_bytes + rec, 4);
-        if (rec + 4 + ((uint64_t)L + 3) / 4 > file_len) PBA_FAIL(PBA_E_INVALID, "pba_loc_stream_submit: truncated record");
-        if (L > (uint32_t)kMaxSeqLen) PBA_FAIL(PBA_E_TOOLONG, "pba_loc_stream_submit: read longer than the engine limit");
+        if (rec + 4 + ((uint64_t)L + 3) / 4 > file_len) return core_fail(c, PBA_E_INVALID, "submit", "truncated record");
+        if (L > (uint32_t)kMaxSeqLen) return core_fail(c, PBA_E_TOOLONG, "submit", "read longer than the engine limit");
         sl.h_off[i] = rec + 4; sl.h_poff[i] = w; sl.h_len[i] = L;      // payload follows the u32 length (dna_seq.h:119-121)
+        if (c.rc) sl.h_roff[i] = rpk;
         max_len = std::max(max_len, L);
         w += ((uint64_t)L + 31) / 32;
+        rpk += (((uint64_t)L + 3) / 4 + 15) & ~15ull;
     }
     sl.h_off[kept] = file_len; sl.h_poff[kept] = w; sl.h_len[kept] = 0;
+    if (c.rc) sl.h_roff[kept] = rpk;
     sl.set->max_len = max_len;
-    *n_out = (uint32_t)kept; *pk_total = file_len; *words = w;
+    *n_out = (uint32_t)kept; *pk_total = file_len; *rc_total = rpk; *words = w;
     return PBA_OK;
 }
 
-static int spend(pba_loc_stream *s, int st) { s->spent = true; return st; }
+static int spend(StreamCore &c, int st) { c.spent = true; return st; }
+
+static int core_buffer(StreamCore &c, void **bytes, uint64_t **offsets) {
+    if (c.spent || !bytes || !offsets || c.npend >= 2) return PBA_E_INVALID;
+    StreamSlot &sl = c.slot[(c.head + c.npend) & 1];
+    *bytes = sl.h_bytes;
+    *offsets = sl.h_offs;
+    return PBA_OK;
+}
+
+static int core_submit(StreamCore &c, uint32_t n) {
+    if (c.spent || c.npend >= 2) return PBA_E_INVALID;
+    pba_ctx *ctx = c.ctx;
+    StreamSlot &sl = c.slot[(c.head + c.npend) & 1];
+    pba_seqs *q = sl.set, *r = sl.rc;
+    uint64_t pk_total = 0, rc_total = 0, words = 0;
+    uint32_t items = 0;
+    const bool text = c.form == PBA_STREAM_TEXT;
+    PBA_TRY(text ? plan_text(c, sl, n, &pk_total, &words, &items) : plan_records(c, sl, &n, &pk_total, &rc_total, &words));
+    if (text) rc_total = pk_total;
+    const uint64_t *h_roff = text ? sl.h_off : sl.h_roff;
+    // from here on the batch is accepted: a failure is the runtime's and spends the stream
+    q->n = n; q->packed_bytes = pk_total; q->non_acgt = false; q->plane_words = words + 2 * kPlaneSlack;
+    q->h_off.assign(sl.h_off, sl.h_off + n + 1);       // (within the capacity reserved at creation)
+    q->h_len.assign(sl.h_len, sl.h_len + n + 1);
+    if (r) {
+        r->n = n; r->max_len = q->max_len; r->packed_bytes = rc_total; r->non_acgt = false; r->plane_words = q->plane_words;
+        r->h_off.assign(h_roff, h_roff + n + 1);
+        r->h_len.assign(sl.h_len, sl.h_len + n + 1);
+    }
+    sl.n = n; sl.n_bytes = text ? sl.h_offs[n] : pk_total;
+    *sl.h_bad = 0;
+    const size_t n1 = (size_t)n + 1;
+    uint32_t *plane0 = q->d_planes + 2 * kPlaneSlack, *rplane0 = r ? r->d_planes + 2 * kPlaneSlack : nullptr;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e == hipSuccess) e = hipEventRecord(sl.ev_begin, c.copy);
+    if (e == hipSuccess && sl.n_bytes) e = hipMemcpyAsync(text ? sl.d_text : q->d_packed, sl.h_bytes, sl.n_bytes, hipMemcpyHostToDevice, c.copy);
+    if (e == hipSuccess) e = hipEventRecord(sl.ev_h2d, c.copy);
+    if (e == hipSuccess) e = hipMemcpyAsync(q->d_off, sl.h_off, sizeof(uint64_t) * n1, hipMemcpyHostToDevice, c.copy);
+    if (e == hipSuccess) e = hipMemcpyAsync(q->d_poff, sl.h_poff, sizeof(uint64_t) * n1, hipMemcpyHostToDevice, c.copy);
+    if (e == hipSuccess) e = hipMemcpyAsync(q->d_len, sl.h_len, sizeof(uint32_t) * n1, hipMemcpyHostToDevice, c.copy);
+    if (e == hipSuccess && r) e = hipMemcpyAsync(r->d_off, h_roff, sizeof(uint64_t) * n1, hipMemcpyHostToDevice, c.copy);
+    if (e == hipSuccess && text) {
+        e = hipMemcpyAsync(sl.d_toff, sl.h_offs, sizeof(uint64_t) * n1, hipMemcpyHostToDevice, c.copy);
+        if (e == hipSuccess) e = hipMemcpyAsync(sl.d_item, sl.h_item, sizeof(uint32_t) * n1, hipMemcpyHostToDevice, c.copy);
+        if (e == hipSuccess) e = hipMemsetAsync(sl.d_bad, 0, sizeof(uint32_t), c.copy);
+        const dim3 grid(elem_grid(((uint64_t)items + 1) * PBA_WAVE, 256));
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_pack_planes<false>, grid, dim3(256), 0, c.copy, sl.d_text, sl.d_toff, q->d_off, q->d_poff, q->d_len,
+                               sl.d_item, n, items, pk_total, words, q->d_packed, plane0, sl.d_bad);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess && r) {        // rc(batch) from the same staged text, into the slot's second arena and planes
+            hipLaunchKernelGGL(k_pack_planes<true>, grid, dim3(256), 0, c.copy, sl.d_text, sl.d_toff, r->d_off, q->d_poff, q->d_len,
+                               sl.d_item, n, items, pk_total, words, r->d_packed, rplane0, sl.d_bad);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(sl.h_bad, sl.d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, c.copy);
+    } else if (e == hipSuccess) {          // the file is the packed arena: zero behind it, planes by k_make_planes, zero behind them
+        e = hipMemsetAsync(q->d_packed + pk_total, 0, kRecordSlack + kSlack, c.copy);
+        if (e == hipSuccess && planes_enqueue(ctx, q, words, c.copy) != PBA_OK) return spend(c, PBA_E_HIP);
+        if (e == hipSuccess) e = hipMemsetAsync(plane0 + 2 * words, 0, kPlaneSlack * 2 * sizeof(uint32_t), c.copy);
+        if (e == hipSuccess && r) {        // rc(batch) by k_revcomp from the file's records (it skips the alignment padding: zero first)
+            e = hipMemsetAsync(r->d_packed, 0, rc_total + kSlack, c.copy);
+            if (e == hipSuccess && (revcomp_enqueue(ctx, q, r, nullptr, c.copy) != PBA_OK || planes_enqueue(ctx, r, words, c.copy) != PBA_OK))
+                return spend(c, PBA_E_HIP);
+            if (e == hipSuccess) e = hipMemsetAsync(rplane0 + 2 * words, 0, kPlaneSlack * 2 * sizeof(uint32_t), c.copy);
+        }
+    }
+    if (e == hipSuccess) e = hipEventRecord(sl.ev_pack, c.copy);
+    if (e != hipSuccess) return spend(c, core_fail(c, PBA_E_HIP, "submit", hipGetErrorString(e)));
+    ++c.npend;
+    return PBA_OK;
+}
+
+// the oldest pending slot once its packs are through, the verdict of the pack on both of its sets
+static int core_pending(StreamCore &c, StreamSlot **out) {
+    if (c.spent || c.npend == 0) return PBA_E_INVALID;
+    StreamSlot &sl = c.slot[c.head];
+    const hipError_t e = hipEventSynchronize(sl.ev_pack);
+    if (e != hipSuccess) return spend(c, core_fail(c, PBA_E_HIP, "pending", hipGetErrorString(e)));
+    sl.set->non_acgt = *sl.h_bad != 0;     // (the aligning entry points refuse such a set, as they do a resident one)
+    if (sl.rc) sl.rc->non_acgt = sl.set->non_acgt;
+    *out = &sl;
+    return PBA_OK;
+}
+
+// The collect of both kinds: the checks, the wait for the pack, the dropped batch, the profile and the running ids around
+// walk(slot, read_base, nseq_base) -- the driver of the stream's kind on the ctx's stream behind slot.ev_pack.
+template <class Walk>
+static int core_collect(StreamCore &c, bool have_rows, uint32_t cap, uint32_t *n, Walk walk) {
+    if (c.spent || !n || c.npend == 0) return PBA_E_INVALID;
+    pba_ctx *ctx = c.ctx;
+    StreamSlot &sl = c.slot[c.head];
+    if (cap < sl.n || (!have_rows && sl.n)) return core_fail(c, PBA_E_INVALID, "collect", "cap below the batch size");
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e == hipSuccess) e = hipEventSynchronize(sl.ev_pack);      // the flag of the pack is read before anything is launched
+    if (e != hipSuccess) return spend(c, core_fail(c, PBA_E_HIP, "collect", hipGetErrorString(e)));
+    pba_stream_profile pr;
+    memset(&pr, 0, sizeof pr);
+    pr.n_reads = sl.n; pr.n_bytes = sl.n_bytes;
+    (void)hipEventElapsedTime(&pr.h2d_ms, sl.ev_begin, sl.ev_h2d);
+    (void)hipEventElapsedTime(&pr.pack_ms, sl.ev_h2d, sl.ev_pack);
+    // what of the upload was NOT hidden: the ctx's stream had nothing to do from the end of the walk before (or, with none
+    // since this batch was submitted, from the submit) until the pack was through
+    float exposed = 0.f, since_loc = 0.f;
+    (void)hipEventElapsedTime(&exposed, sl.ev_begin, sl.ev_pack);
+    if (c.have_loc1 && hipEventElapsedTime(&since_loc, c.ev_loc1, sl.ev_pack) == hipSuccess) exposed = std::min(exposed, since_loc);
+    (void)hipGetLastError();
+    pr.stall_ms = std::max(0.f, exposed);
+    *n = sl.n;
+    int64_t kept = 0;
+    for (uint32_t r = 0; r < sl.n; ++r) kept += (int)sl.h_len[r] >= c.min_len;
+    if (*sl.h_bad) {                       // dropped: its reads still take their ids
+        c.nseq_base += kept;
+        c.read_base += sl.n;
+        c.head ^= 1; --c.npend;
+        c.prof = pr;
+        return core_fail(c, PBA_E_ALPHABET, "collect", "the batch holds bytes outside ACGT");
+    }
+    (void)hipEventRecord(c.ev_loc0, ctx->stream);
+    const int rc = walk(sl, c.read_base, c.nseq_base);
+    if (rc != PBA_OK) return spend(c, rc);
+    e = hipEventRecord(c.ev_loc1, ctx->stream);
+    if (e == hipSuccess) e = hipEventSynchronize(c.ev_loc1);       // (the walk ended in a synchronise: nothing reads the slot any more)
+    if (e != hipSuccess) return spend(c, core_fail(c, PBA_E_HIP, "collect", hipGetErrorString(e)));
+    c.have_loc1 = true;
+    (void)hipEventElapsedTime(&pr.locate_ms, c.ev_loc0, c.ev_loc1);
+    c.read_base += sl.n;
+    c.nseq_base += kept;
+    c.head ^= 1; --c.npend;
+    c.prof = pr;
+    return PBA_OK;
+}
+
+// what both creates refuse about the slot
+static int slot_ok(pba_ctx *ctx, const char *who, uint64_t slot_bytes, uint32_t slot_reads, int form) {
+    if (form != PBA_STREAM_TEXT && form != PBA_STREAM_RECORDS) return ctx_fail_as(ctx, PBA_E_INVALID, who, "unknown form");
+    // work items and plane words of a batch are 32-bit counts in the kernel's prefix
+    if (slot_bytes / 8 + slot_reads >= (1ull << 31)) return ctx_fail_as(ctx, PBA_E_TOOLONG, who, "slot too large");
+    return PBA_OK;
+}
 
 extern "C" {
 
+// ---------------------------------------------------------------------------------------------
+// host API: streamed locate
+// ---------------------------------------------------------------------------------------------
 int pba_loc_stream_create(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, uint32_t target_seq, double R, int trials,
                           int min_len, int maxn, int maxm, int kernel, uint64_t slot_bytes, uint32_t slot_reads, int form,
                           pba_loc_stream **out) {
     if (!ctx || !ix || !target || !out || target_seq >= target->n || trials < 0) return PBA_E_INVALID;
     *out = nullptr;
-    if (form != PBA_STREAM_TEXT && form != PBA_STREAM_RECORDS) PBA_FAIL(PBA_E_INVALID, "pba_loc_stream_create: unknown form");
     if (ix->mode != PBA_INDEX_ALL || ix->seq_len != target->h_len[target_seq])      // pba_locate's own checks, at the door
         PBA_FAIL(PBA_E_INVALID, "pba_locate needs a PBA_INDEX_ALL index of the target sequence");
     if (target->non_acgt) PBA_FAIL(PBA_E_ALPHABET, "pba_locate: a sequence set holds bytes outside ACGT");
     Plan pl;
     PBA_TRY(make_plan(ctx, R, maxn, maxm, kernel, 1, &pl));
-    // work items and plane words of a batch are 32-bit counts in the kernel's prefix
-    if (slot_bytes / 8 + slot_reads >= (1ull << 31)) PBA_FAIL(PBA_E_TOOLONG, "pba_loc_stream_create: slot too large");
+    PBA_TRY(slot_ok(ctx, "pba_loc_stream_create", slot_bytes, slot_reads, form));
     HIPCHK(hipSetDevice(ctx->device));
     pba_loc_stream *s = new (std::nothrow) pba_loc_stream();
     if (!s) PBA_FAIL(PBA_E_NOMEM, "pba_loc_stream");
-    s->ctx = ctx; s->ix = ix; s->target = target; s->target_seq = target_seq; s->R = R; s->trials = trials; s->min_len = min_len;
-    s->maxn = maxn; s->maxm = maxm; s->kernel = kernel; s->form = form; s->slot_bytes = slot_bytes; s->slot_reads = slot_reads;
-    if (form == PBA_STREAM_TEXT) {         // every read rounds up to 16 packed bytes and to one plane word
-        s->pk_cap = ((slot_bytes + 3) / 4 + 16ull * slot_reads + 15) & ~15ull;
-        s->plane_cap = slot_bytes / 32 + slot_reads + 1;
-    } else {                               // the file is the arena; four bases per payload byte
-        s->pk_cap = (slot_bytes + 15) & ~15ull;
-        s->plane_cap = slot_bytes / 8 + slot_reads + 1;
-    }
-    bool ok = hipStreamCreateWithFlags(&s->copy, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipEventCreate(&s->ev_loc0) == hipSuccess && hipEventCreate(&s->ev_loc1) == hipSuccess;
-    ok = ok && slot_alloc(s, s->slot[0]) && slot_alloc(s, s->slot[1]);
-    ok = ok && hipStreamSynchronize(s->copy) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        stream_free(s);
+    s->ix = ix; s->target = target; s->target_seq = target_seq; s->R = R; s->trials = trials; s->maxn = maxn; s->maxm = maxm;
+    s->kernel = kernel;
+    if (core_create(s->c, ctx, "pba_loc_stream", form, min_len, false, slot_bytes, slot_reads) != PBA_OK) {
+        core_free(s->c);
+        delete s;
         PBA_FAIL(PBA_E_NOMEM, "pba_loc_stream_create");
     }
     *out = s;
@@ -266,124 +477,107 @@ int pba_loc_stream_create(pba_ctx *ctx, const pba_index *ix, const pba_seqs *tar
 }
 
 int pba_loc_stream_buffer(pba_loc_stream *s, void **bytes, uint64_t **offsets) {
-    if (!s || s->spent || !bytes || !offsets || s->npend >= 2) return PBA_E_INVALID;
-    StreamSlot &sl = s->slot[(s->head + s->npend) & 1];
-    *bytes = sl.h_bytes;
-    *offsets = sl.h_offs;
-    return PBA_OK;
+    return s ? core_buffer(s->c, bytes, offsets) : PBA_E_INVALID;
 }
 
-int pba_loc_stream_submit(pba_loc_stream *s, uint32_t n) {
-    if (!s || s->spent || s->npend >= 2) return PBA_E_INVALID;
-    pba_ctx *ctx = s->ctx;
-    StreamSlot &sl = s->slot[(s->head + s->npend) & 1];
-    pba_seqs *q = sl.set;
-    uint64_t pk_total = 0, words = 0;
-    uint32_t items = 0;
-    const bool text = s->form == PBA_STREAM_TEXT;
-    PBA_TRY(text ? plan_text(s, sl, n, &pk_total, &words, &items) : plan_records(s, sl, &n, &pk_total, &words));
-    // from here on the batch is accepted: a failure is the runtime's and spends the stream
-    q->n = n; q->packed_bytes = pk_total; q->non_acgt = false; q->plane_words = words + 2 * kPlaneSlack;
-    q->h_off.assign(sl.h_off, sl.h_off + n + 1);       // (within the capacity reserved at creation)
-    q->h_len.assign(sl.h_len, sl.h_len + n + 1);
-    sl.n = n; sl.n_bytes = text ? sl.h_offs[n] : pk_total;
-    *sl.h_bad = 0;
-    const size_t n1 = (size_t)n + 1;
-    uint32_t *plane0 = q->d_planes + 2 * kPlaneSlack;
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e == hipSuccess) e = hipEventRecord(sl.ev_begin, s->copy);
-    if (e == hipSuccess && sl.n_bytes) e = hipMemcpyAsync(text ? sl.d_text : q->d_packed, sl.h_bytes, sl.n_bytes, hipMemcpyHostToDevice, s->copy);
-    if (e == hipSuccess) e = hipEventRecord(sl.ev_h2d, s->copy);
-    if (e == hipSuccess) e = hipMemcpyAsync(q->d_off, sl.h_off, sizeof(uint64_t) * n1, hipMemcpyHostToDevice, s->copy);
-    if (e == hipSuccess) e = hipMemcpyAsync(q->d_poff, sl.h_poff, sizeof(uint64_t) * n1, hipMemcpyHostToDevice, s->copy);
-    if (e == hipSuccess) e = hipMemcpyAsync(q->d_len, sl.h_len, sizeof(uint32_t) * n1, hipMemcpyHostToDevice, s->copy);
-    if (e == hipSuccess && text) {
-        e = hipMemcpyAsync(sl.d_toff, sl.h_offs, sizeof(uint64_t) * n1, hipMemcpyHostToDevice, s->copy);
-        if (e == hipSuccess) e = hipMemcpyAsync(sl.d_item, sl.h_item, sizeof(uint32_t) * n1, hipMemcpyHostToDevice, s->copy);
-        if (e == hipSuccess) e = hipMemsetAsync(sl.d_bad, 0, sizeof(uint32_t), s->copy);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_pack_planes, dim3(elem_grid(((uint64_t)items + 1) * PBA_WAVE, 256)), dim3(256), 0, s->copy, sl.d_text,
-                               sl.d_toff, q->d_off, q->d_poff, q->d_len, sl.d_item, n, items, pk_total, words, q->d_packed, plane0, sl.d_bad);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(sl.h_bad, sl.d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, s->copy);
-    } else if (e == hipSuccess) {          // the file is the packed arena: zero behind it, planes by k_make_planes, zero behind them
-        e = hipMemsetAsync(q->d_packed + pk_total, 0, kRecordSlack + kSlack, s->copy);
-        if (e == hipSuccess && planes_enqueue(ctx, q, words, s->copy) != PBA_OK) return spend(s, PBA_E_HIP);
-        if (e == hipSuccess) e = hipMemsetAsync(plane0 + 2 * words, 0, kPlaneSlack * 2 * sizeof(uint32_t), s->copy);
-    }
-    if (e == hipSuccess) e = hipEventRecord(sl.ev_pack, s->copy);
-    if (e != hipSuccess) return spend(s, ctx_fail(ctx, PBA_E_HIP, "pba_loc_stream_submit", e));
-    ++s->npend;
-    return PBA_OK;
-}
+int pba_loc_stream_submit(pba_loc_stream *s, uint32_t n) { return s ? core_submit(s->c, n) : PBA_E_INVALID; }
 
 int pba_loc_stream_pending(pba_loc_stream *s, const pba_seqs **set) {
-    if (!s || s->spent || !set || s->npend == 0) return PBA_E_INVALID;
-    pba_ctx *ctx = s->ctx;
-    StreamSlot &sl = s->slot[s->head];
-    const hipError_t e = hipEventSynchronize(sl.ev_pack);
-    if (e != hipSuccess) return spend(s, ctx_fail(ctx, PBA_E_HIP, "pba_loc_stream_pending", e));
-    sl.set->non_acgt = *sl.h_bad != 0;     // (the aligning entry points refuse such a set, as they do a resident one)
-    *set = sl.set;
+    if (!s || !set) return PBA_E_INVALID;
+    StreamSlot *sl = nullptr;
+    PBA_TRY(core_pending(s->c, &sl));
+    *set = sl->set;
     return PBA_OK;
 }
 
 int pba_loc_stream_collect(pba_loc_stream *s, pba_loc_row *rows, uint32_t cap, uint32_t *n, pba_loc_stats *stats) {
-    if (!s || s->spent || !n || s->npend == 0) return PBA_E_INVALID;
-    pba_ctx *ctx = s->ctx;
-    StreamSlot &sl = s->slot[s->head];
-    if (cap < sl.n || (!rows && sl.n)) PBA_FAIL(PBA_E_INVALID, "pba_loc_stream_collect: cap below the batch size");
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e == hipSuccess) e = hipEventSynchronize(sl.ev_pack);      // the flag of the pack is read before anything is launched
-    if (e != hipSuccess) return spend(s, ctx_fail(ctx, PBA_E_HIP, "pba_loc_stream_collect", e));
-    pba_stream_profile pr;
-    memset(&pr, 0, sizeof pr);
-    pr.n_reads = sl.n; pr.n_bytes = sl.n_bytes;
-    (void)hipEventElapsedTime(&pr.h2d_ms, sl.ev_begin, sl.ev_h2d);
-    (void)hipEventElapsedTime(&pr.pack_ms, sl.ev_h2d, sl.ev_pack);
-    // what of the upload was NOT hidden: the ctx's stream had nothing to do from the end of the locate before (or, with none
-    // since this batch was submitted, from the submit) until the pack was through
-    float exposed = 0.f, since_loc = 0.f;
-    (void)hipEventElapsedTime(&exposed, sl.ev_begin, sl.ev_pack);
-    if (s->have_loc1 && hipEventElapsedTime(&since_loc, s->ev_loc1, sl.ev_pack) == hipSuccess) exposed = std::min(exposed, since_loc);
-    (void)hipGetLastError();
-    pr.stall_ms = std::max(0.f, exposed);
-    *n = sl.n;
-    if (*sl.h_bad) {                       // dropped: its reads still take their ids
-        for (uint32_t r = 0; r < sl.n; ++r) s->nseq_base += (int)sl.h_len[r] >= s->min_len;
-        s->read_base += sl.n;
-        s->head ^= 1; --s->npend;
-        s->prof = pr;
-        PBA_FAIL(PBA_E_ALPHABET, "pba_loc_stream_collect: the batch holds bytes outside ACGT");
-    }
+    if (!s) return PBA_E_INVALID;
     pba_loc_row none;
     pba_loc_stats st;
-    (void)hipEventRecord(s->ev_loc0, ctx->stream);
-    const int rc = locate_core(ctx, s->ix, s->target, s->target_seq, sl.set, s->R, s->trials, s->min_len, s->maxn, s->maxm,
-                               s->kernel, rows ? rows : &none, &st, s->read_base, s->nseq_base, sl.ev_pack);
-    if (rc != PBA_OK) return spend(s, rc);
-    e = hipEventRecord(s->ev_loc1, ctx->stream);
-    if (e == hipSuccess) e = hipEventSynchronize(s->ev_loc1);      // (the locate ended in a synchronise: nothing reads the slot any more)
-    if (e != hipSuccess) return spend(s, ctx_fail(ctx, PBA_E_HIP, "pba_loc_stream_collect", e));
-    s->have_loc1 = true;
-    (void)hipEventElapsedTime(&pr.locate_ms, s->ev_loc0, s->ev_loc1);
-    s->read_base += sl.n;
-    s->nseq_base += st.n_reads_kept;
-    s->head ^= 1; --s->npend;
-    s->prof = pr;
+    PBA_TRY(core_collect(s->c, rows != nullptr, cap, n, [&](StreamSlot &sl, int64_t read_base, int64_t nseq_base) {
+        return locate_core(s->c.ctx, s->ix, s->target, s->target_seq, sl.set, s->R, s->trials, s->c.min_len, s->maxn, s->maxm,
+                           s->kernel, rows ? rows : &none, &st, read_base, nseq_base, sl.ev_pack);
+    }));
     if (stats) *stats = st;
     return PBA_OK;
 }
 
 int pba_loc_stream_last_profile(const pba_loc_stream *s, pba_stream_profile *out) {
     if (!s || !out) return PBA_E_INVALID;
-    *out = s->prof;
+    *out = s->c.prof;
     return PBA_OK;
 }
 
 void pba_loc_stream_destroy(pba_loc_stream *s) {
-    if (s) stream_free(s);
+    if (!s) return;
+    core_free(s->c);
+    delete s;
+}
+
+// ---------------------------------------------------------------------------------------------
+// host API: streamed mapping
+// ---------------------------------------------------------------------------------------------
+int pba_map_stream_create(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, double R, int trials, int min_len, int maxn,
+                          int maxm, int kernel, int strands, uint64_t slot_bytes, uint32_t slot_reads, int form,
+                          pba_map_stream **out) {
+    if (!ctx || !ix || !target || !out || trials < 0 || strands < 1 || strands > 3) return PBA_E_INVALID;
+    *out = nullptr;
+    PBA_TRY(map_target_ok(ctx, ix, target));                       // pba_map_reads' own checks, at the door
+    if (target->non_acgt) PBA_FAIL(PBA_E_ALPHABET, "pba_map_reads: a sequence set holds bytes outside ACGT");
+    Plan pl;
+    PBA_TRY(make_plan(ctx, R, maxn, maxm, kernel, 1, &pl));
+    PBA_TRY(slot_ok(ctx, "pba_map_stream_create", slot_bytes, slot_reads, form));
+    HIPCHK(hipSetDevice(ctx->device));
+    pba_map_stream *s = new (std::nothrow) pba_map_stream();
+    if (!s) PBA_FAIL(PBA_E_NOMEM, "pba_map_stream");
+    s->ix = ix; s->target = target; s->R = R; s->trials = trials; s->maxn = maxn; s->maxm = maxm; s->kernel = kernel;
+    s->strands = strands;
+    if (core_create(s->c, ctx, "pba_map_stream", form, min_len, (strands & 2) != 0, slot_bytes, slot_reads) != PBA_OK) {
+        core_free(s->c);
+        delete s;
+        PBA_FAIL(PBA_E_NOMEM, "pba_map_stream_create");
+    }
+    *out = s;
+    return PBA_OK;
+}
+
+int pba_map_stream_buffer(pba_map_stream *s, void **bytes, uint64_t **offsets) {
+    return s ? core_buffer(s->c, bytes, offsets) : PBA_E_INVALID;
+}
+
+int pba_map_stream_submit(pba_map_stream *s, uint32_t n) { return s ? core_submit(s->c, n) : PBA_E_INVALID; }
+
+int pba_map_stream_pending(pba_map_stream *s, const pba_seqs **fwd, const pba_seqs **rc) {
+    if (!s || !fwd || !rc) return PBA_E_INVALID;
+    StreamSlot *sl = nullptr;
+    PBA_TRY(core_pending(s->c, &sl));
+    *fwd = sl->set;
+    *rc = sl->rc;
+    return PBA_OK;
+}
+
+int pba_map_stream_collect(pba_map_stream *s, pba_map_row *rows, uint32_t cap, uint32_t *n, pba_map_stats *stats) {
+    if (!s) return PBA_E_INVALID;
+    pba_map_row none;
+    pba_map_stats st;
+    PBA_TRY(core_collect(s->c, rows != nullptr, cap, n, [&](StreamSlot &sl, int64_t read_base, int64_t nseq_base) {
+        return map_core(s->c.ctx, s->ix, s->target, sl.set, sl.rc, s->R, s->trials, s->c.min_len, s->maxn, s->maxm, s->kernel,
+                        s->strands, rows ? rows : &none, &st, read_base, nseq_base, sl.ev_pack);
+    }));
+    if (stats) *stats = st;
+    return PBA_OK;
+}
+
+int pba_map_stream_last_profile(const pba_map_stream *s, pba_stream_profile *out) {
+    if (!s || !out) return PBA_E_INVALID;
+    *out = s->c.prof;
+    return PBA_OK;
+}
+
+void pba_map_stream_destroy(pba_map_stream *s) {
+    if (!s) return;
+    core_free(s->c);
+    delete s;
 }
 
 }  // extern "C"

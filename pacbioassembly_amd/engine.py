@@ -676,6 +676,10 @@ class LocStream:
     a copy stream while the locate of batch k runs.  Per batch: fill buffer() (or submit_reads), submit, collect -- and submit
     the next batch before collecting this one to hide its upload.  The rows of all batches, concatenated, are the rows of
     one Context.locate over the concatenated reads."""
+    _api = "pba_loc_stream"                             # (MapStream: the same protocol under another prefix)
+
+    def _call(self, fn: str, *args):
+        self.ctx.check(getattr(self.ctx.lib, f"{self._api}_{fn}")(self.h, *args), f"{self._api[4:]}_{fn}")
 
     def __init__(self, ctx: "Context", ix, target, target_seq: int, R: float, trials: int = 50, min_len: int = 500, maxn: int = 0,
                  maxm: int = 0, kernel: int = PBA_KERNEL_AUTO, slot_bytes: int = 1 << 20, slot_reads: int = 1024,
@@ -688,7 +692,7 @@ class LocStream:
 
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):
-            self.ctx.lib.pba_loc_stream_destroy(self.h)
+            getattr(self.ctx.lib, self._api + "_destroy")(self.h)
         self.h = None
 
     __del__ = close
@@ -697,13 +701,13 @@ class LocStream:
         """(bytes uint8[slot_bytes], offsets uint64[max(slot_reads + 1, 3)]): numpy views of the next free slot's pinned memory,
         to be filled in place and left alone between submit and the collect of that batch."""
         b, o = C.c_void_p(), C.c_void_p()
-        self.ctx.check(self.ctx.lib.pba_loc_stream_buffer(self.h, C.byref(b), C.byref(o)), "loc_stream_buffer")
+        self._call("buffer", C.byref(b), C.byref(o))
         nb, no = max(self.slot_bytes, 1), max(self.slot_reads + 1, 3)
         return (np.ctypeslib.as_array(C.cast(b, C.POINTER(C.c_uint8)), shape=(nb,))[:self.slot_bytes],
                 np.ctypeslib.as_array(C.cast(o, C.POINTER(C.c_uint64)), shape=(no,)))
 
     def submit(self, n: int = 0):
-        self.ctx.check(self.ctx.lib.pba_loc_stream_submit(self.h, n), "loc_stream_submit")
+        self._call("submit", n)
 
     def submit_reads(self, reads: Sequence[bytes]):
         """Text form: write the reads into the slot and submit them."""
@@ -742,7 +746,7 @@ class LocStream:
 
     def profile(self) -> dict:
         pr = _lib.PbaStreamProfile()
-        self.ctx.check(self.ctx.lib.pba_loc_stream_last_profile(self.h, C.byref(pr)), "loc_stream_last_profile")
+        self._call("last_profile", C.byref(pr))
         return {k: getattr(pr, k) for k, _ in _lib.PbaStreamProfile._fields_}
 
 
@@ -752,6 +756,46 @@ def _locate_stream(self, ix, target, target_seq, R, trials=50, min_len=500, maxn
 
 
 Context.locate_stream = _locate_stream
+
+
+class MapStream(LocStream):
+    """Streamed mapping (pba_map_stream): LocStream's slots and protocol under Context.map_reads -- many contigs, both strands.
+    With strands & 2 a slot also holds the reverse complement of its batch, packed on the copy stream behind the forward pack.
+    The rows of all batches, concatenated, are the rows of one Context.map_reads over the concatenated reads, and the stats
+    of the batches sum to that call's."""
+    _api = "pba_map_stream"
+
+    def __init__(self, ctx: "Context", ix, target, R: float, trials: int = 50, min_len: int = 500, maxn: int = 0, maxm: int = 0,
+                 kernel: int = PBA_KERNEL_AUTO, strands: int = 3, slot_bytes: int = 1 << 20, slot_reads: int = 1024,
+                 form: int = PBA_STREAM_TEXT):
+        self.ctx, self.form, self.slot_bytes, self.slot_reads = ctx, form, int(slot_bytes), int(slot_reads)
+        self._keep = (ix, target)                       # the stream looks into both until it is closed
+        self.h = C.c_void_p()
+        ctx.check(ctx.lib.pba_map_stream_create(ctx.h, ix.h, target.h, R, trials, min_len, maxn, maxm, kernel, strands,
+                                                self.slot_bytes, self.slot_reads, form, C.byref(self.h)), "map_stream_create")
+
+    def collect(self):
+        """(rows of MAP_ROW_DTYPE, stats as Context.map_reads returns them) of the oldest pending batch."""
+        rows = np.zeros(max(self.slot_reads, 1), MAP_ROW_DTYPE)
+        st, n = PbaMapStats(), C.c_uint32()
+        self._call("collect", _ptr(rows), self.slot_reads, C.byref(n), C.byref(st))
+        per = [{k: getattr(st.strand[i], k) for k, _ in PbaLocStats._fields_} for i in range(2)]
+        return rows[:n.value].copy(), {"strand": per, "n_second_walk": int(st.n_second_walk)}
+
+    def pending(self):
+        """(fwd, rc): both sets of the batch collect() would run next, borrowed from its slot (valid until that collect);
+        rc is None with strands == 1."""
+        f, r = C.c_void_p(), C.c_void_p()
+        self._call("pending", C.byref(f), C.byref(r))
+        return BorrowedSeqSet(self.ctx, f), (BorrowedSeqSet(self.ctx, r) if r.value else None)
+
+
+def _map_stream(self, ix, target, R, trials=50, min_len=500, maxn=0, maxm=0, kernel=PBA_KERNEL_AUTO, strands=3,
+                slot_bytes=1 << 20, slot_reads=1024, form=PBA_STREAM_TEXT) -> MapStream:
+    return MapStream(self, ix, target, R, trials, min_len, maxn, maxm, kernel, strands, slot_bytes, slot_reads, form)
+
+
+Context.map_stream = _map_stream
 
 
 class SeqSet:
