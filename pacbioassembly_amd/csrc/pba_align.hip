@@ -362,15 +362,15 @@ static bool pack_acgt(const uint8_t *src, int len, uint8_t *packed, uint32_t *pl
 
 // A staged pair as a two-sequence set in one pooled device buffer (sequence 0 = a, sequence 1 = b, both stored in text
 // order; a backward accessor starts at its last base with the BACKWARD flag): header, packed bases with kSlack zero bytes
-// around them, bit planes with kPlaneSlack zero word pairs around them -- the layout pba_seqs gives a set (pba_core.hip).
+// around them, bit planes with kPlaneSlack zero word pairs around them -- the text layout of seq_layout.h.
 struct TextStage {
     size_t o_pair, o_off, o_len, o_poff, o_ooff, o_packed, o_plane, bytes;
     uint64_t pkA, pkB, wA, wB;
 };
 static inline TextStage text_stage_layout(const TextClip &c) {
     TextStage t;
-    t.pkA = (((uint64_t)c.len_a + 3) / 4 + 15) & ~15ull; t.pkB = (((uint64_t)c.len_b + 3) / 4 + 15) & ~15ull;
-    t.wA = ((uint64_t)c.len_a + 31) / 32; t.wB = ((uint64_t)c.len_b + 31) / 32;
+    t.pkA = seq_packed_bytes((uint64_t)c.len_a); t.pkB = seq_packed_bytes((uint64_t)c.len_b);
+    t.wA = seq_plane_words((uint64_t)c.len_a); t.wB = seq_plane_words((uint64_t)c.len_b);
     t.o_pair = 0; t.o_off = 32; t.o_len = 64; t.o_poff = 80; t.o_ooff = 128;
     t.o_packed = 256 + kSlack;
     t.o_plane = ((t.o_packed + t.pkA + t.pkB + kSlack + 63) & ~(size_t)63) + kPlaneSlack * 8;

@@ -201,35 +201,32 @@ int pba_ctx_device_info(const pba_ctx *ctx, char *name, size_t cap, int *n_cu, i
 // ---------------------------------------------------------------------------------------------
 // host API: sequence sets
 // ---------------------------------------------------------------------------------------------
-static int seqs_alloc(pba_ctx *ctx, pba_seqs *s, uint64_t packed_bytes) {
-    s->packed_bytes = packed_bytes;
-    HIPCHK(hipMalloc((void **)&s->d_alloc, packed_bytes + 2 * kSlack));
-    HIPCHK(memset_big(s->d_alloc, 0, packed_bytes + 2 * kSlack, ctx->stream));
-    s->d_packed = s->d_alloc + kSlack;
-    HIPCHK(hipMalloc((void **)&s->d_off, sizeof(uint64_t) * (s->n + 1)));
-    HIPCHK(hipMalloc((void **)&s->d_len, sizeof(uint32_t) * (s->n + 1)));
-    HIPCHK(hipMemcpyAsync(s->d_off, s->h_off.data(), sizeof(uint64_t) * s->n, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(s->d_len, s->h_len.data(), sizeof(uint32_t) * s->n, hipMemcpyHostToDevice, ctx->stream));
-    return PBA_OK;
+// Every maker: its own checks, which fill h_off / h_len up to entry n; its own arena (seqs_arena) and where the payload comes
+// from; seqs_finish, with its pack step if it has one.  The layout is seq_layout.h's.
+void seqs_free(pba_seqs *s) {
+    if (!s) return;
+    (void)hipSetDevice(s->ctx->device);
+    for (void *d : {(void *)s->d_planes, (void *)s->d_poff, (void *)s->d_alloc, (void *)s->d_off, (void *)s->d_len}) if (d) (void)hipFree(d);
+    delete s;
 }
 
-// the bit planes of a set whose packed bytes, offsets and lengths are on the device (enqueued on the ctx's stream)
-static int seqs_planes(pba_ctx *ctx, pba_seqs *s) {
-    std::vector<uint64_t> poff(s->n + 1);
-    uint64_t w = 0;
-    for (uint32_t i = 0; i < s->n; ++i) { poff[i] = w; w += ((uint64_t)s->h_len[i] + 31) / 32; }
-    poff[s->n] = w;
-    s->plane_words = w + 2 * kPlaneSlack;
-    HIPCHK(hipMalloc((void **)&s->d_planes, s->plane_words * 2 * sizeof(uint32_t)));
-    HIPCHK(memset_big(s->d_planes, 0, s->plane_words * 2 * sizeof(uint32_t), ctx->stream));
-    HIPCHK(hipMalloc((void **)&s->d_poff, sizeof(uint64_t) * (s->n + 1)));
-    HIPCHK(hipMemcpyAsync(s->d_poff, poff.data(), sizeof(uint64_t) * (s->n + 1), hipMemcpyHostToDevice, ctx->stream));
-    if (w) {
-        hipLaunchKernelGGL(k_make_planes, dim3(elem_grid(w, 256)), dim3(256), 0, ctx->stream, s->d_packed, s->d_off, s->d_len,
-                           s->d_poff, s->n, w, s->d_planes + 2 * kPlaneSlack);
-        HIPCHK(hipGetLastError());
+// (a stream's set is left alone: pba_loc_stream_destroy frees the slot it looks into)
+void pba_seqs_destroy(pba_seqs *s) { if (s && !s->borrowed) seqs_free(s); }
+
+// a set under construction: freed with whatever it holds so far unless the maker hands it out (release)
+typedef std::unique_ptr<pba_seqs, void (*)(pba_seqs *)> SeqsGuard;
+
+// The arena of a set, `bytes` packed bytes between the kind's slacks.  Zeroed throughout -- the pack kernels skip the alignment
+// padding, a file image is copied over it -- but for device-packed bytes, which are copied over everything between the slacks.
+static int seqs_arena(pba_ctx *ctx, pba_seqs *s, ArenaKind kind, uint64_t bytes) {
+    s->packed_bytes = bytes;
+    HIPCHK(hipMalloc((void **)&s->d_alloc, arena_bytes(kind, bytes)));
+    s->d_packed = s->d_alloc + kSlack;
+    if (kind != ARENA_DEVICE_PACKED) HIPCHK(memset_big(s->d_alloc, 0, arena_bytes(kind, bytes), ctx->stream));
+    else {
+        HIPCHK(hipMemsetAsync(s->d_alloc, 0, kSlack, ctx->stream));
+        HIPCHK(hipMemsetAsync(s->d_packed + bytes, 0, kSlack, ctx->stream));
     }
-    HIPCHK(hipStreamSynchronize(ctx->stream));      // poff (host vector) must outlive the copy
     return PBA_OK;
 }
 
@@ -241,58 +238,58 @@ int planes_enqueue(pba_ctx *ctx, const pba_seqs *s, uint64_t words, hipStream_t 
     return PBA_OK;
 }
 
-void pba_seqs_destroy(pba_seqs *s) {
-    if (!s || s->borrowed) return;      // (a stream's set: pba_loc_stream_destroy frees the slot it looks into)
-    (void)hipSetDevice(s->ctx->device);
-    if (s->d_planes) (void)hipFree(s->d_planes);
-    if (s->d_poff) (void)hipFree(s->d_poff);
-    if (s->d_alloc) (void)hipFree(s->d_alloc);
-    if (s->d_off) (void)hipFree(s->d_off);
-    if (s->d_len) (void)hipFree(s->d_len);
-    delete s;
+// The one way a set is finished, on the ctx's stream: off / len / poff to the device (n + 1 entries each), the maker's pack
+// step where it has one (it reads them and writes the arena), the zeroed planes, k_make_planes, and the synchronise that lets
+// the host prefix and whatever the maker staged go.
+static int seqs_finish(pba_ctx *ctx, pba_seqs *s, const std::function<int()> &pack = nullptr) {
+    const size_t n1 = (size_t)s->n + 1;
+    std::vector<uint64_t> poff(n1);
+    const SeqTotals t = seq_layout(s->h_len.data(), s->n, nullptr, poff.data(), nullptr);
+    s->max_len = t.max_len; s->plane_words = t.words + 2 * kPlaneSlack;
+    HIPCHK(hipMalloc((void **)&s->d_off, sizeof(uint64_t) * n1));
+    HIPCHK(hipMalloc((void **)&s->d_len, sizeof(uint32_t) * n1));
+    HIPCHK(hipMalloc((void **)&s->d_poff, sizeof(uint64_t) * n1));
+    HIPCHK(hipMemcpyAsync(s->d_off, s->h_off.data(), sizeof(uint64_t) * n1, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(s->d_len, s->h_len.data(), sizeof(uint32_t) * n1, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(s->d_poff, poff.data(), sizeof(uint64_t) * n1, hipMemcpyHostToDevice, ctx->stream));
+    if (pack) PBA_TRY(pack());
+    HIPCHK(hipMalloc((void **)&s->d_planes, s->plane_words * 2 * sizeof(uint32_t)));
+    HIPCHK(memset_big(s->d_planes, 0, s->plane_words * 2 * sizeof(uint32_t), ctx->stream));
+    PBA_TRY(planes_enqueue(ctx, s, t.words, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return PBA_OK;
 }
 
 // shared tail of the two text constructors: d_text / d_toff are on the device, h_toff on the host
 static int seqs_pack(pba_ctx *ctx, const uint8_t *d_text, const uint64_t *d_toff, const uint64_t *h_toff, uint32_t n,
                      int strict, pba_seqs **out) {
-    pba_seqs *s = new (std::nothrow) pba_seqs();
+    SeqsGuard g(seqs_new(ctx, n), seqs_free);
+    pba_seqs *s = g.get();
     if (!s) PBA_FAIL(PBA_E_NOMEM, "pba_seqs");
-    s->ctx = ctx; s->n = n; s->max_len = 0; s->non_acgt = false; s->d_alloc = nullptr; s->d_packed = nullptr; s->d_off = nullptr; s->d_len = nullptr; s->d_planes = nullptr; s->d_poff = nullptr; s->plane_words = 0;
-    s->h_off.resize(n + 1); s->h_len.resize(n + 1);
-    uint64_t pk = 0;
     for (uint32_t i = 0; i < n; ++i) {
-        if (h_toff[i + 1] < h_toff[i] || h_toff[i + 1] - h_toff[i] > 0x7FFFFFF0ull) {
-            delete s;
+        if (h_toff[i + 1] < h_toff[i] || h_toff[i + 1] - h_toff[i] > 0x7FFFFFF0ull)
             PBA_FAIL(PBA_E_INVALID, "offsets must be non-decreasing and each sequence < 2^31 bases");
-        }
-        const uint32_t L = (uint32_t)(h_toff[i + 1] - h_toff[i]);
-        s->h_off[i] = pk; s->h_len[i] = L;
-        s->max_len = std::max(s->max_len, L);
-        pk += (((uint64_t)L + 3) / 4 + 15) & ~15ull;     // every sequence starts 16-byte aligned
+        s->h_len[i] = (uint32_t)(h_toff[i + 1] - h_toff[i]);
     }
-    s->h_off[n] = pk; s->h_len[n] = 0;
-    int st = seqs_alloc(ctx, s, pk);
-    if (st != PBA_OK) { pba_seqs_destroy(s); return st; }
-    DevBuf bad;
-    if (hipMalloc(&bad.p, 4) != hipSuccess) { pba_seqs_destroy(s); PBA_FAIL(PBA_E_NOMEM, "hipMalloc"); }
-    (void)hipMemsetAsync(bad.p, 0, 4, ctx->stream);
-    // the kernel bisects over n+1 offsets: upload the end offset too
-    (void)hipMemcpyAsync(s->d_off + n, &s->h_off[n], sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream);
-    const uint64_t total_dwords = pk / 4;
-    if (total_dwords) {
-        hipLaunchKernelGGL(k_pack_text, dim3(elem_grid(total_dwords, 256)), dim3(256), 0, ctx->stream, d_text, d_toff, s->d_off,
-                           s->d_len, n, total_dwords, s->d_packed, strict, bad.as<uint32_t>());
-    }
-    uint32_t h_bad = 0;
-    hipError_t e = hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) { pba_seqs_destroy(s); return ctx_fail(ctx, PBA_E_HIP, "k_pack_text", e); }
-    if (strict && h_bad) { pba_seqs_destroy(s); PBA_FAIL(PBA_E_ALPHABET, "pba_seqs_from_text"); }
-    s->non_acgt = h_bad != 0;
-    st = seqs_planes(ctx, s);
-    if (st != PBA_OK) { pba_seqs_destroy(s); return st; }
-    *out = s;
+    PBA_TRY(seqs_arena(ctx, s, ARENA_TEXT, seq_layout(s->h_len.data(), n, s->h_off.data(), nullptr, nullptr).packed));
+    PBA_TRY(seqs_finish(ctx, s, [&]() -> int {
+        DevBuf bad;
+        if (hipMalloc(&bad.p, 4) != hipSuccess) PBA_FAIL(PBA_E_NOMEM, "hipMalloc");
+        (void)hipMemsetAsync(bad.p, 0, 4, ctx->stream);
+        const uint64_t total_dwords = s->packed_bytes / 4;
+        if (total_dwords)
+            hipLaunchKernelGGL(k_pack_text, dim3(elem_grid(total_dwords, 256)), dim3(256), 0, ctx->stream, d_text, d_toff, s->d_off,
+                               s->d_len, n, total_dwords, s->d_packed, strict, bad.as<uint32_t>());
+        uint32_t h_bad = 0;
+        hipError_t e = hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) return ctx_fail(ctx, PBA_E_HIP, "k_pack_text", e);
+        if (strict && h_bad) PBA_FAIL(PBA_E_ALPHABET, "pba_seqs_from_text");
+        s->non_acgt = h_bad != 0;
+        return PBA_OK;
+    }));
+    *out = g.release();
     return PBA_OK;
 }
 
@@ -332,36 +329,22 @@ int pba_seqs_from_records(pba_ctx *ctx, const uint8_t *file, size_t file_len, ui
     if (kept > 0x7FFFFFFFull) PBA_FAIL(PBA_E_TOOLONG, "too many records");
     std::vector<uint64_t> recs(kept + 1);
     pba_open_binary(file, file_len, min_excl, max_excl, recs.data(), kept, nullptr);
-    pba_seqs *s = new (std::nothrow) pba_seqs();
+    SeqsGuard g(seqs_new(ctx, (uint32_t)kept), seqs_free);
+    pba_seqs *s = g.get();
     if (!s) PBA_FAIL(PBA_E_NOMEM, "pba_seqs");
-    s->ctx = ctx; s->n = (uint32_t)kept; s->max_len = 0; s->non_acgt = false; s->d_alloc = nullptr; s->d_packed = nullptr; s->d_off = nullptr; s->d_len = nullptr; s->d_planes = nullptr; s->d_poff = nullptr; s->plane_words = 0;
-    s->h_off.resize(kept + 1); s->h_len.resize(kept + 1);
     for (size_t i = 0; i < kept; ++i) {
         uint32_t L;
         memcpy(&L, file + recs[i], 4);
-        if (recs[i] + 4 + ((uint64_t)L + 3) / 4 > file_len) { delete s; PBA_FAIL(PBA_E_INVALID, "truncated record"); }
+        if (recs[i] + 4 + ((uint64_t)L + 3) / 4 > file_len) PBA_FAIL(PBA_E_INVALID, "truncated record");
         s->h_off[i] = recs[i] + 4;      // payload follows the u32 length (dna_seq.h:119-121)
         s->h_len[i] = L;
-        s->max_len = std::max(s->max_len, L);
     }
-    s->h_off[kept] = file_len; s->h_len[kept] = 0;
-    // the file image goes up as it is (no re-packing); the slack after it is large enough for
-    // seed_at's byte-offset reads to stay inside the allocation and read zeros
-    const uint64_t slack = 65536;
-    s->packed_bytes = file_len;
-    hipError_t e = hipMalloc((void **)&s->d_alloc, file_len + slack + kSlack);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_alloc, 0, file_len + slack + kSlack, ctx->stream);
-    if (e == hipSuccess) s->d_packed = s->d_alloc + kSlack;
-    if (e == hipSuccess && file_len) e = hipMemcpyAsync(s->d_packed, file, file_len, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMalloc((void **)&s->d_off, sizeof(uint64_t) * (kept + 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&s->d_len, sizeof(uint32_t) * (kept + 1));
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_off, s->h_off.data(), sizeof(uint64_t) * (kept + 1), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_len, s->h_len.data(), sizeof(uint32_t) * (kept + 1), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { pba_seqs_destroy(s); return ctx_fail(ctx, PBA_E_HIP, "pba_seqs_from_records", e); }
-    const int stp = seqs_planes(ctx, s);
-    if (stp != PBA_OK) { pba_seqs_destroy(s); return stp; }
-    *out = s;
+    s->h_off[kept] = file_len;
+    // the file image goes up as it is (no re-packing), over an arena zeroed to the end of its slack
+    PBA_TRY(seqs_arena(ctx, s, ARENA_RECORDS, file_len));
+    if (file_len) HIPCHK(hipMemcpyAsync(s->d_packed, file, file_len, hipMemcpyHostToDevice, ctx->stream));
+    PBA_TRY(seqs_finish(ctx, s));
+    *out = g.release();
     return PBA_OK;
 }
 
@@ -380,32 +363,20 @@ int pba_seqs_from_device_packed(pba_ctx *ctx, const void *d_packed, uint64_t n_b
     if (!ctx || !out || (!d_packed && n_bytes) || (n && (!offsets || !lengths))) return PBA_E_INVALID;
     *out = nullptr;
     HIPCHK(hipSetDevice(ctx->device));
-    pba_seqs *s = new (std::nothrow) pba_seqs();
+    SeqsGuard g(seqs_new(ctx, n), seqs_free);
+    pba_seqs *s = g.get();
     if (!s) PBA_FAIL(PBA_E_NOMEM, "pba_seqs");
-    s->ctx = ctx; s->n = n; s->max_len = 0; s->non_acgt = non_acgt != 0; s->d_alloc = nullptr; s->d_packed = nullptr; s->d_off = nullptr; s->d_len = nullptr; s->d_planes = nullptr; s->d_poff = nullptr; s->plane_words = 0;
-    s->h_off.resize((size_t)n + 1); s->h_len.resize((size_t)n + 1);
+    s->non_acgt = non_acgt != 0;
     for (uint32_t i = 0; i < n; ++i) {
-        if (offsets[i] + ((uint64_t)lengths[i] + 3) / 4 > n_bytes) { delete s; PBA_FAIL(PBA_E_INVALID, "pba_seqs_from_device_packed: sequence outside the buffer"); }
+        if (offsets[i] + ((uint64_t)lengths[i] + 3) / 4 > n_bytes) PBA_FAIL(PBA_E_INVALID, "pba_seqs_from_device_packed: sequence outside the buffer");
         s->h_off[i] = offsets[i]; s->h_len[i] = lengths[i];
-        s->max_len = std::max(s->max_len, lengths[i]);
     }
-    s->h_off[n] = n_bytes; s->h_len[n] = 0;
-    s->packed_bytes = n_bytes;
-    // like a binary read file: the bytes go in as they are, offsets point into them; slack on both sides for the streaming reads
-    hipError_t e = hipMalloc((void **)&s->d_alloc, n_bytes + 2 * kSlack);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_alloc, 0, kSlack, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_alloc + kSlack + n_bytes, 0, kSlack, ctx->stream);
-    if (e == hipSuccess) s->d_packed = s->d_alloc + kSlack;
-    if (e == hipSuccess && n_bytes) e = copy_d2d(s->d_packed, d_packed, n_bytes, ctx->stream);
-    if (e == hipSuccess) e = hipMalloc((void **)&s->d_off, sizeof(uint64_t) * ((size_t)n + 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&s->d_len, sizeof(uint32_t) * ((size_t)n + 1));
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_off, s->h_off.data(), sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_len, s->h_len.data(), sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { pba_seqs_destroy(s); return ctx_fail(ctx, PBA_E_HIP, "pba_seqs_from_device_packed", e); }
-    const int stp = seqs_planes(ctx, s);
-    if (stp != PBA_OK) { pba_seqs_destroy(s); return stp; }
-    *out = s;
+    s->h_off[n] = n_bytes;
+    // like a binary read file: the bytes go in as they are, offsets point into them; zeroed slack on both sides for the streaming reads
+    PBA_TRY(seqs_arena(ctx, s, ARENA_DEVICE_PACKED, n_bytes));
+    if (n_bytes) HIPCHK(copy_d2d(s->d_packed, d_packed, n_bytes, ctx->stream));
+    PBA_TRY(seqs_finish(ctx, s));
+    *out = g.release();
     return PBA_OK;
 }
 
@@ -424,32 +395,18 @@ int pba_seqs_revcomp(pba_ctx *ctx, const pba_seqs *src, const uint8_t *flip, pba
     if (src->non_acgt) PBA_FAIL(PBA_E_ALPHABET, "pba_seqs_revcomp: the set holds bytes outside ACGT (code 3 has no complement)");
     HIPCHK(hipSetDevice(ctx->device));
     const uint32_t n = src->n;
-    pba_seqs *s = new (std::nothrow) pba_seqs();
+    SeqsGuard g(seqs_new(ctx, n), seqs_free);
+    pba_seqs *s = g.get();
     if (!s) PBA_FAIL(PBA_E_NOMEM, "pba_seqs");
-    s->ctx = ctx; s->n = n; s->max_len = src->max_len; s->non_acgt = false; s->d_alloc = nullptr; s->d_packed = nullptr; s->d_off = nullptr; s->d_len = nullptr; s->d_planes = nullptr; s->d_poff = nullptr; s->plane_words = 0;
-    struct Guard { pba_seqs *p; ~Guard() { if (p) pba_seqs_destroy(p); } } guard{s};
-    s->h_off.resize((size_t)n + 1); s->h_len.resize((size_t)n + 1);
-    uint64_t pk = 0;
-    for (uint32_t i = 0; i < n; ++i) {                      // pba_seqs_from_text's layout (seqs_pack)
-        const uint32_t L = src->h_len[i];
-        s->h_off[i] = pk; s->h_len[i] = L;
-        pk += (((uint64_t)L + 3) / 4 + 15) & ~15ull;
-    }
-    s->h_off[n] = pk; s->h_len[n] = 0;
-    int st = seqs_alloc(ctx, s, pk);
-    if (st != PBA_OK) return st;
-    HIPCHK(hipMemcpyAsync(s->d_off + n, &s->h_off[n], sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));   // (the bisection reads n + 1 offsets)
-    DevBuf d_flip;
+    s->h_len = src->h_len;
+    PBA_TRY(seqs_arena(ctx, s, ARENA_TEXT, seq_layout(s->h_len.data(), n, s->h_off.data(), nullptr, nullptr).packed));
+    DevBuf d_flip;                                            // (outlives its copy: seqs_finish synchronises)
     if (flip && n) {
         HIPCHK(hipMalloc(&d_flip.p, n));
         HIPCHK(hipMemcpyAsync(d_flip.p, flip, n, hipMemcpyHostToDevice, ctx->stream));
     }
-    st = revcomp_enqueue(ctx, src, s, flip ? d_flip.as<uint8_t>() : nullptr, ctx->stream);
-    if (st != PBA_OK) return st;
-    st = seqs_planes(ctx, s);                                 // (synchronises: d_flip and the host offsets outlive their copies)
-    if (st != PBA_OK) return st;
-    guard.p = nullptr;
-    *out = s;
+    PBA_TRY(seqs_finish(ctx, s, [&] { return revcomp_enqueue(ctx, src, s, flip ? d_flip.as<uint8_t>() : nullptr, ctx->stream); }));
+    *out = g.release();
     return PBA_OK;
 }
 

@@ -16,6 +16,7 @@
 
 #include <algorithm>
 #include <functional>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -24,6 +25,7 @@
 #include "dev_common.h"
 #include "pba.h"
 #include "seed_index.h"
+#include "seq_layout.h"
 
 #define PBA_INTERNAL __attribute__((visibility("hidden")))
 // a kernel that takes more than the default 64 KB of dynamic LDS; every translation unit does this once for the kernels
@@ -64,7 +66,6 @@ struct pba_ctx {
     char err[512];
 };
 
-static const size_t kPlaneSlack = 64;           // zero words before the first and after the last sequence of a bit plane
 struct pba_seqs {
     pba_ctx *ctx;
     uint32_t n, max_len;
@@ -82,6 +83,12 @@ struct pba_seqs {
     bool borrowed;           // the arrays belong to a stream's slot (pba_stream.hip): pba_seqs_destroy leaves the set alone, the stream frees it
     SeqSetDev dev() const { return SeqSetDev{d_packed, d_off, d_len, d_planes + 2 * kPlaneSlack, d_poff}; }
 };
+// a set of n sequences with nothing on the device yet: every other field is zero, h_off / h_len hold n + 1 zeros
+static inline pba_seqs *seqs_new(pba_ctx *ctx, uint32_t n) {
+    pba_seqs *s = new (std::nothrow) pba_seqs();
+    if (s) { s->ctx = ctx; s->n = n; s->h_off.resize((size_t)n + 1); s->h_len.resize((size_t)n + 1); }
+    return s;
+}
 
 struct pba_index {
     pba_ctx *ctx;
@@ -121,10 +128,7 @@ static inline int ctx_fail_as(pba_ctx *ctx, int st, const char *who, const char 
 #define PBA_TRY(call) do { const int rc__ = (call); if (rc__ != PBA_OK) return rc__; } while (0)
 
 // engine limits
-static const int kMaxSeqLen = 65000;            // u16 DP costs: D(i,j) <= max(i,j) < 65535
-static const int kRowSweepLdsCap = 96 * 1024;   // LDS bytes one wavefront may take for its band row
-static const size_t kSlack = 1024;              // readable bytes before the first and after the last packed byte
-                                                // (the bit-vector kernel streams a few hundred bases past an accessor)
+static const int kRowSweepLdsCap = 96 * 1024;   // LDS bytes one wavefront may take for its band row (kMaxSeqLen, kSlack: seq_layout.h)
 
 // pool slots
 enum { POOL_OVL_CAND = 0, POOL_OVL_TMP, POOL_OVL_ITEMS, POOL_OVL_REDO, POOL_OVL_REDO_IN, POOL_OVL_OUT, POOL_OVL_SMALL,
@@ -491,6 +495,8 @@ PBA_INTERNAL int spaced_round_subset(pba_ctx *ctx, const pba_index *ix, const pb
 PBA_INTERNAL int locate_core(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, uint32_t target_seq, const pba_seqs *reads,
                              double R, int trials, int min_len, int maxn, int maxm, int kernel, pba_loc_row *rows,
                              pba_loc_stats *stats, int64_t read_base, int64_t nseq_base, hipEvent_t packed);
+// what pba_seqs_destroy does to a set it owns, whoever owns this one: a stream frees its slots' sets with it (pba_core.hip)
+PBA_INTERNAL void seqs_free(pba_seqs *s);
 // k_make_planes over a set's first `words` plane words on `stream`: the arrays of `s` are on the device (pba_core.hip)
 PBA_INTERNAL int planes_enqueue(pba_ctx *ctx, const pba_seqs *s, uint64_t words, hipStream_t stream);
 // k_revcomp of `src` into `dst` on `stream`: dst has pba_seqs_from_text's layout of src's lengths (h_off[0 .. n] on the host,

@@ -9,7 +9,7 @@
 // kernel: ASCII -> packed arena and bit planes in one pass
 // ---------------------------------------------------------------------------------------------
 // A thread owns 32 bases of one sequence: 32 bytes of text (two 16-byte loads), two packed dwords, one pair of plane words.
-// A work item is one wavefront over 2 048 consecutive bases of one sequence; item[s] = work items of the sequences before s
+// A work item is one wavefront over PBA_PP_BASES (seq_layout.h) consecutive bases of one sequence; item[s] = work items of the sequences before s
 // (host prefix, copied with the offsets), so the sequence of an item is found once per wavefront, on wave-uniform values
 // (k_pack_text / k_make_planes bisect once per dword).  The last work item zeroes the slack behind the last sequence.
 // The slot is reused: every dword of the used extent is written -- alignment padding and pad bits as zero, plane bits
@@ -17,7 +17,6 @@
 // RC = true writes rc(s) in the same layout (what pba_seqs_revcomp gives of the forward set) from the same text: the 32 OUTPUT
 // bases 32u .. 32u + 31 of a thread are the complements of text bytes L - 1 - 32u downwards, so its window ends at L - 32u
 // and, in the sequence's last unit, begins before the sequence's first byte -- the bytes there fall under the masks.
-#define PBA_PP_BASES 2048          // bases per work item: 64 lanes x 32
 template <bool RC>
 __global__ void __launch_bounds__(256)
 k_pack_planes(const uint8_t *__restrict__ text, const uint64_t *__restrict__ text_off, const uint64_t *__restrict__ pk_off,
@@ -95,7 +94,6 @@ k_pack_planes(const uint8_t *__restrict__ text, const uint64_t *__restrict__ tex
 // ---------------------------------------------------------------------------------------------
 // host side: the slots, under both kinds of stream
 // ---------------------------------------------------------------------------------------------
-static const uint64_t kRecordSlack = 65536;      // zero bytes behind a binary read file (pba_seqs_from_records)
 static const size_t kTextFront = 64;             // staging bytes in front of the text: k_pack_planes<true> begins up to 31 bytes early
 
 struct StreamSlot {
@@ -164,18 +162,9 @@ static void core_free(StreamCore &c) {
             if (h) (void)hipHostFree(h);
         for (void *d : {(void *)sl.d_text_alloc, (void *)sl.d_toff, (void *)sl.d_item, (void *)sl.d_bad})
             if (d) (void)hipFree(d);
-        if (sl.rc) {                           // (len / poff belong to the forward set)
-            pba_seqs *q = sl.rc;
-            for (void *d : {(void *)q->d_alloc, (void *)q->d_planes, (void *)q->d_off})
-                if (d) (void)hipFree(d);
-            delete q;
-        }
-        if (sl.set) {
-            pba_seqs *q = sl.set;
-            for (void *d : {(void *)q->d_alloc, (void *)q->d_planes, (void *)q->d_off, (void *)q->d_len, (void *)q->d_poff})
-                if (d) (void)hipFree(d);
-            delete q;
-        }
+        if (sl.rc) sl.rc->d_len = nullptr, sl.rc->d_poff = nullptr;      // (len / poff belong to the forward set)
+        seqs_free(sl.rc);
+        seqs_free(sl.set);
         for (hipEvent_t e : {sl.ev_begin, sl.ev_h2d, sl.ev_pack})
             if (e) (void)hipEventDestroy(e);
     }
@@ -194,11 +183,10 @@ template <class T> static bool device(T **p, size_t count) {
 // a borrowed set over an arena of `arena` bytes and the slot's planes, both zeroed once (the slack in front of the arena and
 // of the planes is never written again)
 static pba_seqs *set_alloc(StreamCore &c, pba_seqs **at, size_t arena, size_t nr) {
-    pba_seqs *q = new (std::nothrow) pba_seqs();
+    pba_seqs *q = seqs_new(c.ctx, c.slot_reads);      // (h_off / h_len of every batch stay within these nr entries)
     if (!q) return nullptr;
     *at = q;
-    q->ctx = c.ctx; q->borrowed = true;
-    q->h_off.reserve(nr); q->h_len.reserve(nr);
+    q->n = 0; q->borrowed = true;
     const size_t planes = (c.plane_cap + 2 * kPlaneSlack) * 2 * sizeof(uint32_t);
     if (!device(&q->d_alloc, arena) || !device(&q->d_planes, planes / sizeof(uint32_t)) || !device(&q->d_off, nr)) return nullptr;
     q->d_packed = q->d_alloc + kSlack;
@@ -207,7 +195,8 @@ static pba_seqs *set_alloc(StreamCore &c, pba_seqs **at, size_t arena, size_t nr
 }
 
 static bool slot_alloc(StreamCore &c, StreamSlot &sl) {
-    const size_t nr = (size_t)c.slot_reads + 1, trail = c.form == PBA_STREAM_RECORDS ? kRecordSlack + kSlack : kSlack;
+    const size_t nr = (size_t)c.slot_reads + 1;      // (a records slot keeps kSlack more behind the record slack: core_submit zeroes both)
+    const size_t arena = c.form == PBA_STREAM_RECORDS ? arena_bytes(ARENA_RECORDS, c.pk_cap) + kSlack : arena_bytes(ARENA_TEXT, c.pk_cap);
     const bool text = c.form == PBA_STREAM_TEXT;
     if (!pinned(&sl.h_bytes, c.slot_bytes) || !pinned(&sl.h_offs, std::max<size_t>(nr, 3)) || !pinned(&sl.h_off, nr) ||
         !pinned(&sl.h_poff, nr) || !pinned(&sl.h_len, nr) || !pinned(&sl.h_item, nr) || !pinned(&sl.h_bad, 1))
@@ -215,10 +204,10 @@ static bool slot_alloc(StreamCore &c, StreamSlot &sl) {
     if (c.rc && !text && !pinned(&sl.h_roff, nr)) return false;
     if (text && (!device(&sl.d_text_alloc, kTextFront + c.slot_bytes + 64) || !device(&sl.d_toff, nr) || !device(&sl.d_item, nr))) return false;
     if (!device(&sl.d_bad, 1)) return false;
-    pba_seqs *q = set_alloc(c, &sl.set, kSlack + c.pk_cap + trail, nr);
+    pba_seqs *q = set_alloc(c, &sl.set, arena, nr);
     if (!q || !device(&q->d_len, nr) || !device(&q->d_poff, nr)) return false;
     if (c.rc) {
-        pba_seqs *r = set_alloc(c, &sl.rc, kSlack + c.rc_cap + kSlack, nr);
+        pba_seqs *r = set_alloc(c, &sl.rc, arena_bytes(ARENA_TEXT, c.rc_cap), nr);
         if (!r) return false;
         r->d_len = q->d_len; r->d_poff = q->d_poff;
     }
@@ -234,15 +223,8 @@ static bool slot_alloc(StreamCore &c, StreamSlot &sl) {
 static int core_create(StreamCore &c, pba_ctx *ctx, const char *name, int form, int min_len, bool rc, uint64_t slot_bytes,
                        uint32_t slot_reads) {
     c.ctx = ctx; c.name = name; c.form = form; c.min_len = min_len; c.rc = rc; c.slot_bytes = slot_bytes; c.slot_reads = slot_reads;
-    if (form == PBA_STREAM_TEXT) {         // every read rounds up to 16 packed bytes and to one plane word
-        c.pk_cap = ((slot_bytes + 3) / 4 + 16ull * slot_reads + 15) & ~15ull;
-        c.rc_cap = c.pk_cap;
-        c.plane_cap = slot_bytes / 32 + slot_reads + 1;
-    } else {                               // the file is the arena; four bases per payload byte
-        c.pk_cap = (slot_bytes + 15) & ~15ull;
-        c.rc_cap = (slot_bytes + 16ull * slot_reads + 15) & ~15ull;      // (rc: every payload rounds up to 16 bytes)
-        c.plane_cap = slot_bytes / 8 + slot_reads + 1;
-    }
+    const SlotCaps caps = slot_caps(form == PBA_STREAM_TEXT, slot_bytes, slot_reads, rc);
+    c.pk_cap = caps.pk_cap; c.rc_cap = caps.rc_cap; c.plane_cap = caps.plane_cap;
     bool ok = hipStreamCreateWithFlags(&c.copy, hipStreamNonBlocking) == hipSuccess;
     ok = ok && hipEventCreate(&c.ev_loc0) == hipSuccess && hipEventCreate(&c.ev_loc1) == hipSuccess;
     ok = ok && slot_alloc(c, c.slot[0]) && slot_alloc(c, c.slot[1]);
@@ -251,55 +233,44 @@ static int core_create(StreamCore &c, pba_ctx *ctx, const char *name, int form, 
     return ok ? PBA_OK : PBA_E_NOMEM;
 }
 
-// the host half of a text batch: layout of pba_seqs_from_text (seqs_pack) plus the work-item prefix of k_pack_planes
+// the host half of a text batch: the text layout of seq_layout.h with the work-item prefix of k_pack_planes
 static int plan_text(StreamCore &c, StreamSlot &sl, uint32_t n, uint64_t *pk_total, uint64_t *words, uint32_t *items) {
     if (n > c.slot_reads) return core_fail(c, PBA_E_TOOLONG, "submit", "more reads than slot_reads");
     const uint64_t *to = sl.h_offs;
     for (uint32_t i = 0; i < n; ++i)
         if (to[i + 1] < to[i]) return core_fail(c, PBA_E_INVALID, "submit", "offsets must be non-decreasing");
     if (to[n] > c.slot_bytes) return core_fail(c, PBA_E_TOOLONG, "submit", "more bytes than slot_bytes");
-    uint64_t pk = 0, w = 0, it = 0;
-    uint32_t max_len = 0;
     for (uint32_t i = 0; i < n; ++i) {
         const uint64_t L = to[i + 1] - to[i];
         if (L > (uint64_t)kMaxSeqLen) return core_fail(c, PBA_E_TOOLONG, "submit", "read longer than the engine limit");
-        sl.h_off[i] = pk; sl.h_poff[i] = w; sl.h_len[i] = (uint32_t)L; sl.h_item[i] = (uint32_t)it;
-        max_len = std::max(max_len, (uint32_t)L);
-        pk += ((L + 3) / 4 + 15) & ~15ull;
-        w += (L + 31) / 32;
-        it += (L + PBA_PP_BASES - 1) / PBA_PP_BASES;
+        sl.h_len[i] = (uint32_t)L;
     }
-    sl.h_off[n] = pk; sl.h_poff[n] = w; sl.h_len[n] = 0; sl.h_item[n] = (uint32_t)it;
-    sl.set->max_len = max_len;
-    *pk_total = pk; *words = w; *items = (uint32_t)it;
+    sl.h_len[n] = 0;
+    const SeqTotals t = seq_layout(sl.h_len, n, sl.h_off, sl.h_poff, sl.h_item);
+    sl.set->max_len = t.max_len;
+    *pk_total = t.packed; *words = t.words; *items = (uint32_t)t.items;
     return PBA_OK;
 }
 
-// ... of a binary read file: pba_seqs_from_records' walk; the file is the arena (rc: pba_seqs_revcomp's layout beside it)
+// ... of a binary read file: pba_seqs_from_records' walk; the file is the arena (rc: the text layout of the same lengths beside it)
 static int plan_records(StreamCore &c, StreamSlot &sl, uint32_t *n_out, uint64_t *pk_total, uint64_t *rc_total, uint64_t *words) {
     const uint64_t file_len = sl.h_offs[0];
     if (file_len > c.slot_bytes) return core_fail(c, PBA_E_TOOLONG, "submit", "more bytes than slot_bytes");
     const uint32_t min_excl = (uint32_t)sl.h_offs[1], max_excl = (uint32_t)sl.h_offs[2];
     const size_t kept = pba_open_binary(sl.h_bytes, file_len, min_excl, max_excl, sl.h_off, c.slot_reads, nullptr);
     if (kept > c.slot_reads) return core_fail(c, PBA_E_TOOLONG, "submit", "more reads than slot_reads");
-    uint64_t w = 0, rpk = 0;
-    uint32_t max_len = 0;
     for (size_t i = 0; i < kept; ++i) {
         const uint64_t rec = sl.h_off[i];
         uint32_t L;
         memcpy(&L, sl.h_bytes + rec, 4);
         if (rec + 4 + ((uint64_t)L + 3) / 4 > file_len) return core_fail(c, PBA_E_INVALID, "submit", "truncated record");
         if (L > (uint32_t)kMaxSeqLen) return core_fail(c, PBA_E_TOOLONG, "submit", "read longer than the engine limit");
-        sl.h_off[i] = rec + 4; sl.h_poff[i] = w; sl.h_len[i] = L;      // payload follows the u32 length (dna_seq.h:119-121)
-        if (c.rc) sl.h_roff[i] = rpk;
-        max_len = std::max(max_len, L);
-        w += ((uint64_t)L + 31) / 32;
-        rpk += (((uint64_t)L + 3) / 4 + 15) & ~15ull;
+        sl.h_off[i] = rec + 4; sl.h_len[i] = L;      // payload follows the u32 length (dna_seq.h:119-121)
     }
-    sl.h_off[kept] = file_len; sl.h_poff[kept] = w; sl.h_len[kept] = 0;
-    if (c.rc) sl.h_roff[kept] = rpk;
-    sl.set->max_len = max_len;
-    *n_out = (uint32_t)kept; *pk_total = file_len; *rc_total = rpk; *words = w;
+    sl.h_off[kept] = file_len; sl.h_len[kept] = 0;
+    const SeqTotals t = seq_layout(sl.h_len, kept, c.rc ? sl.h_roff : nullptr, sl.h_poff, nullptr);
+    sl.set->max_len = t.max_len;
+    *n_out = (uint32_t)kept; *pk_total = file_len; *rc_total = t.packed; *words = t.words;
     return PBA_OK;
 }
 
