@@ -117,6 +117,12 @@ __device__ __forceinline__ uint32_t or_of_and(uint32_t a, uint32_t b, uint32_t c
     asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xf8" : "=v"(d) : "v"(a), "v"(b), "v"(c));   // 0xF0 | (0xCC & 0xAA)
     return d;
 }
+// the same with c wave-uniform, from a scalar register (a VOP3 instruction takes one)
+__device__ __forceinline__ uint32_t or_of_and_s(uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t d;
+    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xf8" : "=v"(d) : "v"(a), "v"(b), "s"(c));
+    return d;
+}
 // ~a & ~(b ^ c): the match mask of a block from one xor and one bitop3 (left to itself the compiler rebuilds
 // Eq & Pv from the two xors separately, one instruction more per block)
 __device__ __forceinline__ uint32_t eq_mask(uint32_t a, uint32_t b, uint32_t c) {
@@ -138,7 +144,8 @@ __device__ __forceinline__ uint32_t bit_mask(uint32_t x, int k) {
 // ~2.5 cycles per SIMD, shifts, bfe, alignbit, lshl_or, add3, addc and DPP moves every ~4.3): a Myers block is
 // 9 full-rate ops + 3 v_addc_co (the carries are the horizontal deltas entering / leaving the block, kept as lane
 // masks in SGPR pairs), and the lane-to-lane hand-off of those deltas is a SCALAR rotate of the two masks -- no
-// DPP, no VALU.  The diagonal's D0 bits are collected with one bitop3 per block and a rotating one-hot; text
+// DPP, no VALU.  The diagonal's D0 bits are collected with one bitop3 (in the diagonal's block only, at one or two
+// blocks per lane) under a wave-uniform one-hot that a scalar shift advances; text
 // elements come from two 32-step bit-plane registers.  Everything rare is scheduled: the events of the sweep fall at
 // steps known in advance, kept as wave-uniform timers, and the step loop runs from one to the next without a test.
 //
@@ -214,6 +221,19 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     int T_diag = 1, s_dg = 0;
     int T_seg = min(32, m) + 1, s_sg = 0;
     int s_next = 1;                              // the earliest of the five
+    // Where the diagonal is: at any step it is in one block of one lane, or in none (the one-step gap between two
+    // superblocks, and past row m).  Both are wave-uniform and belong to the schedule: `one` is the one-hot of the diagonal
+    // cell's bit in its block's word (0: in no block), qd that block.  The diagonal-entry event and segment_done set them; the
+    // step shifts `one` on the scalar side.
+    uint32_t one = 0;
+    int qd = 0;
+    // Not in the BAIL form (the all-vs-all walk): its candidates are mostly false ones that die within their first segments,
+    // on the ramp, where a window opens at every step and a stretch is one step long -- there the scalar one-hot's two
+    // instructions per stretch (read in front, written back behind) cost more than the step saves (measured: walk + 4 to 6 %,
+    // DESIGN.md 4.3 round 8).  That form keeps the one-hot in the diagonal's lane, advanced by a vector add: dmw.
+    constexpr bool LANE_HOT = BAIL;
+    uint32_t dmw = 0;                            // LANE_HOT: bit of the diagonal cell in its block's word (0: not in this lane)
+    (void)dmw; (void)one; (void)qd;
 
     uint32_t wl = 0, wh = 0;                     // text bit planes: bit k = low / high bit of the element of step tb+k
     // wave-uniform, in scalar registers: the running D(i,i) at the end of the last segment judged (segments end in row
@@ -225,7 +245,6 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     // the superblock): written once per superblock that reaches the last column, read once at the end -- as registers
     // they were live through the whole step loop, and at 64 registers per lane the compiler spilled them to scratch memory.
     fin[2 * NB * PBA_WAVE + lane] = 0xFFFFFFFFu;
-    uint32_t dmw = 0;                            // one-hot: bit of the diagonal cell in its block's word (0: not in this lane)
     uint64_t hp_last = ~0ull, hn_last = 0ull;    // lane masks: delta +1 / -1 leaving each lane's last block in the previous step
     // lanes whose first block still receives the lane above's hout (the others see "+1 per column"): lane s & 63 from the
     // step it takes superblock s (0 < s < S) up to the step before the lane above closes
@@ -238,7 +257,10 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     // against seq_aligner.h:185 and carry the diagonal score on.  Judged on the scalar side: s, i, the running score and
     // the verdict are wave-uniform, and the one datum a lane holds -- the segment's word, acc[q] of lane s & 63 -- comes
     // over with one v_readlane.  The FP64 comparisons run on uniform operands (the scalar unit has no FP64) and their
-    // result is a scalar condition.  What is left for the lane: its acc[] cleared and its one-hot re-armed.
+    // result is a scalar condition.  What is left for the lane: its acc[] cleared.  The one-hot is re-armed on the scalar side.
+    // Every lane ORs D0 bits into its acc[qd] under the wave's one-hot, whether the diagonal is in it or not; only acc[q] of
+    // lane s & 63 is ever read, here.  That is harmless only because a lane's acc[] is cleared when the diagonal enters the
+    // lane (the diagonal-entry event) and at every segment end (below): both clears must stay.
     // Returns 0, or the first failing row (PBA_BV_BAIL: the sweep is given up); a sweep ends at its first failure, so
     // no segment is judged after one.
     auto segment_done = [&](int s, int i) -> int {
@@ -267,8 +289,10 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
         if (lane == L) {
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) acc[nb] = 0; // the next block's word starts clean
-            dmw = (i == m || rr == RB - 1) ? 0u : 1u;    // the diagonal leaves this lane's rows, or enters its next block at bit 0
+            if constexpr (LANE_HOT) dmw = (i == m || rr == RB - 1) ? 0u : 1u;   // (as `one` below)
         }
+        one = (i == m || rr == RB - 1) ? 0u : 1u;        // the diagonal leaves this lane's rows, or enters its next block at bit 0
+        qd = (q + 1) % NB;
         return fr;
     };
 
@@ -315,9 +339,10 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
         }                                                                             \
         if (DIAG && t == T_diag) {                                                    \
             if (lane == (s_dg & (PBA_WAVE - 1))) {                                    \
-                dmw = 1u;                                                             \
                 _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) acc[nb] = 0;        \
+                if constexpr (LANE_HOT) dmw = 1u;                                      \
             }                                                                         \
+            one = 1u; qd = 0;                                                         \
             s_dg += 1;                                                                \
             T_diag = s_dg * RB < m ? s_dg * (RB + 1) + 1 : INT_MAX;                   \
         }                                                                             \
@@ -360,13 +385,41 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     bool st_on = false;          // TRACE: some lane of this lane's 16-lane group is inside its window (updated at events)
     (void)st_on;
 #define PBA_BV_TRP() (tr_lane + (size_t)(t - 1) * (NB * 64))
+    // One stretch of phase 1: plain steps from k up to kstop.  QD: the block the diagonal is in, as a constant (its word
+    // alone collects), or -1: every block's word collects (garbage in all but the diagonal's, cleared at the segment's end).
+    // LANE_HOT: every block's word collects under the lane's own one-hot.
+#define PBA_BV_STRETCH1(QD)                                                          \
+        do {                                                                         \
+        const int t = tb + k;                                                        \
+        (void)t;                                                                     \
+        const uint32_t clo = bit_mask(wl, k), chi = bit_mask(wh, k);                 \
+        PBA_BV_HIN();                                                                \
+        _Pragma("unroll")                                                            \
+        for (int nb = 0; nb < NB; ++nb) {                                            \
+            uint32_t d0, php, mhp, eq;                                               \
+            PBA_BV_BLOCK(nb, php, mhp, d0, eq);                                      \
+            (void)php; (void)mhp; (void)eq;                                          \
+            if constexpr (TRACE == 1) {      /* whole 128-byte lines only: a 16-lane group stores when any of its lanes is */ \
+                if (st_on)                   /* inside its window (masking lane by lane was measured 1.5x SLOWER: partial lines) */ \
+                    PBA_BV_TRP()[nb * 64] = make_uint2(eq | ~d0, swap_roles ? Pv[nb] : php); \
+            }                                                                        \
+            /* keep the diagonal cell's D0 bit: in every lane, under the wave's one-hot (what a lane without the diagonal \
+               collects is cleared when the diagonal enters it) */                   \
+            if constexpr (LANE_HOT) acc[nb] = or_of_and(acc[nb], d0, dmw); else       \
+            if ((QD) < 0 || nb == (QD)) acc[nb] = or_of_and_s(acc[nb], d0, oh);      \
+        }                                                                            \
+        hp_last = hp; hn_last = hn;                                                  \
+        /* next row of the block, on the scalar side; re-armed every 32 rows.  (LANE_HOT: a full-rate add the compiler cannot \
+           turn back into the slower shift) */                                       \
+        if constexpr (LANE_HOT) asm("v_add_u32 %0, %1, %1" : "=v"(dmw) : "v"(dmw)); else oh <<= 1; \
+        } while (++k < kstop)
     // ------------------------------------------------------------------ phase 1: down to cell (m,m)
     // The step loop is cut into chunks of 32 steps (one pair of text planes): the scalar unit is shared by the CU's
     // four SIMDs, so every SALU instruction of the step costs four issue cycles -- the inner loop carries nothing
     // but its counter.  Everything in it is wave-uniform and stays in SGPRs.
     // Within a chunk the steps run in stretches that end at the next scheduled event: the stretch's bound is its loop
-    // counter, and its body is the block updates, the hand-off rotate and the one-hot add -- no compare, no branch on a
-    // lane mask.
+    // counter, and its body is the block updates, the hand-off rotate and the one-hot's scalar shift -- no compare, no
+    // branch on a lane mask.
     for (int tbv = 1; tbv <= t1; tbv += 32) {
         const int tb = __builtin_amdgcn_readfirstlane(tbv);   // (the early exit below makes the compiler treat tbv as divergent)
         if constexpr (TRACE == 2) bv_ckpt_store<NB>(tr, tb, lane, Pv, Mv, s_cur, opened, hp_last, hn_last);
@@ -383,28 +436,20 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
             if (seg_fail) { fail_row = seg_fail; kend = k + 1; }
         }
         const int kstop = min(kend, s_next - tb);
-        do {
-        const int t = tb + k;
-        (void)t;
-        const uint32_t clo = bit_mask(wl, k), chi = bit_mask(wh, k);
-        PBA_BV_HIN();
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            uint32_t d0, php, mhp, eq;
-            PBA_BV_BLOCK(nb, php, mhp, d0, eq);
-            (void)php; (void)mhp; (void)eq;
-            if constexpr (TRACE == 1) {      // whole 128-byte lines only: a 16-lane group stores when any of its lanes is
-                if (st_on)                   // inside its window (masking lane by lane was measured 1.5x SLOWER: partial lines)
-                    PBA_BV_TRP()[nb * 64] = make_uint2(eq | ~d0, swap_roles ? Pv[nb] : php);
-            }
-            // keep the diagonal cell's D0 bit (garbage while the diagonal is in another block: the word is
-            // cleared when the diagonal enters)
-            acc[nb] = or_of_and(acc[nb], d0, dmw);
+        // The one-hot goes through the stretch in a local read with v_readfirstlane: `one` is set inside a loop that a
+        // failing segment leaves early, so the compiler would carry it in a vector register and shift it there (the
+        // same effect as for tbv and score).  qd is constant within a stretch (a segment end is a scheduled event), so with
+        // two blocks the stretch exists once per block, behind a scalar branch: no word of the other block is touched.
+        // Not in the streamed trace form, where the second copy costs k_trace_pairs<2, false> a wave per SIMD, and not for
+        // NB >= 3, where the copies cost registers or scratch in every kernel: there every block's
+        // word collects under the scalar one-hot.
+        uint32_t oh = LANE_HOT ? 0u : __builtin_amdgcn_readfirstlane(one);
+        if constexpr (NB == 2 && TRACE != 1 && !LANE_HOT) {
+            if (__builtin_amdgcn_readfirstlane(qd) == 0) { PBA_BV_STRETCH1(0); } else { PBA_BV_STRETCH1(1); }
+        } else {
+            PBA_BV_STRETCH1(NB == 1 ? 0 : -1);
         }
-        hp_last = hp; hn_last = hn;
-        asm("v_add_u32 %0, %1, %1" : "=v"(dmw) : "v"(dmw));   // next row of the block: a full-rate add (left to itself the compiler
-                                                               // turns dmw += dmw into the slower shift); segment_done re-arms it every 32 rows
-        } while (++k < kstop);
+        if constexpr (!LANE_HOT) one = oh;
         }
     }
     if (fail_row == 0) fail_row = segment_done(s_m, m);   // the segment that ended in the last step: the one holding row m
@@ -448,6 +493,7 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
         }
         tb += kend - k0;
     }
+#undef PBA_BV_STRETCH1
 #undef PBA_BV_BLOCK
 #undef PBA_BV_TRP
 #undef PBA_BV_HIN
