@@ -95,7 +95,11 @@ int pba_ctx_sync(pba_ctx *ctx);
  * gigabytes anew costs more than the kernels that use them).  pba_ctx_trim gives them back to the device. */
 int pba_ctx_trim(pba_ctx *ctx);
 /* HIP-event timings (on the ctx's stream) of the most recent pba_index_build / pba_locate /
- * pba_align_batch / pba_spaced_round on this ctx: measurement support for bench.py */
+ * pba_align_batch / pba_spaced_round on this ctx: measurement support for bench.py.
+ * The all-vs-all entry points (pba_overlap_all*, pba_overlap_strands*: the profile of the last pass) fill the four ring
+ * fields for their walk and leave the timings alone: nb_first / n_first = ring and work items of the call's first walk
+ * launch (0 = row sweep, or no launch at all), nb_redo / n_redo = ring and runs of the last launch that resumed parked
+ * (target, query) runs (0 = none). */
 typedef struct {
     float index_ms;        /* pba_index_build: first kernel to last kernel */
     float align_ms;        /* first launch of the aligning kernel (all pairs / reads) */

@@ -270,6 +270,7 @@ struct OvlCall {
     uint64_t cap = 0, dev_cap = 0, redo_cap = 0; // rows the caller takes, the device list holds, runs the redo list holds
     uint64_t n_items = 0;
     int nb_mid = 0;                              // the widest ring between the narrow one and the reference band's (0: none)
+    bool launched = false;                       // the walk has had its first launch (ctx->prof names it)
     pba_overlap_stats st;
 
     unsigned long long *cnt(OvlCnt k) const { return d_cnt.as<unsigned long long>() + k; }
@@ -506,6 +507,11 @@ static int ovl_walk_once(OvlCall &c, int nb, const uint2 *items, uint32_t n_item
     HIPCHK(c.cnt_clear(CNT_PARKED, 1));
     PBA_DISPATCH_NB(nb, PBA_OVL_WALK);
     HIPCHK(hipGetLastError());
+    // the ctx profile of the most recent walk: its first launch, and the last one that resumed parked runs
+    pba_profile &pr = ctx->prof;
+    if (redo_in) { pr.nb_redo = (uint32_t)nb; pr.n_redo = n_items; }
+    else if (!c.launched) { pr.nb_first = (uint32_t)nb; pr.n_first = n_items; }
+    c.launched = true;
     return PBA_OK;
 }
 
@@ -639,6 +645,7 @@ static int overlap_table(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *qs
     c.ctx = ctx; c.reads = reads; c.qset = qset; c.t_lo = t_lo; c.nt = t_hi - t_lo; c.tab = tab; c.T = tab_dev(tab); c.cap = cap;
     c.hooks = ovl_hooks_from_env();
     memset(&c.st, 0, sizeof c.st);
+    ctx->prof.nb_first = ctx->prof.n_first = ctx->prof.nb_redo = ctx->prof.n_redo = 0;
     c.st.n_probe_entries = tab->n_entries;
     c.st.table_ms = tab->build_ms;
     const uint32_t nt = c.nt;

@@ -92,13 +92,15 @@ def seedmap(text: bytes, mask: int):
     return keys, pos
 
 
-def candidates(texts, qtexts, mask: int, max_trial: int, overlap_min: int, table=None):
-    """([(target, query, jd, k, pos)] in try order -- k: the position's place in its key's list --, n_match)"""
+def candidates(texts, qtexts, mask: int, max_trial: int, overlap_min: int, table=None, t_lo: int = 0, t_hi=None):
+    """([(target, query, jd, k, pos)] in try order -- k: the position's place in its key's list --, n_match) of the targets
+    [t_lo, t_hi); the queries are the whole set, the target's own read left out by its index in the set"""
     qtexts = texts if qtexts is None else qtexts
     table = table or ProbeTable(qtexts, mask, max_trial)
     pkeys = np.array(sorted(table.by_key), np.uint32)
     out, n_match = [], 0
-    for t, text in enumerate(texts):
+    for t in range(t_lo, len(texts) if t_hi is None else t_hi):
+        text = texts[t]
         keys, pos = seedmap(text, mask)
         if not keys.size or not pkeys.size:
             continue
@@ -122,13 +124,15 @@ def sides(text: bytes, qtext: bytes, jd: int, p: int):
     return text[p:], qtext[j:]
 
 
-def walk_composition(oracle, texts, qtexts, R: float, mask: int, max_trial: int, overlap_min: int, cache=None):
+def walk_composition(oracle, texts, qtexts, R: float, mask: int, max_trial: int, overlap_min: int, cache=None, t_lo: int = 0,
+                     t_hi=None):
     """What the all-vs-all call has to answer, from the enumeration and the oracle's verdict per candidate alone:
     dict(n_match, n_gate, n_pre, n_listed, rows = [(target, query, j, dir, ref_pos, cost, matlen_a, matlen_b)], pairs,
-    pairs_by = {(target, query): pairs}, cands = [dict(t, q, jd, k, p, x, ok, pre, tried)] in try order, probes = entries)."""
+    pairs_by = {(target, query): pairs}, cands = [dict(t, q, jd, k, p, x, ok, pre, tried)] in try order, probes = entries).
+    t_lo, t_hi: the call's target range (the probe table is that of every query whatever the range)."""
     qtexts = texts if qtexts is None else qtexts
     table = ProbeTable(qtexts, mask, max_trial)
-    cands, n_match = candidates(texts, qtexts, mask, max_trial, overlap_min, table)
+    cands, n_match = candidates(texts, qtexts, mask, max_trial, overlap_min, table, t_lo, t_hi)
     cache = {} if cache is None else cache
     rows, pairs_by, out, n_pre, done = [], {}, [], 0, None
     for t, q, jd, k, p in cands:
@@ -151,14 +155,15 @@ def walk_composition(oracle, texts, qtexts, R: float, mask: int, max_trial: int,
                 pairs=sum(pairs_by.values()), pairs_by=pairs_by, cands=out, n_probe_entries=table.n_entries)
 
 
-def oracle_composition(oracle, texts, qtexts, R: float, mask: int, max_trial: int, overlap_min: int, text2bin):
-    """(rows, pairs_by) of the oracle's locked spaced_seed round of every target against the file of the queries, the target's
-    own read left out: rows and pairs_by as walk_composition's"""
+def oracle_composition(oracle, texts, qtexts, R: float, mask: int, max_trial: int, overlap_min: int, text2bin, t_lo: int = 0,
+                       t_hi=None):
+    """(rows, pairs_by) of the oracle's locked spaced_seed round of every target of [t_lo, t_hi) against the file of the
+    queries, the target's own read left out: rows and pairs_by as walk_composition's"""
     qtexts = texts if qtexts is None else qtexts
     file = b"".join(text2bin(t) for t in qtexts)
     offs = np.cumsum([0] + [4 + (len(t) + 3) // 4 for t in qtexts[:-1]]).astype(np.uint64)
     rows, pairs_by = [], {}
-    for t in range(len(texts)):
+    for t in range(t_lo, len(texts) if t_hi is None else t_hi):
         r = oracle.spaced_round(texts[t], mask, R, file, offs, max_trial, overlap_min, buggy=False, nthreads=8)
         for q in range(len(qtexts)):
             if q == t:

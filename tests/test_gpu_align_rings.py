@@ -211,5 +211,5 @@ def test_votes_in_forced_rings(ctx, row):
     assert one.evolve() == many.evolve()
 
 
-# Not covered yet: the all-vs-all walk (pba_overlap_all) picks its rings itself, through nb_mid and the sampled decision, and
-# is compared with the oracle in rings 1 and 2 only (tests/test_gpu_parity.py); forcing its NB = 3, 4, 6, 8 is the next gap.
+# The all-vs-all walk (pba_overlap_all) picks its rings itself, through nb_mid and the sampled decision: its first launch,
+# middle ring and reference band in every plan row are in tests/test_gpu_walk_rings.py (inputs: tests/walk_ring_inputs.py).
