@@ -277,6 +277,42 @@ int pba_align_batch_trace(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, co
                           double R, int maxn, int maxm, int kernel, pba_result *out, uint8_t *ops,
                           const uint64_t *ops_off, int32_t *nedit);
 
+/* Run-length alignments (CIGAR over = X I D).  A run is one 32-bit word, len << 4 | op, op in BAM's numbering; the four
+ * counts are the bases of each kind.  By default a is the CIGAR's query and b its reference: I consumes a only (the
+ * reference's DELETE, seq_aligner.h:170), D consumes b only (its INSERT, seq_aligner.h:167); a MATCH (seq_aligner.h:164) is
+ * `=` where the two elements are equal and X where they are not. */
+#define PBA_CIG_INS 1
+#define PBA_CIG_DEL 2
+#define PBA_CIG_EQ  7
+#define PBA_CIG_X   8
+typedef struct { int32_t n_eq, n_x, n_ins, n_del; } pba_aln_counts;
+#define PBA_CIG_REVERSED   1u   /* runs goal-first (text order of two backward accessors) */
+#define PBA_CIG_B_IS_QUERY 2u   /* I consumes b only, D consumes a only */
+/* Host arithmetic, no ctx: an upper bound on the runs of a successful pair.  After the clip of seq_aligner.h:94-102, with
+ * m = min(len_a, len_b): m > 10 gives 2 * max_dst - 1 (every edit adds at most two runs to the single run of an exact copy,
+ * and a pair that passed the early-failure test at row m, seq_aligner.h:185, costs at most floor(m * R) = max_dst - 1);
+ * m <= 10, where no such test ran, gives len_a + len_b.  0 for a negative length or an R outside (0, 1). */
+uint32_t pba_cigar_bound(int a_len, int b_len, double R);
+/* The alignments of pba_align_batch_trace as runs, made on the device from the traceback walk (no script exists): pair q's
+ * runs go to cigar[cig_off[q] .. ), their number to ncig[q], the bases of each kind to counts[q].  cig_off (n + 1 entries)
+ * must leave at least pba_cigar_bound(a_len, b_len, R) slots per pair, else PBA_E_INVALID.  A pair with rc < 0 has
+ * ncig = 0 and zero counts.  For every other pair n_eq + n_x + n_ins = matlen_a, n_eq + n_x + n_del = matlen_b (I and D
+ * exchanged under PBA_CIG_B_IS_QUERY) and n_x + n_ins + n_del = cost.  Runs are origin-first, the order of edits[], or
+ * goal-first under PBA_CIG_REVERSED.  Bit-vector kernel only: a band too wide for it is PBA_E_TOOLONG.  Sets with bytes
+ * outside ACGT: PBA_E_ALPHABET.  A pair whose runs outgrow its slot (the bound would be wrong) is PBA_E_HIP, text in
+ * pba_ctx_error; nothing is written beyond a slot. */
+int pba_align_batch_cigar(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R,
+                          int maxn, int maxm, uint32_t flags, pba_result *out, uint32_t *cigar, const uint64_t *cig_off,
+                          int32_t *ncig, pba_aln_counts *counts);
+/* Host helpers, no ctx.  The same encoding from a script (pba_align_text_trace, pba_align_batch_trace: origin-first ops) and
+ * the elements of its two accessors in element order (a_elems[k] = element k of a; any bytes; each array holds at least the
+ * elements the script consumes, matlen_a and matlen_b): at most cap runs are written, the number of runs is returned (-1
+ * for a NULL or an op outside 1 .. 3); counts is nullable. */
+int pba_cigar_from_script(const uint8_t *ops, int32_t nedit, const char *a_elems, const char *b_elems, uint32_t flags,
+                          uint32_t *cigar, int32_t cap, pba_aln_counts *counts);
+/* "12=1X3I..." with a terminating NUL; returns the length, 0 if cap is too small (or n == 0: the empty string) */
+int pba_cigar_string(const uint32_t *cigar, int32_t n, char *out, int32_t cap);
+
 /* ------------------------------------------------------------------------ */
 /* Consensus voting and reference growth: the unlocked half of ref_seq      */
 /* (ref_seq.h:25-188 base_vote / vote_box, :207-242 ctor / append / prepend, */
@@ -734,6 +770,45 @@ int pba_map_row_pair(const pba_map_row *row, uint32_t contig_len, uint32_t read_
 int pba_pileup_vote_mapped(pba_ctx *ctx, pba_pileup *p, const pba_seqs *target, const pba_seqs *reads,
                            const pba_seqs *reads_rc /* nullable if no row has strand -1 */, const pba_map_row *rows, uint64_t n,
                            double R, int overlap_min, pba_result *res /* nullable */, uint64_t *n_voted /* nullable */);
+/* ------------------------------------------------------------------------ */
+/* How a mapped read or an overlap aligns: run-length alignments per row,     */
+/* for PAF with a cg:Z: tag (what the reference's visual_align.cpp shows).    */
+/* ------------------------------------------------------------------------ */
+/* Host arithmetic, no ctx: the pair the mapper itself aligned for a found row (locator.cpp:78-82), roles as it had them:
+ *   a_seq = row->read, forward from row->j, rest of the read;  b_seq = row->contig, forward from row->pos, rest of the contig
+ *   each side clipped to the other side's length + ITS max_dst, exactly as align clips it (seq_aligner.h:94-102)
+ * For a strand -1 row a indexes the set of reverse-complemented reads.  The clip never changes which branch of
+ * seq_aligner.h:94 is taken: with b the longer side (len_b >= len_a) it is cut to len_a + max_dst >= len_a, with a the
+ * longer one to len_b + max_dst > len_b, so align on the clipped pair takes the same branch, derives the same max_dst and
+ * clips to the same lengths again.  It is made here because an accessor holds at most 65 000 elements and a contig remainder
+ * is megabases long.  Refusals as pba_map_row_pair's. */
+int pba_map_row_aln_pair(const pba_map_row *row, uint32_t contig_len, uint32_t read_len, double R, pba_pair *out);
+/* The alignments of n pba_map_reads rows as runs: SAM's CIGAR, the read (rc(read) for strand -1) is the query, the contig
+ * forward the reference, runs origin-first.  Rows with found == 0 get no runs (counts and res zeroed, res rc = -1).  Every
+ * other row is re-run in the mapper's own roles (pba_map_row_aln_pair) and IS held to the row's cost, matlen_a and matlen_b:
+ * a disagreement is PBA_E_INVALID with text in pba_ctx_error.  cig_off (n + 1 entries) is always complete and *n_slots the
+ * total; the runs of row k go to cigar[cig_off[k] ..) for the rows, in order, up to the first whose end exceeds cap.  counts
+ * and res (n entries each) are nullable.  The rows go through the device in chunks whose bounded slots
+ * (pba_cigar_bound) stay under a fixed budget (2^28 slots) or, in the _budget form, under max_slots (0 = the default; a
+ * chunk holds at least one row); each chunk's runs are compacted on the device before they are copied.  The answer does not
+ * depend on the cut.  reads_rc may be NULL if no row has strand -1. */
+int pba_map_rows_cigar(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
+                       const pba_map_row *rows, uint64_t n, double R, uint32_t *cigar, uint64_t cap, uint64_t *cig_off,
+                       uint64_t *n_slots, pba_aln_counts *counts, pba_result *res);
+int pba_map_rows_cigar_budget(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
+                              const pba_map_row *rows, uint64_t n, double R, uint32_t *cigar, uint64_t cap, uint64_t *cig_off,
+                              uint64_t *n_slots, pba_aln_counts *counts, pba_result *res, uint64_t max_slots);
+/* The same for pba_strand_overlap rows: the pair is pba_overlap_row_pair's (a = the target), the query read is the CIGAR's
+ * query (PBA_CIG_B_IS_QUERY; for strand -1 its text is rc(q), as the row defines it) and the runs are in the target's
+ * forward order: origin-first for dir +1, goal-first (PBA_CIG_REVERSED) for dir -1.  Held to the row's cost and match
+ * lengths. */
+int pba_overlap_rows_cigar(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, const pba_strand_overlap *rows,
+                           uint64_t n, double R, uint32_t *cigar, uint64_t cap, uint64_t *cig_off, uint64_t *n_slots,
+                           pba_aln_counts *counts, pba_result *res);
+int pba_overlap_rows_cigar_budget(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, const pba_strand_overlap *rows,
+                                  uint64_t n, double R, uint32_t *cigar, uint64_t cap, uint64_t *cig_off, uint64_t *n_slots,
+                                  pba_aln_counts *counts, pba_result *res, uint64_t max_slots);
+
 typedef struct { int32_t contig, n_rows, len_in, len_out; } pba_polish_row;      /* per contig, last round */
 typedef struct {
     int32_t round;                 /* 1-based */

@@ -13,6 +13,8 @@ PBA_INDEX_ALL, PBA_INDEX_HEAD_TAIL = 0, 1
 PBA_KERNEL_AUTO, PBA_KERNEL_ROWSWEEP, PBA_KERNEL_BITVEC = 0, 1, 2
 PBA_A_BACKWARD, PBA_B_BACKWARD = 1, 2
 PBA_STREAM_TEXT, PBA_STREAM_RECORDS = 0, 1
+PBA_CIG_INS, PBA_CIG_DEL, PBA_CIG_EQ, PBA_CIG_X = 1, 2, 7, 8
+PBA_CIG_REVERSED, PBA_CIG_B_IS_QUERY = 1, 2
 
 
 class PbaPair(C.Structure):
@@ -22,6 +24,10 @@ class PbaPair(C.Structure):
 
 class PbaResult(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("rc", "cost", "matlen_a", "matlen_b", "len_a", "len_b", "max_dst", "diag_cost")]
+
+
+class PbaAlnCounts(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_eq", "n_x", "n_ins", "n_del")]
 
 
 class PbaLocRow(C.Structure):
@@ -228,6 +234,17 @@ SYMBOLS = {
     "pba_place_row_pair": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_double, _P]),
     "pba_pileup_vote_placed": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_double, C.c_int, _P, C.POINTER(C.c_uint64)]),
     "pba_layout_consensus": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.c_double, C.c_int, C.c_int, C.c_uint64, C.POINTER(_P), _P, _P]),
+    "pba_cigar_bound": (C.c_uint32, [C.c_int, C.c_int, C.c_double]),
+    "pba_align_batch_cigar": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_double, C.c_int, C.c_int, C.c_uint32, _P, _P, _P, _P, _P]),
+    "pba_cigar_from_script": (C.c_int, [_P, C.c_int32, _P, _P, C.c_uint32, _P, C.c_int32, _P]),
+    "pba_cigar_string": (C.c_int, [_P, C.c_int32, C.c_char_p, C.c_int32]),
+    "pba_map_row_aln_pair": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_double, _P]),
+    "pba_map_rows_cigar": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.c_double, _P, C.c_uint64, _P, C.POINTER(C.c_uint64), _P, _P]),
+    "pba_map_rows_cigar_budget": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.c_double, _P, C.c_uint64, _P, C.POINTER(C.c_uint64), _P, _P,
+                                            C.c_uint64]),
+    "pba_overlap_rows_cigar": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_double, _P, C.c_uint64, _P, C.POINTER(C.c_uint64), _P, _P]),
+    "pba_overlap_rows_cigar_budget": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_double, _P, C.c_uint64, _P, C.POINTER(C.c_uint64), _P, _P,
+                                                C.c_uint64]),
     "pba_strerror": (C.c_char_p, [C.c_int]),
 }
 

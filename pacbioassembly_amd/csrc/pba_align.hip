@@ -3,6 +3,7 @@
 // (PBA_E_NODEVICE / PBA_E_HIP): there is no CPU path behind these entry points.
 #include "pba_host.h"
 #include "align_bvtrace.h"
+#include "align_cigar.h"
 
 // ids (nullable): the subset of pairs / reads to process (second, full-band launch)
 template <int NB>
@@ -133,6 +134,42 @@ k_vote_pairs(SeqSetDev A, SeqSetDev B, const pba_pair *pairs, const uint32_t *id
                                        cfg.row_cap, mine, cap_words, overlap_min, sink, o, s_tile[wave]))
             sink.finish();
         store_result(out + q, o);
+    }
+}
+
+// The same sweep and walk once more, the path run-length encoded on its way out (align_cigar.h: CigarSink): pair q's runs go
+// to cig[cig_off[q] ..), their number to ncig[q], the bases of each kind to counts[q].  Checkpoint form only.  The
+// wavefront's goal-first temporary sits behind cap_words, as OpSink's does: wave_words - cap_words runs.
+// pair_flags (nullable): PBA_CIG_* per pair, else `flags` for all of them.
+template <int NB>
+__global__ void __launch_bounds__(PBA_WAVE * 4, NB <= 4 ? (NB <= 2 ? PBA_TR_OCC12 : 4) : 2)
+k_cigar_pairs(SeqSetDev A, SeqSetDev B, const pba_pair *pairs, const uint32_t *ids, uint32_t n, AlignCfg cfg, pba_result *out,
+              uint32_t *scratch, uint64_t wave_words, uint64_t cap_words, uint32_t *cig, const uint64_t *cig_off, int32_t *ncig,
+              pba_aln_counts *counts, const uint32_t *pair_flags, uint32_t flags, uint32_t *queue) {
+    extern __shared__ __align__(16) uint8_t lds_all[];
+    __shared__ uint2 s_tile[4][PBA_BV_TILE_WORDS(NB)];
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / PBA_WAVE));
+    uint8_t *lds = lds_all + (size_t)wave * cfg.row_cap * 2;
+    uint32_t *mine = scratch + ((uint64_t)blockIdx.x * 4 + wave) * wave_words;
+    for (;;) {
+        const uint32_t slot = next_slot(queue);
+        if (slot >= n) break;
+        const uint32_t q = ids ? ids[slot] : slot;
+        const pba_pair pr = pairs[q];
+        const PackedFetch fa = fetch_of(A, pr.a_seq, pr.a_pos, (pr.flags & PBA_A_BACKWARD) ? -1 : 1);
+        const PackedFetch fb = fetch_of(B, pr.b_seq, pr.b_pos, (pr.flags & PBA_B_BACKWARD) ? -1 : 1);
+        const uint32_t fl = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pair_flags ? pair_flags[q] : flags));
+        AlnOut o;
+        int nr = 0;
+        const uint64_t o0 = cig_off[q], o1 = cig_off[q + 1];
+        CigarSink sink;
+        sink.init(fa, fb, mine + cap_words, (uint32_t)(wave_words - cap_words), (fl & PBA_CIG_B_IS_QUERY) != 0);
+        if (align_bitvec_trace<NB, true>(fa, pr.a_len, fb, pr.b_len, cfg.R, cfg.maxn, cfg.maxm, cfg.full_band != 0, (uint16_t *)lds,
+                                         cfg.row_cap, mine, cap_words, 0, sink, o, s_tile[wave]))
+            nr = sink.finish(cig + o0, o1 - o0, (fl & PBA_CIG_REVERSED) != 0, counts + q);
+        else if ((threadIdx.x & (PBA_WAVE - 1)) == 0) counts[q] = pba_aln_counts{0, 0, 0, 0};
+        store_result(out + q, o);
+        if ((threadIdx.x & (PBA_WAVE - 1)) == 0) ncig[q] = nr;
     }
 }
 
@@ -270,6 +307,7 @@ struct TracedLaunch {
     int32_t *nedit;
     const VoteInto *vote;                 // ... or, non-null, votes gated by overlap_min (host pointer; passed by value)
     int overlap_min;
+    const CigarInto *cig;                 // ... or, non-null, runs (host pointer; its members are passed)
 };
 // (PBA_DISPATCH_NB without its case 0: these kernels have no row-sweep form)
 #define PBA_DISPATCH_BV_NB(nb, K) \
@@ -287,7 +325,13 @@ static void launch_traced(pba_ctx *ctx, const TracedLaunch &t, int nb, const Ali
         if (!t.vote->box_off) k = t.ck ? k_vote_pairs<NBV, true, false> : k_vote_pairs<NBV, false, false>;           \
         hipLaunchKernelGGL(k, grid, block, t.lds * 4, ctx->stream, t.A, t.B, t.pairs, ids, cnt, cfg, t.overlap_min, t.out, scr, \
                            tp.wave_words, tp.cap_words, *t.vote, ctx->d_queue); }
-    if (!t.vote) { PBA_DISPATCH_BV_NB(nb, PBA_SCRIPTS); } else { PBA_DISPATCH_BV_NB(nb, PBA_VOTES); }
+#define PBA_RUNS(NBV)                                                                                                 \
+        hipLaunchKernelGGL(k_cigar_pairs<NBV>, grid, block, t.lds * 4, ctx->stream, t.A, t.B, t.pairs, ids, cnt, cfg, t.out, scr, \
+                           tp.wave_words, tp.cap_words, t.cig->cig, t.cig->off, t.cig->ncig, t.cig->counts, t.cig->pair_flags, \
+                           t.cig->flags, ctx->d_queue)
+    if (t.cig) { PBA_DISPATCH_BV_NB(nb, PBA_RUNS); }
+    else if (!t.vote) { PBA_DISPATCH_BV_NB(nb, PBA_SCRIPTS); } else { PBA_DISPATCH_BV_NB(nb, PBA_VOTES); }
+#undef PBA_RUNS
 #undef PBA_VOTES
 #undef PBA_SCRIPTS
 }
@@ -651,9 +695,10 @@ static int trace_rowsweep(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, co
 // paths go straight into the boxes it names, gated by overlap_min; ops / ops_off / nedit unused).
 int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R,
                        int maxn, int maxm, int kernel, pba_result *out, uint8_t *ops, const uint64_t *ops_off,
-                       int32_t *nedit, const VoteInto *vote, int overlap_min) {
+                       int32_t *nedit, const VoteInto *vote, int overlap_min, const CigarInto *cig) {
     const bool seg = vote && vote->box_off;
-    if (!ctx || !A || !B || (!pairs && n) || (!out && n) || (!vote && ((!ops_off && n) || (!nedit && n)))) return PBA_E_INVALID;
+    const bool sunk = vote || cig;                           // the path goes to a sink of its own: no script leaves the device
+    if (!ctx || !A || !B || (!pairs && n) || (!out && n) || (!sunk && ((!ops_off && n) || (!nedit && n))) || (vote && cig)) return PBA_E_INVALID;
     if (n == 0) return PBA_OK;
     if (n > 0x7FFFFFFFull) PBA_FAIL(PBA_E_INVALID, "too many pairs in one batch");
     if (A->non_acgt || B->non_acgt) PBA_FAIL(PBA_E_ALPHABET, "a sequence set holds bytes outside ACGT: use pba_align_text_trace");
@@ -661,7 +706,7 @@ int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pa
     tu_attrs(ctx);
     int mdmax;
     uint64_t ops_max;
-    int st = check_pairs(ctx, A, B, pairs, n, R, vote ? nullptr : ops_off, &mdmax, &ops_max);
+    int st = check_pairs(ctx, A, B, pairs, n, R, sunk ? nullptr : ops_off, &mdmax, &ops_max);
     if (st != PBA_OK) return st;
     Plan pl;
     st = make_plan(ctx, R, maxn, maxm, kernel, mdmax, &pl);
@@ -671,15 +716,19 @@ int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pa
         if (pl.nb1 == 0) PBA_FAIL(PBA_E_TOOLONG, "votes from the walk need the bit-vector kernel (band too wide)");
         ops_max = 0;                                             // no goal-first temporary
     }
+    if (cig) {
+        if (pl.nb1 == 0) PBA_FAIL(PBA_E_TOOLONG, "runs from the walk need the bit-vector kernel (band too wide)");
+        ops_max = cig->run_max * 4;                              // the goal-first temporary holds runs, 4 bytes each
+    }
     TraceBufs d;
-    d.ops_total = vote ? 0 : ops_off[n] - ops_off[0];
+    d.ops_total = sunk ? 0 : ops_off[n] - ops_off[0];
     HIPCHK(hipMalloc(&d.pairs.p, sizeof(pba_pair) * n));
     HIPCHK(hipMalloc(&d.out.p, sizeof(pba_result) * n));
     HIPCHK(hipMalloc(&d.ops.p, d.ops_total + 16));
     HIPCHK(hipMalloc(&d.ooff.p, sizeof(uint64_t) * (n + 1)));
     HIPCHK(hipMalloc(&d.ne.p, sizeof(int32_t) * n));
     std::vector<uint64_t> rel(n + 1, 0);
-    if (!vote) for (size_t q = 0; q <= n; ++q) rel[q] = ops_off[q] - ops_off[0];
+    if (!sunk) for (size_t q = 0; q <= n; ++q) rel[q] = ops_off[q] - ops_off[0];
     HIPCHK(hipMemcpyAsync(d.pairs.p, pairs, sizeof(pba_pair) * n, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(d.ooff.p, rel.data(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, ctx->stream));
     const TraceHooks hooks = trace_hooks_from_env();
@@ -693,9 +742,9 @@ int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pa
     // First launch: every pair, narrow window, scratch sized for it (so more wavefronts fit the budget); second
     // launch: the pairs that came back uncertified, reference band.
     t.A = A->dev(); t.B = B->dev(); t.pairs = d.pairs.as<pba_pair>(); t.out = d.out.as<pba_result>(); t.lds = pl.lds;
-    t.ck = seg || !hooks.stream;
+    t.ck = seg || cig || !hooks.stream;
     t.ops = d.ops.as<uint8_t>(); t.ops_off = d.ooff.as<uint64_t>(); t.nedit = d.ne.as<int32_t>();
-    t.vote = vote; t.overlap_min = overlap_min;
+    t.vote = vote; t.overlap_min = overlap_min; t.cig = cig;
     TracePass tp{};
     auto before = [&](int pass, const std::vector<uint32_t> &redo) {
         return trace_pass_size(ctx, pairs, pass ? redo.data() : nullptr, pass ? (uint32_t)redo.size() : (uint32_t)n, R,
@@ -703,7 +752,7 @@ int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pa
     };
     auto launch = [&](int nb, const uint32_t *ids, uint32_t cnt) { launch_traced(ctx, t, nb, pl.cfg, ids, cnt, tp); };
     auto collect = [&](std::vector<uint32_t> &redo) { return fetch_results(ctx, d.out.p, out, n, &redo); };
-    auto finish = [&](bool redone) { return trace_results(ctx, d, n, redone, out, ops, ops_off, nedit, vote != nullptr); };
+    auto finish = [&](bool redone) { return trace_results(ctx, d, n, redone, out, ops, ops_off, nedit, sunk); };
     return narrow_then_redo(ctx, pl, nullptr, (uint32_t)n, launch, collect, finish, before);
 }
 

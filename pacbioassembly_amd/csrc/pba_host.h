@@ -478,14 +478,27 @@ static inline void launch_seg_sort(pba_ctx *ctx, const uint64_t *src, uint64_t *
     }
 }
 
+// Where a batch of walks leaves its runs (k_cigar_pairs, pba_align.hip).  All pointers: device, owned by the caller, who
+// copies them back once trace_batch has returned (synchronised).  Pair q's slot is cig[off[q] .. off[q + 1]).
+struct CigarInto {
+    uint32_t *cig;
+    const uint64_t *off;
+    int32_t *ncig;
+    pba_aln_counts *counts;
+    const uint32_t *pair_flags;           // PBA_CIG_* per pair; nullable: `flags` for every pair
+    uint32_t flags;
+    uint64_t run_max;                     // the widest slot any pair may fill: sizes the wavefronts' goal-first temporaries
+};
+
 // ---- internal entry points that cross translation units
 extern "C" {
 // sort one oversize partition / candidate piece in global memory (pba_core.hip)
 PBA_INTERNAL int sort_partition_global(pba_ctx *ctx, uint64_t *d_part, uint32_t n);
-// edit scripts of a batch, or (vote non-null) their votes into the boxes it names, gated by overlap_min (pba_align.hip)
+// edit scripts of a batch, or (vote non-null) their votes into the boxes it names, gated by overlap_min, or (cig non-null)
+// their runs into the device arrays it names (pba_align.hip)
 PBA_INTERNAL int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R,
                              int maxn, int maxm, int kernel, pba_result *out, uint8_t *ops, const uint64_t *ops_off,
-                             int32_t *nedit, const VoteInto *vote = nullptr, int overlap_min = 0);
+                             int32_t *nedit, const VoteInto *vote = nullptr, int overlap_min = 0, const CigarInto *cig = nullptr);
 // one locked round over a subset of the reads (pba_drivers.hip)
 PBA_INTERNAL int spaced_round_subset(pba_ctx *ctx, const pba_index *ix, const pba_seqs *ref, uint32_t ref_seq, const pba_seqs *reads,
                                      double R, int max_trial, int overlap_min, int buggy_seed_at, int kernel,

@@ -48,6 +48,11 @@ assert LOC_ROW_DTYPE.itemsize == C.sizeof(PbaLocRow) and SS_ROW_DTYPE.itemsize =
 assert MAP_ROW_DTYPE.itemsize == C.sizeof(PbaMapRow)
 assert POLISH_LOG_DTYPE.itemsize == C.sizeof(_lib.PbaPolishRoundLog)
 assert PLACE_ROW_DTYPE.itemsize == 32
+# pba_aln_counts: the bases of each kind of a run-length alignment; a run is len << 4 | op
+ALN_COUNTS_DTYPE = np.dtype([(n, "<i4") for n in ("n_eq", "n_x", "n_ins", "n_del")])
+PBA_CIG_INS, PBA_CIG_DEL, PBA_CIG_EQ, PBA_CIG_X = _lib.PBA_CIG_INS, _lib.PBA_CIG_DEL, _lib.PBA_CIG_EQ, _lib.PBA_CIG_X
+PBA_CIG_REVERSED, PBA_CIG_B_IS_QUERY = _lib.PBA_CIG_REVERSED, _lib.PBA_CIG_B_IS_QUERY
+assert ALN_COUNTS_DTYPE.itemsize == C.sizeof(_lib.PbaAlnCounts)
 
 
 class PbaError(RuntimeError):
@@ -340,6 +345,21 @@ class Context:
                                                   _ptr(off), _ptr(ne)), "align_batch_trace")
         return out, [ops[int(off[q]):int(off[q]) + int(ne[q])].copy() for q in range(pairs.size)]
 
+    def align_batch_cigar(self, A: "SeqSet", B: "SeqSet", pairs: np.ndarray, R: float, maxn: int = 0, maxm: int = 0, flags: int = 0):
+        """The alignments of a batch as runs (pba_align_batch_cigar), made on the device from the traceback walk.  Returns
+        (results, list of run arrays -- views into one array --, counts of ALN_COUNTS_DTYPE)."""
+        pairs = np.ascontiguousarray(pairs, PAIR_DTYPE)
+        n = pairs.size
+        out = np.zeros(n, RESULT_DTYPE)
+        off = np.zeros(n + 1, np.uint64)
+        off[1:] = np.cumsum([cigar_bound(int(p["a_len"]), int(p["b_len"]), R) for p in pairs], dtype=np.uint64) if n else 0
+        cig = np.zeros(int(off[-1]) + 1, np.uint32)
+        ncig = np.zeros(max(n, 1), np.int32)
+        counts = np.zeros(max(n, 1), ALN_COUNTS_DTYPE)
+        self.check(self.lib.pba_align_batch_cigar(self.h, A.h, B.h, _ptr(pairs), n, R, maxn, maxm, flags, _ptr(out), _ptr(cig), _ptr(off),
+                                                  _ptr(ncig), _ptr(counts)), "align_batch_cigar")
+        return out, [cig[int(off[q]):int(off[q]) + int(ncig[q])] for q in range(n)], counts[:n]
+
     # -- drivers
     def locate(self, ix: "SeedIndex", target: "SeqSet", target_seq: int, reads: "SeqSet", R: float,
                trials: int = 50, min_len: int = 500, maxn: int = 0, maxm: int = 0, kernel: int = PBA_KERNEL_AUTO):
@@ -601,6 +621,105 @@ def map_row_pair(row, contig_len: int, read_len: int, R: float) -> np.ndarray:
     return out[0]
 
 
+def map_row_aln_pair(row, contig_len: int, read_len: int, R: float) -> np.ndarray:
+    """The pair the mapper itself aligned for a found map_reads row (pba_map_row_aln_pair; host arithmetic): one PAIR_DTYPE
+    record with a = the read from j, b = the contig from pos, each clipped as align clips it -- for a strand -1 row a
+    indexes the reverse-complemented set."""
+    r = np.zeros(1, MAP_ROW_DTYPE)
+    for f in ("read", "found", "strand", "contig", "j", "pos"):          # what the pair is made of
+        r[f] = row[f]
+    out = np.zeros(1, PAIR_DTYPE)
+    st = _lib.load().pba_map_row_aln_pair(_ptr(r), contig_len, read_len, R, _ptr(out))
+    if st != 0:
+        raise PbaError(st, "map_row_aln_pair")
+    return out[0]
+
+
+def cigar_bound(a_len: int, b_len: int, R: float) -> int:
+    """Upper bound on the runs of a successful pair (pba_cigar_bound; host arithmetic)."""
+    return int(_lib.load().pba_cigar_bound(a_len, b_len, R))
+
+
+def cigar_from_script(ops, a_elems: bytes, b_elems: bytes, flags: int = 0):
+    """(runs, counts) of a script and the elements of its two accessors in element order (pba_cigar_from_script)."""
+    ops = np.ascontiguousarray(ops, np.uint8)
+    cig = np.zeros(max(ops.size, 1), np.uint32)
+    counts = np.zeros(1, ALN_COUNTS_DTYPE)
+    n = _lib.load().pba_cigar_from_script(_ptr(ops), ops.size, a_elems, b_elems, flags, _ptr(cig), cig.size, _ptr(counts))
+    if n < 0:
+        raise PbaError(_lib.PBA_E_INVALID, "cigar_from_script")
+    return cig[:n], counts[0]
+
+
+def cigar_string(cigar) -> str:
+    """"12=1X3I..." of an array of runs (pba_cigar_string)."""
+    cigar = np.ascontiguousarray(cigar, np.uint32)
+    buf = C.create_string_buffer(11 * cigar.size + 1)
+    n = _lib.load().pba_cigar_string(_ptr(cigar), cigar.size, buf, len(buf))
+    return buf.raw[:n].decode()
+
+
+def _rows_cigar(self, fn, what, head, rows, dtype, R, cap, max_slots):
+    rows = np.ascontiguousarray(rows, dtype)
+    n = rows.size
+    off = np.zeros(n + 1, np.uint64)
+    counts = np.zeros(max(n, 1), ALN_COUNTS_DTYPE)
+    res = np.zeros(max(n, 1), RESULT_DTYPE)
+    total = C.c_uint64()
+    if cap is None:                                  # one call to learn the total, one to fetch: the runs are not kept between
+        self.check(fn(self.h, *head, _ptr(rows), n, R, None, 0, _ptr(off), C.byref(total), None, None, max_slots), what)
+        cap = total.value
+    cig = np.zeros(max(int(cap), 1), np.uint32)
+    self.check(fn(self.h, *head, _ptr(rows), n, R, _ptr(cig), int(cap), _ptr(off), C.byref(total), _ptr(counts), _ptr(res), max_slots), what)
+    runs, pos_ok = [], True
+    for k in range(n):
+        pos_ok = pos_ok and int(off[k + 1]) <= int(cap)
+        runs.append(cig[int(off[k]):int(off[k + 1])] if pos_ok else None)
+    return runs, counts[:n], off, res[:n], total.value
+
+
+def _map_cigar(self, target, reads, rows, R, reads_rc=None, cap=None, max_slots=0):
+    """Run-length alignments of map_reads rows (pba_map_rows_cigar_budget): SAM's CIGAR, the read (rc(read) for strand -1) is
+    the query, the contig the reference.  Returns (runs per row -- views into one array, None for a row beyond cap --, counts of
+    ALN_COUNTS_DTYPE, offsets, results, total runs).  max_slots: bounded slots of one chunk on the device (0: the default)."""
+    head = (target.h, reads.h, reads_rc.h if reads_rc is not None else None)
+    return _rows_cigar(self, self.lib.pba_map_rows_cigar_budget, "map_cigar", head, rows, MAP_ROW_DTYPE, R, cap, max_slots)
+
+
+def _overlap_cigar(self, reads, rows, R, reads_rc=None, cap=None, max_slots=0):
+    """Run-length alignments of overlap_strands rows (pba_overlap_rows_cigar_budget): the query read is the CIGAR's query, runs
+    in the target's forward order.  Returns what map_cigar returns."""
+    head = (reads.h, reads_rc.h if reads_rc is not None else None)
+    return _rows_cigar(self, self.lib.pba_overlap_rows_cigar_budget, "overlap_cigar", head, rows, STRAND_OVERLAP_DTYPE, R, cap, max_slots)
+
+
+def _paf(qname, qlen, qbeg, qend, strand, tname, tlen, tbeg, tend, c, nm, cigar):
+    block = int(c["n_eq"]) + int(c["n_x"]) + int(c["n_ins"]) + int(c["n_del"])
+    return "\t".join(str(x) for x in (qname, qlen, qbeg, qend, "+" if strand == 1 else "-", tname, tlen, tbeg, tend, int(c["n_eq"]),
+                                      block, 255, f"NM:i:{nm}", "cg:Z:" + cigar_string(cigar)))
+
+
+def paf_map_lines(rows, counts, cigars, read_lens, contig_lens, read_names=None, contig_names=None):
+    """One PAF line (twelve columns, NM:i: and cg:Z:) per found map_reads row.  Default names: read<i> / contig<c>."""
+    out = []
+    for k, r in enumerate(rows):
+        if not r["found"]:
+            continue
+        q, t = int(r["read"]), int(r["contig"])
+        out.append(_paf(read_names[q] if read_names is not None else f"read{q}", int(read_lens[q]), int(r["r_beg"]), int(r["r_end"]),
+                        int(r["strand"]), contig_names[t] if contig_names is not None else f"contig{t}", int(contig_lens[t]),
+                        int(r["c_beg"]), int(r["c_end"]), counts[k], int(r["cost"]), cigars[k]))
+    return out
+
+
+def paf_overlap_lines(rows, counts, cigars, read_lens, read_names=None):
+    """One PAF line per overlap_strands row: the query read is the PAF query, the target read the PAF target."""
+    name = (lambda i: read_names[i]) if read_names is not None else (lambda i: f"read{i}")
+    return [_paf(name(int(r["query"])), int(read_lens[int(r["query"])]), int(r["q_beg"]), int(r["q_end"]), int(r["strand"]),
+                 name(int(r["target"])), int(read_lens[int(r["target"])]), int(r["t_beg"]), int(r["t_end"]), counts[k], int(r["cost"]),
+                 cigars[k]) for k, r in enumerate(rows)]
+
+
 def place_row_pair(row, contig_len: int, read_len: int, R: float) -> np.ndarray:
     """The pair a found placement votes with (pba_place_row_pair; host arithmetic): one PAIR_DTYPE record with a = the contig
     from pos, clipped to b_len + max_dst, b = the read from j, both backward for dir -1 -- for a strand -1 row b indexes the
@@ -659,6 +778,8 @@ def _last_correct_profile(self) -> dict:
 
 
 Context.correct_reads = _correct_reads
+Context.map_cigar = _map_cigar
+Context.overlap_cigar = _overlap_cigar
 Context.polish_contigs = _polish_contigs
 Context.last_correct_profile = _last_correct_profile
 Context.overlap_strands = _overlap_strands
