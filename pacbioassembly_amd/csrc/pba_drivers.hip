@@ -2,6 +2,7 @@
 // One process per GPU, one pba_ctx per process, one HIP stream per ctx.  Everything here fails loudly
 // (PBA_E_NODEVICE / PBA_E_HIP): there is no CPU path behind these entry points.
 #include "pba_host.h"
+#include "locate_walk.h"
 #include "prefilter.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -37,6 +38,24 @@ __device__ __forceinline__ uint32_t set_contig(const LocSet &S, uint32_t g) {
     return lo;
 }
 
+// The lane's number for one phase of the walk.  Opaque to the compiler on purpose: what it derives from a plain
+// threadIdx.x -- LDS addresses, compares -- is invariant over the whole kernel, gets hoisted in front of the persistent loop and
+// then sits in vector registers (in scratch memory, at 64 registers) across every alignment.
+__device__ __forceinline__ uint32_t local_lane() {
+    uint32_t l = threadIdx.x & (PBA_WAVE - 1);
+    asm volatile("" : "+v"(l));
+    return l;
+}
+
+// what a wavefront's walk keeps in LDS (nothing per-lane stays in registers across an alignment)
+struct LocWalkLds {
+    uint64_t off[PBA_LW_PROBES];   // the lane block: where probe l's run starts in the block's list of hits (locate_walk.h)
+    uint32_t cnt[PBA_LW_PROBES];   //   its length
+    uint32_t beg[PBA_LW_PROBES];   //   its first entry in the index
+    int2 grp[PBA_WAVE];            // the 64 list slots in flight: hit position, band cells of a hit the prefilter failed
+    int probe[PBA_WAVE];           //   the probe (within the block) the hit belongs to
+};
+
 // locator.cpp:70-92.  SET = false: against sequence tseq of T (`set` is not looked at).  SET = true: against every sequence of
 // T through a set index -- a hit resolves to (contig, local position) by a search of cum[], per lane in front of the
 // prefilter, wave-uniform for a survivor; the walk is otherwise the same, so a read tries, for j ascending, the hits of its
@@ -46,8 +65,9 @@ __global__ void __launch_bounds__(PBA_WAVE * Wpb<NB>::v, Wpb<NB>::occ)
 k_locate(IndexDev ix, SeqSetDev T, uint32_t tseq, SeqSetDev Rd, const uint32_t *ids, uint32_t n, int trials,
          int min_len, AlignCfg cfg, pba_loc_row *rows, LocAux *aux, uint32_t *queue, LocSet set) {
     extern __shared__ __align__(16) uint8_t lds_all[];
-    __shared__ int2 s_grp[Wpb<NB>::v][PBA_WAVE];      // the hit group in flight: position, band cells of a hit the prefilter failed
+    __shared__ LocWalkLds s_walk[Wpb<NB>::v];
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / PBA_WAVE));   // wave-uniform on purpose: keeps the walk in SGPRs
+    LocWalkLds &W = s_walk[wave];
     uint8_t *lds = lds_all + (size_t)wave * cfg.row_cap * 2;
     const PreThresholds pre_t(cfg.R);
     for (;;) {                                // persistent wavefront: pull the next read until the queue is dry
@@ -69,43 +89,73 @@ k_locate(IndexDev ix, SeqSetDev T, uint32_t tseq, SeqSetDev Rd, const uint32_t *
             clen = __builtin_amdgcn_readfirstlane((int)T.len[tseq]);
         }
         const uint8_t *rseq = rbase.seq;
-        for (int j = 0; j < trials && j < len && !found && !redo; ++j) {    // locator.cpp:74
-            const uint32_t key = (uint32_t)__builtin_amdgcn_readfirstlane((int)(window_key(rseq, (uint32_t)j, (uint32_t)len) & ix.mask));   // locator.cpp:75
-            if (key == 0) continue;                                         // never inserted, locator.cpp:64
-            uint32_t beg, cnt;
-            ix_find(ix, key, beg, cnt);                                     // locator.cpp:76
-            beg = (uint32_t)__builtin_amdgcn_readfirstlane((int)beg);
-            cnt = (uint32_t)__builtin_amdgcn_readfirstlane((int)cnt);
-            if (cnt == 0) continue;
-            ++nhit;
-            // locator.cpp:79, 64 hits at a time: every lane runs the first 32 rows of its hit (prefilter.h), then the
-            // hits are walked in list order -- the ones that failed there are done, the others get the wavefront
-            for (uint32_t h0 = 0; h0 < cnt && !found && !redo; h0 += PBA_WAVE) {
-                const uint32_t lane = threadIdx.x & (PBA_WAVE - 1), ng = min((uint32_t)PBA_WAVE, cnt - h0);
+        const int nprobe = min(trials, len);                                // locator.cpp:74: j < trials && j < len
+        for (int j0 = 0; j0 < nprobe && !found && !redo; j0 += PBA_LW_PROBES) {
+            // A lane block: lane l keys probe j0 + l and looks it up (locator.cpp:75-76).  The runs go to LDS with their place
+            // in the block's one list of hits -- j ascending, inside a probe the index's run order (locate_walk.h).
+            uint64_t hitmask, total;
+            {
+                const uint32_t lane = local_lane();
+                const int j = j0 + (int)lane;
+                uint32_t beg = 0, cnt = 0;
+                if (j < nprobe) {
+                    const uint32_t key = window_key(rseq, (uint32_t)j, (uint32_t)len) & ix.mask;
+                    if (key) ix_find(ix, key, beg, cnt);                    // (0: never inserted, locator.cpp:64)
+                }
+                hitmask = __builtin_amdgcn_ballot_w64(cnt != 0);   // the probes that count as hit
+                __builtin_amdgcn_wave_barrier();                            // (the previous block's reads are done)
+                W.cnt[lane] = cnt;
+                W.beg[lane] = beg;
+                __builtin_amdgcn_wave_barrier();
+                const uint64_t off = lw_offset(W.cnt, (int)lane);
+                W.off[lane] = off;
+                const uint64_t end = off + cnt;                             // lane 63's: the list's length
+                total = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)end, PBA_WAVE - 1) |
+                        (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(end >> 32), PBA_WAVE - 1) << 32;
+                __builtin_amdgcn_wave_barrier();
+            }
+            // probes that found their key, up to and including probe p (hits of the probes behind a success are listed and
+            // prefiltered below; they are never counted and never aligned)
+            auto hits_upto = [&](int p) { return lw_hits_upto(hitmask, p); };
+            // locator.cpp:79, 64 list slots at a time: every lane runs the first 32 rows of its hit (prefilter.h) from its own
+            // probe's read position, then the hits are walked in list order -- the ones that failed there are done, the others
+            // get the wavefront
+            for (uint32_t chunk = 0; !found && !redo; ++chunk) {            // (a list is shorter than 2^38 slots)
+                const uint64_t c0 = (uint64_t)chunk * PBA_WAVE;
+                if (c0 >= total) break;
+                const uint32_t ng = total - c0 < (uint64_t)PBA_WAVE ? (uint32_t)(total - c0) : (uint32_t)PBA_WAVE;
+                const uint32_t lane = local_lane();
                 const bool act = lane < ng;
-                const int mypos = act ? ix_pos_of(ix, (uint32_t)ix.ent[beg + h0 + lane]) : 0;   // (SET: the global position)
+                int mypos = 0, myp = 0;                                     // (SET: mypos is the global position)
+                if (act) {
+                    const uint64_t s = c0 + lane;
+                    myp = lw_slot_probe(W.off, s);
+                    mypos = ix_pos_of(ix, (uint32_t)ix.ent[W.beg[myp] + (uint32_t)(s - W.off[myp])]);
+                }
                 int myfr = 0;
                 long long mycells = 0;
                 if constexpr (NB != 0) {
+                    const int myj = j0 + myp;
                     AlnOut po;
                     if constexpr (SET) {
                         const uint32_t myctg = set_contig(set, (uint32_t)mypos);
                         const int lpos = mypos - (int)set.cum[myctg];
-                        myfr = prefilter32(act, rbase.at(j, 1), len - j, fetch_of(T, myctg, lpos, 1), (int)T.len[myctg] - lpos, cfg.R,
+                        myfr = prefilter32(act, rbase.at(myj, 1), len - myj, fetch_of(T, myctg, lpos, 1), (int)T.len[myctg] - lpos, cfg.R,
                                            cfg.maxn, cfg.maxm, pre_t, po);
                     } else
-                    myfr = prefilter32(act, rbase.at(j, 1), len - j, tbase.at(mypos, 1), clen - mypos, cfg.R,
+                    myfr = prefilter32(act, rbase.at(myj, 1), len - myj, tbase.at(mypos, 1), clen - mypos, cfg.R,
                                        cfg.maxn, cfg.maxm, pre_t, po);
                     mycells = myfr ? band_cells(po.len_b, po.max_dst, myfr) : 0;
                 }
                 // The group's per-lane state goes to LDS before the array takes the wavefront (kept in registers it was
-                // spilled to scratch memory around every alignment): the hit position and the band cells of a hit that
-                // failed in its first 32 rows (<= 32 x 9001, so a group's sum fits 32 bits) -- the hits between two
-                // survivors are counted from there, in list order, up to the first success.
+                // spilled to scratch memory around every alignment): the hit position, the band cells of a hit that
+                // failed in its first 32 rows (<= 32 x 9001, so a group's sum fits 32 bits) and the hit's probe -- the hits
+                // between two survivors are counted from there, in list order, up to the first success.
                 const uint64_t fmask = __builtin_amdgcn_ballot_w64(myfr != 0);
                 uint64_t surv = __builtin_amdgcn_ballot_w64(act && myfr == 0);
                 __builtin_amdgcn_wave_barrier();                        // (the previous group's reads are done)
-                s_grp[wave][lane] = make_int2(mypos, (int)mycells);
+                W.grp[lane] = make_int2(mypos, (int)mycells);
+                W.probe[lane] = myp;
                 __builtin_amdgcn_wave_barrier();
                 uint32_t from = 0;
                 auto count_failed = [&](uint32_t to) {                  // hits [from, to) that failed: seq_aligner.h:185
@@ -114,7 +164,7 @@ k_locate(IndexDev ix, SeqSetDev T, uint32_t tseq, SeqSetDev Rd, const uint32_t *
                         if (m) {
                             const uint32_t l = threadIdx.x & (PBA_WAVE - 1);
                             npairs += __builtin_popcountll(m);
-                            ncell += (unsigned)wave_sum_i32(l >= from && l < to ? s_grp[wave][l].y : 0);
+                            ncell += (unsigned)wave_sum_i32(l >= from && l < to ? W.grp[l].y : 0);
                         }
                     }
                 };
@@ -123,7 +173,9 @@ k_locate(IndexDev ix, SeqSetDev T, uint32_t tseq, SeqSetDev Rd, const uint32_t *
                     surv &= surv - 1ull;
                     count_failed(hh);
                     from = hh + 1;
-                    int pos = __builtin_amdgcn_readfirstlane(s_grp[wave][hh].x);
+                    int pos = __builtin_amdgcn_readfirstlane(W.grp[hh].x);
+                    const int p = __builtin_amdgcn_readfirstlane(W.probe[hh]);
+                    const int j = j0 + p;
                     int ctg = 0;
                     if constexpr (SET) {                                    // the survivor's contig, in scalar registers
                         ctg = __builtin_amdgcn_readfirstlane((int)set_contig(set, (uint32_t)pos));
@@ -135,17 +187,19 @@ k_locate(IndexDev ix, SeqSetDev T, uint32_t tseq, SeqSetDev Rd, const uint32_t *
                     const PackedFetch fb = tbase.at(pos, 1);                // b = contig from pos (locator.cpp:80)
                     AlnOut o;
                     align_dispatch<NB>(fa, len - j, fb, clen - pos, cfg, lds, o, true);
-                    if (o.rc == PBA_RC_UNCERTIFIED) { redo = 1; break; }
+                    if (o.rc == PBA_RC_UNCERTIFIED) { redo = 1; nhit += hits_upto(p); break; }
                     ++npairs;
                     ncell += pair_cells(o, cfg);
                     if (o.rc > 0) {                                         // locator.cpp:82
                         found = 1; fj = j; fpos = pos; fcost = o.cost; fma = o.matlen_a; fmb = o.matlen_b; fdiag = o.diag;
                         fctg = ctg;
+                        nhit += hits_upto(p);
                         break;
                     }
                 }
                 if (!found && !redo) count_failed(ng);
             }
+            if (!found && !redo) nhit += hits_upto(PBA_LW_PROBES - 1);
         }
     }
     if ((threadIdx.x & (PBA_WAVE - 1)) == 0) {
