@@ -164,6 +164,76 @@ int pba_seqs_get_text(pba_ctx *ctx, const pba_seqs *s, uint32_t i, char *text, s
 int pba_seqs_revcomp(pba_ctx *ctx, const pba_seqs *src, const uint8_t *flip, pba_seqs **out);
 
 /* ------------------------------------------------------------------------ */
+/* FASTA / FASTQ in, FASTA out.  The file image goes up as it is; line ends, */
+/* headers and sequence lines are found on the device, the    */
+/* bases are gathered into one device text and packed by the path of         */
+/* pba_seqs_from_device_text.  The reference reads its own binary record     */
+/* file only (spaced_seed.cpp:310-345); this is what its users' files are.   */
+/* ------------------------------------------------------------------------ */
+/* Lines end at '\n'; one '\r' directly before it (or at the very end of a file without a final '\n') is not content; a line
+ * with no content is blank.  FASTA: a line whose first byte is '>' starts a record, every other non-blank line up to the next
+ * header is one of its sequence lines (concatenated; none: a sequence of length 0), blank lines are ignored anywhere, a
+ * non-blank line before the first header is an error.  FASTQ, strictly four lines per record counted from the start of the
+ * file: '@' header, sequence (may be empty), '+' line (the rest of it ignored), quality of the sequence's length (not kept:
+ * qual_off says where it is); blank lines only after the last record.  An empty or all-blank file is a set of 0 sequences.
+ * PBA_FX_AUTO: the first byte of the first non-blank line decides ('>' / '@', else PBA_E_INVALID).  Sequence bytes a-z are
+ * folded to upper case unless PBA_FX_KEEP_CASE; every other byte -- a space or tab too -- goes through and is a base outside
+ * ACGT.  A structural error is PBA_E_INVALID with "line <1-based number of the first offending line>" in pba_ctx_error (a
+ * truncated last FASTQ record: the line that is missing); nothing is returned.  Name = header content after the marker up
+ * to the first space or tab. */
+enum { PBA_FX_AUTO = 0, PBA_FX_FASTA = 1, PBA_FX_FASTQ = 2 };
+#define PBA_FX_KEEP_CASE   1u
+#define PBA_FX_STRICT_ACGT 2u   /* any base outside ACGT after folding: PBA_E_ALPHABET, nothing is returned */
+typedef struct {                /* all offsets into the caller's file image */
+    uint64_t hdr_off;           /* the '>' / '@' */
+    uint64_t seq_off;           /* first byte of the first sequence line (FASTA without one: the byte after the header line) */
+    uint64_t qual_off;          /* FASTQ: first byte of the quality line; FASTA: 0 */
+    uint32_t hdr_len, name_len; /* header content without the marker and without line end; its first token */
+    uint32_t seq_len, n_seq_lines;
+} pba_fastx_rec;
+typedef struct {
+    int32_t format; uint32_t n_records, n_pieces, max_len;   /* format: as resolved; 0 = no non-blank line */
+    uint64_t n_bytes, n_lines, n_bases, n_folded /* lower-case bytes folded */;
+    float h2d_ms, parse_ms, pack_ms;   /* HIP events on the ctx's stream, summed over the pieces */
+} pba_fastx_stats;
+typedef struct pba_fastx_index pba_fastx_index;   /* host object: the records of one parse */
+
+/* The set is a plain pba_seqs in pba_seqs_from_text's layout, byte for byte what pba_seqs_from_text makes of the same
+ * sequences; sequence i is record i in file order; pba_seqs_non_acgt reports what the file held.  The file is cut with
+ * pba_fastx_cut into pieces of at most max_piece_bytes (_budget; 0 or the plain call: 1 GiB; more is clamped to it, so that
+ * line and byte counters inside a piece are 32-bit); the answer does not depend on the cut.  A record longer than a piece:
+ * PBA_E_TOOLONG, its hdr_off in pba_ctx_error.  More than 0x7FFFFFFF records, or a record of 0x7FFFFFF0 bases or more:
+ * PBA_E_TOOLONG.  Work buffers come from the ctx's pool (pba_ctx_trim). */
+int pba_seqs_from_fastx(pba_ctx *ctx, const void *file, uint64_t file_len, int format, uint32_t flags,
+                        pba_seqs **out, pba_fastx_index **index /* nullable */, pba_fastx_stats *stats /* nullable */);
+int pba_seqs_from_fastx_budget(pba_ctx *ctx, const void *file, uint64_t file_len, int format, uint32_t flags,
+                               pba_seqs **out, pba_fastx_index **index /* nullable */, pba_fastx_stats *stats /* nullable */,
+                               uint64_t max_piece_bytes /* 0 = the default */);
+uint32_t pba_fastx_index_count(const pba_fastx_index *index);
+int pba_fastx_index_recs(const pba_fastx_index *index, pba_fastx_rec *out, uint32_t cap);   /* cap below count: PBA_E_INVALID */
+void pba_fastx_index_destroy(pba_fastx_index *index);
+/* host arithmetic, no ctx */
+/* PBA_FX_FASTA / PBA_FX_FASTQ, 0 for no non-blank line, PBA_E_INVALID for another first byte (or file == NULL with bytes) */
+int pba_fastx_sniff(const void *file, uint64_t file_len);
+/* *cut = the largest record start p with 0 < p <= want; file_len if want >= file_len; 0 if there is no such p.  FASTA: a line
+ * start holding '>'.  FASTQ: a line start holding '@' whose line after next exists and starts with '+' -- exact for files
+ * whose sequence lines do not begin with '+' (a quality line may begin with '@' or '+': the line two below such a quality
+ * line is the next record's sequence).  A file that breaks the assumption is cut inside a record, and the parse of that
+ * piece refuses it (PBA_E_INVALID).  format PBA_FX_AUTO: as pba_fastx_sniff finds (PBA_E_INVALID where that does; a file
+ * without a non-blank line has no record start). */
+int pba_fastx_cut(const void *file, uint64_t file_len, int format, uint64_t want, uint64_t *cut);
+/* The bases of sequences [lo, hi) as one FASTA image: record i is '>' + name + '\n', then its bases in lines of `width`
+ * (0: one line) with a '\n' after each; a sequence of length 0 contributes the header line only.  names / name_off: the
+ * name of sequence lo + k is names[name_off[k] .. name_off[k + 1]); both NULL: the decimal index lo + k.  Code 3 prints as
+ * 'T', as pba_seqs_get_text does: a set with bytes outside ACGT does not come back as it went in.  The size is host
+ * arithmetic from the lengths: *n_bytes is always set.  out == NULL: size only.  cap below the size: PBA_E_INVALID, nothing is
+ * written.  One kernel writes bases and line ends into a device image, one copy brings it out, the host fills in the
+ * headers: one synchronise, whatever hi - lo is. */
+int pba_seqs_write_fasta(pba_ctx *ctx, const pba_seqs *s, uint32_t lo, uint32_t hi, const char *names,
+                         const uint64_t *name_off /* hi-lo+1 entries; both NULL: decimal ids */, uint32_t width /* 0: one line */,
+                         char *out /* NULL: size only */, uint64_t cap, uint64_t *n_bytes);
+
+/* ------------------------------------------------------------------------ */
 /* Seed-hit index.  Replaces hash_table = hash_map<unsigned, list<int>>     */
 /* (common.h:54) and its two builders.                                      */
 /* ------------------------------------------------------------------------ */

@@ -94,6 +94,21 @@ class PbaLayoutConsStats(C.Structure):
                 ("evolve_ms", C.c_float)]
 
 
+PBA_FX_AUTO, PBA_FX_FASTA, PBA_FX_FASTQ = 0, 1, 2
+PBA_FX_KEEP_CASE, PBA_FX_STRICT_ACGT = 1, 2
+
+
+class PbaFastxRec(C.Structure):
+    _fields_ = [("hdr_off", C.c_uint64), ("seq_off", C.c_uint64), ("qual_off", C.c_uint64), ("hdr_len", C.c_uint32),
+                ("name_len", C.c_uint32), ("seq_len", C.c_uint32), ("n_seq_lines", C.c_uint32)]
+
+
+class PbaFastxStats(C.Structure):
+    _fields_ = [("format", C.c_int32), ("n_records", C.c_uint32), ("n_pieces", C.c_uint32), ("max_len", C.c_uint32),
+                ("n_bytes", C.c_uint64), ("n_lines", C.c_uint64), ("n_bases", C.c_uint64), ("n_folded", C.c_uint64),
+                ("h2d_ms", C.c_float), ("parse_ms", C.c_float), ("pack_ms", C.c_float)]
+
+
 class PbaSsRow(C.Structure):
     _fields_ = [(n, C.c_int32) for n in
                 ("read", "found", "j", "dir", "ref_pos", "cost", "matlen_a", "matlen_b", "n_trials", "n_pairs")]
@@ -138,6 +153,14 @@ SYMBOLS = {
     "pba_seqs_lengths": (C.c_int, [_P, _P, C.c_uint32]),
     "pba_seqs_get_text": (C.c_int, [_P, _P, C.c_uint32, C.c_char_p, C.c_size_t]),
     "pba_seqs_revcomp": (C.c_int, [_P, _P, _P, C.POINTER(_P)]),
+    "pba_seqs_from_fastx": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(_P), C.POINTER(_P), _P]),
+    "pba_seqs_from_fastx_budget": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(_P), C.POINTER(_P), _P, C.c_uint64]),
+    "pba_fastx_index_count": (C.c_uint32, [_P]),
+    "pba_fastx_index_recs": (C.c_int, [_P, _P, C.c_uint32]),
+    "pba_fastx_index_destroy": (None, [_P]),
+    "pba_fastx_sniff": (C.c_int, [_P, C.c_uint64]),
+    "pba_fastx_cut": (C.c_int, [_P, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "pba_seqs_write_fasta": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "pba_index_build": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_P)]),
     "pba_index_scan": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, _P, C.c_uint64,
                                  C.POINTER(C.c_uint64)]),

@@ -260,9 +260,9 @@ static int seqs_finish(pba_ctx *ctx, pba_seqs *s, const std::function<int()> &pa
     return PBA_OK;
 }
 
-// shared tail of the two text constructors: d_text / d_toff are on the device, h_toff on the host
-static int seqs_pack(pba_ctx *ctx, const uint8_t *d_text, const uint64_t *d_toff, const uint64_t *h_toff, uint32_t n,
-                     int strict, pba_seqs **out) {
+// shared tail of the text constructors (these two, and pba_seqs_from_fastx): d_text / d_toff are on the device, h_toff on the host
+int seqs_pack(pba_ctx *ctx, const uint8_t *d_text, const uint64_t *d_toff, const uint64_t *h_toff, uint32_t n,
+              int strict, pba_seqs **out) {
     SeqsGuard g(seqs_new(ctx, n), seqs_free);
     pba_seqs *s = g.get();
     if (!s) PBA_FAIL(PBA_E_NOMEM, "pba_seqs");

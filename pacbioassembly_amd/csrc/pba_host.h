@@ -1,6 +1,6 @@
 // pba_host.h -- host-side objects and helpers shared by the translation units of libpba.so (pba_core.hip: context,
 // sequence sets, seed index; pba_align.hip: explicit pairs and edit scripts; pba_drivers.hip: the reference's ordered
-// first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction; pba_stream.hip: streamed locate and mapping; pba_layout.hip: layout).  Internal: nothing here is part of
+// first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction; pba_stream.hip: streamed locate and mapping; pba_layout.hip: layout; pba_fastx.hip: FASTA / FASTQ in, FASTA out).  Internal: nothing here is part of
 // the C ABI (include/pba.h).
 // Also here, once for all of them: the clip of seq_aligner.h:94-102 (text_clip), the launch plan (make_plan), the host
 // protocol of every aligning entry point but the all-vs-all walk -- narrow window first, the uncertified items again at the
@@ -53,7 +53,7 @@ struct pba_ctx {
     // Work buffers of the drivers, kept between calls for the same reason (hipMalloc / hipFree of the 11 GB candidate
     // array of a million-read target range cost more than the kernels that fill it; the 4 MB of per-read rows of a
     // locate step cost 1 ms of a 50 ms step): grown on demand (pool_reserve), released by pba_ctx_trim or with the ctx.
-    struct { void *p; size_t cap; } pool[24];
+    struct { void *p; size_t cap; } pool[28];
     // pinned host staging of the one-pair text entry points (pba_align_text*: one H2D and one D2H copy per call)
     void *h_stage;
     size_t h_stage_cap;
@@ -133,7 +133,8 @@ static const int kRowSweepLdsCap = 96 * 1024;   // LDS bytes one wavefront may t
 // pool slots
 enum { POOL_OVL_CAND = 0, POOL_OVL_TMP, POOL_OVL_ITEMS, POOL_OVL_REDO, POOL_OVL_REDO_IN, POOL_OVL_OUT, POOL_OVL_SMALL,
        POOL_LOC_ROWS, POOL_LOC_AUX, POOL_REDO_IDS, POOL_IX_OFFS, POOL_IX_WORK, POOL_OVL_BLOOM, POOL_OVL_ENDS,
-       POOL_TXT_IN, POOL_TXT_OUT, POOL_TXT_PAR, POOL_TXT_CST, POOL_LOC_IDS, POOL_LOC_CTG, POOL_LAY_WORK, POOL_LAY_ROWS };
+       POOL_TXT_IN, POOL_TXT_OUT, POOL_TXT_PAR, POOL_TXT_CST, POOL_LOC_IDS, POOL_LOC_CTG, POOL_LAY_WORK, POOL_LAY_ROWS,
+       POOL_FX_FILE, POOL_FX_TILES, POOL_FX_LINES, POOL_FX_RECS, POOL_FX_IMG };
 // a buffer of at least `bytes` in pool slot `slot` (contents undefined); grows by reallocation with 1/8 headroom
 static inline int pool_reserve(pba_ctx *ctx, int slot, size_t bytes, void **out) {
     if (ctx->pool[slot].cap < bytes) {
@@ -519,6 +520,10 @@ PBA_INTERNAL int revcomp_enqueue(pba_ctx *ctx, const pba_seqs *src, const pba_se
 PBA_INTERNAL int map_core(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
                           double R, int trials, int min_len, int maxn, int maxm, int kernel, int strands, pba_map_row *rows,
                           pba_map_stats *stats, int64_t read_base, int64_t nseq_base, hipEvent_t packed);
+// the shared tail of the text makers: d_text / d_toff on the device, h_toff the same n + 1 offsets on the host; strict: a byte
+// outside ACGT is PBA_E_ALPHABET (pba_core.hip).  pba_seqs_from_fastx hands its gathered text to it (pba_fastx.hip).
+PBA_INTERNAL int seqs_pack(pba_ctx *ctx, const uint8_t *d_text, const uint64_t *d_toff, const uint64_t *h_toff, uint32_t n,
+                           int strict, pba_seqs **out);
 // pba_map_reads' checks of its index and target (pba_drivers.hip)
 PBA_INTERNAL int map_target_ok(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target);
 }  // extern "C"

@@ -53,6 +53,12 @@ ALN_COUNTS_DTYPE = np.dtype([(n, "<i4") for n in ("n_eq", "n_x", "n_ins", "n_del
 PBA_CIG_INS, PBA_CIG_DEL, PBA_CIG_EQ, PBA_CIG_X = _lib.PBA_CIG_INS, _lib.PBA_CIG_DEL, _lib.PBA_CIG_EQ, _lib.PBA_CIG_X
 PBA_CIG_REVERSED, PBA_CIG_B_IS_QUERY = _lib.PBA_CIG_REVERSED, _lib.PBA_CIG_B_IS_QUERY
 assert ALN_COUNTS_DTYPE.itemsize == C.sizeof(_lib.PbaAlnCounts)
+# pba_fastx_rec: one per record of a parsed FASTA / FASTQ file, offsets into the file image
+PBA_FX_AUTO, PBA_FX_FASTA, PBA_FX_FASTQ = _lib.PBA_FX_AUTO, _lib.PBA_FX_FASTA, _lib.PBA_FX_FASTQ
+PBA_FX_KEEP_CASE, PBA_FX_STRICT_ACGT = _lib.PBA_FX_KEEP_CASE, _lib.PBA_FX_STRICT_ACGT
+FASTX_REC_DTYPE = np.dtype([("hdr_off", "<u8"), ("seq_off", "<u8"), ("qual_off", "<u8"), ("hdr_len", "<u4"), ("name_len", "<u4"),
+                            ("seq_len", "<u4"), ("n_seq_lines", "<u4")])
+assert FASTX_REC_DTYPE.itemsize == C.sizeof(_lib.PbaFastxRec) == 40
 
 
 class PbaError(RuntimeError):
@@ -157,6 +163,52 @@ def concat(seqs: Sequence[bytes]):
     return text, offs
 
 
+# ----------------------------------------------------------------------------- FASTA / FASTQ
+def _u8(data) -> np.ndarray:
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        return np.frombuffer(data, np.uint8)
+    a = np.asarray(data)
+    if a.dtype != np.uint8 or not a.flags.c_contiguous:
+        a = np.ascontiguousarray(a, np.uint8)
+    return a.reshape(-1)
+
+
+def fastx_sniff(data) -> int:
+    """PBA_FX_FASTA / PBA_FX_FASTQ by the first byte of the first non-blank line, 0 for no such line (host arithmetic)"""
+    buf = _u8(data)
+    st = _lib.load().pba_fastx_sniff(_ptr(buf) if buf.size else None, buf.size)
+    if st < 0:
+        raise PbaError(st, "fastx_sniff")
+    return st
+
+
+def fastx_cut(data, want: int, format: int = PBA_FX_AUTO) -> int:
+    """the largest record start p with 0 < p <= want; len(data) if want >= len(data); 0 if there is none (host arithmetic)"""
+    buf = _u8(data)
+    cut = C.c_uint64()
+    st = _lib.load().pba_fastx_cut(_ptr(buf) if buf.size else None, buf.size, format, want, C.byref(cut))
+    if st != 0:
+        raise PbaError(st, "fastx_cut")
+    return cut.value
+
+
+class FastxIndex:
+    """The records of one parse (pba_fastx_index, copied to the host): recs() as FASTX_REC_DTYPE, offsets into the file image."""
+
+    def __init__(self, recs: np.ndarray, stats: dict):
+        self._recs, self.stats = recs, stats
+
+    def __len__(self):
+        return len(self._recs)
+
+    def recs(self) -> np.ndarray:
+        return self._recs
+
+    def names(self, data) -> list:
+        buf = _u8(data)
+        return [bytes(buf[int(r["hdr_off"]) + 1:int(r["hdr_off"]) + 1 + int(r["name_len"])]).decode("latin-1") for r in self._recs]
+
+
 # ----------------------------------------------------------------------------- device objects
 class Context:
     """One GPU, one stream (pba_ctx).  Raises PbaError(PBA_E_NODEVICE) without a gfx950 device."""
@@ -250,6 +302,27 @@ class Context:
             fp = _ptr(flip)
         self.check(self.lib.pba_seqs_revcomp(self.h, S.h, fp, C.byref(h)), "seqs_revcomp")
         return SeqSet(self, h)
+
+    def seqs_from_fastx(self, data, format: int = PBA_FX_AUTO, flags: int = 0, max_piece: int = 0):
+        """(SeqSet, FastxIndex) of a FASTA / FASTQ file image (pba_seqs_from_fastx: line ends, headers and sequence lines are
+        found on the device).  data: bytes or a u8 array, np.memmap included."""
+        buf = _u8(data)
+        h, ih, st = C.c_void_p(), C.c_void_p(), _lib.PbaFastxStats()
+        self.check(self.lib.pba_seqs_from_fastx_budget(self.h, _ptr(buf) if buf.size else None, buf.size, format, flags, C.byref(h),
+                                                       C.byref(ih), C.byref(st), max_piece), "seqs_from_fastx")
+        try:
+            n = self.lib.pba_fastx_index_count(ih)
+            recs = np.zeros(max(n, 1), FASTX_REC_DTYPE)
+            self.check(self.lib.pba_fastx_index_recs(ih, _ptr(recs), n), "fastx_index_recs")
+        finally:
+            self.lib.pba_fastx_index_destroy(ih)
+        return SeqSet(self, h), FastxIndex(recs[:n], {k: getattr(st, k) for k, _ in _lib.PbaFastxStats._fields_})
+
+    def read_fastx(self, path: str, format: int = PBA_FX_AUTO, flags: int = 0, max_piece: int = 0):
+        """seqs_from_fastx of a file, mapped rather than read"""
+        import os
+        data = np.memmap(path, np.uint8, "r") if os.path.getsize(path) else np.zeros(0, np.uint8)
+        return self.seqs_from_fastx(data, format, flags, max_piece)
 
     # -- index
     def index_build(self, target: "SeqSet", seq: int, mask: int, mode: int = PBA_INDEX_ALL) -> "SeedIndex":
@@ -962,6 +1035,26 @@ class SeqSet:
         buf = C.create_string_buffer(ln + 1)
         self.ctx.check(self.ctx.lib.pba_seqs_get_text(self.ctx.h, self.h, i, buf, ln + 1), "get_text")
         return buf.raw[:ln]
+
+    def write_fasta(self, names=None, width: int = 60, lo: int = 0, hi: Optional[int] = None) -> bytes:
+        """Sequences [lo, hi) as one FASTA image (pba_seqs_write_fasta: one kernel, one copy, one synchronise).  names: one per
+        sequence of the range (str or bytes); None: the decimal index.  Code 3 prints as T."""
+        hi = self.count if hi is None else hi
+        if names is None:
+            nm = no = None
+        else:
+            bn = [x if isinstance(x, bytes) else str(x).encode("latin-1") for x in names]
+            if len(bn) != hi - lo:
+                raise ValueError(f"{len(bn)} names for {hi - lo} sequences")
+            nm_a, no_a = concat(bn)
+            nm_a = np.concatenate([nm_a, np.zeros(1, np.uint8)])
+            nm, no = _ptr(nm_a), _ptr(no_a)
+        size = C.c_uint64()
+        self.ctx.check(self.ctx.lib.pba_seqs_write_fasta(self.ctx.h, self.h, lo, hi, nm, no, width, None, 0, C.byref(size)), "write_fasta")
+        out = np.zeros(max(size.value, 1), np.uint8)
+        self.ctx.check(self.ctx.lib.pba_seqs_write_fasta(self.ctx.h, self.h, lo, hi, nm, no, width, _ptr(out), size.value, C.byref(size)),
+                       "write_fasta")
+        return out[:size.value].tobytes()
 
 
 class BorrowedSeqSet(SeqSet):
