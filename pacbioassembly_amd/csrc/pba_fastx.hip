@@ -231,20 +231,6 @@ struct pba_fastx_index {
     std::vector<pba_fastx_rec> recs;
 };
 
-static size_t fx_scan_scratch(uint64_t n) { return (size_t)((n + PBA_SCAN_TILE - 1) / PBA_SCAN_TILE + 1); }
-// in-place inclusive scan of a[0 .. n) on the ctx's stream; scr: fx_scan_scratch(n) words
-static void fx_scan(pba_ctx *ctx, uint32_t *a, uint64_t n, uint32_t *scr) {
-    if (!n) return;
-    if (n <= PBA_SCAN_SMALL_MAX) {
-        hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, ctx->stream, a, (uint32_t)n, (uint32_t *)nullptr);
-        return;
-    }
-    const uint32_t n_tiles = (uint32_t)((n + PBA_SCAN_TILE - 1) / PBA_SCAN_TILE);
-    hipLaunchKernelGGL(k_scan_tiles, dim3(n_tiles), dim3(256), 0, ctx->stream, a, n, scr);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, scr, n_tiles);
-    hipLaunchKernelGGL(k_scan_add, dim3(n_tiles), dim3(256), 0, ctx->stream, a, n, scr);
-}
-
 // the u64 text offsets of the records parsed so far, on the device: grown by doubling
 struct FxOffsets {
     DevBuf buf;
@@ -294,13 +280,13 @@ static int fx_piece(FxRun &R, const uint8_t *piece, uint32_t P, uint64_t base, b
     // ---- the line table
     const uint32_t n_tiles = (P + FX_TILE - 1) / FX_TILE;
     uint32_t *cnt = nullptr;                                     // [n_tiles + 1] shifted counts, scan scratch, 4 words: last_nb1, bad, folded
-    POOL(POOL_FX_TILES, sizeof(uint32_t) * ((size_t)n_tiles + 1 + fx_scan_scratch(n_tiles) + 4), cnt);
-    uint32_t *scr = cnt + n_tiles + 1, *small = scr + fx_scan_scratch(n_tiles);
+    POOL(POOL_FX_TILES, sizeof(uint32_t) * ((size_t)n_tiles + 1 + scan_scratch_words(n_tiles) + 4), cnt);
+    uint32_t *scr = cnt + n_tiles + 1, *small = scr + scan_scratch_words(n_tiles);
     HIPCHK(hipMemsetAsync(cnt, 0, sizeof(uint32_t), ctx->stream));
     HIPCHK(hipMemsetAsync(small, 0, 4 * sizeof(uint32_t), ctx->stream));
     HIPCHK(hipMemsetAsync(small + 1, 0xFF, sizeof(uint32_t), ctx->stream));      // FX_NO_LINE
     hipLaunchKernelGGL(k_fx_count, dim3(n_tiles), dim3(256), 0, ctx->stream, d_file, P, cnt + 1);
-    fx_scan(ctx, cnt + 1, n_tiles, scr);
+    scan_inclusive(ctx, cnt + 1, n_tiles, scr);
     uint32_t n_nl = 0;
     HIPCHK(hipMemcpyAsync(&n_nl, cnt + n_tiles, sizeof n_nl, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -308,14 +294,14 @@ static int fx_piece(FxRun &R, const uint8_t *piece, uint32_t P, uint64_t base, b
     const uint32_t n_lines = n_nl + (piece[P - 1] != '\n');     // a last line without '\n' is a line (P <= 2^30: no overflow)
     const size_t n1 = (size_t)n_lines + 1;
     uint32_t *start = nullptr;
-    POOL(POOL_FX_LINES, sizeof(uint32_t) * (4 * n1 + fx_scan_scratch(n_lines)), start);
+    POOL(POOL_FX_LINES, sizeof(uint32_t) * (4 * n1 + scan_scratch_words(n_lines)), start);
     uint32_t *hdr1 = start + n1, *sq1 = hdr1 + n1, *by1 = sq1 + n1, *scr2 = by1 + n1;
     const uint32_t line_grid = (n_lines + 255) / 256;
     hipLaunchKernelGGL(k_fx_lines, dim3(n_tiles), dim3(256), 0, ctx->stream, d_file, P, cnt, n_lines, start);
     // ---- per line
     hipLaunchKernelGGL(k_fx_classify, dim3(line_grid), dim3(256), 0, ctx->stream, d_file, start, n_lines, format, hdr1, sq1, by1, small);
-    if (format == FX_FASTA) { fx_scan(ctx, hdr1 + 1, n_lines, scr2); fx_scan(ctx, sq1 + 1, n_lines, scr2); }
-    fx_scan(ctx, by1 + 1, n_lines, scr2);
+    if (format == FX_FASTA) { scan_inclusive(ctx, hdr1 + 1, n_lines, scr2); scan_inclusive(ctx, sq1 + 1, n_lines, scr2); }
+    scan_inclusive(ctx, by1 + 1, n_lines, scr2);
     uint32_t n_hdr = 0, nb = 0, last_nb1 = 0;
     if (format == FX_FASTA) HIPCHK(hipMemcpyAsync(&n_hdr, hdr1 + n_lines, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(&nb, by1 + n_lines, 4, hipMemcpyDeviceToHost, ctx->stream));

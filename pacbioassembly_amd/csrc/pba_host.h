@@ -1,5 +1,5 @@
 // pba_host.h -- host-side objects and helpers shared by the translation units of libpba.so (pba_core.hip: context,
-// sequence sets, seed index; pba_align.hip: explicit pairs and edit scripts; pba_drivers.hip: the reference's ordered
+// sequence sets; pba_index.hip: seed index; pba_align.hip: explicit pairs and edit scripts; pba_drivers.hip: the reference's ordered
 // first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction; pba_stream.hip: streamed locate and mapping; pba_layout.hip: layout; pba_fastx.hip: FASTA / FASTQ in, FASTA out).  Internal: nothing here is part of
 // the C ABI (include/pba.h).
 // Also here, once for all of them: the clip of seq_aligner.h:94-102 (text_clip), the launch plan (make_plan), the host
@@ -41,6 +41,29 @@
 // ---------------------------------------------------------------------------------------------
 // host-side objects
 // ---------------------------------------------------------------------------------------------
+// The entry / offset arrays of the index destroyed last, kept for the next build, one deep per slot (a step of the locate loop
+// builds and drops one index: the hipFree / hipMalloc pair of its 40 MB cost 0.2 ms of a 48 ms step).  IXC_ENT / IXC_OFF: a
+// destroyed index's arrays; IXC_ENT2: the entry buffer a build did not keep.
+enum { IXC_ENT = 0, IXC_OFF, IXC_ENT2 };
+struct IxCache {
+    struct { void *p; size_t cap; } slot[3] = {};
+    // a device array of at least `bytes`: the slot's if it is large enough, else a new one
+    hipError_t take(int s, size_t bytes, void **p, size_t *cap) {
+        if (slot[s].p && slot[s].cap >= bytes) { *p = slot[s].p; *cap = slot[s].cap; slot[s].p = nullptr; slot[s].cap = 0; return hipSuccess; }
+        const hipError_t e = hipMalloc(p, bytes);
+        if (e == hipSuccess) *cap = bytes; else *p = nullptr;
+        return e;
+    }
+    // kept when the slot is empty (the work that used the array was synchronised by the call that returned its results),
+    // else back to the device
+    void give(int s, void *p, size_t cap) {
+        if (!p) return;
+        if (!slot[s].p) { slot[s].p = p; slot[s].cap = cap; }
+        else (void)hipFree(p);
+    }
+    void release() { for (auto &x : slot) { if (x.p) (void)hipFree(x.p); x.p = nullptr; x.cap = 0; } }
+};
+
 struct pba_ctx {
     int device;
     hipStream_t own_stream, stream;
@@ -58,9 +81,7 @@ struct pba_ctx {
     void *h_stage;
     size_t h_stage_cap;
     uint32_t attr_done;      // translation units whose big-LDS kernel attributes are set on this ctx's device (tu_attrs)
-    // the entry / offset arrays of the index destroyed last, for the next build (a step of the locate loop builds and drops
-    // one index: the hipFree / hipMalloc pair of its 40 MB cost 0.2 ms of a 48 ms step)
-    struct { void *ent; size_t ent_cap; void *off; size_t off_cap; void *ent2; size_t ent2_cap; } ix_cache;
+    IxCache ix_cache;
     pba_profile prof;
     pba_correct_profile cprof;   // the most recent pba_correct_reads
     char err[512];
@@ -479,6 +500,26 @@ static inline void launch_seg_sort(pba_ctx *ctx, const uint64_t *src, uint64_t *
     }
 }
 
+// u32 words of scratch scan_inclusive wants for n values
+static inline size_t scan_scratch_words(uint64_t n) { return (size_t)((n + PBA_SCAN_TILE - 1) / PBA_SCAN_TILE + 1); }
+// In-place inclusive scan of a[0 .. n) on the ctx's stream (seed_index.h: k_scan_*): one workgroup up to PBA_SCAN_SMALL_MAX
+// values, else tiles, their sums, and the carry-in added back.  scratch: scan_scratch_words(n) words.  shifted (nullable): see
+// k_scan_small; true when it was written (else the caller copies).
+static inline bool scan_inclusive(pba_ctx *ctx, uint32_t *a, uint64_t n, uint32_t *scratch, uint32_t *shifted = nullptr) {
+    if (n && n <= PBA_SCAN_SMALL_MAX) {
+        hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, ctx->stream, a, (uint32_t)n, shifted);
+        return shifted != nullptr;
+    }
+    const uint32_t n_tiles = (uint32_t)((n + PBA_SCAN_TILE - 1) / PBA_SCAN_TILE);
+    if (!n_tiles) return false;
+    hipLaunchKernelGGL(k_scan_tiles, dim3(n_tiles), dim3(256), 0, ctx->stream, a, n, scratch);
+    if (n_tiles > 1) {
+        hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, scratch, n_tiles);
+        hipLaunchKernelGGL(k_scan_add, dim3(n_tiles), dim3(256), 0, ctx->stream, a, n, scratch);
+    }
+    return false;
+}
+
 // Where a batch of walks leaves its runs (k_cigar_pairs, pba_align.hip).  All pointers: device, owned by the caller, who
 // copies them back once trace_batch has returned (synchronised).  Pair q's slot is cig[off[q] .. off[q + 1]).
 struct CigarInto {
@@ -493,8 +534,10 @@ struct CigarInto {
 
 // ---- internal entry points that cross translation units
 extern "C" {
-// sort one oversize partition / candidate piece in global memory (pba_core.hip)
+// sort one oversize partition / candidate piece in global memory (pba_index.hip)
 PBA_INTERNAL int sort_partition_global(pba_ctx *ctx, uint64_t *d_part, uint32_t n);
+// an index build of at most n_upper entries takes tiles of 4 096 entries in its generic level kernels (pba_core.hip)
+PBA_INTERNAL bool index_small_tiles(uint64_t n_upper);
 // edit scripts of a batch, or (vote non-null) their votes into the boxes it names, gated by overlap_min, or (cig non-null)
 // their runs into the device arrays it names (pba_align.hip)
 PBA_INTERNAL int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R,

@@ -197,12 +197,9 @@ int pba_probe_table_create(pba_ctx *ctx, const void *d_probe_entries, uint64_t n
     const uint64_t *ent = (const uint64_t *)d_probe_entries;
     if (grid) PBA_PT_LAUNCH(t->hashed, k_pt_count, dim3(grid), dim3(256), 0, ctx->stream, ent, n, T);
     // start[b + 1] = entries of bucket b  ->  inclusive scan  ->  start[b] = first entry of bucket b
-    const uint32_t n_tiles = (uint32_t)((B + PBA_SCAN_TILE - 1) / PBA_SCAN_TILE);
     DevBuf d_tiles, d_cursor;
-    HIPCHK(hipMalloc(&d_tiles.p, sizeof(uint32_t) * n_tiles));
-    hipLaunchKernelGGL(k_scan_tiles, dim3(n_tiles), dim3(256), 0, ctx->stream, T.start + 1, B, d_tiles.as<uint32_t>());
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, d_tiles.as<uint32_t>(), n_tiles);
-    hipLaunchKernelGGL(k_scan_add, dim3(n_tiles), dim3(256), 0, ctx->stream, T.start + 1, B, d_tiles.as<uint32_t>());
+    HIPCHK(hipMalloc(&d_tiles.p, sizeof(uint32_t) * scan_scratch_words(B)));
+    scan_inclusive(ctx, T.start + 1, B, d_tiles.as<uint32_t>());
     uint32_t total = 0;
     HIPCHK(hipMemcpyAsync(&total, T.start + B, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));

@@ -36,6 +36,8 @@
 #endif
 #define PBA_IX_TILE_POS (PBA_IX_TILE_THREADS * 16 * PBA_IX_TILE_ITERS)   // positions per workgroup
 
+#include "index_plan.h"   // what the host plans from these constants; ScanSeg, ix_ord_pos
+
 struct IndexDev {
     const uint64_t *ent;        // entries, partition by partition, each partition sorted
     const uint32_t *part_off;   // 2^logP + 1 offsets into ent
@@ -51,7 +53,7 @@ __device__ __forceinline__ uint32_t ix_part(uint32_t key, int logP) {
 }
 
 __device__ __forceinline__ int32_t ix_pos_of(const IndexDev &ix, uint32_t ord) {
-    return ord < ix.nhead ? (int32_t)ord : ix.tail_top - (int32_t)(ord - ix.nhead);
+    return ix_ord_pos(ix.nhead, ix.tail_top, ord);
 }
 
 __device__ __forceinline__ uint32_t ix_lower_bound(const uint64_t *ent, uint32_t lo, uint32_t hi, uint64_t x) {
@@ -90,13 +92,6 @@ __device__ __forceinline__ void ix_find(const IndexDev &ix, uint32_t key, uint32
     beg = ix_lower_bound(ix.ent, lo, hi, (uint64_t)key << 32);
     cnt = ix_run_end(ix.ent, beg, hi, key) - beg;
 }
-
-// One scan segment: positions [lo, hi) of a sequence, visited ascending (ord = ord0 + pos - lo)
-// or descending (ord = ord0 + hi - 1 - pos).
-struct ScanSeg {
-    uint32_t lo, hi, ord0;
-    int descending;
-};
 
 // keys of the 16 positions [16*chunk, 16*chunk+16) from one 8-byte load of packed bases
 __device__ __forceinline__ uint64_t chunk_bits(const uint8_t *seq, uint32_t chunk) {

@@ -109,6 +109,11 @@ def cases():
     add("bad_forced_fasta_on_fastq", fastq([(b"r0", s[0], b"+", qual(rs, 40))]), format=FASTA, ok=False)
     add("bad_forced_fastq_on_fasta", fasta([(b"a", rnd(rs, 100))]), format=FASTQ, ok=False)
     add("bad_fq_late", fastq([(b"q%d" % i, s[0], b"+", qual(rs, 40)) for i in range(150)]) + b"@z\nACGT\n+\nIII\n", ok=False)
+    # ---- one record wrapped at width 1: 8 192 and 8 193 lines, either side of the one-workgroup scan of the per-line counts
+    # (PBA_SCAN_SMALL_MAX); a generator of their own, so that the cases above keep their bytes
+    rs2 = np.random.RandomState(4012)
+    for n_lines in (8192, 8193):
+        add(f"fa_lines{n_lines}", fasta([(b"one per line", rnd(rs2, n_lines - 1))], 1))
     assert len({c["name"] for c in out}) == len(out)
     return out
 

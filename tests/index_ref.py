@@ -6,8 +6,52 @@ masked key is not zero, sorted by key, and inside a key in visiting order -- the
 tests/test_index_ref_cpu.py pins it to Oracle.index.  It is the reference for checking a device index through
 pba_index_find over all distinct keys at once (SeedIndex.dump() sorts on the host and cannot witness device order):
 runs() gives the distinct keys and the per-key counts to compare np.diff(hit_off) and hit_pos with.
+Also here, restated once for the tests: the regime rules of csrc/index_plan.h (logp_of, levels_of, first_n_with_levels) over the
+constants read from the sources (define, tile_switch).
 """
+import os
+import re
+
 import numpy as np
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pacbioassembly_amd", "csrc")
+
+
+def define(name: str, header: str = "seed_index.h") -> int:
+    """a numeric #define of one of the builder's headers: the regime boundaries of the index tests are computed from them"""
+    m = re.search(r"^#define[ \t]+%s[ \t]+(\d+)\b" % name, open(os.path.join(CSRC, header)).read(), re.M)
+    assert m, f"#define {name} <number> not found in {header}: the regime boundaries of the index tests are computed from it"
+    return int(m.group(1))
+
+
+def tile_switch() -> int:
+    """n_upper <= this: tiles of 4 096 entries in the generic level kernels (index_small_tiles, pba_core.hip)"""
+    src = open(os.path.join(CSRC, "pba_core.hip")).read()
+    m = re.search(r"index_small_tiles\(uint64_t n_upper\)\s*\{\s*return n_upper <= \((\d+)ull << (\d+)\);", src)
+    assert m, "index_small_tiles(n_upper) { return n_upper <= (Aull << B); } not found in pba_core.hip"
+    return int(m.group(1)) << int(m.group(2))
+
+
+# ----------------------------------------------------------------------------- the regime rules of index_plan.h, restated
+PART_AVG = define("PBA_IX_PART_AVG", "seed_index.h")
+LVL_BITS = define("PBA_IX_LVL_BITS", "seed_index.h")
+MAX_LOGP = define("PBA_IX_MAX_LOGP", "seed_index.h")
+
+
+def logp_of(n_upper: int) -> int:                  # index_logp
+    lp = 0
+    while lp < MAX_LOGP and (n_upper >> lp) > PART_AVG:
+        lp += 1
+    return lp
+
+
+def levels_of(n_upper: int) -> int:
+    return max(1, -(-logp_of(n_upper) // LVL_BITS))
+
+
+def first_n_with_levels(k: int) -> int:            # the smallest n_upper that takes k partition levels
+    return 1 if k == 1 else (PART_AVG + 1) << ((k - 1) * LVL_BITS)
+
 
 MAX_READ_LEN = 20000      # common.h:33
 N_SEQ_WORD = 16           # dna_seq.h:26

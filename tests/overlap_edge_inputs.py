@@ -376,6 +376,28 @@ def _census_set(attempt):
     return S
 
 
+# ----------------------------------------------------------------------------- short masks: the probe table's small scan
+# Masks of six and of seven care bases: 4 096 and 16 384 buckets, either side of the one-workgroup scan of the probe table's
+# bucket counts (PBA_SCAN_SMALL_MAX).  Such masks hit by chance all over -- no input is clean under them, and none has to be.
+SHORT_PATS = ("1**1*1**1**1***1", "1**1*1**1*11***1")
+SHORT_R, SHORT_MIN, SHORT_TRIALS = 0.15, 40, 3
+
+
+@functools.lru_cache(maxsize=None)
+def short_mask_set():
+    """twelve reads of 300 bases, 100 bases apart on a 1 400-base text (neighbours overlap by 200 and by 100), every third with
+    a few substitutions"""
+    S = Set(4242)
+    G = S.rand(1400)
+    for i in range(12):
+        r = bytearray(G[100 * i:100 * i + 300])
+        if i % 3 == 1:
+            for at in S.rng.randint(20, 280, 4):
+                r[at:at + 1] = S.other(bytes(r[at:at + 1]))
+        S.add(r, query=True)
+    return S
+
+
 def flipped_view(S):
     """(texts, qtexts) of the reverse-complement pass over the set whose query reads were flipped: the pass's queries are the
     designed bases again (prefilter_inputs.straddle_views)"""
@@ -389,6 +411,7 @@ CASES = ([("run", name, pat) for pat in (MASK_PAT, pi.HEAVY_PAT) for name in RUN
          + [("after", name, mt, om) for name in AFTER_SETS for mt in AFTER_TRIALS for om in AFTER_MINS])
 VIEW_CASES = [("run", "b_small", MASK_PAT), ("run", "shapes", MASK_PAT), ("run", "groups", MASK_PAT), ("run", "full", MASK_PAT),
               ("run", "misc", pi.HEAVY_PAT), ("ht", 40017)]
+SHORT_CASES = [("short", pat) for pat in SHORT_PATS]
 
 
 def case_id(case):
@@ -403,6 +426,8 @@ def case_params(case):
         return headtail_set(case[1]), HT_R, MASK_PAT, 1, HT_MIN
     if case[0] == "after":
         return after_set(case[1]), AFTER_R, MASK_PAT, case[2], case[3]
+    if case[0] == "short":
+        return short_mask_set(), SHORT_R, case[1], SHORT_TRIALS, SHORT_MIN
     return census_set(), RUN_R, MASK_PAT, 1, RUN_MIN
 
 

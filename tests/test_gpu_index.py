@@ -6,38 +6,21 @@ host, so it is compared too but only pins the position mapping.  Every case asse
 constants parsed out of the sources, the property of its input that puts it in the regime it is named for.
 Needs a real MI355X (-m gpu)."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import GOLD, MASK_PAT, ROOT
-from index_ref import np_index, runs
+from conftest import GOLD, MASK_PAT
+from index_ref import define as _define, first_n_with_levels, levels_of, logp_of, np_index, runs, tile_switch as _tile_switch
 from pacbioassembly_amd import engine as eng
 from pacbioassembly_amd.engine import PBA_INDEX_ALL, PBA_INDEX_HEAD_TAIL, PbaError
 
 pytestmark = pytest.mark.gpu
 
 MODES = {"all": PBA_INDEX_ALL, "head_tail": PBA_INDEX_HEAD_TAIL}
-CSRC = os.path.join(ROOT, "pacbioassembly_amd", "csrc")
 
 
 # ----------------------------------------------------------------------------- the builder's constants, from its sources
-def _define(name: str) -> int:
-    src = open(os.path.join(CSRC, "seed_index.h")).read()
-    m = re.search(r"^#define[ \t]+%s[ \t]+(\d+)\b" % name, src, re.M)
-    assert m, f"#define {name} <number> not found in seed_index.h: the regime boundaries of this file are computed from it"
-    return int(m.group(1))
-
-
-def _tile_switch() -> int:
-    src = open(os.path.join(CSRC, "pba_core.hip")).read()
-    m = re.search(r"index_small_tiles\(uint64_t n_upper\)\s*\{\s*return n_upper <= \((\d+)ull << (\d+)\);", src)
-    assert m, "index_small_tiles(n_upper) { return n_upper <= (Aull << B); } not found in pba_core.hip"
-    return int(m.group(1)) << int(m.group(2))
-
-
 PART_AVG = _define("PBA_IX_PART_AVG")
 LVL_BITS = _define("PBA_IX_LVL_BITS")
 MAX_LOGP = _define("PBA_IX_MAX_LOGP")
@@ -47,21 +30,6 @@ SS_AVG = _define("PBA_SS_AVG")
 SS_MAXBKT = _define("PBA_SS_MAXBKT")
 TILE_SWITCH = _tile_switch()                       # n_upper <= this: tiles of 4 096 in the generic level kernels
 WAVE = 64
-
-
-def logp_of(n_upper: int) -> int:                  # index_logp
-    lp = 0
-    while lp < MAX_LOGP and (n_upper >> lp) > PART_AVG:
-        lp += 1
-    return lp
-
-
-def levels_of(n_upper: int) -> int:
-    return max(1, -(-logp_of(n_upper) // LVL_BITS))
-
-
-def first_n_with_levels(k: int) -> int:            # the smallest n_upper that takes k partition levels
-    return 1 if k == 1 else (PART_AVG + 1) << ((k - 1) * LVL_BITS)
 
 
 B2, B3 = first_n_with_levels(2), first_n_with_levels(3)

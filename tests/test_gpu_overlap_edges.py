@@ -92,6 +92,18 @@ def test_census_that_misses(ctx, oracle, monkeypatch):
     check(got, st, W, PBA_KERNEL_ROWSWEEP, "census")
 
 
+@pytest.mark.parametrize("case", oi.SHORT_CASES, ids=oi.case_id)
+def test_probe_table_scan_small_and_tiled(ctx, oracle, case):
+    """masks of six and of seven care bases: the probe table's 4 096 bucket counts are scanned by one workgroup (k_scan_small),
+    its 16 384 by the tiled form; rows and counters of both kernels are the model's"""
+    W = oi.expected(oracle, case)
+    assert eng.mask_from_pattern(case[1]) == W["mask"] and len(W["rows"]) >= 20
+    S = ctx.seqs_from_list(W["texts"], strict_acgt=True)
+    for kernel in KERNELS:
+        got, st = ctx.overlap_all(S, W["mask"], W["R"], W["max_trial"], W["overlap_min"], kernel=kernel)
+        check(got, st, W, kernel, oi.case_id(case))
+
+
 PROBE_CASES = [("run", "misc", MASK_PAT), ("run", "misc", pi.HEAVY_PAT), ("after", "main", 1, 10), ("after", "main", 2, 10),
                ("after", "main", 33, 10), ("after", "main", 63, 10), ("ht", 40017)]
 

@@ -79,6 +79,21 @@ def test_model_equals_the_oracle_round_by_round(oracle, case, view):
     assert len(orf.probe_entries(W["qtexts"], W["mask"], W["max_trial"])) == W["n_probe_entries"]
 
 
+@pytest.mark.parametrize("case", oi.SHORT_CASES, ids=oi.case_id)
+def test_short_masks_model_equals_the_oracle_on_either_side_of_the_small_scan(oracle, case):
+    """masks of six and seven care bases: a direct-address probe table of 4 096 buckets (scanned by one workgroup) and of 16 384
+    (tiled); chance hits everywhere, overlaps found, and the model is still the oracle's round target by target"""
+    small_max = ir.define("PBA_SCAN_SMALL_MAX", "seed_index.h")
+    W = oi.expected(oracle, case)
+    buckets = 1 << bin(W["mask"]).count("1")
+    assert W["mask"] == oracle.mask_from_pattern(case[1]) and not orf.hashed(W["mask"])
+    assert (buckets <= small_max) == (case == oi.SHORT_CASES[0]) and [2 * p.count("1") for p in oi.SHORT_PATS] == [12, 14]
+    rows, pairs_by = orf.oracle_composition(oracle, W["texts"], W["qtexts"], W["R"], W["mask"], W["max_trial"], W["overlap_min"], oracle.text2bin)
+    assert W["rows"] == rows and W["pairs_by"] == pairs_by
+    assert len(rows) >= 20 and not oi.is_clean(W["texts"], W["qtexts"], W["mask"], W["max_trial"], W["overlap_min"])
+    assert W["n_pre"] > 0 and W["n_listed"] > len(rows) and W["n_probe_entries"] > 60
+
+
 # ----------------------------------------------------------------------------- the run lists
 @pytest.mark.parametrize("pat", PATS)
 def test_bucket_sizes(oracle, pat):
