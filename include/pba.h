@@ -1030,6 +1030,84 @@ int pba_layout_consensus(pba_ctx *ctx, const pba_layout *lay, const pba_seqs *re
                          const pba_strand_overlap *rows, uint64_t n_rows, double R, int overlap_min, int weight, uint64_t max_boxes,
                          pba_seqs **consensus, pba_polish_row *rows_out /* nullable */, pba_layout_cons_stats *stats /* nullable */);
 
+/* ------------------------------------------------------------------------ */
+/* Clipping: reads cut to the span their overlap rows support (overlap ->    */
+/* CLIP -> overlap -> layout -> consensus; DESIGN §5.8, tests/clip_ref.py    */
+/* restates the rule).  A row is a semi-global alignment under the ratio R,  */
+/* so it breaks at a chimeric junction or a junk end whenever the foreign    */
+/* part costs more than R leaves room for: no row spans such a place, and a  */
+/* per-base count of the row intervals that span a position with a margin on */
+/* both sides drops to zero there (the coverage rule of miniasm's read       */
+/* selection).  A deterministic function of the rows, exactly as good as     */
+/* they are: what an alignment swallows -- true error that leaves R's budget */
+/* unused lets rows run across a junction -- this rule does not see.         */
+/* ("clip", not "trim": pba_ctx_trim releases the ctx's pooled buffers.)     */
+/* ------------------------------------------------------------------------ */
+enum { PBA_CLIP_DROPPED = 0, PBA_CLIP_WHOLE = 1, PBA_CLIP_CUT = 2 };
+#define PBA_CLIP_TARGETS     1u   /* count [t_beg, t_end) on the row's target */
+#define PBA_CLIP_QUERIES     2u   /* count [q_beg, q_end) on the row's query (forward-strand ends as the row carries them:
+                                     nothing is flipped for strand -1) */
+#define PBA_CLIP_KEEP_UNSEEN 4u   /* a read no counted interval lies on stays WHOLE instead of DROPPED */
+typedef struct {
+    int32_t read, state;
+    int32_t beg, end;        /* kept interval, forward strand, half-open; DROPPED: 0, 0 */
+    int32_t n_iv;            /* intervals counted on this read (before the margin test) */
+    int32_t n_runs;          /* maximal runs of positions with coverage >= min_cov; >= 2: suspect chimera */
+    int32_t max_cov;         /* largest coverage of any position (0 for an empty read) */
+    int32_t n_covered;       /* positions with coverage >= min_cov */
+} pba_clip_row;
+typedef struct {
+    uint64_t n_rows, n_iv, n_iv_short;     /* n_iv_short: counted intervals of length <= 2 * margin (they cover nothing) */
+    uint32_t n_whole, n_cut, n_dropped, n_multi_run, n_unseen, n_chunks;   /* n_multi_run: reads with n_runs >= 2, in any state */
+    uint64_t n_bases_in, n_bases_out;
+    float events_ms, sweep_ms, gather_ms;  /* HIP events on the ctx's stream; gather_ms is filled by pba_clip_apply */
+} pba_clip_stats;
+typedef struct pba_clip pba_clip;
+/* The clip table of `reads` from n_rows overlap rows (host array, any order; only target, query, strand and the four
+ * interval ends are read).  With L a read's length, m = margin, c = min_cov:
+ *   counted     every row counts [t_beg, t_end) on its target (PBA_CLIP_TARGETS) and [q_beg, q_end) on its query
+ *               (PBA_CLIP_QUERIES); n_iv goes up by one for each.  NOTHING is de-duplicated: a pair of reads seen from both
+ *               roles, or on both strands, counts once per row.
+ *   coverage    a counted [b, e) with e - b > 2m adds one to cov[p] for p in [b + m, e - m); a shorter one adds nothing
+ *               (n_iv_short).  cov[p] = the intervals that span p with at least m bases on both sides.
+ *   runs        maximal [s, e) with cov >= c throughout (n_runs, n_covered, max_cov); the winner is the longest, then the
+ *               one with the smallest s.
+ *   kept        [max(s - m, 0), min(e + m, L)): the c intervals that cover s after shrinking reach m further out, so the
+ *               unshrunk coverage is >= c on the extension, and an interval that ends at a junction J shrinks to J - m,
+ *               so the extension never crosses J.
+ *   state       DROPPED (beg = end = 0) without a run or with a kept length below min_len; with PBA_CLIP_KEEP_UNSEEN a read
+ *               with n_iv == 0 is WHOLE, [0, L), whatever its length (n_unseen); else WHOLE if kept == [0, L), else CUT.
+ *               An empty read without the flag is DROPPED.
+ * On the device: the rows go up once (the ctx's pooled row buffer); the reads are cut into consecutive ranges whose int32
+ * difference arenas (L + 1 entries a read, rounded up to a multiple of 4) hold at most max_bases entries -- 0: a quarter of
+ * the free device memory over 4 bytes an entry; always fewer than 2^31; a range holds one read at least -- and for every
+ * range a lane per row adds +1 / -1 with global atomics, then a workgroup per read scans its arena and reduces the runs
+ * (a read of any length is swept by its one workgroup: correct, not fast, for a very long one).  The answer does not depend
+ * on the cut.  Work arrays are pooled (pba_ctx_trim).  Checked on the host before anything is uploaded: the rows as
+ * pba_layout_create checks them (PBA_E_INVALID; none of its PBA_E_TOOLONG limits applies: nothing here is packed into a key);
+ * PBA_E_INVALID also for margin < 0, min_cov < 1, min_len < 0, neither role flag, unknown flag bits.  No reads and no rows
+ * are legal.  A set with bytes outside ACGT is legal here: only the lengths are read. */
+int pba_clip_create(pba_ctx *ctx, const pba_seqs *reads, const pba_strand_overlap *rows, uint64_t n_rows, int margin, int min_cov,
+                    int min_len, uint32_t flags, uint64_t max_bases /* 0 = default */, pba_clip **out,
+                    pba_clip_stats *stats /* nullable */);
+/* the per-read table, out[r] for read r; cap below the number of reads: PBA_E_INVALID */
+int pba_clip_rows(pba_ctx *ctx, const pba_clip *clip, pba_clip_row *out /* one per read */, uint32_t cap);
+/* cov[0 .. L) of one read: *n = L, at most cap entries written.  The event kernel of pba_clip_create on the one-read range
+ * and the same scan, so that a test can pin the events apart from the sweep (as pba_pileup_dump does for the votes).  Checks
+ * as pba_clip_create; read outside the set: PBA_E_INVALID.  PBA_CLIP_KEEP_UNSEEN is accepted and changes nothing. */
+int pba_clip_coverage(pba_ctx *ctx, const pba_seqs *reads, const pba_strand_overlap *rows, uint64_t n_rows, int margin, uint32_t flags,
+                      uint32_t read, int32_t *cov, uint32_t cap, uint32_t *n);
+/* The clipped reads as a NEW set of the same count and ids: sequence i is bases [beg, end) of read i, a DROPPED read an
+ * empty sequence (as an emptied contig stays in pba_polish_contigs).  ASCII is written on the device from the packed arena
+ * and packed by pba_seqs_from_device_text: byte for byte what pba_seqs_from_text makes of the sliced texts; no base crosses
+ * the host.  `reads` must be the set the table was made from (another count or other lengths: PBA_E_INVALID);
+ * PBA_E_ALPHABET for a set with bytes outside ACGT (code 3 would come back as T).
+ * AFTER CLIPPING THE OLD ROWS ARE STALE: their alignments end at read ends that no longer exist.  Run the overlapper again
+ * on the clipped set; no row remapping is offered. */
+int pba_clip_apply(pba_ctx *ctx, const pba_clip *clip, const pba_seqs *reads, pba_seqs **clipped);
+int pba_clip_last_stats(const pba_clip *clip, pba_clip_stats *out);
+void pba_clip_destroy(pba_clip *clip);
+
 const char *pba_strerror(int status);
 
 #ifdef __cplusplus

@@ -94,6 +94,15 @@ class PbaLayoutConsStats(C.Structure):
                 ("evolve_ms", C.c_float)]
 
 
+class PbaClipStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_rows", "n_iv", "n_iv_short")] + \
+               [(n, C.c_uint32) for n in ("n_whole", "n_cut", "n_dropped", "n_multi_run", "n_unseen", "n_chunks")] + \
+               [("n_bases_in", C.c_uint64), ("n_bases_out", C.c_uint64), ("events_ms", C.c_float), ("sweep_ms", C.c_float),
+                ("gather_ms", C.c_float)]
+
+
+PBA_CLIP_DROPPED, PBA_CLIP_WHOLE, PBA_CLIP_CUT = 0, 1, 2
+PBA_CLIP_TARGETS, PBA_CLIP_QUERIES, PBA_CLIP_KEEP_UNSEEN = 1, 2, 4
 PBA_FX_AUTO, PBA_FX_FASTA, PBA_FX_FASTQ = 0, 1, 2
 PBA_FX_KEEP_CASE, PBA_FX_STRICT_ACGT = 1, 2
 
@@ -257,6 +266,12 @@ SYMBOLS = {
     "pba_place_row_pair": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_double, _P]),
     "pba_pileup_vote_placed": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_double, C.c_int, _P, C.POINTER(C.c_uint64)]),
     "pba_layout_consensus": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.c_double, C.c_int, C.c_int, C.c_uint64, C.POINTER(_P), _P, _P]),
+    "pba_clip_create": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint64, C.POINTER(_P), _P]),
+    "pba_clip_rows": (C.c_int, [_P, _P, _P, C.c_uint32]),
+    "pba_clip_coverage": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "pba_clip_apply": (C.c_int, [_P, _P, _P, C.POINTER(_P)]),
+    "pba_clip_last_stats": (C.c_int, [_P, _P]),
+    "pba_clip_destroy": (None, [_P]),
     "pba_cigar_bound": (C.c_uint32, [C.c_int, C.c_int, C.c_double]),
     "pba_align_batch_cigar": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_double, C.c_int, C.c_int, C.c_uint32, _P, _P, _P, _P, _P]),
     "pba_cigar_from_script": (C.c_int, [_P, C.c_int32, _P, _P, C.c_uint32, _P, C.c_int32, _P]),

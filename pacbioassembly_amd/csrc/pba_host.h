@@ -1,6 +1,6 @@
 // pba_host.h -- host-side objects and helpers shared by the translation units of libpba.so (pba_core.hip: context,
 // sequence sets; pba_index.hip: seed index; pba_align.hip: explicit pairs and edit scripts; pba_drivers.hip: the reference's ordered
-// first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction; pba_stream.hip: streamed locate and mapping; pba_layout.hip: layout; pba_fastx.hip: FASTA / FASTQ in, FASTA out).  Internal: nothing here is part of
+// first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction; pba_stream.hip: streamed locate and mapping; pba_layout.hip: layout; pba_clip.hip: clipping; pba_fastx.hip: FASTA / FASTQ in, FASTA out).  Internal: nothing here is part of
 // the C ABI (include/pba.h).
 // Also here, once for all of them: the clip of seq_aligner.h:94-102 (text_clip), the launch plan (make_plan), the host
 // protocol of every aligning entry point but the all-vs-all walk -- narrow window first, the uncertified items again at the
@@ -76,7 +76,7 @@ struct pba_ctx {
     // Work buffers of the drivers, kept between calls for the same reason (hipMalloc / hipFree of the 11 GB candidate
     // array of a million-read target range cost more than the kernels that fill it; the 4 MB of per-read rows of a
     // locate step cost 1 ms of a 50 ms step): grown on demand (pool_reserve), released by pba_ctx_trim or with the ctx.
-    struct { void *p; size_t cap; } pool[28];
+    struct { void *p; size_t cap; } pool[32];
     // pinned host staging of the one-pair text entry points (pba_align_text*: one H2D and one D2H copy per call)
     void *h_stage;
     size_t h_stage_cap;
@@ -155,7 +155,7 @@ static const int kRowSweepLdsCap = 96 * 1024;   // LDS bytes one wavefront may t
 enum { POOL_OVL_CAND = 0, POOL_OVL_TMP, POOL_OVL_ITEMS, POOL_OVL_REDO, POOL_OVL_REDO_IN, POOL_OVL_OUT, POOL_OVL_SMALL,
        POOL_LOC_ROWS, POOL_LOC_AUX, POOL_REDO_IDS, POOL_IX_OFFS, POOL_IX_WORK, POOL_OVL_BLOOM, POOL_OVL_ENDS,
        POOL_TXT_IN, POOL_TXT_OUT, POOL_TXT_PAR, POOL_TXT_CST, POOL_LOC_IDS, POOL_LOC_CTG, POOL_LAY_WORK, POOL_LAY_ROWS,
-       POOL_FX_FILE, POOL_FX_TILES, POOL_FX_LINES, POOL_FX_RECS, POOL_FX_IMG };
+       POOL_FX_FILE, POOL_FX_TILES, POOL_FX_LINES, POOL_FX_RECS, POOL_FX_IMG, POOL_CLIP_ARENA, POOL_CLIP_WORK, POOL_CLIP_TEXT };
 // a buffer of at least `bytes` in pool slot `slot` (contents undefined); grows by reallocation with 1/8 headroom
 static inline int pool_reserve(pba_ctx *ctx, int slot, size_t bytes, void **out) {
     if (ctx->pool[slot].cap < bytes) {
@@ -236,6 +236,31 @@ static inline int scratch_reserve(pba_ctx *ctx, size_t need) {
     ctx->d_scratch = nullptr; ctx->scratch_bytes = 0;
     HIPCHK(hipMalloc(&ctx->d_scratch, need));
     ctx->scratch_bytes = need;
+    return PBA_OK;
+}
+
+// What every entry point that takes pba_strand_overlap rows checks of them on the host, before anything is uploaded (who:
+// its name, in front of the message); want_dir: dir is read too; key_limits: the rows, reads and lengths must also fit the
+// u64 keys of the layout's atomics (pba_layout_create, pba_layout_place; pba_clip_* keeps no key).
+#define ROWS_FAIL(st, what) return ctx_fail_as(ctx, (st), who, (what))
+static inline int check_overlap_rows(pba_ctx *ctx, const char *who, const pba_seqs *reads, const pba_strand_overlap *rows, uint64_t n_rows,
+                                     bool want_dir, bool key_limits) {
+    if (key_limits) {
+        if (n_rows >= (1ull << 32)) ROWS_FAIL(PBA_E_TOOLONG, "2^32 rows or more (a key holds 32 bits of row index)");
+        if (reads->n >= (1u << 28)) ROWS_FAIL(PBA_E_TOOLONG, "2^28 reads or more");
+        if (reads->max_len > 0xFFFFu) ROWS_FAIL(PBA_E_TOOLONG, "a read of more than 65 535 bases (a key holds 16 bits of length)");
+    }
+    const int64_t n = reads->n;
+    for (uint64_t k = 0; k < n_rows; ++k) {
+        const pba_strand_overlap &r = rows[k];
+        if (r.target < 0 || r.target >= n || r.query < 0 || r.query >= n) ROWS_FAIL(PBA_E_INVALID, "a row names a read outside the set");
+        if (r.target == r.query) ROWS_FAIL(PBA_E_INVALID, "a row pairs a read with itself");
+        if (r.strand != 1 && r.strand != -1) ROWS_FAIL(PBA_E_INVALID, "a row's strand is neither +1 nor -1");
+        if (want_dir && r.dir != 1 && r.dir != -1) ROWS_FAIL(PBA_E_INVALID, "a row's dir is neither +1 nor -1");
+        const int64_t lt = reads->h_len[r.target], lq = reads->h_len[r.query];
+        if (r.t_beg < 0 || r.t_beg >= r.t_end || r.t_end > lt || r.q_beg < 0 || r.q_beg >= r.q_end || r.q_end > lq)
+            ROWS_FAIL(PBA_E_INVALID, "a row's interval is empty or outside its read");
+    }
     return PBA_OK;
 }
 

@@ -337,30 +337,10 @@ struct pba_layout {
 
 static const uint64_t kLayMaxContig = 0x7FFFFFF0ull;
 
-// what every entry point that takes rows checks of them (who: its name, in front of the message); want_dir: dir is read too
-#define LAY_FAIL(st, what) do { char m__[192]; snprintf(m__, sizeof m__, "%s: %s", who, (what)); return ctx_fail(ctx, (st), m__, hipSuccess); } while (0)
-static int lay_check_rows(pba_ctx *ctx, const char *who, const pba_seqs *reads, const pba_strand_overlap *rows, uint64_t n_rows, bool want_dir) {
-    if (n_rows >= (1ull << 32)) LAY_FAIL(PBA_E_TOOLONG, "2^32 rows or more (a key holds 32 bits of row index)");
-    if (reads->n >= (1u << 28)) LAY_FAIL(PBA_E_TOOLONG, "2^28 reads or more");
-    if (reads->max_len > 0xFFFFu) LAY_FAIL(PBA_E_TOOLONG, "a read of more than 65 535 bases (a key holds 16 bits of length)");
-    const int64_t n = reads->n;
-    for (uint64_t k = 0; k < n_rows; ++k) {
-        const pba_strand_overlap &r = rows[k];
-        if (r.target < 0 || r.target >= n || r.query < 0 || r.query >= n) LAY_FAIL(PBA_E_INVALID, "a row names a read outside the set");
-        if (r.target == r.query) LAY_FAIL(PBA_E_INVALID, "a row pairs a read with itself");
-        if (r.strand != 1 && r.strand != -1) LAY_FAIL(PBA_E_INVALID, "a row's strand is neither +1 nor -1");
-        if (want_dir && r.dir != 1 && r.dir != -1) LAY_FAIL(PBA_E_INVALID, "a row's dir is neither +1 nor -1");
-        const int64_t lt = reads->h_len[r.target], lq = reads->h_len[r.query];
-        if (r.t_beg < 0 || r.t_beg >= r.t_end || r.t_end > lt || r.q_beg < 0 || r.q_beg >= r.q_end || r.q_end > lq)
-            LAY_FAIL(PBA_E_INVALID, "a row's interval is empty or outside its read");
-    }
-    return PBA_OK;
-}
-
 static int lay_check(pba_ctx *ctx, const pba_seqs *reads, const pba_strand_overlap *rows, uint64_t n_rows, int hang, int min_reads) {
     if (hang < 0) PBA_FAIL(PBA_E_INVALID, "pba_layout_create: hang must be >= 0");
     if (min_reads < 1) PBA_FAIL(PBA_E_INVALID, "pba_layout_create: min_reads must be >= 1");
-    return lay_check_rows(ctx, "pba_layout_create", reads, rows, n_rows, false);
+    return check_overlap_rows(ctx, "pba_layout_create", reads, rows, n_rows, false, true);
 }
 
 static inline dim3 lay_grid(uint64_t n) { return dim3(elem_grid(n, 256)); }
@@ -549,7 +529,7 @@ int pba_layout_place(pba_ctx *ctx, const pba_layout *lay, const pba_seqs *reads,
     if (reads->n != lay->n || !std::equal(lay->h_len.begin(), lay->h_len.end(), reads->h_len.begin()))
         PBA_FAIL(PBA_E_INVALID, "pba_layout_place: the set differs from the layout's in count or lengths");
     if (cap < lay->n || (!out && lay->n)) PBA_FAIL(PBA_E_INVALID, "pba_layout_place: room for fewer rows than the layout has reads");
-    PBA_TRY(lay_check_rows(ctx, "pba_layout_place", reads, rows, n_rows, true));
+    PBA_TRY(check_overlap_rows(ctx, "pba_layout_place", reads, rows, n_rows, true, true));
     HIPCHK(hipSetDevice(ctx->device));
     StageClock clk;
     if (!clk.init()) PBA_FAIL(PBA_E_HIP, "pba_layout_place: hipEventCreate");

@@ -43,6 +43,11 @@ PBA_LAY_UNPLACED, PBA_LAY_PLACED, PBA_LAY_CONTAINED = 0, 1, 2
 # pba_place_row: one per read, where it votes on its layout's contigs
 PLACE_ROW_DTYPE = np.dtype([("read", "<i4"), ("found", "<i4"), ("row", "<u4"), ("contig", "<i4"), ("pos", "<i4"), ("dir", "<i4"),
                             ("strand", "<i4"), ("j", "<i4")])
+# pba_clip_row: one per read of a clip table
+CLIP_ROW_DTYPE = np.dtype([(n, "<i4") for n in ("read", "state", "beg", "end", "n_iv", "n_runs", "max_cov", "n_covered")])
+PBA_CLIP_DROPPED, PBA_CLIP_WHOLE, PBA_CLIP_CUT = _lib.PBA_CLIP_DROPPED, _lib.PBA_CLIP_WHOLE, _lib.PBA_CLIP_CUT
+PBA_CLIP_TARGETS, PBA_CLIP_QUERIES, PBA_CLIP_KEEP_UNSEEN = _lib.PBA_CLIP_TARGETS, _lib.PBA_CLIP_QUERIES, _lib.PBA_CLIP_KEEP_UNSEEN
+assert CLIP_ROW_DTYPE.itemsize == 32 and C.sizeof(_lib.PbaClipStats) == 80
 assert PAIR_DTYPE.itemsize == C.sizeof(PbaPair) and RESULT_DTYPE.itemsize == C.sizeof(PbaResult)
 assert LOC_ROW_DTYPE.itemsize == C.sizeof(PbaLocRow) and SS_ROW_DTYPE.itemsize == C.sizeof(PbaSsRow)
 assert MAP_ROW_DTYPE.itemsize == C.sizeof(PbaMapRow)
@@ -1341,6 +1346,86 @@ def _layout_consensus(self, lay, reads, rows, R, overlap_min=64, weight=1, max_b
 Context.layout = _layout
 Context.layout_reads = _layout_reads
 Context.layout_consensus = _layout_consensus
+
+
+class Clip:
+    """The clip table of a read set from its overlap rows (pba_clip): per-base coverage by the row intervals that span a base
+    with `margin` on both sides, the longest run of bases with coverage >= min_cov, extended by the margin.  rows(): the
+    per-read table; apply(reads): the clipped reads as a new SeqSet, written on the device.  The rows the table was made
+    from are stale for the clipped set: run the overlapper again."""
+
+    def __init__(self, ctx: "Context", reads: "SeqSet", rows: np.ndarray, margin: int = 100, min_cov: int = 2, min_len: int = 0,
+                 roles: int = 3, keep_unseen: bool = False, max_bases: int = 0):
+        self.ctx, self.n = ctx, reads.count
+        rows = np.ascontiguousarray(rows, STRAND_OVERLAP_DTYPE)
+        self.h = C.c_void_p()
+        st = _lib.PbaClipStats()
+        flags = int(roles) | (PBA_CLIP_KEEP_UNSEEN if keep_unseen else 0)
+        ctx.check(ctx.lib.pba_clip_create(ctx.h, reads.h, _ptr(rows), rows.size, margin, min_cov, min_len, flags, max_bases,
+                                          C.byref(self.h), C.byref(st)), "clip_create")
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.ctx.lib.pba_clip_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def stats(self) -> dict:
+        st = _lib.PbaClipStats()
+        self.ctx.check(self.ctx.lib.pba_clip_last_stats(self.h, C.byref(st)), "clip_last_stats")
+        return {n: getattr(st, n) for n, _ in _lib.PbaClipStats._fields_}
+
+    def rows(self) -> np.ndarray:
+        """One CLIP_ROW_DTYPE record per read."""
+        out = np.zeros(max(self.n, 1), CLIP_ROW_DTYPE)
+        self.ctx.check(self.ctx.lib.pba_clip_rows(self.ctx.h, self.h, _ptr(out), self.n), "clip_rows")
+        return out[:self.n]
+
+    def apply(self, reads: "SeqSet") -> "SeqSet":
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.lib.pba_clip_apply(self.ctx.h, self.h, reads.h, C.byref(h)), "clip_apply")
+        return SeqSet(self.ctx, h)
+
+
+def _clip(self, reads, rows, margin=100, min_cov=2, min_len=0, roles=3, keep_unseen=False, max_bases=0) -> "Clip":
+    """The clip table of `reads` from overlap_strands rows (pba_clip_create).  roles: 1 = the rows' target intervals, 2 = their
+    query intervals, 3 = both."""
+    return Clip(self, reads, rows, margin, min_cov, min_len, roles, keep_unseen, max_bases)
+
+
+def _clip_coverage(self, reads, rows, read, margin=100, roles=3) -> np.ndarray:
+    """cov[0 .. L) of one read: how many counted intervals span each base with `margin` on both sides (pba_clip_coverage)."""
+    rows = np.ascontiguousarray(rows, STRAND_OVERLAP_DTYPE)
+    n = C.c_uint32()
+    self.check(self.lib.pba_clip_coverage(self.h, reads.h, _ptr(rows), rows.size, margin, roles, read, None, 0, C.byref(n)), "clip_coverage")
+    out = np.zeros(max(n.value, 1), np.int32)
+    self.check(self.lib.pba_clip_coverage(self.h, reads.h, _ptr(rows), rows.size, margin, roles, read, _ptr(out), n.value, C.byref(n)),
+               "clip_coverage")
+    return out[:n.value]
+
+
+def _clip_reads(self, reads, mask, R, max_trial=32, overlap_min=64, margin=100, min_cov=2, min_len=0, roles=3, keep_unseen=False,
+                max_bases=0, strands=3, targets_per_call=10000, kernel=PBA_KERNEL_AUTO, reads_rc=None):
+    """overlap_strands_sharded -> clip -> apply.  Returns (SeqSet of the clipped reads, the clip table as CLIP_ROW_DTYPE records,
+    the overlap rows, the Clip's stats).  The rows belong to the UNCLIPPED set: overlap the clipped set again before a layout."""
+    rows, _ = self.overlap_strands_sharded(reads, mask, R, max_trial, overlap_min, targets_per_call, kernel, strands=strands,
+                                           reads_rc=reads_rc)
+    clip = self.clip(reads, rows, margin, min_cov, min_len, roles, keep_unseen, max_bases)
+    clipped, table = clip.apply(reads), clip.rows()
+    stats = clip.stats
+    clip.close()
+    return clipped, table, rows, stats
+
+
+Context.clip = _clip
+Context.clip_coverage = _clip_coverage
+Context.clip_reads = _clip_reads
 
 
 def script_vals(ops: np.ndarray, seg: bytes, fwd: bool = True) -> bytes:
