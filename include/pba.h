@@ -1108,6 +1108,76 @@ int pba_clip_apply(pba_ctx *ctx, const pba_clip *clip, const pba_seqs *reads, pb
 int pba_clip_last_stats(const pba_clip *clip, pba_clip_stats *out);
 void pba_clip_destroy(pba_clip *clip);
 
+/* ------------------------------------------------------------------------ */
+/* Homopolymer compression (HPC).  Not a step the reference has.  Long-read  */
+/* errors concentrate in the LENGTH of homopolymer runs; a 16-base seed       */
+/* window that spans a run with a length error does not hit, and the banded  */
+/* aligner spends its R budget on such errors.  So: seed and align on the     */
+/* sequence with every run collapsed to one base, and carry the coordinates   */
+/* back.  For a sequence x of L bases over ACGT:                              */
+/*   head     position p is a run head iff p == 0 or x[p] != x[p - 1]         */
+/*   hpc(x)   the bases at the heads, in order; H = their number              */
+/*   S        S[k] = the position of head k, k < H; S[H] = L; strictly        */
+/*            increasing; L == 0: H == 0 and S == [0]                         */
+/* Two facts the row rules rest on: hpc(rc(x)) == rc(hpc(x)), and             */
+/* hpc(x[S[b]:S[e]]) == hpc(x)[b:e].  (tests/hpc_ref.py restates */
+/* all of this in plain numpy.)                                               */
+/* ------------------------------------------------------------------------ */
+typedef struct pba_hpc pba_hpc;            /* the run starts of one compression, resident on the device */
+typedef struct {
+    uint32_t n_seqs, max_len_in, max_len_out, n_chunks;
+    uint64_t n_bases_in, n_bases_out;
+    float heads_ms, emit_ms, pack_ms;      /* HIP events on the ctx's stream, summed over the chunks */
+} pba_hpc_stats;
+/* *out: hpc of every sequence of src as a NEW plain set of the same count and ids, in pba_seqs_from_text's layout -- byte for
+ * byte what pba_seqs_from_text makes of the compressed texts -- whatever layout src has (a binary read file's records
+ * included, as for pba_seqs_revcomp): the kernels read the bit planes.  An empty sequence stays an empty sequence; a set of 0
+ * sequences is legal.  PBA_E_ALPHABET if src holds bytes outside ACGT (code 3 stands for N as well as T: a run of TNT would
+ * collapse).  No base crosses the host.
+ * *map (nullable: not wanted): S of every sequence, for the lift calls below.  It costs 4 bytes per compressed base plus 8 per
+ * sequence, in one device allocation (a bitmap-and-select form would be smaller: not offered); the lengths stay on the host.
+ * src goes through in chunks of consecutive sequences of at most max_bases input bases -- 0: the largest that keeps every
+ * 32-bit counter of a chunk below 2^31; a chunk holds one sequence at least -- and the answer does not depend on the cut.
+ * Work buffers come from the ctx's pool (pba_ctx_trim). */
+int pba_seqs_hpc(pba_ctx *ctx, const pba_seqs *src, uint64_t max_bases /* 0 = default */,
+                 pba_seqs **out, pba_hpc **map /* nullable */, pba_hpc_stats *stats /* nullable */);
+uint32_t pba_hpc_count(const pba_hpc *m);
+/* L and H of every sequence, at most cap entries each */
+int pba_hpc_lengths(const pba_hpc *m, uint32_t *len_in, uint32_t *len_out, uint32_t cap);   /* either nullable */
+/* S[0 .. H] of one sequence: *n = H + 1, at most cap entries written; seq outside the set: PBA_E_INVALID */
+int pba_hpc_run_starts(pba_ctx *ctx, const pba_hpc *m, uint32_t seq, uint32_t *starts, uint32_t cap, uint32_t *n);
+/* Rows of pba_overlap_strands on the COMPRESSED set (m: its map) into rows on the original set.  A half-open interval [b, e)
+ * on the forward strand of hpc(x) lifts to [S[b], S[e]) on the forward strand of x; because rc and hpc commute, a strand -1
+ * row lifts with the same forward-strand S of each read (the ends it carries are forward-strand already).  Lq = the
+ * original query length:
+ *   target, query, strand, dir, cost   copied: THE COST STAYS THAT OF THE COMPRESSED ALIGNMENT
+ *   t_beg, t_end through S of the target, q_beg, q_end through S of the query
+ *   matlen_a = t_end - t_beg, matlen_b = q_end - q_beg
+ *   ref_pos  dir +1: t_beg;  dir -1: t_end - 16 (not clamped)
+ *   j        with [qb, qe) the walked query interval -- strand +1: [q_beg, q_end); strand -1: [Lq - q_end, Lq - q_beg) --
+ *            dir +1: qb;  dir -1: Lq - qe
+ * so the interval identities stated for pba_strand_overlap hold of the lifted row, and pba_overlap_row_pair and
+ * pba_layout_place's anchor arithmetic work on it.  pba_clip_*, pba_layout_create, pba_layout_place, pba_pileup_vote_placed
+ * (so pba_layout_consensus) take lifted rows: they read ids, strand, dir, cost and the interval ends, and do not hold a row to
+ * its cost or match lengths.  pba_pileup_vote and pba_overlap_rows_cigar DO hold a row to its cost: they refuse lifted rows as
+ * they refuse any row that is not an alignment of the sets given.  Re-aligning lifted rows in original space is not offered.
+ * Checked on the host before anything is uploaded, against the compressed lengths the map remembers: ids, self pairs,
+ * strand, dir, intervals non-empty and inside (PBA_E_INVALID).  The rows go up once through the ctx's pooled row buffer, a
+ * lane per row, and come back; out may alias rows; n == 0 is legal. */
+int pba_hpc_lift_overlaps(pba_ctx *ctx, const pba_hpc *m, const pba_strand_overlap *rows, uint64_t n,
+                          pba_strand_overlap *out /* may alias rows */);
+/* Rows of pba_map_reads of the compressed reads (reads_map) against the compressed contigs (target_map).  found == 0 rows are
+ * copied unchanged.  Otherwise read, nseq, found, strand, contig, cost, n_pairs, diag_cost are copied (the cost stays that of
+ * the compressed alignment); r_beg / r_end go through the read's S, c_beg / c_end through the contig's; pos = c_beg;
+ * matlen_b = c_end - c_beg, matlen_a = r_end - r_beg; j = r_beg for strand +1, Lr - r_end for strand -1 (Lr = the original
+ * read length); seglen = Lr - j.  pba_pileup_vote_mapped takes lifted rows; pba_map_rows_cigar holds a row to its cost and
+ * refuses them.  Checked on the host: a found row with a strand other than +1 / -1, a read or contig outside its map, or an
+ * interval empty or outside its compressed sequence is PBA_E_INVALID.  n == 0 is legal. */
+int pba_hpc_lift_map_rows(pba_ctx *ctx, const pba_hpc *reads_map, const pba_hpc *target_map,
+                          const pba_map_row *rows, uint64_t n, pba_map_row *out /* may alias rows */);
+int pba_hpc_last_stats(const pba_hpc *m, pba_hpc_stats *out);
+void pba_hpc_destroy(pba_hpc *m);
+
 const char *pba_strerror(int status);
 
 #ifdef __cplusplus

@@ -101,6 +101,12 @@ class PbaClipStats(C.Structure):
                 ("gather_ms", C.c_float)]
 
 
+class PbaHpcStats(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("n_seqs", "max_len_in", "max_len_out", "n_chunks")] + \
+               [("n_bases_in", C.c_uint64), ("n_bases_out", C.c_uint64), ("heads_ms", C.c_float), ("emit_ms", C.c_float),
+                ("pack_ms", C.c_float)]
+
+
 PBA_CLIP_DROPPED, PBA_CLIP_WHOLE, PBA_CLIP_CUT = 0, 1, 2
 PBA_CLIP_TARGETS, PBA_CLIP_QUERIES, PBA_CLIP_KEEP_UNSEEN = 1, 2, 4
 PBA_FX_AUTO, PBA_FX_FASTA, PBA_FX_FASTQ = 0, 1, 2
@@ -272,6 +278,14 @@ SYMBOLS = {
     "pba_clip_apply": (C.c_int, [_P, _P, _P, C.POINTER(_P)]),
     "pba_clip_last_stats": (C.c_int, [_P, _P]),
     "pba_clip_destroy": (None, [_P]),
+    "pba_seqs_hpc": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(_P), C.POINTER(_P), _P]),
+    "pba_hpc_count": (C.c_uint32, [_P]),
+    "pba_hpc_lengths": (C.c_int, [_P, _P, _P, C.c_uint32]),
+    "pba_hpc_run_starts": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "pba_hpc_lift_overlaps": (C.c_int, [_P, _P, _P, C.c_uint64, _P]),
+    "pba_hpc_lift_map_rows": (C.c_int, [_P, _P, _P, _P, C.c_uint64, _P]),
+    "pba_hpc_last_stats": (C.c_int, [_P, _P]),
+    "pba_hpc_destroy": (None, [_P]),
     "pba_cigar_bound": (C.c_uint32, [C.c_int, C.c_int, C.c_double]),
     "pba_align_batch_cigar": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_double, C.c_int, C.c_int, C.c_uint32, _P, _P, _P, _P, _P]),
     "pba_cigar_from_script": (C.c_int, [_P, C.c_int32, _P, _P, C.c_uint32, _P, C.c_int32, _P]),

@@ -1,6 +1,6 @@
 // pba_host.h -- host-side objects and helpers shared by the translation units of libpba.so (pba_core.hip: context,
 // sequence sets; pba_index.hip: seed index; pba_align.hip: explicit pairs and edit scripts; pba_drivers.hip: the reference's ordered
-// first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction; pba_stream.hip: streamed locate and mapping; pba_layout.hip: layout; pba_clip.hip: clipping; pba_fastx.hip: FASTA / FASTQ in, FASTA out).  Internal: nothing here is part of
+// first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction; pba_stream.hip: streamed locate and mapping; pba_layout.hip: layout; pba_clip.hip: clipping; pba_hpc.hip: homopolymer compression; pba_fastx.hip: FASTA / FASTQ in, FASTA out).  Internal: nothing here is part of
 // the C ABI (include/pba.h).
 // Also here, once for all of them: the clip of seq_aligner.h:94-102 (text_clip), the launch plan (make_plan), the host
 // protocol of every aligning entry point but the all-vs-all walk -- narrow window first, the uncertified items again at the
@@ -155,7 +155,9 @@ static const int kRowSweepLdsCap = 96 * 1024;   // LDS bytes one wavefront may t
 enum { POOL_OVL_CAND = 0, POOL_OVL_TMP, POOL_OVL_ITEMS, POOL_OVL_REDO, POOL_OVL_REDO_IN, POOL_OVL_OUT, POOL_OVL_SMALL,
        POOL_LOC_ROWS, POOL_LOC_AUX, POOL_REDO_IDS, POOL_IX_OFFS, POOL_IX_WORK, POOL_OVL_BLOOM, POOL_OVL_ENDS,
        POOL_TXT_IN, POOL_TXT_OUT, POOL_TXT_PAR, POOL_TXT_CST, POOL_LOC_IDS, POOL_LOC_CTG, POOL_LAY_WORK, POOL_LAY_ROWS,
-       POOL_FX_FILE, POOL_FX_TILES, POOL_FX_LINES, POOL_FX_RECS, POOL_FX_IMG, POOL_CLIP_ARENA, POOL_CLIP_WORK, POOL_CLIP_TEXT };
+       POOL_FX_FILE, POOL_FX_TILES, POOL_FX_LINES, POOL_FX_RECS, POOL_FX_IMG, POOL_CLIP_ARENA, POOL_CLIP_WORK, POOL_CLIP_TEXT,
+       POOL_HPC_WORK, POOL_HPC_TEXT, POOL_COUNT };
+static_assert(POOL_COUNT <= 32, "pba_ctx::pool has 32 slots");
 // a buffer of at least `bytes` in pool slot `slot` (contents undefined); grows by reallocation with 1/8 headroom
 static inline int pool_reserve(pba_ctx *ctx, int slot, size_t bytes, void **out) {
     if (ctx->pool[slot].cap < bytes) {

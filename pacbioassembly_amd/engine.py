@@ -1428,6 +1428,84 @@ Context.clip_coverage = _clip_coverage
 Context.clip_reads = _clip_reads
 
 
+class Hpc:
+    """The run starts of one homopolymer compression, resident on the device (pba_hpc): S[k] = the original position of head k of
+    every sequence, S[H] = L.  lengths(): (L, H) of every sequence; run_starts(i): S of one; lift_overlaps / lift_map_rows: rows
+    found on the compressed set into rows on the original one.  A lifted row keeps the cost of the compressed alignment."""
+
+    def __init__(self, ctx: "Context", h):
+        self.ctx, self.h = ctx, h
+        self.n = int(ctx.lib.pba_hpc_count(h))
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.ctx.lib.pba_hpc_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def stats(self) -> dict:
+        st = _lib.PbaHpcStats()
+        self.ctx.check(self.ctx.lib.pba_hpc_last_stats(self.h, C.byref(st)), "hpc_last_stats")
+        return {n: getattr(st, n) for n, _ in _lib.PbaHpcStats._fields_}
+
+    def lengths(self):
+        """(original lengths, compressed lengths), one u32 each per sequence."""
+        a, b = np.zeros(max(self.n, 1), np.uint32), np.zeros(max(self.n, 1), np.uint32)
+        self.ctx.check(self.ctx.lib.pba_hpc_lengths(self.h, _ptr(a), _ptr(b), self.n), "hpc_lengths")
+        return a[:self.n], b[:self.n]
+
+    def run_starts(self, i: int) -> np.ndarray:
+        """S[0 .. H] of sequence i (H + 1 entries, the last one its original length)."""
+        n = C.c_uint32()
+        self.ctx.check(self.ctx.lib.pba_hpc_run_starts(self.ctx.h, self.h, i, None, 0, C.byref(n)), "hpc_run_starts")
+        out = np.zeros(n.value, np.uint32)
+        self.ctx.check(self.ctx.lib.pba_hpc_run_starts(self.ctx.h, self.h, i, _ptr(out), n.value, C.byref(n)), "hpc_run_starts")
+        return out
+
+    def lift_overlaps(self, rows: np.ndarray) -> np.ndarray:
+        """overlap_strands rows of the compressed set as rows of the original set (pba_hpc_lift_overlaps); a new array."""
+        out = np.array(rows, STRAND_OVERLAP_DTYPE, order="C")
+        self.ctx.check(self.ctx.lib.pba_hpc_lift_overlaps(self.ctx.h, self.h, _ptr(out), out.size, _ptr(out)), "hpc_lift_overlaps")
+        return out
+
+    def lift_map_rows(self, rows: np.ndarray, target_hpc: "Hpc") -> np.ndarray:
+        """map_reads rows of the compressed reads (this map) against the compressed contigs (target_hpc) as rows of the original
+        sets (pba_hpc_lift_map_rows); a new array."""
+        out = np.array(rows, MAP_ROW_DTYPE, order="C")
+        self.ctx.check(self.ctx.lib.pba_hpc_lift_map_rows(self.ctx.h, self.h, target_hpc.h, _ptr(out), out.size, _ptr(out)),
+                       "hpc_lift_map_rows")
+        return out
+
+
+def _seqs_hpc(self, S, max_bases=0):
+    """(SeqSet, Hpc): S with every homopolymer run collapsed to one base, written on the device in seqs_from_text's layout
+    whatever layout S has, and the map that lifts rows found on it back (pba_seqs_hpc).  max_bases: input bases per internal
+    chunk (0 = the default); the result does not depend on it."""
+    h, mh = C.c_void_p(), C.c_void_p()
+    self.check(self.lib.pba_seqs_hpc(self.h, S.h, max_bases, C.byref(h), C.byref(mh), None), "seqs_hpc")
+    return SeqSet(self, h), Hpc(self, mh)
+
+
+def _overlap_hpc(self, reads, mask, R, max_trial=32, overlap_min=64, strands=3, targets_per_call=10000, kernel=PBA_KERNEL_AUTO):
+    """seqs_hpc -> overlap_strands_sharded on the compressed reads -> lift_overlaps.  Returns (rows in the coordinates of `reads`,
+    [stats of the +1 pass, of the -1 pass], the Hpc).  overlap_min and R apply to the compressed texts; a row's cost is that of
+    the compressed alignment: clip / layout / layout_consensus take the rows, pileup_vote and overlap_rows_cigar refuse them."""
+    comp, hpc = self.seqs_hpc(reads)
+    rows, st2 = self.overlap_strands_sharded(comp, mask, R, max_trial, overlap_min, targets_per_call, kernel, strands=strands)
+    comp.close()
+    return hpc.lift_overlaps(rows), st2, hpc
+
+
+Context.seqs_hpc = _seqs_hpc
+Context.overlap_hpc = _overlap_hpc
+
+
 def script_vals(ops: np.ndarray, seg: bytes, fwd: bool = True) -> bytes:
     """edits[k].val of an edit script (seq_aligner.h:218,224): the b element a MATCH / INSERT consumes, 0 for a DELETE.
     seg: the accessor's elements in memory order (a backward accessor starts at its last byte)."""
