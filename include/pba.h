@@ -326,7 +326,10 @@ int pba_align_text(pba_ctx *ctx, const char *a, int a_fwd, int a_len, const char
  * 2 INSERT, 3 DELETE in the order seq_aligner::edits[] holds them (the `val` of a MATCH / INSERT is the b
  * element it consumes, which the caller can read off b while replaying the ops).
  * Text form: raw bytes, full-band row sweep with one parent code per band cell in HBM
- * ((len_a+1) * (2*max_dst+1) bytes): for single pairs (display, the compat seq_aligner). */
+ * ((len_a+1) * (2*max_dst+1) bytes): for single pairs (display, the compat seq_aligner).
+ * *nedit is always the full length of the script (0 when rc < 0); ops receives its first min(*nedit, ops_cap) ops in
+ * edits[] order (the origin's end of the path), whichever kernel answers, and no byte of ops behind them is written.
+ * ops_cap = a_len + b_len always holds the whole script. */
 int pba_align_text_trace(pba_ctx *ctx, const char *a, int a_fwd, int a_len, const char *b, int b_fwd, int b_len,
                          double R, int maxn, int maxm, pba_result *out, uint8_t *ops, int32_t ops_cap, int32_t *nedit);
 /* The DP matrix itself, for callers that read it (seq_aligner<>::mat, get_cost / get_parent, seq_aligner.h:81,131-134;

@@ -173,7 +173,17 @@ k_cigar_pairs(SeqSetDev A, SeqSetDev B, const pba_pair *pairs, const uint32_t *i
     }
 }
 
-// find_path (seq_aligner.h:214-233) walked iteratively from the goal cell; one thread per pair
+// find_path (seq_aligner.h:214-233) walked iteratively from the goal cell; one thread per pair.  The walk meets the ops
+// goal-first and the caller gets them origin-first, the first min(nedit, cap) of them (pba.h): so the path is walked twice,
+// once for its length K and once to put the op met k-th at o[K - 1 - k] where that is inside the cap.
+__device__ __forceinline__ int trace_walk_step(const uint8_t *p, int W, int md, int &i, int &j) {
+    int src;
+    if (j == 0) src = 3;                       // init_cell: (i,0) has parent DELETE, (0,j) INSERT (seq_aligner.h:140-147)
+    else if (i == 0) src = 2;
+    else src = p[(size_t)i * W + (j - i + md)];
+    if (src == 1) { --i; --j; } else if (src == 2) --j; else --i;
+    return src;
+}
 __global__ void k_trace_walk(const pba_result *res, const uint8_t *par, const uint64_t *par_off, uint8_t *ops,
                              const uint64_t *ops_off, int32_t *nedit, uint32_t n) {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -186,17 +196,17 @@ __global__ void k_trace_walk(const pba_result *res, const uint8_t *par, const ui
     const int md = r.max_dst, W = 2 * md + 1;
     int i = r.matlen_a, j = r.matlen_b;
     uint64_t k = 0;
-    while (i > 0 || j > 0) {
-        int src;
-        if (j == 0) src = 3;                   // init_cell: (i,0) has parent DELETE, (0,j) INSERT (seq_aligner.h:140-147)
-        else if (i == 0) src = 2;
-        else src = p[(size_t)i * W + (j - i + md)];
-        if (k < capq) o[k] = (uint8_t)src;
-        ++k;
-        if (src == 1) { --i; --j; } else if (src == 2) --j; else --i;
+    if ((uint64_t)i + (uint64_t)j <= capq) {   // room for any path (a batch always: check_pairs): one walk, reversed in place
+        while (i > 0 || j > 0) o[k++] = (uint8_t)trace_walk_step(p, W, md, i, j);
+        for (uint64_t x = 0, y = k; x + 1 < y; ++x) { --y; const uint8_t t = o[x]; o[x] = o[y]; o[y] = t; }   // goal-first -> origin-first
+    } else {
+        while (i > 0 || j > 0) { trace_walk_step(p, W, md, i, j); ++k; }
+        i = r.matlen_a; j = r.matlen_b;
+        for (uint64_t x = k; x-- > 0;) {
+            const int src = trace_walk_step(p, W, md, i, j);
+            if (x < capq) o[x] = (uint8_t)src;
+        }
     }
-    const uint64_t m = k < capq ? k : capq;
-    for (uint64_t x = 0, y = m; x + 1 < y; ++x) { --y; const uint8_t t = o[x]; o[x] = o[y]; o[y] = t; }   // goal-first -> origin-first
     nedit[q] = (int32_t)k;
 }
 
