@@ -94,6 +94,16 @@ int pba_ctx_sync(pba_ctx *ctx);
 /* The ctx keeps the work buffers of its drivers between calls (candidate arrays, per-read rows, traceback scratch: mapping
  * gigabytes anew costs more than the kernels that use them).  pba_ctx_trim gives them back to the device. */
 int pba_ctx_trim(pba_ctx *ctx);
+/* Test support: what a call finds in a buffer the ctx kept from an earlier call is undefined, and these two make that
+ * testable.  pba_ctx_kept_bytes: the capacity in bytes of everything the ctx keeps between calls -- its pool slots in the
+ * order of the internal enum (n_pool of them), the three idle arrays of the index cache (entries, offsets, the entry buffer
+ * a build did not keep), the trace / vote scratch, the pinned staging buffer and the work-queue counters; 0 = not allocated.
+ * pba_ctx_scribble: every one of them, over its whole capacity, set to `byte` (its low 8 bits); allocates nothing and frees
+ * nothing.  No call may be in flight on the ctx, and open pba_loc_stream / pba_map_stream objects must be idle (nothing
+ * submitted and not collected): the stream is synchronised before and after, but a batch in flight reads these buffers. */
+typedef struct { uint32_t n_pool; uint64_t pool[32]; uint64_t ix_cache[3]; uint64_t scratch, stage, queue; } pba_kept_bytes;
+int pba_ctx_kept_bytes(pba_ctx *ctx, pba_kept_bytes *out);
+int pba_ctx_scribble(pba_ctx *ctx, int byte);
 /* HIP-event timings (on the ctx's stream) of the most recent pba_index_build / pba_locate /
  * pba_align_batch / pba_spaced_round on this ctx: measurement support for bench.py.
  * The all-vs-all entry points (pba_overlap_all*, pba_overlap_strands*: the profile of the last pass) fill the four ring

@@ -124,6 +124,20 @@ class PbaFastxStats(C.Structure):
                 ("h2d_ms", C.c_float), ("parse_ms", C.c_float), ("pack_ms", C.c_float)]
 
 
+# the ctx's pool slots (csrc/pba_host.h: the POOL_* enum, in its order), as pba_kept_bytes.pool[] lists them
+POOL_SLOTS = ("POOL_OVL_CAND", "POOL_OVL_TMP", "POOL_OVL_ITEMS", "POOL_OVL_REDO", "POOL_OVL_REDO_IN", "POOL_OVL_OUT", "POOL_OVL_SMALL",
+              "POOL_LOC_ROWS", "POOL_LOC_AUX", "POOL_REDO_IDS", "POOL_IX_OFFS", "POOL_IX_WORK",
+              "POOL_TXT_IN", "POOL_TXT_OUT", "POOL_TXT_PAR", "POOL_TXT_CST", "POOL_LOC_IDS", "POOL_LOC_CTG", "POOL_LAY_WORK", "POOL_LAY_ROWS",
+              "POOL_FX_FILE", "POOL_FX_TILES", "POOL_FX_LINES", "POOL_FX_RECS", "POOL_FX_IMG", "POOL_CLIP_ARENA", "POOL_CLIP_WORK",
+              "POOL_CLIP_TEXT", "POOL_HPC_WORK", "POOL_HPC_TEXT")
+IX_CACHE_SLOTS = ("ix_ent", "ix_off", "ix_ent2")
+
+
+class PbaKeptBytes(C.Structure):
+    _fields_ = [("n_pool", C.c_uint32), ("pool", C.c_uint64 * 32), ("ix_cache", C.c_uint64 * 3), ("scratch", C.c_uint64),
+                ("stage", C.c_uint64), ("queue", C.c_uint64)]
+
+
 class PbaSsRow(C.Structure):
     _fields_ = [(n, C.c_int32) for n in
                 ("read", "found", "j", "dir", "ref_pos", "cost", "matlen_a", "matlen_b", "n_trials", "n_pairs")]
@@ -152,6 +166,8 @@ SYMBOLS = {
     "pba_ctx_set_stream": (C.c_int, [_P, _P]),
     "pba_ctx_sync": (C.c_int, [_P]),
     "pba_ctx_trim": (C.c_int, [_P]),
+    "pba_ctx_kept_bytes": (C.c_int, [_P, _P]),
+    "pba_ctx_scribble": (C.c_int, [_P, C.c_int]),
     "pba_ctx_last_profile": (C.c_int, [_P, _P]),
     "pba_ctx_device_info": (C.c_int, [_P, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                       C.POINTER(C.c_uint64)]),

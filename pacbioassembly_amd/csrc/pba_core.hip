@@ -163,6 +163,35 @@ int pba_ctx_trim(pba_ctx *ctx) {
     return PBA_OK;
 }
 
+// ---- test support: what the ctx keeps between calls, and all of it overwritten (pba.h)
+int pba_ctx_kept_bytes(pba_ctx *ctx, pba_kept_bytes *out) {
+    if (!ctx || !out) return PBA_E_INVALID;
+    memset(out, 0, sizeof *out);
+    out->n_pool = POOL_COUNT;
+    for (int s = 0; s < POOL_COUNT; ++s) out->pool[s] = ctx->pool[s].p ? ctx->pool[s].cap : 0;
+    for (int s = 0; s < 3; ++s) out->ix_cache[s] = ctx->ix_cache.slot[s].p ? ctx->ix_cache.slot[s].cap : 0;
+    out->scratch = ctx->d_scratch ? ctx->scratch_bytes : 0;
+    out->stage = ctx->h_stage ? ctx->h_stage_cap : 0;
+    out->queue = 64;
+    return PBA_OK;
+}
+
+int pba_ctx_scribble(pba_ctx *ctx, int byte) {
+    if (!ctx) return PBA_E_INVALID;
+    const int v = byte & 0xFF;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (int s = 0; s < POOL_COUNT; ++s)
+        if (ctx->pool[s].p) HIPCHK(memset_big(ctx->pool[s].p, v, ctx->pool[s].cap, ctx->stream));
+    if (ctx->d_scratch) HIPCHK(memset_big(ctx->d_scratch, v, ctx->scratch_bytes, ctx->stream));
+    for (auto &x : ctx->ix_cache.slot)
+        if (x.p) HIPCHK(memset_big(x.p, v, x.cap, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_queue, v, 64, ctx->stream));
+    if (ctx->h_stage) memset(ctx->h_stage, v, ctx->h_stage_cap);
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return PBA_OK;
+}
+
 const char *pba_ctx_error(const pba_ctx *ctx) { return ctx ? ctx->err : "null ctx"; }
 
 int pba_ctx_set_stream(pba_ctx *ctx, void *hip_stream) {

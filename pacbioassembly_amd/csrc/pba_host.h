@@ -153,7 +153,7 @@ static const int kRowSweepLdsCap = 96 * 1024;   // LDS bytes one wavefront may t
 
 // pool slots
 enum { POOL_OVL_CAND = 0, POOL_OVL_TMP, POOL_OVL_ITEMS, POOL_OVL_REDO, POOL_OVL_REDO_IN, POOL_OVL_OUT, POOL_OVL_SMALL,
-       POOL_LOC_ROWS, POOL_LOC_AUX, POOL_REDO_IDS, POOL_IX_OFFS, POOL_IX_WORK, POOL_OVL_BLOOM, POOL_OVL_ENDS,
+       POOL_LOC_ROWS, POOL_LOC_AUX, POOL_REDO_IDS, POOL_IX_OFFS, POOL_IX_WORK,
        POOL_TXT_IN, POOL_TXT_OUT, POOL_TXT_PAR, POOL_TXT_CST, POOL_LOC_IDS, POOL_LOC_CTG, POOL_LAY_WORK, POOL_LAY_ROWS,
        POOL_FX_FILE, POOL_FX_TILES, POOL_FX_LINES, POOL_FX_RECS, POOL_FX_IMG, POOL_CLIP_ARENA, POOL_CLIP_WORK, POOL_CLIP_TEXT,
        POOL_HPC_WORK, POOL_HPC_TEXT, POOL_COUNT };

@@ -247,6 +247,24 @@ class Context:
         """Give the work buffers kept between calls back to the device (pba_ctx_trim)."""
         self.check(self.lib.pba_ctx_trim(self.h), "trim")
 
+    def kept_bytes(self) -> dict:
+        """Test support: the capacity in bytes of every buffer the ctx keeps between calls (pba_ctx_kept_bytes), keyed by
+        _lib.POOL_SLOTS, "ix_ent" / "ix_off" / "ix_ent2", "scratch", "stage" and "queue"; 0 = not allocated."""
+        kb = _lib.PbaKeptBytes()
+        self.check(self.lib.pba_ctx_kept_bytes(self.h, C.byref(kb)), "kept_bytes")
+        if kb.n_pool != len(_lib.POOL_SLOTS):
+            raise PbaError(_lib.PBA_E_INVALID, f"kept_bytes: the library has {kb.n_pool} pool slots, _lib.POOL_SLOTS names {len(_lib.POOL_SLOTS)}")
+        out = {name: int(kb.pool[i]) for i, name in enumerate(_lib.POOL_SLOTS)}
+        out["scratch"] = int(kb.scratch)
+        out.update({name: int(kb.ix_cache[i]) for i, name in enumerate(_lib.IX_CACHE_SLOTS)})
+        out.update(queue=int(kb.queue), stage=int(kb.stage))
+        return out
+
+    def scribble(self, byte: int):
+        """Test support: every kept buffer, over its whole capacity, set to `byte` (pba_ctx_scribble).  No call may be in
+        flight and open streams must be idle."""
+        self.check(self.lib.pba_ctx_scribble(self.h, int(byte) & 0xFF), "scribble")
+
     def last_profile(self) -> dict:
         pr = _lib.PbaProfile()
         self.check(self.lib.pba_ctx_last_profile(self.h, C.byref(pr)), "last_profile")
