@@ -1191,6 +1191,75 @@ int pba_hpc_lift_map_rows(pba_ctx *ctx, const pba_hpc *reads_map, const pba_hpc 
 int pba_hpc_last_stats(const pba_hpc *m, pba_hpc_stats *out);
 void pba_hpc_destroy(pba_hpc *m);
 
+/* ------------------------------------------------------------------------ */
+/* Seed-key census and repeat masking of overlap probes.  Not a step the     */
+/* reference has.  A probe that lands in a transposon, an rRNA operon or a   */
+/* satellite matches every copy in every read that covers one: candidates    */
+/* grow with the square of the copy number and the layout is handed rows     */
+/* between reads that share a repeat but no locus.  Every overlapper caps    */
+/* seed occurrence (minimap2 -f, MHAP's k-mer filter, daligner -t).  Here:   */
+/* count the keys, overwrite the probe entries of over-frequent keys with    */
+/* the all-ones padding the probe table skips, build the table as before.    */
+/* No existing kernel changes.  (tests/census_ref.py restates  */
+/* the rule in plain numpy.)                                                 */
+/* ------------------------------------------------------------------------ */
+/* A census belongs to a mask m (m != 0, at most 26 care bits: the probe table's direct addressing, one u32 counter per value
+ * of the care bits) and a visiting mode (pba_index_mode).  count[key], key != 0, is the number of (sequence, visited position)
+ * pairs whose window & m equals key; the visited positions of a sequence are exactly those its seed index visits in that mode
+ * (PBA_INDEX_HEAD_TAIL: ref_seq::get_seedmap's; PBA_INDEX_ALL: every position [0, len), windows past the end padded with code
+ * 3).  In PBA_INDEX_HEAD_TAIL mode over a read set that is the number of target positions a probe with that key would match in
+ * an all-vs-all call, the probing read's own positions included.  A zero key is never counted (n_zero_keys).  Sequences are
+ * counted as packed: a byte outside ACGT is code 3, as in the index; no set is refused for its alphabet.
+ * Refusals, decided on the host before any launch: PBA_E_INVALID for a NULL, lo > hi or hi beyond the set, mask 0, a mode
+ * other than the two; PBA_E_TOOLONG for a mask with more than 26 care bits and for a census whose visited positions would reach
+ * 2^32 (a counter is 32 bits; summed in 64 bits from the host lengths).  The counters belong to the census; scratch comes from
+ * the ctx's pool: a repeated add / lookup / mask_probes allocates nothing. */
+typedef struct pba_census pba_census;
+typedef struct {
+    uint32_t n_seqs, bits;                       /* sequences counted so far (create and every add); care bits of the mask */
+    uint64_t n_visited, n_counted, n_zero_keys;  /* n_visited = n_counted + n_zero_keys, over create and every add */
+    float count_ms;                              /* HIP events on the ctx's stream around the count kernels, summed */
+} pba_census_stats;
+/* sequences [lo, hi) of s counted into new counters */
+int pba_census_create(pba_ctx *ctx, const pba_seqs *s, uint32_t lo, uint32_t hi, uint32_t mask, int mode, pba_census **out);
+/* further ranges, or ranges of other sets, into the same counters */
+int pba_census_add(pba_ctx *ctx, pba_census *c, const pba_seqs *s, uint32_t lo, uint32_t hi);
+/* counts[i] = count[keys[i] & mask]; a key whose masked value is 0 gives 0 */
+int pba_census_lookup(pba_ctx *ctx, const pba_census *c, const uint32_t *keys, uint32_t n, uint32_t *counts);
+/* hist: cap >= 2 slots.  hist[0] = counters never counted (2^bits - n_distinct, the zero key's among them); hist[v] for
+ * 1 <= v < cap - 1 = distinct keys with count exactly v; hist[cap - 1] = keys with count >= cap - 1.  n_distinct and max_count
+ * (both nullable) are exact whatever cap is. */
+int pba_census_histogram(pba_ctx *ctx, const pba_census *c, uint64_t *hist, uint32_t cap, uint64_t *n_distinct, uint32_t *max_count);
+/* Host arithmetic, no ctx: the occurrence cutoff that gives up at most `fraction` of the distinct keys.  With
+ * n_distinct = hist[1] + .. + hist[cap - 1] and budget = (uint64_t)(fraction * n_distinct) in FP64 as written: *max_occ = the
+ * smallest c in [max(floor, 1), cap - 2] for which the distinct keys with count > c number at most budget.  No such c (too many
+ * keys sit in the lumped last slot, or the interval is empty): PBA_E_TOOLONG, ask for a longer histogram.  fraction outside
+ * [0, 1] or NaN, cap < 2, a NULL: PBA_E_INVALID. */
+int pba_census_cutoff(const uint64_t *hist, uint32_t cap, double fraction, uint32_t floor, uint32_t *max_occ);
+/* Per sequence of s (any set, not only the one counted; the census's mode): n_over[i] = visited positions whose key is nonzero
+ * with count > max_occ, n_visited[i] = visited positions.  cap below the number of sequences: PBA_E_INVALID.  For flagging reads
+ * that are mostly repeat. */
+int pba_census_read_repeats(pba_ctx *ctx, const pba_census *c, const pba_seqs *s, uint32_t max_occ, uint32_t *n_over,
+                            uint32_t *n_visited, uint32_t cap);
+/* In place on the DEVICE buffer pba_overlap_probes filled (or an all-gathered one), n_slots entries: an entry that is not
+ * all-ones and whose key has count > max_occ becomes all-ones; *n_masked = entries changed.  Idempotent.  mask must be the
+ * census's (PBA_E_INVALID). */
+int pba_census_mask_probes(pba_ctx *ctx, const pba_census *c, void *d_entries, uint64_t n_slots, uint32_t mask, uint32_t max_occ,
+                           uint64_t *n_masked);
+/* pba_overlap_strands with the probes of over-frequent keys left out of both probe tables.  Composed of public calls only:
+ * pba_seqs_revcomp (reads_rc == NULL), then per strand pba_overlap_probes, pba_census_mask_probes, pba_probe_table_create, and
+ * pba_overlap_strands_table.  One census of the FORWARD reads serves both strands: targets are always forward, and the probes
+ * of rc(q) are looked up in the same counters.  c must be a PBA_INDEX_HEAD_TAIL census under `mask` (PBA_E_INVALID).  Rows, order,
+ * stats and refusals are pba_overlap_strands'; stats[s].n_probe_entries is what the masked table holds; n_masked[s] (nullable)
+ * the entries taken out.  max_occ = UINT32_MAX masks nothing: the call equals pba_overlap_strands row for row.  A probe whose
+ * key no read's index visits (count 0) is never masked and never matches. */
+int pba_overlap_strands_masked(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc /* nullable: built inside */,
+                               uint32_t t_lo, uint32_t t_hi, uint32_t mask, double R, int max_trial, int overlap_min, int kernel,
+                               int strands, const pba_census *c, uint32_t max_occ, pba_strand_overlap *out, uint64_t cap,
+                               uint64_t *n_out, pba_overlap_stats stats[2], uint64_t n_masked[2]);
+int pba_census_last_stats(const pba_census *c, pba_census_stats *out);
+void pba_census_destroy(pba_census *c);
+
 const char *pba_strerror(int status);
 
 #ifdef __cplusplus

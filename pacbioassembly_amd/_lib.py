@@ -107,6 +107,11 @@ class PbaHpcStats(C.Structure):
                 ("pack_ms", C.c_float)]
 
 
+class PbaCensusStats(C.Structure):
+    _fields_ = [("n_seqs", C.c_uint32), ("bits", C.c_uint32), ("n_visited", C.c_uint64), ("n_counted", C.c_uint64),
+                ("n_zero_keys", C.c_uint64), ("count_ms", C.c_float)]
+
+
 PBA_CLIP_DROPPED, PBA_CLIP_WHOLE, PBA_CLIP_CUT = 0, 1, 2
 PBA_CLIP_TARGETS, PBA_CLIP_QUERIES, PBA_CLIP_KEEP_UNSEEN = 1, 2, 4
 PBA_FX_AUTO, PBA_FX_FASTA, PBA_FX_FASTQ = 0, 1, 2
@@ -302,6 +307,17 @@ SYMBOLS = {
     "pba_hpc_lift_map_rows": (C.c_int, [_P, _P, _P, _P, C.c_uint64, _P]),
     "pba_hpc_last_stats": (C.c_int, [_P, _P]),
     "pba_hpc_destroy": (None, [_P]),
+    "pba_census_create": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_P)]),
+    "pba_census_add": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32]),
+    "pba_census_lookup": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
+    "pba_census_histogram": (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    "pba_census_cutoff": (C.c_int, [_P, C.c_uint32, C.c_double, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "pba_census_read_repeats": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, C.c_uint32]),
+    "pba_census_mask_probes": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "pba_overlap_strands_masked": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, _P, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64), _P, _P]),
+    "pba_census_last_stats": (C.c_int, [_P, _P]),
+    "pba_census_destroy": (None, [_P]),
     "pba_cigar_bound": (C.c_uint32, [C.c_int, C.c_int, C.c_double]),
     "pba_align_batch_cigar": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_double, C.c_int, C.c_int, C.c_uint32, _P, _P, _P, _P, _P]),
     "pba_cigar_from_script": (C.c_int, [_P, C.c_int32, _P, _P, C.c_uint32, _P, C.c_int32, _P]),

@@ -730,9 +730,19 @@ static __global__ void PBA_OVL_WALK_BOUNDS k_ovl_walk_rc(SeqSetDev Rd, SeqSetDev
 // that sort behind (jd*, ord*): for every probe jd > jd* of q that exists (spaced_seed.cpp:426, key != 0) and passes the gate,
 // the visited positions of t with the same masked key, plus the positions behind ord* under the success's own key.
 // pairs = totals[1] - sum over the overlaps.  (~10 k instructions per success, against ~700 k for the alignment itself.)
+// A later probe counts only if the TABLE holds it (pt_holds): the scan made candidates of the table's entries, and a table
+// need not hold every probe of q -- pba_census_mask_probes takes the probes of over-frequent keys out of the entry list.
 #define PBA_OVL_AFTER_SLOTS 512                    // hash slots per wavefront for <= 126 probe keys
+template <bool HASHED>
+__device__ __forceinline__ bool pt_holds(const ProbeTab &T, uint32_t key, uint32_t pe) {   // pe = query << 7 | (2j + backward), as pid[] holds it
+    const uint32_t b = pt_bucket<HASHED>(T, key);
+    for (uint32_t i = T.start[b], e = T.start[b + 1]; i < e; ++i)
+        if (T.pid[i] == pe && (!HASHED || T.pkey[i] == key)) return true;
+    return false;
+}
+template <bool HASHED>
 static __global__ void __launch_bounds__(PBA_WAVE * 4)
-k_ovl_after(SeqSetDev Rd, SeqSetDev Q, const pba_overlap *ov, uint32_t n_ov, uint32_t mask, uint32_t t2, int overlap_min, unsigned long long *after) {
+k_ovl_after(ProbeTab T, SeqSetDev Rd, SeqSetDev Q, const pba_overlap *ov, uint32_t n_ov, uint32_t mask, uint32_t t2, int overlap_min, unsigned long long *after) {
     __shared__ uint32_t h_key[4][PBA_OVL_AFTER_SLOTS], h_cnt[4][PBA_OVL_AFTER_SLOTS];
     const uint32_t lane = threadIdx.x & (PBA_WAVE - 1), wave = threadIdx.x / PBA_WAVE;
     const uint32_t i = blockIdx.x * 4 + wave;
@@ -756,7 +766,7 @@ k_ovl_after(SeqSetDev Rd, SeqSetDev Q, const pba_overlap *ov, uint32_t n_ov, uin
         const uint32_t key = exists ? window_key(qseq, (uint32_t)pos, (uint32_t)slen) & mask : 0u;
         const uint64_t own = __builtin_amdgcn_ballot_w64(jd == jd0);
         if (own) key0 = (uint32_t)__builtin_amdgcn_readlane((int)key, __builtin_ctzll(own));
-        if (key != 0u && jd != jd0) {
+        if (key != 0u && jd != jd0 && pt_holds<HASHED>(T, key, q << PBA_OVL_JD_BITS | jd)) {
             uint32_t h = (key * 0x9E3779B1u) >> (32 - 9);
             for (;;) {
                 const uint32_t old = atomicCAS(&h_key[wave][h], 0u, key);

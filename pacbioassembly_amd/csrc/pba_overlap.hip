@@ -604,8 +604,8 @@ static int ovl_collect(OvlCall &c, pba_overlap *out, uint64_t *n_out) {
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (c.fused && h_cnt[0]) {
         const uint32_t n_ov = (uint32_t)std::min<uint64_t>(h_cnt[0], c.dev_cap);
-        hipLaunchKernelGGL(k_ovl_after, dim3((n_ov + 3) / 4), dim3(PBA_WAVE * 4), 0, ctx->stream, c.reads->dev(), c.qset->dev(), c.d_out.as<pba_overlap>(), n_ov,
-                           c.T.mask, c.ocfg.t2, c.ocfg.overlap_min, c.cnt(CNT_AFTER_SUCCESS));
+        PBA_PT_LAUNCH(c.tab->hashed, k_ovl_after, dim3((n_ov + 3) / 4), dim3(PBA_WAVE * 4), 0, ctx->stream, c.T, c.reads->dev(), c.qset->dev(),
+                      c.d_out.as<pba_overlap>(), n_ov, c.T.mask, c.ocfg.t2, c.ocfg.overlap_min, c.cnt(CNT_AFTER_SUCCESS));
         HIPCHK(hipGetLastError());
         HIPCHK(c.cnt_read(CNT_AFTER_SUCCESS, 1, &h_after));
         HIPCHK(hipStreamSynchronize(ctx->stream));

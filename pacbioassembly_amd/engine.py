@@ -1524,6 +1524,110 @@ Context.seqs_hpc = _seqs_hpc
 Context.overlap_hpc = _overlap_hpc
 
 
+_INDEX_MODES = {"all": PBA_INDEX_ALL, "head_tail": PBA_INDEX_HEAD_TAIL}
+
+
+def census_cutoff(hist: np.ndarray, fraction: float, floor: int = 1) -> int:
+    """pba_census_cutoff (host arithmetic): the smallest occurrence count c >= max(floor, 1) that leaves at most
+    int(fraction * n_distinct) distinct keys above it; PbaError(PBA_E_TOOLONG) when the histogram is too short to tell."""
+    hist = np.ascontiguousarray(hist, np.uint64)
+    out = C.c_uint32()
+    st = _lib.load().pba_census_cutoff(_ptr(hist), hist.size, fraction, floor, C.byref(out))
+    if st != _lib.PBA_OK:
+        raise PbaError(st, "census_cutoff")
+    return int(out.value)
+
+
+class Census:
+    """How often every masked seed key occurs among the positions the seed index visits (pba_census): one u32 counter per
+    value of the mask's care bits, resident on the device."""
+
+    def __init__(self, ctx: "Context", seqs: "SeqSet", mask: int, mode="head_tail", lo: int = 0, hi: Optional[int] = None):
+        self.ctx, self.mask = ctx, mask
+        self.mode = _INDEX_MODES.get(mode, mode)
+        self.h = C.c_void_p()
+        ctx.check(ctx.lib.pba_census_create(ctx.h, seqs.h, lo, seqs.count if hi is None else hi, mask, self.mode, C.byref(self.h)),
+                  "census_create")
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.ctx.lib.pba_census_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, seqs: "SeqSet", lo: int = 0, hi: Optional[int] = None):
+        """further sequences -- of this or of another set -- into the same counters"""
+        self.ctx.check(self.ctx.lib.pba_census_add(self.ctx.h, self.h, seqs.h, lo, seqs.count if hi is None else hi), "census_add")
+        return self
+
+    @property
+    def stats(self) -> dict:
+        st = _lib.PbaCensusStats()
+        self.ctx.check(self.ctx.lib.pba_census_last_stats(self.h, C.byref(st)), "census_last_stats")
+        return {n: getattr(st, n) for n, _ in _lib.PbaCensusStats._fields_}
+
+    def lookup(self, keys) -> np.ndarray:
+        keys = np.ascontiguousarray(keys, np.uint32)
+        out = np.zeros(keys.size, np.uint32)
+        self.ctx.check(self.ctx.lib.pba_census_lookup(self.ctx.h, self.h, _ptr(keys), keys.size, _ptr(out)), "census_lookup")
+        return out
+
+    def histogram(self, cap: int = 65536):
+        """(hist u64[cap], n_distinct, max_count): hist[0] = counters never counted, hist[cap - 1] = keys with count >= cap - 1"""
+        hist = np.zeros(max(cap, 0), np.uint64)
+        nd, mx = C.c_uint64(), C.c_uint32()
+        self.ctx.check(self.ctx.lib.pba_census_histogram(self.ctx.h, self.h, _ptr(hist), cap, C.byref(nd), C.byref(mx)), "census_histogram")
+        return hist, int(nd.value), int(mx.value)
+
+    def cutoff(self, fraction: float, floor: int = 1, cap: int = 65536) -> int:
+        return census_cutoff(self.histogram(cap)[0], fraction, floor)
+
+    def read_repeats(self, seqs: "SeqSet", max_occ: int):
+        """(n_over, n_visited) per sequence of seqs: visited positions whose key occurs more than max_occ times, visited positions"""
+        n = seqs.count
+        over, vis = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        self.ctx.check(self.ctx.lib.pba_census_read_repeats(self.ctx.h, self.h, seqs.h, max_occ, _ptr(over), _ptr(vis), n), "census_read_repeats")
+        return over, vis
+
+    def mask_probes(self, d_entries_ptr: int, n_slots: int, max_occ: int, mask: Optional[int] = None) -> int:
+        """in place on a device buffer of probe entries: those of keys with count > max_occ become all-ones; returns how many"""
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.lib.pba_census_mask_probes(self.ctx.h, self.h, C.c_void_p(d_entries_ptr), n_slots,
+                                                           self.mask if mask is None else mask, max_occ, C.byref(n)), "census_mask_probes")
+        return int(n.value)
+
+
+def _census(self, seqs, mask, mode="head_tail", lo=0, hi=None) -> "Census":
+    return Census(self, seqs, mask, mode, lo, hi)
+
+
+def _overlap_strands_masked(self, reads, mask, R, census, max_occ, max_trial=32, overlap_min=64, strands=3, t_lo=0, t_hi=None,
+                            kernel=PBA_KERNEL_AUTO, cap=None, reads_rc=None):
+    """overlap_strands with the probes of keys that occur more than max_occ times (census: a head_tail census of the forward
+    reads under `mask`) left out of both probe tables.  Returns (rows, [stats of the +1 pass, of the -1 pass], [probe entries
+    masked on +1, on -1])."""
+    t_hi = reads.count if t_hi is None else t_hi
+    cap = cap if cap is not None else max(1, 2 * (t_hi - t_lo) * max(reads.count - 1, 1))
+    out = np.empty(cap, STRAND_OVERLAP_DTYPE)
+    n = C.c_uint64()
+    st2 = (_lib.PbaOverlapStats * 2)()
+    nm = (C.c_uint64 * 2)()
+    self.check(self.lib.pba_overlap_strands_masked(self.h, reads.h, reads_rc.h if reads_rc is not None else None, t_lo, t_hi, mask, R,
+                                                   max_trial, overlap_min, kernel, strands, census.h if census is not None else None,
+                                                   max_occ, _ptr(out), cap, C.byref(n), C.byref(st2), C.byref(nm)),
+               "overlap_strands_masked")
+    return out[:min(int(n.value), cap)], _stats_pair(st2), [int(nm[0]), int(nm[1])]
+
+
+Context.census = _census
+Context.overlap_strands_masked = _overlap_strands_masked
+
+
 def script_vals(ops: np.ndarray, seg: bytes, fwd: bool = True) -> bytes:
     """edits[k].val of an edit script (seq_aligner.h:218,224): the b element a MATCH / INSERT consumes, 0 for a DELETE.
     seg: the accessor's elements in memory order (a backward accessor starts at its last byte)."""
