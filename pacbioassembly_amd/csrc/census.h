@@ -1,13 +1,13 @@
 // census.h -- device side of the seed-key census (pba_census_*): how often every masked seed key occurs among the
 // positions the seed index visits, counted into the probe table's own direct addressing (one u32 per bucket
-// compress(key, mask), overlap.h: pt_bucket<false>), and what is read off the counters: a histogram, a batch of look-ups, the
-// probe entries of over-frequent keys overwritten with the all-ones padding k_pt_count / k_pt_fill skip, and a per-sequence
-// repeat profile.  Plain HIP: vector stores and global atomics only.
+// ix_compress(key, mv): the function overlap.h's pt_bucket<false> calls, index_plan.h), and what is read off the counters: a
+// histogram, a batch of look-ups, the probe entries of over-frequent keys overwritten with the all-ones padding k_pt_count /
+// k_pt_fill skip, and a per-sequence repeat profile.  Plain HIP: vector stores and global atomics only.
 //
-// The positions of a sequence are those of visit_plan (index_plan.h: the index's own rule, at most two position segments; CensusWalk),
-// walked in aligned chunks of 16 positions as the all-vs-all scan walks them (one 8-byte load of packed bases per chunk,
-// seed_index.h: chunk_bits / chunk_key); a position outside its segment is skipped.  The chunks of a sequence are numbered
-// segment after segment; a tile is CENSUS_TILE_CHUNKS consecutive chunk numbers of ONE sequence, the tiles of all sequences of
+// The positions of a sequence are the index's own: the two position segments of its visiting rule (index_plan.h: VisitRule),
+// walked in the aligned chunks of 16 positions the rule numbers segment after segment (one 8-byte load of packed bases per
+// chunk, seed_index.h: chunk_bits / chunk_key); a position outside the chunk's segment is skipped.  A tile is
+// CENSUS_TILE_CHUNKS consecutive chunk numbers of ONE sequence, the tiles of all sequences of
 // a call are numbered flat (the host prefix-sums the per-sequence tile counts from the lengths) and a workgroup finds the
 // sequence of its tile by bisection: one long contig and many short reads both fill the chip.
 #ifndef PBA_CENSUS_H
@@ -26,36 +26,10 @@ struct CensusDev {
     uint32_t *count;            // 2^bits counters
     uint32_t mask, mv[5];       // compress_masks(mask)
 };
-__device__ __forceinline__ uint32_t census_bucket(const CensusDev &C, uint32_t key) {   // compress(key, mask): Hacker's Delight 7-4
-    uint32_t x = key;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        const uint32_t t = x & C.mv[i];
-        x = (x ^ t) | (t >> (1 << i));
-    }
-    return x;
-}
+__device__ __forceinline__ uint32_t census_bucket(const CensusDev &C, uint32_t key) { return ix_compress(key, C.mv); }
 
-// The chunks of one sequence.  Its visited positions are the (at most two) position segments of visit_plan (index_plan.h),
-// written out here without the plan's indexed stores so that the kernels keep them in registers; the host holds every
-// sequence it counts to visit_plan itself (pba_census.hip: census_tiles).  Segment k holds positions [lo_k, hi_k) and takes
-// the aligned chunks first_k .. first_k + n_k - 1; a segment the sequence does not have has no chunk and an empty interval.
-struct CensusWalk {
-    uint32_t lo0, hi0, lo1, hi1, first0, first1, n0, n1;
-    __host__ __device__ CensusWalk(uint32_t len, int mode) {
-        lo0 = 0; lo1 = 1; hi1 = 0;
-        if (mode == PBA_INDEX_ALL) hi0 = len;                                  // locator.cpp:62
-        else {                                                                 // ref_seq.h:291-311
-            hi0 = len > 16 ? (len - 16 < 20000u ? len - 16 : 20000u) : 0u;
-            if (len > 20016u) { const uint32_t nt = len - 20016u < 20000u ? len - 20016u : 20000u; hi1 = len - 15; lo1 = hi1 - nt; }
-        }
-        first0 = 0; n0 = hi0 ? ((hi0 - 1) >> 4) + 1 : 0u;
-        first1 = lo1 >> 4; n1 = hi1 ? ((hi1 - 1) >> 4) - first1 + 1 : 0u;
-    }
-    __host__ __device__ uint32_t chunks() const { return n0 + n1; }
-    __host__ __device__ uint32_t positions() const { return hi0 + (hi1 ? hi1 - lo1 : 0u); }
-    __host__ __device__ uint32_t tiles() const { return (chunks() + CENSUS_TILE_CHUNKS - 1) / CENSUS_TILE_CHUNKS; }
-};
+// tiles of a sequence: host (the tile offsets) and device agree on them through the rule's chunk numbering
+static inline uint32_t census_tiles_of(const VisitRule &w) { return (w.chunks() + CENSUS_TILE_CHUNKS - 1) / CENSUS_TILE_CHUNKS; }
 
 // the sequence (relative to the call's first) whose tiles hold tile `b`: the last one that begins at or before it; sequences
 // without tiles share their offset with the sequence after them.  tile_at: n_seqs + 1 offsets, tile_at[n_seqs] > b.
@@ -73,18 +47,18 @@ template <int MODE, class F>
 __device__ __forceinline__ void census_walk_tile(const SeqSetDev &S, uint32_t seq, uint32_t tile, uint32_t mask, F f) {
     const uint32_t len = S.len[seq];
     const uint8_t *p = S.packed + S.off[seq];
-    const CensusWalk w(len, MODE);
-    const uint32_t nchunks = w.chunks();
+    const VisitRule w = visit_rule(len, MODE);
+    const uint32_t n0 = w.head_chunks(), nchunks = w.chunks();
     uint64_t be[CENSUS_ITERS];
     uint32_t c[CENSUS_ITERS], lo[CENSUS_ITERS], hi[CENSUS_ITERS];
 #pragma unroll
     for (int it = 0; it < CENSUS_ITERS; ++it) {                 // all loads of the thread in flight before the first key is used
         const uint32_t u = tile * CENSUS_TILE_CHUNKS + it * CENSUS_THREADS + threadIdx.x;
         const bool live = u < nchunks;
-        const bool tail = u >= w.n0;
-        c[it] = tail ? w.first1 + (u - w.n0) : u;
-        lo[it] = live ? (tail ? w.lo1 : 0u) : 1u;               // (not live: an empty interval)
-        hi[it] = live ? (tail ? w.hi1 : w.hi0) : 0u;
+        const bool tail = u >= n0;
+        c[it] = tail ? w.tail_chunk0() + (u - n0) : u;
+        lo[it] = live ? (tail ? w.tail_begin() : 0u) : 1u;      // (not live: an empty interval)
+        hi[it] = live ? (tail ? w.tail_end() : w.nhead) : 0u;
         be[it] = live ? chunk_bits(p, c[it]) : 0ull;
     }
 #pragma unroll

@@ -61,17 +61,10 @@ k_probe_emit(SeqSetDev Rd, uint32_t q_lo, uint32_t n_queries, uint32_t t2, uint3
     if (o < cap) out[o] = (uint64_t)key << 32 | (uint32_t)gid;
 }
 
-// visiting order of ref_seq::get_seedmap for a sequence of `len` bases
-struct HeadTail {
-    int nhead, visited, tail_top;
-    __device__ __forceinline__ HeadTail(int len) {
-        const int nh = min(len - 16, 20000), nt = min(len - 20000 - 16, 20000);
-        nhead = nh > 0 ? nh : 0;
-        visited = nhead + (nt > 0 ? nt : 0);
-        tail_top = len - 16;
-    }
-    __device__ __forceinline__ int pos_of(int ord) const { return ord < nhead ? ord : tail_top - (ord - nhead); }
-};
+// A target's visiting order is ref_seq::get_seedmap's: the index's own rule (index_plan.h: VisitRule; ord_of, pos_of).  The scans
+// walk the chunks of ALL positions 0 .. tail_top -- the gap between head and tail of a long read too, which ord_of drops.
+__device__ __forceinline__ VisitRule ovl_rule(int len) { return visit_rule((uint32_t)len, PBA_INDEX_HEAD_TAIL); }
+__device__ __forceinline__ int ovl_nchunks(const VisitRule &v) { return v.visited ? (v.tail_top >> 4) + 1 : 0; }
 
 // ---------------------------------------------------------------------------------------------------------------
 // The probe table: a direct-address CSR over the probe keys ("LDS-staged hash buckets" of the north star, sized for HBM:
@@ -99,13 +92,7 @@ struct ProbeTab {
 template <bool HASHED>
 __device__ __forceinline__ uint32_t pt_bucket(const ProbeTab &T, uint32_t key) {
     if (HASHED) return (key * 0x9E3779B1u) >> (32 - T.bits);
-    uint32_t x = key;                                   // compress(key, mask): Hacker's Delight 7-4, move masks from the host
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        const uint32_t t = x & T.mv[i];
-        x = (x ^ t) | (t >> (1 << i));
-    }
-    return x;
+    return ix_compress(key, T.mv);                      // (index_plan.h; the census counts into the same buckets: census.h)
 }
 
 // entries (key << 32 | probe id; all-ones = padding of an all-gathered buffer) -> bucket sizes at start[b + 1], presence bits
@@ -168,19 +155,6 @@ k_pt_ctx(ProbeTab T, SeqSetDev Rd, uint32_t n_entries) {
 #endif                                                         // of 400 k reads: 16 -> 347 ms, 8 -> 296 ms, 4 -> 300 ms: LDS per workgroup, so occupancy)
 #define PBA_OVL_RUNS (PBA_WAVE * PBA_OVL_HALF)                 // runs a wavefront can meet in one round
 
-struct TargetWalk {          // visiting order of ref_seq::get_seedmap as a function of the position
-    int nhead, tail_lo, tail_top, nchunks;
-    __device__ __forceinline__ TargetWalk(int len) {
-        const HeadTail ht(len);
-        nhead = ht.nhead; tail_top = ht.tail_top;
-        tail_lo = tail_top - (ht.visited - ht.nhead) + 1;
-        nchunks = ht.visited > 0 ? (tail_top >> 4) + 1 : 0;  // positions 0 .. len - 16
-    }
-    __device__ __forceinline__ int ord_of(int pos) const {   // -1: not visited (ref_seq.h:297-308)
-        return pos < nhead ? pos : (pos >= tail_lo && pos <= tail_top ? nhead + (tail_top - pos) : -1);
-    }
-};
-
 template <bool HASHED>
 static __global__ void __launch_bounds__(PBA_WAVE * PBA_OVL_WAVES)
 k_ovl_count(ProbeTab T, SeqSetDev Rd, uint32_t t_lo, uint32_t n_targets, uint32_t *slice) {
@@ -188,9 +162,10 @@ k_ovl_count(ProbeTab T, SeqSetDev Rd, uint32_t t_lo, uint32_t n_targets, uint32_
     const uint32_t tl = blockIdx.x;
     const int len = (int)Rd.len[t_lo + tl];
     const uint8_t *seq = Rd.packed + Rd.off[t_lo + tl];
-    const TargetWalk tw(len);
+    const VisitRule tw = ovl_rule(len);
+    const int nchunks = ovl_nchunks(tw);
     uint32_t sum = 0;
-    for (int c = (int)threadIdx.x; c < tw.nchunks; c += PBA_WAVE * PBA_OVL_WAVES) {
+    for (int c = (int)threadIdx.x; c < nchunks; c += PBA_WAVE * PBA_OVL_WAVES) {
         const uint64_t be = chunk_bits(seq, (uint32_t)c);
         uint32_t b[PBA_OVL_PPT], pw[PBA_OVL_PPT];
 #pragma unroll
@@ -279,15 +254,16 @@ k_ovl_fill(ProbeTab T, SeqSetDev Rd, uint32_t t_lo, uint32_t n_targets, const ui
     __syncthreads();
     const int len = (int)Rd.len[t];
     const uint8_t *seq = Rd.packed + Rd.off[t];
-    const TargetWalk tw(len);
+    const VisitRule tw = ovl_rule(len);
+    const int nchunks = ovl_nchunks(tw);
     uint64_t *out = cand + cand_off[tl];
     uint32_t myvalid = 0;
     // every wavefront runs the same number of steps (the ballots and shuffles below need all its lanes; a lane past the
     // end just has nothing to contribute)
-    const int steps = (tw.nchunks + PBA_WAVE * PBA_OVL_WAVES - 1) / (PBA_WAVE * PBA_OVL_WAVES);
+    const int steps = (nchunks + PBA_WAVE * PBA_OVL_WAVES - 1) / (PBA_WAVE * PBA_OVL_WAVES);
     for (int st = 0; st < steps; ++st) {
         const int c = st * PBA_WAVE * PBA_OVL_WAVES + (int)threadIdx.x;
-        const bool live = c < tw.nchunks;
+        const bool live = c < nchunks;
         const uint64_t be = live ? chunk_bits(seq, (uint32_t)c) : 0ull;
         PBA_OVL_LOOKUP16();
 #pragma unroll
@@ -368,14 +344,14 @@ k_ovl_scan(ProbeTab T, SeqSetDev Rd, uint32_t t_lo, uint32_t t_stride, const uin
         for (int k = (int)threadIdx.x; k < nw; k += PBA_WAVE * PBA_OVL_WAVES) s_planes[k] = gp[k];
     }
     __syncthreads();
-    const TargetWalk tw(len);
-    const HeadTail ht(len);
+    const VisitRule tw = ovl_rule(len);
+    const int nchunks = ovl_nchunks(tw);
     uint64_t *out = surv_off ? surv + surv_off[tl] : nullptr;
     uint32_t ncand = 0, nok = 0;
-    const int steps = (tw.nchunks + PBA_WAVE * PBA_OVL_WAVES - 1) / (PBA_WAVE * PBA_OVL_WAVES);
+    const int steps = (nchunks + PBA_WAVE * PBA_OVL_WAVES - 1) / (PBA_WAVE * PBA_OVL_WAVES);
     for (int st = 0; st < steps; ++st) {
         const int c = st * PBA_WAVE * PBA_OVL_WAVES + (int)threadIdx.x;
-        const bool live = c < tw.nchunks;
+        const bool live = c < nchunks;
         const uint64_t be = live ? chunk_bits(seq, (uint32_t)c) : 0ull;
         PBA_OVL_LOOKUP16();
 #pragma unroll
@@ -425,7 +401,7 @@ k_ovl_scan(ProbeTab T, SeqSetDev Rd, uint32_t t_lo, uint32_t t_stride, const uin
                 const int s_len = (int)rec.y - j;                        // spaced_seed.cpp:274-275: slen - j in both directions
                 const bool ok = valid && s_len >= cfg.overlap_min;       // spaced_seed.cpp:280
                 const uint32_t ord = r_ord[w][lo_r];
-                const int hit = ht.pos_of((int)ord);
+                const int hit = tw.pos_of(ord);
                 const int r_off = fwd ? hit : hit + 15;                  // spaced_seed.cpp:285
                 const int r_len = fwd ? len - r_off : r_off + 1;         // ref_seq.h:284-285
                 bool failed = false;
@@ -550,11 +526,11 @@ struct OvlCand {
     uint32_t q;
     int j, hit, r_off, r_len, s_off, s_len;
 };
-__device__ __forceinline__ OvlCand ovl_decode_len(int slen, int ref_len, const HeadTail &ht, uint64_t cd, const OvlCfg &cfg) {
+__device__ __forceinline__ OvlCand ovl_decode_len(int slen, int ref_len, const VisitRule &ht, uint64_t cd, const OvlCfg &cfg) {
     OvlCand c;
     c.q = (uint32_t)(cd >> PBA_OVL_Q_SHIFT);
     const uint32_t jd = (uint32_t)(cd >> PBA_OVL_ORD_BITS) & ((1u << PBA_OVL_JD_BITS) - 1);
-    c.hit = ht.pos_of((int)(cd & ((1u << PBA_OVL_ORD_BITS) - 1)));
+    c.hit = ht.pos_of((uint32_t)cd & ((1u << PBA_OVL_ORD_BITS) - 1));
     c.j = (int)(jd >> 1);
     c.fwd = (jd & 1) == 0;
     const int pos = c.fwd ? c.j : slen - c.j - 16;
@@ -565,7 +541,7 @@ __device__ __forceinline__ OvlCand ovl_decode_len(int slen, int ref_len, const H
     c.r_len = c.fwd ? ref_len - c.r_off : c.r_off + 1;          // ref_seq.h:284-285
     return c;
 }
-__device__ __forceinline__ OvlCand ovl_decode(const SeqSetDev &Rd, int ref_len, const HeadTail &ht, uint64_t cd,
+__device__ __forceinline__ OvlCand ovl_decode(const SeqSetDev &Rd, int ref_len, const VisitRule &ht, uint64_t cd,
                                               const OvlCfg &cfg) {
     return ovl_decode_len((int)Rd.len[(uint32_t)(cd >> PBA_OVL_Q_SHIFT)], ref_len, ht, cd, cfg);
 }
@@ -648,7 +624,8 @@ __device__ __forceinline__ void ovl_walk(const SeqSetDev &Rd, const SeqSetDev &Q
         const uint32_t t = t_lo + tl;
         const PackedFetch ref = fetch_of_uniform(Rd, t, 0, 1);
         const int ref_len = __builtin_amdgcn_readfirstlane((int)Rd.len[t]);
-        const HeadTail ht(ref_len);
+        __builtin_assume(ref_len >= 0);               // (the rule's clamps stay the one signed v_med3_i32 each that this sweep was tuned with)
+        const VisitRule ht = ovl_rule(ref_len);
         uint32_t done_q = NONE, last_q = NONE;
         bool stop = false;
         // 64 candidates at a time: every lane decodes its candidate; then the group is walked in order and only the
@@ -751,7 +728,8 @@ k_ovl_after(ProbeTab T, SeqSetDev Rd, SeqSetDev Q, const pba_overlap *ov, uint32
     const uint32_t t = (uint32_t)o.target, q = (uint32_t)o.query;
     const uint32_t jd0 = 2u * (uint32_t)o.j + (o.dir < 0 ? 1u : 0u);
     const int tlen = (int)Rd.len[t], slen = (int)Rd.len[q];
-    const TargetWalk tw(tlen);
+    const VisitRule tw = ovl_rule(tlen);
+    const int nchunks = ovl_nchunks(tw);
     const int ord0 = tw.ord_of(o.ref_pos);
     const uint8_t *tseq = Rd.packed + Rd.off[t], *qseq = Q.packed + Q.off[q];
     for (uint32_t k = lane; k < PBA_OVL_AFTER_SLOTS; k += PBA_WAVE) { h_key[wave][k] = 0u; h_cnt[wave][k] = 0u; }   // key 0 = empty: no probe has it
@@ -777,7 +755,7 @@ k_ovl_after(ProbeTab T, SeqSetDev Rd, SeqSetDev Q, const pba_overlap *ov, uint32
     }
     __builtin_amdgcn_wave_barrier();
     uint32_t cnt = 0;
-    for (int c = (int)lane; c < tw.nchunks; c += PBA_WAVE) {
+    for (int c = (int)lane; c < nchunks; c += PBA_WAVE) {
         const uint64_t be = chunk_bits(tseq, (uint32_t)c);
 #pragma unroll 4
         for (int k = 0; k < 16; ++k) {

@@ -40,13 +40,9 @@ static int census_tiles(pba_ctx *ctx, const char *who, const pba_seqs *s, uint32
     uint64_t tiles = 0, v = 0;
     for (uint32_t r = lo; r < hi; ++r) {
         tile_at[r - lo] = (uint32_t)tiles;
-        const CensusWalk w(s->h_len[r], mode);
-        const VisitPlan vp = visit_plan(s->h_len[r], mode);                 // the index's own rule: the walk must be it
-        const bool same0 = vp.nseg > 0 ? (vp.segs[0].lo == 0 && vp.segs[0].hi == w.hi0) : w.hi0 == 0;
-        const bool same1 = vp.nseg > 1 ? (vp.segs[1].lo == w.lo1 && vp.segs[1].hi == w.hi1) : w.hi1 == 0;
-        if (!same0 || !same1) return ctx_fail_as(ctx, PBA_E_HIP, who, "the census walk is not the index's visiting order (an inconsistency inside the engine)");
-        tiles += w.tiles();
-        v += w.positions();
+        const VisitRule w = visit_rule(s->h_len[r], mode);                  // the index's own rule, as the kernels read it
+        tiles += census_tiles_of(w);
+        v += w.visited;
         if (tiles >= (1ull << 31)) return ctx_fail_as(ctx, PBA_E_TOOLONG, who, "2^31 tiles or more in one call");
     }
     tile_at[hi - lo] = (uint32_t)tiles;

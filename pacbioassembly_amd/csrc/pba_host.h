@@ -1,7 +1,8 @@
 // pba_host.h -- host-side objects and helpers shared by the translation units of libpba.so (pba_core.hip: context,
 // sequence sets; pba_index.hip: seed index; pba_align.hip: explicit pairs and edit scripts; pba_drivers.hip: the reference's ordered
-// first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction; pba_stream.hip: streamed locate and mapping; pba_layout.hip: layout; pba_clip.hip: clipping; pba_hpc.hip: homopolymer compression; pba_fastx.hip: FASTA / FASTQ in, FASTA out).  Internal: nothing here is part of
-// the C ABI (include/pba.h).
+// first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction; pba_stream.hip: streamed locate and mapping; pba_layout.hip: layout; pba_clip.hip: clipping; pba_hpc.hip: homopolymer compression; pba_census.hip: seed-key census; pba_cigar.hip: run-length alignments and PAF;
+// pba_fastx.hip: FASTA / FASTQ in, FASTA out).  Internal: nothing here is part of the C ABI (include/pba.h).
+// (What host and device share about the seed index -- the visiting rule, compress / compress_masks -- is index_plan.h's.)
 // Also here, once for all of them: the clip of seq_aligner.h:94-102 (text_clip), the launch plan (make_plan), the host
 // protocol of every aligning entry point but the all-vs-all walk -- narrow window first, the uncertified items again at the
 // reference band (narrow_then_redo) --, the owner of a set of vote boxes (VoteBoxes), a found row's accessors (row_accessors,
@@ -488,18 +489,6 @@ static inline int seed_rounds(uint32_t n_reads, const uint32_t *masks, int n_mas
     return PBA_OK;
 }
 
-// the five move masks of compress(x, mask) (Hacker's Delight 7-4): gathers the bits of x under `mask` into a number
-static inline void compress_masks(uint32_t mask, uint32_t mv[5]) {
-    uint32_t m = mask, mk = ~m << 1;
-    for (int i = 0; i < 5; ++i) {
-        uint32_t mp = mk ^ (mk << 1);
-        mp ^= mp << 2; mp ^= mp << 4; mp ^= mp << 8; mp ^= mp << 16;
-        const uint32_t mvi = mp & m;
-        mv[i] = mvi;
-        m = (m ^ mvi) | (mvi >> (1 << i));
-        mk &= ~mp;
-    }
-}
 // how segments are spread over buckets by k_seg_sort (seed_index.h)
 static inline SegBkt seg_bkt_range() { SegBkt b; memset(&b, 0, sizeof b); b.mode = 0; return b; }
 static inline SegBkt seg_bkt_key(uint32_t mask) {

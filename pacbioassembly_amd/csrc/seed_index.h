@@ -36,7 +36,7 @@
 #endif
 #define PBA_IX_TILE_POS (PBA_IX_TILE_THREADS * 16 * PBA_IX_TILE_ITERS)   // positions per workgroup
 
-#include "index_plan.h"   // what the host plans from these constants; ScanSeg, ix_ord_pos
+#include "index_plan.h"   // what the host plans from these constants; the visiting rule (VisitRule, ScanSeg, ix_ord_pos); compress
 
 struct IndexDev {
     const uint64_t *ent;        // entries, partition by partition, each partition sorted
@@ -472,7 +472,7 @@ k_scan_add(uint32_t *a, uint64_t n, const uint32_t *tile_pre) {
 #endif
 struct SegBkt {
     int mode;
-    uint32_t mask, mv[5];     // mode 1: compress(key, mask) (Hacker's Delight 7-4)
+    uint32_t mask, mv[5];     // mode 1: ix_compress(key & mask, mv) (index_plan.h)
     int care;
 };
 struct SegRef { uint32_t off, n; };
@@ -567,9 +567,7 @@ k_seg_sort(const uint64_t *src, uint64_t *dst, const uint32_t *seg_off, const Se
     auto bucket = [&](uint64_t v) -> uint32_t {
         if (v == ~0ull) return nbkt;                                 // empty slots: behind everything, never sorted
         if (bk.mode == 0) return (uint32_t)((v - mn) >> shift);
-        uint32_t x = (uint32_t)(v >> 32) & bk.mask;
-#pragma unroll
-        for (int i = 0; i < 5; ++i) { const uint32_t t = x & bk.mv[i]; x = (x ^ t) | (t >> (1 << i)); }
+        const uint32_t x = ix_compress((uint32_t)(v >> 32) & bk.mask, bk.mv);
         return lg == 0 ? 0u : (bk.care > lg ? x >> (bk.care - lg) : x);              // (lg == 0: one bucket; a shift by 32 is not a shift)
     };
 #pragma unroll

@@ -63,6 +63,40 @@ def test_census_edges(ctx, shape, mask_name, mode):
     cen.close()
 
 
+RULE_EDGES = (16, 17, 33, 20016, 20017, 40016, 40017, 40100)      # no position; one; the head alone up to its last length; the first
+                                                                  # tail position; head and tail whole; the first lengths with a gap
+
+
+def test_census_and_index_visit_the_same_positions_at_the_rule_edges(ctx):
+    """The two device consumers of the visiting rule (csrc/index_plan.h) held to each other through the library, one random
+    sequence per edge length of the rule: the head_tail census of a sequence alone has visited what the head_tail index of that
+    sequence reports, has counted the index's entries, and holds for a key of the index the length of the run find returns."""
+    import index_ref as ir
+    mask = cr.MASKS["w12"]
+    rng = np.random.default_rng(20016)
+    texts = [cr.ACGT[rng.integers(0, 4, n)].tobytes() for n in RULE_EDGES]
+    S = ctx.seqs_from_list(texts, strict_acgt=True)
+    for i, (n, text) in enumerate(zip(RULE_EDGES, texts)):
+        ref_keys, _, _ = ir.np_index(text, mask, "head_tail")
+        n_visited = ir.visit_order(n, "head_tail")[0].size
+        assert ref_keys.size == n_visited and (n_visited > 0) == (n > 16), n      # no zero key in this text: counted == visited is no accident
+        cen = ctx.census(S, mask, "head_tail", i, i + 1)
+        ix = ctx.index_build(S, i, mask, eng.PBA_INDEX_HEAD_TAIL)
+        visited = ix.visited if ix.visited < 1 << 31 else 0                       # (below 16 bases the index reports a negative count as it is)
+        st = cen.stats
+        print(n, {k: st[k] for k in ("n_visited", "n_counted", "n_zero_keys")}, ix.visited, ix.entries)
+        assert st["n_visited"] == visited == n_visited, n
+        assert st["n_counted"] == ix.entries == ref_keys.size, n
+        keys, _ = ix.dump()
+        if keys.size:
+            sel = rng.choice(keys, 64)
+            off, _ = ix.find(sel)
+            runs = np.diff(off.astype(np.int64))
+            assert runs.min() >= 1 and cen.lookup(sel).tolist() == runs.tolist(), n
+        ix.close()
+        cen.close()
+
+
 def test_add_ranges_and_sets(ctx):
     """create(0, k) + add(k, n) is create(0, n); two different sets added are the sum of their censuses"""
     S, mask = edge_set(ctx, "random"), cr.MASKS["w12"]

@@ -8,7 +8,7 @@ held to the model, never only to each other.
                               three slot groups with survivors at lanes 0, 31, 32, 63 of each, a full round of 512 runs, runs in
                               every wavefront, both halves, a second step and the last live chunk -- n_candidates, n_prefiltered,
                               n_listed and the rows say whether every slot met its own run's record
-  HeadTail, TargetWalk        targets of 20 015 .. 50 000 bases with copies on either side of position 20 000, of tail_lo and of
+  ovl_rule: ord_of, pos_of    targets of 20 015 .. 50 000 bases with copies on either side of position 20 000, of tail_lo and of
                               tail_top, and one key at two head and two tail positions: the scan, count / fill, the walk's
                               decode and k_ovl_after
   k_ovl_after                 max_trial 1, 2, 33, 63 (t2 = 66 and 126: the second ballot round) on queries whose later probes do

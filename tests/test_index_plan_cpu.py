@@ -1,7 +1,9 @@
-"""csrc/index_plan.h alone -- what the host decides about a seed index before anything is launched -- as a stand-alone host
-program (tests/cpp/index_plan_main.cpp, under ASan + UBSan where the compiler has the runtimes): visit_plan against
-index_ref.visit_order in both modes, index_plan (compiled with seed_index.h's regime constants) against the regime rules
-restated in index_ref.py and the sizes the build has always reserved in its two pooled arenas.  No GPU, nothing loaded into python."""
+"""csrc/index_plan.h alone -- what host and device agree on about a seed index before anything is launched -- as a stand-alone
+host program (tests/cpp/index_plan_main.cpp, under ASan + UBSan where the compiler has the runtimes): the one statement of the
+visiting rule (visit_rule: head, tail, ord_of / pos_of, the chunk numbering of its segments) and visit_plan over it against
+index_ref.visit_order and its closed forms, at every length 0 .. 40 100 in both modes; ix_compress(x, compress_masks(mask)) against a
+bit-by-bit gather; index_plan (compiled with seed_index.h's regime constants) against the regime rules restated in index_ref.py
+and the sizes the build has always reserved in its two pooled arenas.  No GPU, nothing loaded into python."""
 import os
 import subprocess
 
@@ -9,11 +11,18 @@ import numpy as np
 import pytest
 
 from conftest import HERE, ROOT
-from index_ref import LVL_BITS, MAX_LOGP, PART_AVG, define, first_n_with_levels, levels_of, logp_of, tile_switch, visit_order
+from index_ref import (LVL_BITS, MAX_LOGP, MAX_READ_LEN, N_SEQ_WORD, PART_AVG, define, first_n_with_levels, levels_of, logp_of, tile_switch,
+                       visit_order)
+from overlap_ref import mask_of
 
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-fno-omit-frame-pointer", "-g"]
 LENS = [0, 1, 15, 16, 17, 31, 32, 33, 20000, 20015, 20016, 20017, 20031, 20032, 40015, 40016, 40017, 100000]
 MODES = {"all": 0, "head_tail": 1}                 # PBA_INDEX_ALL, PBA_INDEX_HEAD_TAIL (include/pba.h)
+RULE_MAX = 40100                                   # the rule at EVERY length up to here: past the last length at which it changes (40 016)
+ORD_LENS = LENS + [40100, 65535]
+HUGE = (1 << 31) - 17, (1 << 31) + 20100           # ... and around 2^31, where len - 16 leaves the signed arithmetic the rule is written in
+SEED_MASKS = [mask_of(ln.strip()) for ln in open(os.path.join(HERE, "golden", "seeds.txt")) if ln.strip()]
+COMPRESS_MASKS = SEED_MASKS + [1, 0x80000000, 0xFFFFFFFF] + np.random.default_rng(11).integers(1, 1 << 32, 300, dtype=np.uint64).tolist()
 SCAN_TILE = define("PBA_SCAN_TILE", "seed_index.h")
 B2, B3 = first_n_with_levels(2), first_n_with_levels(3)
 TILE_SWITCH = tile_switch()                        # (the tile is the builder's choice, not the plan's: its switch is a size like the others here)
@@ -26,7 +35,8 @@ def scan_scratch_words(n: int) -> int:             # pba_host.h
 
 @pytest.fixture(scope="module")
 def answers(tmp_path_factory):
-    """the program, once: ({(len, mode): visit fields}, {n_upper: plan fields}, the constants line)"""
+    """the program, once: ({(len, mode): visit fields}, {n_upper: plan fields}, the constants line, the rule table -- one row per
+    length 0 .. RULE_MAX, HUGE[0] .. HUGE[1] and 2^32 - 1 --, {(len, mode): ord fields}, {mask: compress fields})"""
     exe = str(tmp_path_factory.mktemp("index_plan") / "index_plan_main")
     consts = [f"-DPBA_IX_{k}={v}" for k, v in (("MAX_LOGP", MAX_LOGP), ("LVL_BITS", LVL_BITS), ("PART_AVG", PART_AVG))]   # seed_index.h's
     cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror"] + consts + ["-I", os.path.join(ROOT, "pacbioassembly_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
@@ -34,14 +44,21 @@ def answers(tmp_path_factory):
     if subprocess.run(cmd + SAN, capture_output=True).returncode != 0:       # a compiler without the sanitizer runtimes
         subprocess.run(cmd, check=True)
     args = [f"v:{n}:{m}" for n in LENS for m in MODES.values()] + [f"p:{n}" for n in N_UPPER]
-    p = subprocess.run([exe] + args, capture_output=True, timeout=120)
+    extra = [f"r:0:{RULE_MAX}", f"r:{HUGE[0]}:{HUGE[1]}", f"r:{0xFFFFFFFF}:{0xFFFFFFFF}"] + [f"o:{n}:{m}" for n in ORD_LENS for m in MODES.values()] + [f"c:{m}" for m in COMPRESS_MASKS]
+    p = subprocess.run([exe] + args + extra, capture_output=True, timeout=120)
     assert p.returncode == 0 and p.stderr == b"", p.stderr.decode(errors="replace")[-4000:]
     lines = [ln.split() for ln in p.stdout.decode().splitlines()]
-    assert lines[0][0] == "consts" and len(lines) == 1 + len(args)
+    assert lines[0][0] == "consts" and len(lines) == 1 + len(args) + RULE_MAX + (HUGE[1] - HUGE[0]) + len(extra)   # (an r: argument prints hi - lo + 1 lines)
     visits = {(int(ln[1]), int(ln[2])): [int(x) for x in ln[3:]] for ln in lines[1:] if ln[0] == "visit"}
     plans = {int(ln[1]): [int(x) for x in ln[2:]] for ln in lines[1:] if ln[0] == "plan"}
     assert len(visits) == 2 * len(LENS) and len(plans) == len(N_UPPER)
-    return visits, plans, [int(x) for x in lines[0][1:]]
+    rules = np.array([ln[1:] for ln in lines if ln[0] == "rule"], np.int64)
+    want_len = np.concatenate([np.arange(RULE_MAX + 1), np.arange(HUGE[0], HUGE[1] + 1), [0xFFFFFFFF]])
+    assert rules.shape == (want_len.size, 1 + 2 * 19) and np.array_equal(rules[:, 0], want_len)
+    ords = {(int(ln[1]), int(ln[2])): [int(x) for x in ln[3:]] for ln in lines if ln[0] == "ord"}
+    gathers = {int(ln[1]): [int(x) for x in ln[2:]] for ln in lines if ln[0] == "compress"}
+    assert len(ords) == 2 * len(ORD_LENS) and len(gathers) == len(set(COMPRESS_MASKS))
+    return visits, plans, [int(x) for x in lines[0][1:]], rules, ords, gathers
 
 
 def test_constants(answers):
@@ -72,6 +89,65 @@ def test_visit_plan_is_the_reference_order(answers, mode):
             assert nhead == max(min(n - 16, 20000), 0) and tail_top == n - 16, (n, nhead, tail_top)
     if mode == "head_tail":
         assert answers[0][(0, 1)][0] == 0xFFFFFFF0 and answers[0][(15, 1)][0] == 0xFFFFFFFF     # the negative head, added as it is
+
+
+def closed_forms(n: np.ndarray, mode: str):
+    """index_ref.visit_order as closed forms over an array of lengths: (nhead, tail_lo, tail_top, visited -- the clamped counts and
+    the tail interval --, what the builder returns as visited)"""
+    if mode == "all":
+        return n, np.ones_like(n), np.zeros_like(n), n, n
+    nh, nt = np.minimum(n - N_SEQ_WORD, MAX_READ_LEN), np.clip(n - MAX_READ_LEN - N_SEQ_WORD, 0, MAX_READ_LEN)
+    top = n - N_SEQ_WORD
+    return np.maximum(nh, 0), top - nt + 1, top, np.maximum(nh, 0) + nt, (nh + nt) & 0xFFFFFFFF
+
+
+@pytest.mark.parametrize("mode", ["all", "head_tail"])
+def test_the_rule_at_every_length(answers, mode):
+    """visit_rule's fields and chunk numbering, and visit_plan over it, at every length 0 .. RULE_MAX, HUGE[0] .. HUGE[1] and at
+    2^32 - 1 (tail_lo / tail_top as the int32 the program prints; the tail's first chunk only where there is a tail: without one it
+    numbers nothing)"""
+    n = answers[3][:, 0]
+    i32 = lambda a: ((a + (1 << 31)) & 0xFFFFFFFF) - (1 << 31)
+    nhead, tail_lo, tail_top, visited, returned = closed_forms(n, mode)
+    for k in sorted(set(LENS + [20000 + N_SEQ_WORD, 2 * MAX_READ_LEN + N_SEQ_WORD, RULE_MAX]) & set(n[:RULE_MAX + 1].tolist())):   # the closed forms are visit_order's
+        pos, ret = visit_order(k, mode)
+        assert (pos.size, ret) == (visited[k], returned[k]) and np.array_equal(pos[:nhead[k]], np.arange(nhead[k])), (k, mode)
+        assert np.array_equal(pos[nhead[k]:], np.arange(tail_top[k], tail_lo[k] - 1, -1)), (k, mode)
+    ntail = visited - nhead
+    got = answers[3][:, 1 + 19 * MODES[mode]:][:, :19]
+    r_nhead, r_lo, r_top, r_visited, head_chunks, tail_chunk0, tail_chunks, p_visited, p_nhead, p_top, nseg = got[:, :11].T
+    for name, a, b in (("nhead", r_nhead, nhead), ("tail_lo", r_lo, i32(tail_lo)), ("tail_top", r_top, i32(tail_top)), ("visited", r_visited, visited),
+                       ("head_chunks", head_chunks, (nhead + 15) // 16), ("tail_chunks", tail_chunks, np.where(ntail > 0, tail_top // 16 - tail_lo // 16 + 1, 0)),   # (the chunks: of the unsigned positions)
+                       ("tail_chunk0", np.where(ntail > 0, tail_chunk0, 0), np.where(ntail > 0, tail_lo // 16, 0)),
+                       ("visit_plan.visited", p_visited, returned), ("visit_plan.tail_top", p_top, i32(tail_top)),
+                       ("visit_plan.nhead", p_nhead, nhead if mode == "head_tail" else np.full_like(n, 0xFFFFFFFF)),
+                       ("visit_plan.nseg", nseg, (nhead > 0).astype(np.int64) + (ntail > 0))):
+        assert np.array_equal(a, b), (mode, name, n[a != b][:8])
+    zero = np.zeros_like(n)
+    head = np.stack([zero, nhead, zero, zero], 1)
+    tail = np.stack([tail_lo, tail_top + 1, nhead, zero + 1], 1)
+    want0 = np.where((nhead > 0)[:, None], head, 0)                  # (a tail without a head does not exist: ntail > 0 needs len > 20 016)
+    want1 = np.where((ntail > 0)[:, None], tail, 0)
+    assert not (ntail[nhead == 0] > 0).any()
+    assert np.array_equal(got[:, 11:15], want0) and np.array_equal(got[:, 15:19], want1), mode
+    if mode == "head_tail":
+        assert (p_visited[0], p_visited[15], p_visited[16]) == (0xFFFFFFF0, 0xFFFFFFFF, 0)     # the negative head, added as it is
+
+
+@pytest.mark.parametrize("mode", ["all", "head_tail"])
+def test_ord_of_inverts_pos_of_and_the_chunks_cover_the_visited_set_once(answers, mode):
+    for n in ORD_LENS:
+        visited, seen, bad_inverse, bad_cover = answers[4][(n, MODES[mode])]
+        assert visited == seen == visit_order(n, mode)[0].size, (n, mode)       # ord_of >= 0 at exactly as many positions as are visited ...
+        assert bad_inverse == 0, (n, mode)                                      # ... which are pos_of's: each maps back, and every ordinal has one
+        assert bad_cover == 0, (n, mode)
+
+
+def test_compress_is_the_bit_gather(answers):
+    assert len(SEED_MASKS) >= 4 and all(bin(m).count("1") % 2 == 0 for m in SEED_MASKS)
+    for mask in COMPRESS_MASKS:
+        tried, bad = answers[5][mask]
+        assert tried >= 256 and bad == 0, hex(mask)
 
 
 @pytest.mark.parametrize("n", N_UPPER)
