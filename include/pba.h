@@ -892,7 +892,98 @@ int pba_overlap_rows_cigar_budget(pba_ctx *ctx, const pba_seqs *reads, const pba
                                   uint64_t n, double R, uint32_t *cigar, uint64_t cap, uint64_t *cig_off, uint64_t *n_slots,
                                   pba_aln_counts *counts, pba_result *res, uint64_t max_slots);
 
-typedef struct { int32_t contig, n_rows, len_in, len_out; } pba_polish_row;      /* per contig, last round */
+/* ------------------------------------------------------------------------ */
+/* Per-window alignment counts, and rows trimmed where they break (DESIGN    */
+/* 5.11; tests/windows_ref.py restates all of this in plain Python).  The a  */
+/* sequence of a pair carries a grid of W-base windows fixed on ITS OWN      */
+/* coordinates: a-element e lies at x(e) = a_pos + e (forward accessor) or   */
+/* a_pos - e (backward), g(e) = x(e) div W, and the pair's local window      */
+/* index is w(e) = |g(e) - g(0)|.  Windows of different pairs on one         */
+/* sequence coincide.  Of a successful pair's script (origin-first):         */
+/*   MATCH / DELETE consuming a-element e      -> window w(e)                 */
+/*   INSERT met after i a-elements were consumed -> window w(max(i - 1, 0))   */
+/* A window is one pba_aln_counts: = / X per element, I / D named as         */
+/* pba_align_batch_cigar names them (PBA_CIG_B_IS_QUERY exchanges them).     */
+/* n_win = w(max(matlen_a - 1, 0)) + 1; a pair with rc < 0 has none.  The    */
+/* windows sum to the pair's counts, every window consumes at least one      */
+/* a-element (matlen_a >= 1) and interior windows consume exactly W.         */
+/* Origin-first, or goal-first under PBA_CIG_REVERSED.                       */
+/* ------------------------------------------------------------------------ */
+/* Host arithmetic: the windows the clipped len_a (seq_aligner.h:94-102) of a pair touches, which bounds n_win.  0 for W < 1,
+ * a negative length or position, R outside (0,1) or a backward accessor that would start before position 0. */
+uint32_t pba_windows_bound(int a_pos, int a_len, int b_len, double R, int W, int a_backward);
+/* The host twin of the device sink, shaped like pba_cigar_from_script: the windows of a script and the elements of its two
+ * accessors in element order.  Returns n_win (the first min(n_win, cap) written), -1 for an op outside 1..3, W < 1 or
+ * unknown flag bits.  An empty script has one empty window. */
+int pba_windows_from_script(const uint8_t *ops, int32_t nedit, const char *a_elems, const char *b_elems, int a_pos, int a_backward,
+                            int W, uint32_t flags, pba_aln_counts *win, int32_t cap);
+/* The windows of a batch, made on the device by the traceback walk (no script, no CIGAR in memory).  Pair q's windows go to
+ * win[win_off[q] ..), nwin[q] of them; win_off (n + 1 entries) must leave pba_windows_bound(...) slots per pair, else
+ * PBA_E_INVALID.  A pair with rc < 0: nwin = 0, its slot untouched, counts zero.  counts[q]: the pair's totals, as
+ * pba_align_batch_cigar gives them.  Refusals and the alphabet rule as pba_align_batch_cigar; W < 1: PBA_E_INVALID. */
+int pba_align_batch_windows(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R, int maxn,
+                            int maxm, int W, uint32_t flags, pba_result *out, pba_aln_counts *win, const uint64_t *win_off,
+                            int32_t *nwin, pba_aln_counts *counts);
+/* The windows of rows: the same re-run pairs, roles and order as pba_map_rows_cigar / pba_overlap_rows_cigar (the grid lies on
+ * the read for mapped rows -- a is the read --, on the TARGET for overlap rows, whose windows come in the target's forward order,
+ * I / D named with the query read as the query), held to the row's cost and match lengths.  Dense and in row order: row k's
+ * windows at win[win_off[k] .. win_off[k + 1]) for the rows, in order, up to the first whose end exceeds cap; win_off (n + 1)
+ * is always complete and *n_slots the total.  The rows go through the device in chunks whose bounded slots
+ * (pba_windows_bound) stay under max_slots windows (0: 2^26; a chunk holds at least one row); the answer does not depend on
+ * the cut.  counts / res nullable. */
+int pba_map_rows_windows(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc, const pba_map_row *rows,
+                         uint64_t n, double R, int W, pba_aln_counts *win, uint64_t cap, uint64_t *win_off, uint64_t *n_slots,
+                         pba_aln_counts *counts, pba_result *res);
+int pba_map_rows_windows_budget(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
+                                const pba_map_row *rows, uint64_t n, double R, int W, pba_aln_counts *win, uint64_t cap,
+                                uint64_t *win_off, uint64_t *n_slots, pba_aln_counts *counts, pba_result *res, uint64_t max_slots);
+int pba_overlap_rows_windows(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, const pba_strand_overlap *rows, uint64_t n,
+                             double R, int W, pba_aln_counts *win, uint64_t cap, uint64_t *win_off, uint64_t *n_slots,
+                             pba_aln_counts *counts, pba_result *res);
+int pba_overlap_rows_windows_budget(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, const pba_strand_overlap *rows,
+                                    uint64_t n, double R, int W, pba_aln_counts *win, uint64_t cap, uint64_t *win_off,
+                                    uint64_t *n_slots, pba_aln_counts *counts, pba_result *res, uint64_t max_slots);
+
+/* The trim rule, per item, over its windows in the order given, I / D named AS UNDER THE DEFAULT FLAGS (I consumes a):
+ *   na_k = n_eq + n_x + n_ins, nb_k = n_eq + n_x + n_del, err_k = n_x + n_ins + n_del
+ *   good     window k is good when err_k <= thr[na_k], thr[m] = (int32_t)(max_err * (double)m), computed on the host in FP64
+ *   runs     the maximal runs of consecutive good windows (n_runs; n_good windows in them); the winner has the largest sum
+ *            of na, a tie goes to the first run in the order given
+ *   state    DROPPED without a run, with a winner whose na sum is below min_span, or whose nb sum is 0 (every other field but
+ *            n_win, n_good, n_runs is 0 then); WHOLE when the winner is all windows; else CUT
+ *   reported the winner [w_beg, w_end), the a- and b-elements before it (a0, b0) and inside it (na, nb), cost = its err sum */
+enum { PBA_TRIM_DROPPED = 0, PBA_TRIM_WHOLE = 1, PBA_TRIM_CUT = 2 };
+typedef struct { int32_t state, n_win, n_good, n_runs, w_beg, w_end, a0, b0, na, nb, cost; } pba_trim_span;
+/* The trim kernel on windows the caller supplies (item q: win[win_off[q] .. win_off[q + 1])), so that the rule can be pinned
+ * apart from the aligner.  PBA_E_INVALID for W < 1, max_err outside [0, 1], min_span < 0, offsets that decrease, a negative
+ * count or a window with na_k > W.  No items are legal. */
+int pba_windows_trim(pba_ctx *ctx, const pba_aln_counts *win, const uint64_t *win_off, uint64_t n, int W, double max_err, int min_span,
+                     pba_trim_span *spans);
+/* Overlap rows trimmed to the longest run of good target windows.  The windows are made as pba_overlap_rows_windows makes
+ * them (target forward) and judged by the trim kernel on the device: no window crosses the host.  With a0, b0, na, nb
+ * counted in ELEMENT order (the reverse of the target's order for dir -1), j, dir, slen as pba_strand_overlap defines them:
+ *   target            dir +1: [t_beg + a0, t_beg + a0 + na)            dir -1: [t_end - a0 - na, t_end - a0)
+ *   walked query text dir +1: [j + b0, j + b0 + nb)                    dir -1: [slen - j - b0 - nb, slen - j - b0)
+ *   strand -1: a walked query interval [w0, w1) is given as [slen - w1, slen - w0)
+ * They lie inside the row's own intervals.  A DROPPED row's four ends are 0. */
+typedef struct { int32_t state, n_win, n_good, n_runs, w_beg, w_end, t_beg, t_end, q_beg, q_end, cost; } pba_trim_row;
+typedef struct {
+    uint64_t n_rows, n_windows;
+    uint32_t n_whole, n_cut, n_dropped, n_chunks;
+    float windows_ms, trim_ms;          /* HIP events on the ctx's stream: the traced passes, the trim kernels */
+} pba_trim_stats;
+int pba_overlap_rows_trim(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, const pba_strand_overlap *rows, uint64_t n,
+                          double R, int W, double max_err, int min_span, pba_trim_row *out, pba_trim_stats *stats /* nullable */);
+int pba_overlap_rows_trim_budget(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, const pba_strand_overlap *rows,
+                                 uint64_t n, double R, int W, double max_err, int min_span, pba_trim_row *out,
+                                 pba_trim_stats *stats /* nullable */, uint64_t max_slots);
+/* Host: the rows that are not DROPPED, in order, with their four interval ends replaced by the trimmed ones; returns their
+ * number (out_rows holds up to n; may alias rows), -1 for a NULL.  These are INTERVAL ROWS: valid for pba_clip_create, which
+ * reads only target, query, strand and the four ends; NOT valid for anything that re-runs the alignment from j / ref_pos
+ * (pba_*_rows_cigar, pba_*_rows_windows, votes, layout): j, dir, ref_pos, cost and the match lengths are the untrimmed row's. */
+int64_t pba_trim_rows_apply(const pba_strand_overlap *rows, const pba_trim_row *trims, uint64_t n, pba_strand_overlap *out_rows);
+
+typedef struct { int32_t contig, n_rows, len_in, len_out; } pba_polish_row;     /* per contig, last round */
 typedef struct {
     int32_t round;                 /* 1-based */
     uint32_t n_mapped, n_voted, n_chunks;   /* found rows, rows that voted, pile-ups of the round */

@@ -101,6 +101,15 @@ class PbaClipStats(C.Structure):
                 ("gather_ms", C.c_float)]
 
 
+class PbaTrimStats(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_windows", C.c_uint64)] + \
+               [(n, C.c_uint32) for n in ("n_whole", "n_cut", "n_dropped", "n_chunks")] + \
+               [("windows_ms", C.c_float), ("trim_ms", C.c_float)]
+
+
+PBA_TRIM_DROPPED, PBA_TRIM_WHOLE, PBA_TRIM_CUT = 0, 1, 2
+
+
 class PbaHpcStats(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("n_seqs", "max_len_in", "max_len_out", "n_chunks")] + \
                [("n_bases_in", C.c_uint64), ("n_bases_out", C.c_uint64), ("heads_ms", C.c_float), ("emit_ms", C.c_float),
@@ -329,6 +338,19 @@ SYMBOLS = {
     "pba_overlap_rows_cigar": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_double, _P, C.c_uint64, _P, C.POINTER(C.c_uint64), _P, _P]),
     "pba_overlap_rows_cigar_budget": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_double, _P, C.c_uint64, _P, C.POINTER(C.c_uint64), _P, _P,
                                                 C.c_uint64]),
+    "pba_windows_bound": (C.c_uint32, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int]),
+    "pba_windows_from_script": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int, C.c_int, C.c_int, C.c_uint32, _P, C.c_int32]),
+    "pba_align_batch_windows": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_double, C.c_int, C.c_int, C.c_int, C.c_uint32, _P, _P, _P, _P, _P]),
+    "pba_map_rows_windows": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.c_double, C.c_int, _P, C.c_uint64, _P, C.POINTER(C.c_uint64), _P, _P]),
+    "pba_map_rows_windows_budget": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.c_double, C.c_int, _P, C.c_uint64, _P, C.POINTER(C.c_uint64),
+                                              _P, _P, C.c_uint64]),
+    "pba_overlap_rows_windows": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_double, C.c_int, _P, C.c_uint64, _P, C.POINTER(C.c_uint64), _P, _P]),
+    "pba_overlap_rows_windows_budget": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_double, C.c_int, _P, C.c_uint64, _P, C.POINTER(C.c_uint64),
+                                                  _P, _P, C.c_uint64]),
+    "pba_windows_trim": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, C.c_double, C.c_int, _P]),
+    "pba_overlap_rows_trim": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_double, C.c_int, C.c_double, C.c_int, _P, _P]),
+    "pba_overlap_rows_trim_budget": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_double, C.c_int, C.c_double, C.c_int, _P, _P, C.c_uint64]),
+    "pba_trim_rows_apply": (C.c_int64, [_P, _P, C.c_uint64, _P]),
     "pba_strerror": (C.c_char_p, [C.c_int]),
 }
 

@@ -4,6 +4,7 @@
 #include "pba_host.h"
 #include "align_bvtrace.h"
 #include "align_cigar.h"
+#include "align_windows.h"
 
 // ids (nullable): the subset of pairs / reads to process (second, full-band launch)
 template <int NB>
@@ -173,6 +174,42 @@ k_cigar_pairs(SeqSetDev A, SeqSetDev B, const pba_pair *pairs, const uint32_t *i
     }
 }
 
+// ... and once more with the path counted per window of a's own grid (align_windows.h: WindowSink): pair q's windows go to
+// win[win_off[q] ..), their number to nwin[q], their sum to counts[q].  Checkpoint form only.  No temporary: a closed window
+// goes straight to its final place.  pair_flags (nullable): PBA_CIG_* per pair, else `flags` for all of them.
+template <int NB>
+__global__ void __launch_bounds__(PBA_WAVE * 4, NB <= 4 ? (NB <= 2 ? PBA_TR_OCC12 : 4) : 2)
+k_window_pairs(SeqSetDev A, SeqSetDev B, const pba_pair *pairs, const uint32_t *ids, uint32_t n, AlignCfg cfg, pba_result *out,
+               uint32_t *scratch, uint64_t wave_words, uint64_t cap_words, pba_aln_counts *win, const uint64_t *win_off, int32_t *nwin,
+               pba_aln_counts *counts, const uint32_t *pair_flags, uint32_t flags, int W, uint32_t *queue) {
+    extern __shared__ __align__(16) uint8_t lds_all[];
+    __shared__ uint2 s_tile[4][PBA_BV_TILE_WORDS(NB)];
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / PBA_WAVE));
+    uint8_t *lds = lds_all + (size_t)wave * cfg.row_cap * 2;
+    uint32_t *mine = scratch + ((uint64_t)blockIdx.x * 4 + wave) * wave_words;
+    for (;;) {
+        const uint32_t slot = next_slot(queue);
+        if (slot >= n) break;
+        const uint32_t q = ids ? ids[slot] : slot;
+        const pba_pair pr = pairs[q];
+        const bool a_back = (pr.flags & PBA_A_BACKWARD) != 0;
+        const PackedFetch fa = fetch_of(A, pr.a_seq, pr.a_pos, a_back ? -1 : 1);
+        const PackedFetch fb = fetch_of(B, pr.b_seq, pr.b_pos, (pr.flags & PBA_B_BACKWARD) ? -1 : 1);
+        const uint32_t fl = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pair_flags ? pair_flags[q] : flags));
+        AlnOut o;
+        int nw = 0;
+        const uint64_t o0 = win_off[q], o1 = win_off[q + 1];
+        WindowSink sink;
+        sink.init(fa, fb, pr.a_pos, a_back, W, win + o0, o1 - o0, (fl & PBA_CIG_B_IS_QUERY) != 0, (fl & PBA_CIG_REVERSED) != 0);
+        if (align_bitvec_trace<NB, true>(fa, pr.a_len, fb, pr.b_len, cfg.R, cfg.maxn, cfg.maxm, cfg.full_band != 0, (uint16_t *)lds,
+                                         cfg.row_cap, mine, cap_words, 0, sink, o, s_tile[wave]))
+            nw = sink.finish(counts + q);
+        else if ((threadIdx.x & (PBA_WAVE - 1)) == 0) counts[q] = pba_aln_counts{0, 0, 0, 0};
+        store_result(out + q, o);
+        if ((threadIdx.x & (PBA_WAVE - 1)) == 0) nwin[q] = nw;
+    }
+}
+
 // find_path (seq_aligner.h:214-233) walked iteratively from the goal cell; one thread per pair.  The walk meets the ops
 // goal-first and the caller gets them origin-first, the first min(nedit, cap) of them (pba.h): so the path is walked twice,
 // once for its length K and once to put the op met k-th at o[K - 1 - k] where that is inside the cap.
@@ -318,6 +355,7 @@ struct TracedLaunch {
     const VoteInto *vote;                 // ... or, non-null, votes gated by overlap_min (host pointer; passed by value)
     int overlap_min;
     const CigarInto *cig;                 // ... or, non-null, runs (host pointer; its members are passed)
+    const WindowInto *win;                // ... or, non-null, per-window counts (host pointer; its members are passed)
 };
 // (PBA_DISPATCH_NB without its case 0: these kernels have no row-sweep form)
 #define PBA_DISPATCH_BV_NB(nb, K) \
@@ -339,8 +377,14 @@ static void launch_traced(pba_ctx *ctx, const TracedLaunch &t, int nb, const Ali
         hipLaunchKernelGGL(k_cigar_pairs<NBV>, grid, block, t.lds * 4, ctx->stream, t.A, t.B, t.pairs, ids, cnt, cfg, t.out, scr, \
                            tp.wave_words, tp.cap_words, t.cig->cig, t.cig->off, t.cig->ncig, t.cig->counts, t.cig->pair_flags, \
                            t.cig->flags, ctx->d_queue)
-    if (t.cig) { PBA_DISPATCH_BV_NB(nb, PBA_RUNS); }
+#define PBA_WINS(NBV)                                                                                                 \
+        hipLaunchKernelGGL(k_window_pairs<NBV>, grid, block, t.lds * 4, ctx->stream, t.A, t.B, t.pairs, ids, cnt, cfg, t.out, scr, \
+                           tp.wave_words, tp.cap_words, t.win->win, t.win->off, t.win->nwin, t.win->counts, t.win->pair_flags, \
+                           t.win->flags, t.win->W, ctx->d_queue)
+    if (t.win) { PBA_DISPATCH_BV_NB(nb, PBA_WINS); }
+    else if (t.cig) { PBA_DISPATCH_BV_NB(nb, PBA_RUNS); }
     else if (!t.vote) { PBA_DISPATCH_BV_NB(nb, PBA_SCRIPTS); } else { PBA_DISPATCH_BV_NB(nb, PBA_VOTES); }
+#undef PBA_WINS
 #undef PBA_RUNS
 #undef PBA_VOTES
 #undef PBA_SCRIPTS
@@ -702,13 +746,15 @@ static int trace_rowsweep(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, co
 }
 
 // Edit scripts of a batch (vote == nullptr: ops / ops_off / nedit receive them) or their votes (vote != nullptr: the
-// paths go straight into the boxes it names, gated by overlap_min; ops / ops_off / nedit unused).
+// paths go straight into the boxes it names, gated by overlap_min; ops / ops_off / nedit unused), their runs (cig) or their
+// per-window counts (win): one sink a call.
 int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R,
                        int maxn, int maxm, int kernel, pba_result *out, uint8_t *ops, const uint64_t *ops_off,
-                       int32_t *nedit, const VoteInto *vote, int overlap_min, const CigarInto *cig) {
+                       int32_t *nedit, const VoteInto *vote, int overlap_min, const CigarInto *cig, const WindowInto *win) {
     const bool seg = vote && vote->box_off;
-    const bool sunk = vote || cig;                           // the path goes to a sink of its own: no script leaves the device
-    if (!ctx || !A || !B || (!pairs && n) || (!out && n) || (!sunk && ((!ops_off && n) || (!nedit && n))) || (vote && cig)) return PBA_E_INVALID;
+    const bool sunk = vote || cig || win;                    // the path goes to a sink of its own: no script leaves the device
+    if (!ctx || !A || !B || (!pairs && n) || (!out && n) || (!sunk && ((!ops_off && n) || (!nedit && n))) ||
+        (vote != nullptr) + (cig != nullptr) + (win != nullptr) > 1) return PBA_E_INVALID;
     if (n == 0) return PBA_OK;
     if (n > 0x7FFFFFFFull) PBA_FAIL(PBA_E_INVALID, "too many pairs in one batch");
     if (A->non_acgt || B->non_acgt) PBA_FAIL(PBA_E_ALPHABET, "a sequence set holds bytes outside ACGT: use pba_align_text_trace");
@@ -729,6 +775,10 @@ int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pa
     if (cig) {
         if (pl.nb1 == 0) PBA_FAIL(PBA_E_TOOLONG, "runs from the walk need the bit-vector kernel (band too wide)");
         ops_max = cig->run_max * 4;                              // the goal-first temporary holds runs, 4 bytes each
+    }
+    if (win) {
+        if (pl.nb1 == 0) PBA_FAIL(PBA_E_TOOLONG, "windows from the walk need the bit-vector kernel (band too wide)");
+        ops_max = 0;                                             // no goal-first temporary
     }
     TraceBufs d;
     d.ops_total = sunk ? 0 : ops_off[n] - ops_off[0];
@@ -752,9 +802,9 @@ int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pa
     // First launch: every pair, narrow window, scratch sized for it (so more wavefronts fit the budget); second
     // launch: the pairs that came back uncertified, reference band.
     t.A = A->dev(); t.B = B->dev(); t.pairs = d.pairs.as<pba_pair>(); t.out = d.out.as<pba_result>(); t.lds = pl.lds;
-    t.ck = seg || cig || !hooks.stream;
+    t.ck = seg || cig || win || !hooks.stream;
     t.ops = d.ops.as<uint8_t>(); t.ops_off = d.ooff.as<uint64_t>(); t.nedit = d.ne.as<int32_t>();
-    t.vote = vote; t.overlap_min = overlap_min; t.cig = cig;
+    t.vote = vote; t.overlap_min = overlap_min; t.cig = cig; t.win = win;
     TracePass tp{};
     auto before = [&](int pass, const std::vector<uint32_t> &redo) {
         return trace_pass_size(ctx, pairs, pass ? redo.data() : nullptr, pass ? (uint32_t)redo.size() : (uint32_t)n, R,

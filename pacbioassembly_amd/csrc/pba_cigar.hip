@@ -202,14 +202,11 @@ int pba_align_batch_cigar(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, co
 // ---- rows ----------------------------------------------------------------------------------------------------------------
 static const uint64_t kCigChunkSlots = 1ull << 28;      // bounded slots of one chunk of rows on the device (1 GiB)
 
-// one row's alignment to re-run: its pair, the batch it goes with (0: strand +1, 1: strand -1), what the row says of it
-struct CigJob { pba_pair pr; uint64_t row; uint32_t flags; int batch; int32_t cost, matlen_a, matlen_b; };
-
 // The jobs (in row order) in chunks whose bounded slots stay under max_slots, each chunk as up to two batches (A[s] against
 // B[s]); every batch compacted on the device, its real runs copied to the host and laid out in row order.  row_n[k]: runs
 // of row k (0 for a row without a job).
 static int rows_cigar(pba_ctx *ctx, const char *who, const pba_seqs *const A[2], const pba_seqs *const B[2],
-                      const std::vector<CigJob> &jobs, uint64_t n_rows, double R, uint32_t *cigar, uint64_t cap, uint64_t *cig_off,
+                      const std::vector<RowJob> &jobs, uint64_t n_rows, double R, uint32_t *cigar, uint64_t cap, uint64_t *cig_off,
                       uint64_t *n_slots, pba_aln_counts *counts, pba_result *res, uint64_t max_slots) {
     if (max_slots == 0) max_slots = kCigChunkSlots;
     std::vector<uint32_t> row_n(n_rows, 0);
@@ -247,7 +244,7 @@ static int rows_cigar(pba_ctx *ctx, const char *who, const pba_seqs *const A[2],
             PBA_TRY(cigar_run(ctx, A[s], B[s], pairs.data(), nb, R, 0, 0, 0u, pflags.data(), rel.data(), run_max, out.data(),
                               ncig.data(), cnt.data(), d));
             for (size_t q = 0; q < nb; ++q) {           // held to the row: the same roles, the same lengths, the same R
-                const CigJob &jb = jobs[j0 + which[q]];
+                const RowJob &jb = jobs[j0 + which[q]];
                 if (res) res[jb.row] = out[q];
                 if (counts) counts[jb.row] = cnt[q];
                 if (!walk_agrees(out[q], jb.cost, jb.matlen_a, jb.matlen_b)) {
@@ -279,7 +276,7 @@ static int rows_cigar(pba_ctx *ctx, const char *who, const pba_seqs *const A[2],
     return PBA_OK;
 }
 
-// what both row-level entry points check before they look at a row
+// what every row-level entry point, here and in pba_windows.hip, checks before it looks at a row
 static int rows_cigar_check(pba_ctx *ctx, const char *who, const pba_seqs *reads, const pba_seqs *reads_rc, const pba_seqs *target,
                             uint64_t n, double R) {
     if (!(R > 0.0) || !(R < 1.0)) PBA_FAIL(PBA_E_INVALID, "R must be in (0,1)");
@@ -291,13 +288,9 @@ static int rows_cigar_check(pba_ctx *ctx, const char *who, const pba_seqs *reads
     return PBA_OK;
 }
 
-int pba_map_rows_cigar_budget(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
-                              const pba_map_row *rows, uint64_t n, double R, uint32_t *cigar, uint64_t cap, uint64_t *cig_off,
-                              uint64_t *n_slots, pba_aln_counts *counts, pba_result *res, uint64_t max_slots) {
-    static const char who[] = "pba_map_rows_cigar";
-    if (!ctx || !target || !reads || (!rows && n) || !cig_off || !n_slots || (cap && !cigar)) return PBA_E_INVALID;
+int map_rows_jobs(pba_ctx *ctx, const char *who, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
+                  const pba_map_row *rows, uint64_t n, double R, pba_aln_counts *counts, pba_result *res, std::vector<RowJob> *jobs) {
     PBA_TRY(rows_cigar_check(ctx, who, reads, reads_rc, target, n, R));
-    std::vector<CigJob> jobs;
     for (uint64_t k = 0; k < n; ++k) {
         const pba_map_row &r = rows[k];
         if (counts) counts[k] = pba_aln_counts{0, 0, 0, 0};
@@ -306,14 +299,24 @@ int pba_map_rows_cigar_budget(pba_ctx *ctx, const pba_seqs *target, const pba_se
         if (r.contig < 0 || (uint32_t)r.contig >= target->n) return ctx_fail_as(ctx, PBA_E_INVALID, who, "a row's contig is not a contig of the set");
         if (r.read < 0 || (uint32_t)r.read >= reads->n) return ctx_fail_as(ctx, PBA_E_INVALID, who, "a row's read is not a read of the set");
         if (r.strand == -1 && !reads_rc) return ctx_fail_as(ctx, PBA_E_INVALID, who, "a strand -1 row needs reads_rc");
-        CigJob jb{};
+        RowJob jb{};
         const int st = pba_map_row_aln_pair(&r, target->h_len[r.contig], reads->h_len[r.read], R, &jb.pr);
         if (st == PBA_E_TOOLONG) return ctx_fail_as(ctx, PBA_E_TOOLONG, who, "a row's accessor is longer than the engine limit");
         if (st != PBA_OK) return ctx_fail_as(ctx, PBA_E_INVALID, who, "a row's strand or anchor is not valid for its sequences");
         jb.row = k; jb.flags = 0u; jb.batch = r.strand == 1 ? 0 : 1;
         jb.cost = r.cost; jb.matlen_a = r.matlen_a; jb.matlen_b = r.matlen_b;
-        jobs.push_back(jb);
+        jobs->push_back(jb);
     }
+    return PBA_OK;
+}
+
+int pba_map_rows_cigar_budget(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
+                              const pba_map_row *rows, uint64_t n, double R, uint32_t *cigar, uint64_t cap, uint64_t *cig_off,
+                              uint64_t *n_slots, pba_aln_counts *counts, pba_result *res, uint64_t max_slots) {
+    static const char who[] = "pba_map_rows_cigar";
+    if (!ctx || !target || !reads || (!rows && n) || !cig_off || !n_slots || (cap && !cigar)) return PBA_E_INVALID;
+    std::vector<RowJob> jobs;
+    PBA_TRY(map_rows_jobs(ctx, who, target, reads, reads_rc, rows, n, R, counts, res, &jobs));
     const pba_seqs *const A[2] = {reads, reads_rc}, *const B[2] = {target, target};
     return rows_cigar(ctx, who, A, B, jobs, n, R, cigar, cap, cig_off, n_slots, counts, res, max_slots);
 }
@@ -324,13 +327,9 @@ int pba_map_rows_cigar(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *rea
     return pba_map_rows_cigar_budget(ctx, target, reads, reads_rc, rows, n, R, cigar, cap, cig_off, n_slots, counts, res, 0);
 }
 
-int pba_overlap_rows_cigar_budget(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, const pba_strand_overlap *rows,
-                                  uint64_t n, double R, uint32_t *cigar, uint64_t cap, uint64_t *cig_off, uint64_t *n_slots,
-                                  pba_aln_counts *counts, pba_result *res, uint64_t max_slots) {
-    static const char who[] = "pba_overlap_rows_cigar";
-    if (!ctx || !reads || (!rows && n) || !cig_off || !n_slots || (cap && !cigar)) return PBA_E_INVALID;
+int overlap_rows_jobs(pba_ctx *ctx, const char *who, const pba_seqs *reads, const pba_seqs *reads_rc, const pba_strand_overlap *rows,
+                      uint64_t n, double R, pba_aln_counts *counts, pba_result *res, std::vector<RowJob> *jobs) {
     PBA_TRY(rows_cigar_check(ctx, who, reads, reads_rc, nullptr, n, R));
-    std::vector<CigJob> jobs;
     for (uint64_t k = 0; k < n; ++k) {
         const pba_strand_overlap &r = rows[k];
         if (counts) counts[k] = pba_aln_counts{0, 0, 0, 0};
@@ -338,7 +337,7 @@ int pba_overlap_rows_cigar_budget(pba_ctx *ctx, const pba_seqs *reads, const pba
         if (r.target < 0 || (uint32_t)r.target >= reads->n || r.query < 0 || (uint32_t)r.query >= reads->n)
             return ctx_fail_as(ctx, PBA_E_INVALID, who, "a row's target or query is not a read of the set");
         if (r.strand == -1 && !reads_rc) return ctx_fail_as(ctx, PBA_E_INVALID, who, "a strand -1 row needs reads_rc");
-        CigJob jb{};
+        RowJob jb{};
         if (pba_overlap_row_pair(&r, reads->h_len[r.target], reads->h_len[r.query], &jb.pr) != PBA_OK)
             return ctx_fail_as(ctx, PBA_E_INVALID, who, "a row's accessors lie outside its reads");
         if (jb.pr.a_len > kMaxSeqLen || jb.pr.b_len > kMaxSeqLen)
@@ -346,8 +345,18 @@ int pba_overlap_rows_cigar_budget(pba_ctx *ctx, const pba_seqs *reads, const pba
         // the target's forward order: a backward pair's goal lies at the low end of the target
         jb.row = k; jb.flags = PBA_CIG_B_IS_QUERY | (r.dir == -1 ? PBA_CIG_REVERSED : 0u); jb.batch = r.strand == 1 ? 0 : 1;
         jb.cost = r.cost; jb.matlen_a = r.matlen_a; jb.matlen_b = r.matlen_b;
-        jobs.push_back(jb);
+        jobs->push_back(jb);
     }
+    return PBA_OK;
+}
+
+int pba_overlap_rows_cigar_budget(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, const pba_strand_overlap *rows,
+                                  uint64_t n, double R, uint32_t *cigar, uint64_t cap, uint64_t *cig_off, uint64_t *n_slots,
+                                  pba_aln_counts *counts, pba_result *res, uint64_t max_slots) {
+    static const char who[] = "pba_overlap_rows_cigar";
+    if (!ctx || !reads || (!rows && n) || !cig_off || !n_slots || (cap && !cigar)) return PBA_E_INVALID;
+    std::vector<RowJob> jobs;
+    PBA_TRY(overlap_rows_jobs(ctx, who, reads, reads_rc, rows, n, R, counts, res, &jobs));
     const pba_seqs *const A[2] = {reads, reads}, *const B[2] = {reads, reads_rc};
     return rows_cigar(ctx, who, A, B, jobs, n, R, cigar, cap, cig_off, n_slots, counts, res, max_slots);
 }

@@ -1,6 +1,6 @@
 // pba_host.h -- host-side objects and helpers shared by the translation units of libpba.so (pba_core.hip: context,
 // sequence sets; pba_index.hip: seed index; pba_align.hip: explicit pairs and edit scripts; pba_drivers.hip: the reference's ordered
-// first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction; pba_stream.hip: streamed locate and mapping; pba_layout.hip: layout; pba_clip.hip: clipping; pba_hpc.hip: homopolymer compression; pba_census.hip: seed-key census; pba_cigar.hip: run-length alignments and PAF;
+// first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction; pba_stream.hip: streamed locate and mapping; pba_layout.hip: layout; pba_clip.hip: clipping; pba_hpc.hip: homopolymer compression; pba_census.hip: seed-key census; pba_cigar.hip: run-length alignments and PAF; pba_windows.hip: per-window counts and trimmed rows;
 // pba_fastx.hip: FASTA / FASTQ in, FASTA out).  Internal: nothing here is part of the C ABI (include/pba.h).
 // (What host and device share about the seed index -- the visiting rule, compress / compress_masks -- is index_plan.h's.)
 // Also here, once for all of them: the clip of seq_aligner.h:94-102 (text_clip), the launch plan (make_plan), the host
@@ -548,6 +548,22 @@ struct CigarInto {
     uint64_t run_max;                     // the widest slot any pair may fill: sizes the wavefronts' goal-first temporaries
 };
 
+// Where a batch of walks leaves its per-window counts (k_window_pairs, pba_align.hip; align_windows.h).  All pointers: device,
+// owned by the caller.  Pair q's slot is win[off[q] .. off[q + 1]): nothing is written unless all of its windows fit.
+struct WindowInto {
+    pba_aln_counts *win;
+    const uint64_t *off;
+    int32_t *nwin;
+    pba_aln_counts *counts;
+    const uint32_t *pair_flags;           // PBA_CIG_* per pair; nullable: `flags` for every pair
+    uint32_t flags;
+    int W;                                // window size on a's own coordinates, >= 1
+};
+
+// One row's alignment to re-run for its runs or its windows: its pair, the batch it goes with (0: strand +1, 1: strand -1),
+// the PBA_CIG_* flags that put it in the target's forward order, what the row says of it.
+struct RowJob { pba_pair pr; uint64_t row; uint32_t flags; int batch; int32_t cost, matlen_a, matlen_b; };
+
 // ---- internal entry points that cross translation units
 extern "C" {
 // sort one oversize partition / candidate piece in global memory (pba_index.hip)
@@ -555,10 +571,19 @@ PBA_INTERNAL int sort_partition_global(pba_ctx *ctx, uint64_t *d_part, uint32_t 
 // an index build of at most n_upper entries takes tiles of 4 096 entries in its generic level kernels (pba_core.hip)
 PBA_INTERNAL bool index_small_tiles(uint64_t n_upper);
 // edit scripts of a batch, or (vote non-null) their votes into the boxes it names, gated by overlap_min, or (cig non-null)
-// their runs into the device arrays it names (pba_align.hip)
+// their runs, or (win non-null) their per-window counts, into the device arrays it names (pba_align.hip)
 PBA_INTERNAL int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R,
                              int maxn, int maxm, int kernel, pba_result *out, uint8_t *ops, const uint64_t *ops_off,
-                             int32_t *nedit, const VoteInto *vote = nullptr, int overlap_min = 0, const CigarInto *cig = nullptr);
+                             int32_t *nedit, const VoteInto *vote = nullptr, int overlap_min = 0, const CigarInto *cig = nullptr,
+                             const WindowInto *win = nullptr);
+// The re-run jobs of overlap / mapped rows, in row order, after the checks both the CIGAR and the window entry points make of
+// their sets and rows (who: the public function's name); counts / res (nullable, n entries): zeroed, res rc = -1 (pba_cigar.hip)
+PBA_INTERNAL int overlap_rows_jobs(pba_ctx *ctx, const char *who, const pba_seqs *reads, const pba_seqs *reads_rc,
+                                   const pba_strand_overlap *rows, uint64_t n, double R, pba_aln_counts *counts, pba_result *res,
+                                   std::vector<RowJob> *jobs);
+PBA_INTERNAL int map_rows_jobs(pba_ctx *ctx, const char *who, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
+                               const pba_map_row *rows, uint64_t n, double R, pba_aln_counts *counts, pba_result *res,
+                               std::vector<RowJob> *jobs);
 // one locked round over a subset of the reads (pba_drivers.hip)
 PBA_INTERNAL int spaced_round_subset(pba_ctx *ctx, const pba_index *ix, const pba_seqs *ref, uint32_t ref_seq, const pba_seqs *reads,
                                      double R, int max_trial, int overlap_min, int buggy_seed_at, int kernel,

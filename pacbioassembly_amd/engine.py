@@ -58,6 +58,12 @@ ALN_COUNTS_DTYPE = np.dtype([(n, "<i4") for n in ("n_eq", "n_x", "n_ins", "n_del
 PBA_CIG_INS, PBA_CIG_DEL, PBA_CIG_EQ, PBA_CIG_X = _lib.PBA_CIG_INS, _lib.PBA_CIG_DEL, _lib.PBA_CIG_EQ, _lib.PBA_CIG_X
 PBA_CIG_REVERSED, PBA_CIG_B_IS_QUERY = _lib.PBA_CIG_REVERSED, _lib.PBA_CIG_B_IS_QUERY
 assert ALN_COUNTS_DTYPE.itemsize == C.sizeof(_lib.PbaAlnCounts)
+# pba_trim_span: the trim rule's answer for one item's windows; pba_trim_row: the same as a row's trimmed intervals
+TRIM_SPAN_DTYPE = np.dtype([(n, "<i4") for n in ("state", "n_win", "n_good", "n_runs", "w_beg", "w_end", "a0", "b0", "na", "nb", "cost")])
+TRIM_ROW_DTYPE = np.dtype([(n, "<i4") for n in ("state", "n_win", "n_good", "n_runs", "w_beg", "w_end", "t_beg", "t_end", "q_beg", "q_end",
+                                                "cost")])
+PBA_TRIM_DROPPED, PBA_TRIM_WHOLE, PBA_TRIM_CUT = _lib.PBA_TRIM_DROPPED, _lib.PBA_TRIM_WHOLE, _lib.PBA_TRIM_CUT
+assert TRIM_SPAN_DTYPE.itemsize == 44 and TRIM_ROW_DTYPE.itemsize == 44 and C.sizeof(_lib.PbaTrimStats) == 40
 # pba_fastx_rec: one per record of a parsed FASTA / FASTQ file, offsets into the file image
 PBA_FX_AUTO, PBA_FX_FASTA, PBA_FX_FASTQ = _lib.PBA_FX_AUTO, _lib.PBA_FX_FASTA, _lib.PBA_FX_FASTQ
 PBA_FX_KEEP_CASE, PBA_FX_STRICT_ACGT = _lib.PBA_FX_KEEP_CASE, _lib.PBA_FX_STRICT_ACGT
@@ -1444,6 +1450,146 @@ def _clip_reads(self, reads, mask, R, max_trial=32, overlap_min=64, margin=100, 
 Context.clip = _clip
 Context.clip_coverage = _clip_coverage
 Context.clip_reads = _clip_reads
+
+
+# ---- per-window alignment counts and rows trimmed where they break (pba_windows.hip)
+def windows_bound(a_pos: int, a_len: int, b_len: int, R: float, W: int, a_backward: bool = False) -> int:
+    """Windows the clipped len_a of a pair touches: the bound on n_win (pba_windows_bound; host arithmetic)."""
+    return int(_lib.load().pba_windows_bound(a_pos, a_len, b_len, R, W, int(bool(a_backward))))
+
+
+def windows_from_script(ops, a_elems: bytes, b_elems: bytes, a_pos: int, a_backward: bool, W: int, flags: int = 0) -> np.ndarray:
+    """The windows (ALN_COUNTS_DTYPE) of a script and the elements of its two accessors in element order
+    (pba_windows_from_script): the host twin of the device sink."""
+    ops = np.ascontiguousarray(ops, np.uint8)
+    cap = max(windows_bound(a_pos, len(a_elems), len(a_elems), 0.5, W, a_backward), 1) + 1
+    win = np.zeros(cap, ALN_COUNTS_DTYPE)
+    n = _lib.load().pba_windows_from_script(_ptr(ops), ops.size, a_elems, b_elems, a_pos, int(bool(a_backward)), W, flags, _ptr(win), cap)
+    if n < 0 or n > cap:
+        raise PbaError(_lib.PBA_E_INVALID, "windows_from_script")
+    return win[:n]
+
+
+def trim_rows_apply(rows: np.ndarray, trims: np.ndarray) -> np.ndarray:
+    """The rows that are not DROPPED with their four interval ends replaced by the trimmed ones (pba_trim_rows_apply).  INTERVAL
+    ROWS: good for clip, which reads only target, query, strand and the four ends; not for anything that re-runs the alignment."""
+    rows = np.ascontiguousarray(rows, STRAND_OVERLAP_DTYPE)
+    trims = np.ascontiguousarray(trims, TRIM_ROW_DTYPE)
+    if rows.size != trims.size:
+        raise PbaError(_lib.PBA_E_INVALID, "trim_rows_apply: one trim per row")
+    out = np.zeros(max(rows.size, 1), STRAND_OVERLAP_DTYPE)
+    n = _lib.load().pba_trim_rows_apply(_ptr(rows), _ptr(trims), rows.size, _ptr(out))
+    if n < 0:
+        raise PbaError(_lib.PBA_E_INVALID, "trim_rows_apply")
+    return out[:n]
+
+
+def _align_batch_windows(self, A, B, pairs, R, W, maxn=0, maxm=0, flags=0):
+    """The alignments of a batch as per-window counts on a's own grid of W bases (pba_align_batch_windows), made on the device
+    from the traceback walk.  Returns (results, list of window arrays of ALN_COUNTS_DTYPE -- views into one array --, counts)."""
+    pairs = np.ascontiguousarray(pairs, PAIR_DTYPE)
+    n = pairs.size
+    out = np.zeros(n, RESULT_DTYPE)
+    off = np.zeros(n + 1, np.uint64)
+    off[1:] = np.cumsum([windows_bound(int(p["a_pos"]), int(p["a_len"]), int(p["b_len"]), R, W, int(p["flags"]) & 1)     # PBA_A_BACKWARD
+                         for p in pairs], dtype=np.uint64) if n else 0
+    win = np.zeros(int(off[-1]) + 1, ALN_COUNTS_DTYPE)
+    nwin = np.zeros(max(n, 1), np.int32)
+    counts = np.zeros(max(n, 1), ALN_COUNTS_DTYPE)
+    self.check(self.lib.pba_align_batch_windows(self.h, A.h, B.h, _ptr(pairs), n, R, maxn, maxm, W, flags, _ptr(out), _ptr(win), _ptr(off),
+                                                _ptr(nwin), _ptr(counts)), "align_batch_windows")
+    return out, [win[int(off[q]):int(off[q]) + int(nwin[q])] for q in range(n)], counts[:n]
+
+
+def _rows_windows(self, fn, what, head, rows, dtype, R, W, cap, max_slots):
+    rows = np.ascontiguousarray(rows, dtype)
+    n = rows.size
+    off = np.zeros(n + 1, np.uint64)
+    counts = np.zeros(max(n, 1), ALN_COUNTS_DTYPE)
+    res = np.zeros(max(n, 1), RESULT_DTYPE)
+    total = C.c_uint64()
+    if cap is None:                                  # one call to learn the total, one to fetch: the windows are not kept between
+        self.check(fn(self.h, *head, _ptr(rows), n, R, W, None, 0, _ptr(off), C.byref(total), None, None, max_slots), what)
+        cap = total.value
+    win = np.zeros(max(int(cap), 1), ALN_COUNTS_DTYPE)
+    self.check(fn(self.h, *head, _ptr(rows), n, R, W, _ptr(win), int(cap), _ptr(off), C.byref(total), _ptr(counts), _ptr(res), max_slots), what)
+    wins, pos_ok = [], True
+    for k in range(n):
+        pos_ok = pos_ok and int(off[k + 1]) <= int(cap)
+        wins.append(win[int(off[k]):int(off[k + 1])] if pos_ok else None)
+    return wins, counts[:n], off, res[:n], total.value
+
+
+def _map_windows(self, target, reads, rows, R, W, reads_rc=None, cap=None, max_slots=0):
+    """Per-window counts of map_reads rows on the read's own grid (pba_map_rows_windows_budget).  Returns (windows per row --
+    views into one array, None for a row beyond cap --, counts, offsets, results, total windows)."""
+    head = (target.h, reads.h, reads_rc.h if reads_rc is not None else None)
+    return _rows_windows(self, self.lib.pba_map_rows_windows_budget, "map_windows", head, rows, MAP_ROW_DTYPE, R, W, cap, max_slots)
+
+
+def _overlap_windows(self, reads, rows, R, W, reads_rc=None, cap=None, max_slots=0):
+    """Per-window counts of overlap_strands rows on the TARGET's own grid, in the target's forward order, I / D named with the
+    query read as the query (pba_overlap_rows_windows_budget).  Returns what map_windows returns."""
+    head = (reads.h, reads_rc.h if reads_rc is not None else None)
+    return _rows_windows(self, self.lib.pba_overlap_rows_windows_budget, "overlap_windows", head, rows, STRAND_OVERLAP_DTYPE, R, W, cap,
+                         max_slots)
+
+
+def _windows_trim(self, wins, W, max_err, min_span):
+    """The trim rule on windows the caller supplies (pba_windows_trim): wins is a list of ALN_COUNTS_DTYPE arrays, one per item,
+    I / D named as under the default flags.  Returns TRIM_SPAN_DTYPE records."""
+    n = len(wins)
+    off = np.zeros(n + 1, np.uint64)
+    off[1:] = np.cumsum([len(w) for w in wins], dtype=np.uint64) if n else 0
+    flat = np.zeros(int(off[-1]) + 1, ALN_COUNTS_DTYPE)
+    for k, w in enumerate(wins):
+        flat[int(off[k]):int(off[k + 1])] = w
+    spans = np.zeros(max(n, 1), TRIM_SPAN_DTYPE)
+    self.check(self.lib.pba_windows_trim(self.h, _ptr(flat), _ptr(off), n, W, max_err, min_span, _ptr(spans)), "windows_trim")
+    return spans[:n]
+
+
+def _overlap_trim(self, reads, rows, R, W=100, max_err=0.25, min_span=64, reads_rc=None, max_slots=0):
+    """overlap_strands rows trimmed to their longest run of good target windows (pba_overlap_rows_trim_budget): windows and the
+    trim rule on the device.  Returns (TRIM_ROW_DTYPE records, one per row; stats dict)."""
+    rows = np.ascontiguousarray(rows, STRAND_OVERLAP_DTYPE)
+    out = np.zeros(max(rows.size, 1), TRIM_ROW_DTYPE)
+    st = _lib.PbaTrimStats()
+    self.check(self.lib.pba_overlap_rows_trim_budget(self.h, reads.h, reads_rc.h if reads_rc is not None else None, _ptr(rows), rows.size, R,
+                                                     W, max_err, min_span, _ptr(out), C.byref(st), max_slots), "overlap_trim")
+    return out[:rows.size], {n: getattr(st, n) for n, _ in _lib.PbaTrimStats._fields_}
+
+
+def _clip_reads_trimmed(self, reads, mask, R, W=100, max_err=0.25, min_span=64, max_trial=32, overlap_min=64, margin=100, min_cov=2,
+                        min_len=0, roles=3, keep_unseen=False, max_bases=0, strands=3, targets_per_call=10000, kernel=PBA_KERNEL_AUTO,
+                        reads_rc=None):
+    """overlap_strands_sharded -> overlap_trim -> trim_rows_apply -> clip -> apply: clip_reads with every row first narrowed to
+    its longest run of good W-base target windows, so that a row an alignment carried across a junction stops there.  Returns
+    (SeqSet of the clipped reads, the clip table, the UNTRIMMED overlap rows, the Clip's stats, the trim records, the trim stats).
+    A strand -1 row needs the reverse complements: reads_rc is built when it is not given."""
+    rc_own = None
+    if reads_rc is None and strands != 1:
+        reads_rc = rc_own = self.seqs_revcomp(reads)
+    try:
+        rows, _ = self.overlap_strands_sharded(reads, mask, R, max_trial, overlap_min, targets_per_call, kernel, strands=strands,
+                                               reads_rc=reads_rc)
+        trims, tstats = self.overlap_trim(reads, rows, R, W, max_err, min_span, reads_rc=reads_rc)
+    finally:
+        if rc_own is not None:
+            rc_own.close()
+    clip = self.clip(reads, trim_rows_apply(rows, trims), margin, min_cov, min_len, roles, keep_unseen, max_bases)
+    clipped, table = clip.apply(reads), clip.rows()
+    stats = clip.stats
+    clip.close()
+    return clipped, table, rows, stats, trims, tstats
+
+
+Context.align_batch_windows = _align_batch_windows
+Context.map_windows = _map_windows
+Context.overlap_windows = _overlap_windows
+Context.windows_trim = _windows_trim
+Context.overlap_trim = _overlap_trim
+Context.clip_reads_trimmed = _clip_reads_trimmed
 
 
 class Hpc:
