@@ -1135,6 +1135,92 @@ int pba_layout_consensus(pba_ctx *ctx, const pba_layout *lay, const pba_seqs *re
                          pba_seqs **consensus, pba_polish_row *rows_out /* nullable */, pba_layout_cons_stats *stats /* nullable */);
 
 /* ------------------------------------------------------------------------ */
+/* Per-base evidence and Phred qualities of an evolved set; FASTQ out        */
+/* (tests/qual_ref.py restates the rule).  Evolve decides      */
+/* every output character from a vote box (sel, sup, tot).  The *_qual calls */
+/* below keep, for every character, what the box said.  A pile-up is fresh:  */
+/* sel = weight on the target's own base, sup = 0, tot = 1.  For box i       */
+/* (input position i) of a target, w the pile-up's weight:                   */
+/*   N = tot - 1 + w: the rows that consumed the box by MATCH or DELETE      */
+/*   plus the weight of the target's own base (the weight counts as w        */
+/*   observations);                                                           */
+/*   the selection's character, if max4(sel) > tot / 2:                      */
+/*     agree = max4(sel), src = i;                                            */
+/*   then the suppliment's, if max4(sup) > tot / 2:                          */
+/*     agree = max4(sup), src = i | PBA_QUAL_SUP;                            */
+/*   both: depth = min(tot - 1, 65535), qv = phred(agree, N, qmax).          */
+/* phred, in integers alone (host, device and numpy agree bit for bit):      */
+/*   against = max(N - agree, 0)  (a suppliment counter can exceed N);       */
+/*   S[q] = d[q mod 10] * 10^(q div 10), d = {1000, 1258, 1584, 1995, 2511,  */
+/*   3162, 3981, 5011, 6309, 7943} = floor(1000 * 10^(r / 10));              */
+/*   qv = the largest q in [0, qmax] with (against + 1) * S[q] <=            */
+/*   (N + 2) * 1000 in u64: the Laplace estimate (against + 1) / (N + 2) on  */
+/*   the Phred scale, rounded down.  qmax in [0, PBA_QUAL_QMAX].             */
+/* The own base won iff the output base equals input base src.               */
+/* ------------------------------------------------------------------------ */
+#define PBA_QUAL_QMAX 60
+#define PBA_QUAL_QCAP 93            /* largest qv a pba_qual may hold: '!' + 93 = '~' */
+#define PBA_QUAL_SUP  0x80000000u
+typedef struct pba_qual pba_qual;   /* per-base evidence of one evolved set, resident on the device: 9 bytes a base */
+
+/* host arithmetic; -1 for qmax outside [0, 60] */
+int pba_qual_phred(uint32_t agree, uint64_t n, int qmax);
+/* the DEVICE function on host arrays, so the rule is pinned apart from the pile-ups (as pba_windows_trim) */
+int pba_qual_phred_device(pba_ctx *ctx, const uint32_t *agree, const uint64_t *n, uint64_t count, int qmax, uint8_t *qv);
+/* pba_pileup_evolve with the evidence of every character: the set and rows_out are byte for byte pba_pileup_evolve's, *qual
+ * has the set's count and lengths, the pile-up is spent afterwards.  A qmax outside [0, 60] is PBA_E_INVALID before anything
+ * happens: the pile-up stays usable. */
+int pba_pileup_evolve_qual(pba_ctx *ctx, pba_pileup *p, int qmax, pba_seqs **corrected, pba_correct_row *rows_out /* nullable */,
+                           pba_qual **qual);
+/* Evidence from host arrays, sequence k at [sum of lengths[0 .. k), + lengths[k]) of each.  A qv above PBA_QUAL_QCAP is
+ * PBA_E_INVALID, a total of 2^32 bases or more PBA_E_TOOLONG; n == 0 and empty sequences are legal. */
+int pba_qual_create(pba_ctx *ctx, const uint32_t *lengths, uint32_t n, const uint8_t *qv, const uint16_t *depth /* nullable: 0 */,
+                    const uint16_t *agree /* nullable: 0 */, const uint32_t *src /* nullable: position in its sequence */, pba_qual **out);
+uint32_t pba_qual_count(const pba_qual *q);
+int pba_qual_lengths(const pba_qual *q, uint32_t *len, uint32_t cap);
+/* sequences [lo, hi) back to back; every array nullable; *n always set; cap below *n: PBA_E_INVALID, nothing written */
+int pba_qual_get(pba_ctx *ctx, const pba_qual *q, uint32_t lo, uint32_t hi, uint8_t *qv, uint16_t *depth, uint16_t *agree, uint32_t *src,
+                 uint64_t cap, uint64_t *n);
+typedef struct { int32_t seq, len, n_sel, n_sup, n_unvoted /* depth == 0 */, n_below /* qv < qmin */, n_low_runs, min_qv /* -1: empty */,
+                 max_depth, pad; uint64_t sum_qv, sum_depth; } pba_qual_row;
+/* One row per sequence, reduced on the device (a long sequence by tiles of 4 096 bases): the per-base arrays do not cross to
+ * the host.  n_low_runs: the maximal runs of qv < qmin (the spans pba_qual_low_spans reports at min_run = 1).  qmin outside
+ * [0, 94] is PBA_E_INVALID; cap: entries of rows, at least the count. */
+int pba_qual_summary(pba_ctx *ctx, const pba_qual *q, int qmin, pba_qual_row *rows, uint32_t cap);
+typedef struct { int32_t seq, beg, end, min_qv; } pba_qual_span;
+/* The low spans: a span is a maximal run of positions with qv < qmin inside one sequence (a run never crosses into the next
+ * sequence); one of length end - beg >= min_run is reported with the smallest qv in it, sorted by (seq, beg).  Found, ranked,
+ * reduced and filtered on the device.  *n_out may exceed cap; then only cap spans are written.  qmin outside [0, 94] or
+ * min_run < 1 is PBA_E_INVALID. */
+int pba_qual_low_spans(pba_ctx *ctx, const pba_qual *q, int qmin, int min_run, pba_qual_span *out, uint64_t cap, uint64_t *n_out);
+/* Sequences [lo, hi) of s as one FASTQ image: record k is '@' name '\n' bases '\n' "+\n" quals '\n', the bases on one line,
+ * qual = '!' + qv.  Names as pba_seqs_write_fasta (the decimal id when both are NULL), code 3 prints as T, an empty sequence
+ * gives two empty lines.  *n_bytes is host arithmetic and always set; out == NULL asks for the size only; cap below the size is
+ * PBA_E_INVALID and nothing is written.  qual must have the set's count and lengths, else PBA_E_INVALID.  One kernel writes
+ * bases, quality characters and line ends into a device image, one copy brings it out, the host fills in the headers;
+ * pba_seqs_from_fastx reads the image back into the same set. */
+int pba_seqs_write_fastq(pba_ctx *ctx, const pba_seqs *s, const pba_qual *qual, uint32_t lo, uint32_t hi, const char *names,
+                         const uint64_t *name_off, char *out, uint64_t cap, uint64_t *n_bytes);
+void pba_qual_destroy(pba_qual *q);
+/* The three drivers with the evidence of what they return: the set, rows, log and stats are exactly those of
+ * pba_correct_reads_budget / pba_polish_contigs_budget / pba_layout_consensus, and *qual belongs to the returned set whatever
+ * the chunk or range cut.  A qmax outside [0, 60] is PBA_E_INVALID before anything happens.  pba_polish_contigs_qual returns
+ * the evidence of the LAST round: src addresses the contigs that entered that round (the caller's target when rounds == 1). */
+int pba_correct_reads_qual(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t t_lo, uint32_t t_hi,
+                           uint32_t mask, double R, int max_trial, int overlap_min, int kernel, int strands, int weight,
+                           uint64_t max_boxes, pba_seqs **corrected, pba_correct_row *rows_out, pba_overlap_stats stats[2], int qmax,
+                           pba_qual **qual);
+int pba_polish_contigs_qual(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc /* nullable */,
+                            uint32_t mask, double R, int trials, int min_len, int maxn, int maxm, int kernel, int strands,
+                            int overlap_min, int weight, int rounds, uint64_t max_boxes, pba_seqs **polished,
+                            pba_polish_row *rows_out /* nullable */, pba_polish_round_log *log /* nullable */, int log_cap, int qmax,
+                            pba_qual **qual);
+int pba_layout_consensus_qual(pba_ctx *ctx, const pba_layout *lay, const pba_seqs *reads, const pba_seqs *reads_rc /* nullable */,
+                              const pba_strand_overlap *rows, uint64_t n_rows, double R, int overlap_min, int weight,
+                              uint64_t max_boxes, pba_seqs **consensus, pba_polish_row *rows_out /* nullable */,
+                              pba_layout_cons_stats *stats /* nullable */, int qmax, pba_qual **qual);
+
+/* ------------------------------------------------------------------------ */
 /* Clipping: reads cut to the span their overlap rows support (overlap ->    */
 /* CLIP -> overlap -> layout -> consensus; DESIGN §5.8, tests/clip_ref.py    */
 /* restates the rule).  A row is a semi-global alignment under the ratio R,  */

@@ -125,6 +125,7 @@ PBA_CLIP_DROPPED, PBA_CLIP_WHOLE, PBA_CLIP_CUT = 0, 1, 2
 PBA_CLIP_TARGETS, PBA_CLIP_QUERIES, PBA_CLIP_KEEP_UNSEEN = 1, 2, 4
 PBA_FX_AUTO, PBA_FX_FASTA, PBA_FX_FASTQ = 0, 1, 2
 PBA_FX_KEEP_CASE, PBA_FX_STRICT_ACGT = 1, 2
+PBA_QUAL_QMAX, PBA_QUAL_QCAP, PBA_QUAL_SUP = 60, 93, 0x80000000
 
 
 class PbaFastxRec(C.Structure):
@@ -351,6 +352,24 @@ SYMBOLS = {
     "pba_overlap_rows_trim": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_double, C.c_int, C.c_double, C.c_int, _P, _P]),
     "pba_overlap_rows_trim_budget": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_double, C.c_int, C.c_double, C.c_int, _P, _P, C.c_uint64]),
     "pba_trim_rows_apply": (C.c_int64, [_P, _P, C.c_uint64, _P]),
+    "pba_qual_phred": (C.c_int, [C.c_uint32, C.c_uint64, C.c_int]),
+    "pba_qual_phred_device": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, _P]),
+    "pba_pileup_evolve_qual": (C.c_int, [_P, _P, C.c_int, C.POINTER(_P), _P, C.POINTER(_P)]),
+    "pba_qual_create": (C.c_int, [_P, _P, C.c_uint32, _P, _P, _P, _P, C.POINTER(_P)]),
+    "pba_qual_count": (C.c_uint32, [_P]),
+    "pba_qual_lengths": (C.c_int, [_P, _P, C.c_uint32]),
+    "pba_qual_get": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "pba_qual_summary": (C.c_int, [_P, _P, C.c_int, _P, C.c_uint32]),
+    "pba_qual_low_spans": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "pba_seqs_write_fastq": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "pba_qual_destroy": (None, [_P]),
+    "pba_correct_reads_qual": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, C.c_uint64, C.POINTER(_P), _P, _P, C.c_int, C.POINTER(_P)]),
+    "pba_polish_contigs_qual": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(_P), _P, _P, C.c_int, C.c_int,
+                                          C.POINTER(_P)]),
+    "pba_layout_consensus_qual": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.c_double, C.c_int, C.c_int, C.c_uint64, C.POINTER(_P), _P, _P,
+                                            C.c_int, C.POINTER(_P)]),
     "pba_strerror": (C.c_char_p, [C.c_int]),
 }
 

@@ -1,7 +1,7 @@
 // pba_host.h -- host-side objects and helpers shared by the translation units of libpba.so (pba_core.hip: context,
 // sequence sets; pba_index.hip: seed index; pba_align.hip: explicit pairs and edit scripts; pba_drivers.hip: the reference's ordered
 // first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction; pba_stream.hip: streamed locate and mapping; pba_layout.hip: layout; pba_clip.hip: clipping; pba_hpc.hip: homopolymer compression; pba_census.hip: seed-key census; pba_cigar.hip: run-length alignments and PAF; pba_windows.hip: per-window counts and trimmed rows;
-// pba_fastx.hip: FASTA / FASTQ in, FASTA out).  Internal: nothing here is part of the C ABI (include/pba.h).
+// pba_fastx.hip: FASTA / FASTQ in, FASTA out; pba_qual.hip: per-base evidence, its summaries and spans, FASTQ out).  Internal: nothing here is part of the C ABI (include/pba.h).
 // (What host and device share about the seed index -- the visiting rule, compress / compress_masks -- is index_plan.h's.)
 // Also here, once for all of them: the clip of seq_aligner.h:94-102 (text_clip), the launch plan (make_plan), the host
 // protocol of every aligning entry point but the all-vs-all walk -- narrow window first, the uncertified items again at the
@@ -608,6 +608,9 @@ PBA_INTERNAL int map_core(pba_ctx *ctx, const pba_index *ix, const pba_seqs *tar
 // outside ACGT is PBA_E_ALPHABET (pba_core.hip).  pba_seqs_from_fastx hands its gathered text to it (pba_fastx.hip).
 PBA_INTERNAL int seqs_pack(pba_ctx *ctx, const uint8_t *d_text, const uint64_t *d_toff, const uint64_t *h_toff, uint32_t n,
                            int strict, pba_seqs **out);
+// a pba_qual of n sequences under the offsets h_off[0 .. n] from four device arrays (qv u8, depth u16, agree u16, src u32) that
+// become its own; they are freed where it fails (pba_qual.hip).  The write passes of pba_pileup.hip fill them.
+PBA_INTERNAL int qual_adopt(pba_ctx *ctx, uint32_t n, const uint64_t *h_off, void *arr[4], pba_qual **out);
 // pba_map_reads' checks of its index and target (pba_drivers.hip)
 PBA_INTERNAL int map_target_ok(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target);
 }  // extern "C"

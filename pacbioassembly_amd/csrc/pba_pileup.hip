@@ -23,6 +23,7 @@
 // lengths, the host scans them, and a write pass puts every target's text at its final offset of one contiguous text,
 // which pba_seqs_from_device_text packs.
 #include "pba_host.h"
+#include "qual.h"
 
 #include <deque>
 #include <memory>
@@ -136,6 +137,61 @@ static __global__ void __launch_bounds__(256)
 k_pile_write_tiles(VoteInto P, const PileTile *tiles, uint32_t tile0, const unsigned long long *tile_off, char *text) {
     const PileTile t = tiles[tile0 + blockIdx.x];
     pile_block_write(P.C, P.box_off[t.seg] + t.first, pile_tile_len(P, t), text + tile_off[tile0 + blockIdx.x]);
+}
+
+// ---- the write pass with evidence (pba_pileup_evolve_qual; qual.h): pile_block_write's offsets, and for every
+// character the record of the box it came from, in the one pass that reads the boxes.  i0: the position inside its segment of
+// box `first`; at: where the block's first character goes in the text and in the four arrays of Q.
+static __device__ __forceinline__ void pile_block_write_qual(const ConsDev &C, unsigned long long first, unsigned long long len, uint32_t i0,
+                                                             char *text, const QualInto &Q, unsigned long long at0) {
+    __shared__ int part[4];
+    const int lane = threadIdx.x & (PBA_WAVE - 1), wave = threadIdx.x / PBA_WAVE;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    unsigned long long done = 0;
+    for (unsigned long long base = 0; base < len; base += 256) {
+        const unsigned long long i = base + threadIdx.x;
+        unsigned long long sel = 0, sup = 0;
+        int y = 0, tot = 0;
+        if (i < len) { sel = C.sel[first + i]; sup = C.sup[first + i]; tot = C.tot[first + i]; y = cons_yield(sel, sup, tot); }
+        const unsigned long long mv = __builtin_amdgcn_ballot_w64((y & 1) != 0), ms = __builtin_amdgcn_ballot_w64((y & 2) != 0);
+        if (lane == 0) part[wave] = __builtin_popcountll(mv) + __builtin_popcountll(ms);
+        __syncthreads();
+        int before = __builtin_popcountll(mv & below) + __builtin_popcountll(ms & below);
+        for (int w = 0; w < wave; ++w) before += part[w];
+        const int step = part[0] + part[1] + part[2] + part[3];
+        unsigned long long at = at0 + done + (unsigned long long)before;
+        if (y) {
+            const uint64_t n = (uint64_t)(tot - 1) + (uint64_t)Q.weight;
+            const uint16_t depth = (uint16_t)min(tot - 1, 65535);
+            const uint32_t pos = i0 + (uint32_t)i;
+            if (y & 1) {
+                const int a = cons_max4(sel);
+                text[at] = cons_winner(sel);
+                Q.qv[at] = (uint8_t)qual_phred((uint32_t)a, n, Q.qmax); Q.depth[at] = depth; Q.agree[at] = (uint16_t)a; Q.src[at] = pos;
+                ++at;
+            }
+            if (y & 2) {                                       // the split box sits right behind, as in pile_block_write
+                const int a = cons_max4(sup);
+                text[at] = cons_winner(sup);
+                Q.qv[at] = (uint8_t)qual_phred((uint32_t)a, n, Q.qmax); Q.depth[at] = depth; Q.agree[at] = (uint16_t)a; Q.src[at] = pos | PBA_QUAL_SUP;
+            }
+        }
+        done += (unsigned long long)step;
+        __syncthreads();                                       // part[] is rewritten by the next step
+    }
+}
+
+static __global__ void __launch_bounds__(256)
+k_pile_write_qual(VoteInto P, uint32_t k0, const unsigned long long *text_off, char *text, QualInto Q) {
+    const uint32_t k = k0 + blockIdx.x;
+    const unsigned long long first = P.box_off[k];
+    pile_block_write_qual(P.C, first, P.box_off[k + 1] - first, 0u, text, Q, text_off[k]);
+}
+
+static __global__ void __launch_bounds__(256)
+k_pile_write_tiles_qual(VoteInto P, const PileTile *tiles, uint32_t tile0, const unsigned long long *tile_off, char *text, QualInto Q) {
+    const PileTile t = tiles[tile0 + blockIdx.x];
+    pile_block_write_qual(P.C, P.box_off[t.seg] + t.first, pile_tile_len(P, t), t.first, text, Q, tile_off[tile0 + blockIdx.x]);
 }
 
 extern "C" {
@@ -439,7 +495,13 @@ int pba_pileup_dump(pba_ctx *ctx, const pba_pileup *p, uint32_t target, uint16_t
 }
 
 // a pile-up evolved to one contiguous device text: target k at text[off[k] .. off[k+1]); d_off: off on the device (nt + 1 u64)
-struct PileText { DevBuf text, d_off; std::vector<uint64_t> off; };
+// qmax >= 0: evolve also writes the evidence of every character (qual.h), one entry per text byte
+struct PileText {
+    DevBuf text, d_off;
+    std::vector<uint64_t> off;
+    int qmax = -1;
+    DevBuf qv, depth, agree, src;
+};
 
 // count pass: len_out[k] of every target; tiled form: also tile_off[i], where tile i's text starts inside the one text
 // (the scan runs on the host, which needs the lengths anyway: 2^31 boxes are 524 288 tiles)
@@ -479,7 +541,16 @@ static int pile_write(pba_ctx *ctx, const pba_pileup *p, const PileText *T, cons
         HIPCHK(hipMalloc(&d_toff.p, sizeof(uint64_t) * tile_off.size()));
         HIPCHK(hipMemcpyAsync(d_toff.p, tile_off.data(), sizeof(uint64_t) * tile_off.size(), hipMemcpyHostToDevice, ctx->stream));
     }
-    for (uint32_t k0 = 0; k0 < n; k0 += kPileSlice) {
+    const QualInto Q{T->qv.as<uint8_t>(), T->depth.as<uint16_t>(), T->agree.as<uint16_t>(), T->src.as<uint32_t>(), p->weight, T->qmax};
+    for (uint32_t k0 = 0; T->qmax >= 0 && k0 < n; k0 += kPileSlice) {
+        const dim3 grid(std::min(kPileSlice, n - k0));
+        if (p->d_tiles)
+            hipLaunchKernelGGL(k_pile_write_tiles_qual, grid, dim3(256), 0, ctx->stream, P, p->d_tiles, k0, d_toff.as<unsigned long long>(),
+                               T->text.as<char>(), Q);
+        else
+            hipLaunchKernelGGL(k_pile_write_qual, grid, dim3(256), 0, ctx->stream, P, k0, T->d_off.as<unsigned long long>(), T->text.as<char>(), Q);
+    }
+    for (uint32_t k0 = 0; T->qmax < 0 && k0 < n; k0 += kPileSlice) {
         const dim3 grid(std::min(kPileSlice, n - k0));
         if (p->d_tiles)
             hipLaunchKernelGGL(k_pile_write_tiles, grid, dim3(256), 0, ctx->stream, P, p->d_tiles, k0, d_toff.as<unsigned long long>(),
@@ -503,6 +574,13 @@ static int pile_evolve_text(pba_ctx *ctx, pba_pileup *p, PileText *T, pba_correc
     T->off.assign((size_t)nt + 1, 0);
     for (uint32_t k = 0; k < nt; ++k) T->off[k + 1] = T->off[k] + (uint64_t)len_out[k];
     HIPCHK(hipMalloc(&T->text.p, T->off[nt] + kSlack));
+    if (T->qmax >= 0) {
+        const size_t nc = (size_t)T->off[nt] + 16;
+        HIPCHK(hipMalloc(&T->qv.p, nc));
+        HIPCHK(hipMalloc(&T->depth.p, nc * 2));
+        HIPCHK(hipMalloc(&T->agree.p, nc * 2));
+        HIPCHK(hipMalloc(&T->src.p, nc * 4));
+    }
     HIPCHK(hipMalloc(&T->d_off.p, sizeof(uint64_t) * ((size_t)nt + 1)));
     HIPCHK(hipMemcpyAsync(T->d_off.p, T->off.data(), sizeof(uint64_t) * ((size_t)nt + 1), hipMemcpyHostToDevice, ctx->stream));
     PBA_TRY(pile_write(ctx, p, T, tile_off));
@@ -521,6 +599,27 @@ int pba_pileup_evolve(pba_ctx *ctx, pba_pileup *p, pba_seqs **corrected, pba_cor
     PileText T;
     PBA_TRY(pile_evolve_text(ctx, p, &T, rows_out));
     return pba_seqs_from_device_text(ctx, T.text.p, T.d_off.p, p->t_hi - p->t_lo, T.off.back(), 0, corrected);
+}
+
+// the evidence arrays of T into a pba_qual of its nt sequences (they leave T)
+static int pile_text_qual(pba_ctx *ctx, PileText &T, uint32_t nt, pba_qual **qual) {
+    void *arr[4] = {T.qv.p, T.depth.p, T.agree.p, T.src.p};
+    T.qv.p = T.depth.p = T.agree.p = T.src.p = nullptr;
+    return qual_adopt(ctx, nt, T.off.data(), arr, qual);
+}
+
+int pba_pileup_evolve_qual(pba_ctx *ctx, pba_pileup *p, int qmax, pba_seqs **corrected, pba_correct_row *rows_out, pba_qual **qual) {
+    if (!ctx || !p || !corrected || !qual) return PBA_E_INVALID;
+    *corrected = nullptr; *qual = nullptr;
+    if (qmax < 0 || qmax > PBA_QUAL_QMAX) PBA_FAIL(PBA_E_INVALID, "pba_pileup_evolve_qual: qmax must be in [0, 60]");
+    PileText T;
+    T.qmax = qmax;
+    const uint32_t nt = p->t_hi - p->t_lo;
+    PBA_TRY(pile_evolve_text(ctx, p, &T, rows_out));
+    PBA_TRY(pba_seqs_from_device_text(ctx, T.text.p, T.d_off.p, nt, T.off.back(), 0, corrected));
+    const int st = pile_text_qual(ctx, T, nt, qual);
+    if (st != PBA_OK) { pba_seqs_destroy(*corrected); *corrected = nullptr; }
+    return st;
 }
 
 int pba_ctx_last_correct_profile(const pba_ctx *ctx, pba_correct_profile *out) {
@@ -549,6 +648,7 @@ struct PileRun {
     StageClock clk;
     std::deque<PileText> chunks;                 // the evolved text of every range so far
     std::vector<pba_correct_row> crows;          // per contig (the contig drivers)
+    int qmax = -1;                               // >= 0: the next chunks evolve with their evidence (the *_qual drivers)
     ~PileRun() { pba_pileup_destroy(pile); if (rc) pba_seqs_destroy(rc); }
     // the reverse complement of the reads, made once where the caller gave none
     int need_rc() {
@@ -563,6 +663,7 @@ struct PileRun {
         {
             const auto timed = clk.time(ctx->stream, ms);
             chunks.emplace_back();
+            chunks.back().qmax = qmax;
             PBA_TRY(pile_evolve_text(ctx, pile, &chunks.back(), rows_out));
         }
         pba_pileup_destroy(pile); pile = nullptr;            // (host memory only by now: not part of the stage's time)
@@ -669,7 +770,7 @@ static int correct_vote(CorrectRun &c, uint32_t lo, uint32_t hi) {
 
 // The chunks' texts as one packed set of nt sequences.  One chunk: its text and device offsets as they are, no copy.
 // Otherwise (none: an empty range) the texts side by side in one buffer under offsets that run through.
-static int stitch_chunks(pba_ctx *ctx, std::deque<PileText> &chunks, uint32_t nt, uint64_t *n_bases_out, pba_seqs **out) {
+static int stitch_text(pba_ctx *ctx, std::deque<PileText> &chunks, uint32_t nt, uint64_t *n_bases_out, pba_seqs **out) {
     if (chunks.size() == 1) {
         const PileText &T = chunks[0];
         *n_bases_out = T.off.back();
@@ -696,9 +797,44 @@ static int stitch_chunks(pba_ctx *ctx, std::deque<PileText> &chunks, uint32_t nt
     return pba_seqs_from_device_text(ctx, all.p, d_off.p, nt, all_off.back(), 0, out);
 }
 
-static int correct_stitch(CorrectRun &c, pba_seqs **corrected) {
+// The chunks' evidence as one pba_qual of nt sequences, under the offsets stitch_text gives the texts.  One chunk: its arrays
+// as they are.
+static int stitch_qual(pba_ctx *ctx, std::deque<PileText> &chunks, uint32_t nt, pba_qual **qual) {
+    if (chunks.size() == 1) return pile_text_qual(ctx, chunks[0], nt, qual);
+    std::vector<uint64_t> all_off(1, 0);
+    for (const PileText &T : chunks) {
+        const uint64_t base = all_off.back();
+        for (size_t k = 1; k < T.off.size(); ++k) all_off.push_back(base + T.off[k]);
+    }
+    static const size_t width[4] = {1, 2, 2, 4};
+    DevBuf all[4];
+    for (int a = 0; a < 4; ++a) HIPCHK(hipMalloc(&all[a].p, ((size_t)all_off.back() + 16) * width[a]));
+    uint64_t at = 0;
+    for (const PileText &T : chunks) {
+        const void *from[4] = {T.qv.p, T.depth.p, T.agree.p, T.src.p};
+        for (int a = 0; a < 4 && T.off.back(); ++a)
+            HIPCHK(copy_d2d((uint8_t *)all[a].p + at * width[a], from[a], T.off.back() * width[a], ctx->stream));
+        at += T.off.back();
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    void *arr[4] = {all[0].p, all[1].p, all[2].p, all[3].p};
+    for (int a = 0; a < 4; ++a) all[a].p = nullptr;
+    return qual_adopt(ctx, nt, all_off.data(), arr, qual);
+}
+
+// the texts, and where qual is asked for (every chunk evolved with its evidence) the evidence that belongs to them
+static int stitch_chunks(pba_ctx *ctx, std::deque<PileText> &chunks, uint32_t nt, uint64_t *n_bases_out, pba_seqs **out,
+                         pba_qual **qual = nullptr) {
+    if (!qual) return stitch_text(ctx, chunks, nt, n_bases_out, out);
+    PBA_TRY(stitch_qual(ctx, chunks, nt, qual));
+    const int st = stitch_text(ctx, chunks, nt, n_bases_out, out);
+    if (st != PBA_OK) { pba_qual_destroy(*qual); *qual = nullptr; }
+    return st;
+}
+
+static int correct_stitch(CorrectRun &c, pba_seqs **corrected, pba_qual **qual) {
     const auto timed = c.clk.time(c.ctx->stream, &c.prof.evolve_ms);
-    return stitch_chunks(c.ctx, c.chunks, c.t_hi - c.t_lo, &c.prof.n_bases_out, corrected);
+    return stitch_chunks(c.ctx, c.chunks, c.t_hi - c.t_lo, &c.prof.n_bases_out, corrected, qual);
 }
 
 int pba_correct_reads(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t t_lo, uint32_t t_hi,
@@ -708,14 +844,17 @@ int pba_correct_reads(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads
                                     corrected, rows_out, stats);
 }
 
-int pba_correct_reads_budget(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t t_lo, uint32_t t_hi,
-                             uint32_t mask, double R, int max_trial, int overlap_min, int kernel, int strands, int weight,
-                             uint64_t max_boxes, pba_seqs **corrected, pba_correct_row *rows_out, pba_overlap_stats stats[2]) {
+// pba_correct_reads_budget, and with qual non-null pba_correct_reads_qual: every chunk evolves with its evidence at qmax
+static int correct_run(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t t_lo, uint32_t t_hi,
+                       uint32_t mask, double R, int max_trial, int overlap_min, int kernel, int strands, int weight,
+                       uint64_t max_boxes, pba_seqs **corrected, pba_correct_row *rows_out, pba_overlap_stats stats[2], int qmax,
+                       pba_qual **qual) {
     if (!ctx || !reads || !corrected || t_lo > t_hi || t_hi > reads->n) return PBA_E_INVALID;
     *corrected = nullptr;
     PBA_TRY(correct_check(ctx, reads, reads_rc, max_trial, strands, weight));
     HIPCHK(hipSetDevice(ctx->device));
     CorrectRun c{{ctx, reads, reads_rc}, t_lo, t_hi, R, overlap_min, kernel, strands, weight};
+    c.qmax = qual ? qmax : -1;
     if (!c.clk.init()) PBA_FAIL(PBA_E_HIP, "pba_correct_reads: events");
     memset(&c.prof, 0, sizeof c.prof);
     memset(c.tot, 0, sizeof c.tot);
@@ -736,10 +875,34 @@ int pba_correct_reads_budget(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs
         c.prof.n_rows += c.n_rows; c.prof.n_bases_in += boxes; ++c.prof.n_chunks;
         lo = hi;
     }
-    PBA_TRY(correct_stitch(c, corrected));
+    PBA_TRY(correct_stitch(c, corrected, qual));
     ctx->cprof = c.prof;
     if (stats) { stats[0] = c.tot[0]; stats[1] = c.tot[1]; }
     return PBA_OK;
+}
+
+int pba_correct_reads_budget(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t t_lo, uint32_t t_hi,
+                             uint32_t mask, double R, int max_trial, int overlap_min, int kernel, int strands, int weight,
+                             uint64_t max_boxes, pba_seqs **corrected, pba_correct_row *rows_out, pba_overlap_stats stats[2]) {
+    return correct_run(ctx, reads, reads_rc, t_lo, t_hi, mask, R, max_trial, overlap_min, kernel, strands, weight, max_boxes, corrected,
+                       rows_out, stats, -1, nullptr);
+}
+
+// what every *_qual driver checks before anything happens
+static int qual_args_ok(pba_ctx *ctx, const char *who, int qmax, pba_qual **qual) {
+    if (!ctx || !qual) return PBA_E_INVALID;
+    *qual = nullptr;
+    if (qmax < 0 || qmax > PBA_QUAL_QMAX) return ctx_fail_as(ctx, PBA_E_INVALID, who, "qmax must be in [0, 60]");
+    return PBA_OK;
+}
+
+int pba_correct_reads_qual(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t t_lo, uint32_t t_hi,
+                           uint32_t mask, double R, int max_trial, int overlap_min, int kernel, int strands, int weight,
+                           uint64_t max_boxes, pba_seqs **corrected, pba_correct_row *rows_out, pba_overlap_stats stats[2], int qmax,
+                           pba_qual **qual) {
+    PBA_TRY(qual_args_ok(ctx, "pba_correct_reads_qual", qmax, qual));
+    return correct_run(ctx, reads, reads_rc, t_lo, t_hi, mask, R, max_trial, overlap_min, kernel, strands, weight, max_boxes, corrected,
+                       rows_out, stats, qmax, qual);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -764,10 +927,10 @@ struct RoundResult { uint64_t n_voted, n_bases_in, n_bases_out; uint32_t n_chunk
 // One round over a contig set: pile-ups over consecutive ranges [lo, hi) under the budget (one contig at least, whatever
 // max_boxes says -- but a single contig beyond what the card can hold is PBA_E_NOMEM), each created and voted with
 // vote(first[lo], first[hi] - first[lo], &voted) -- the bucketed rows of its contigs -- then evolved into c.crows; the texts
-// stitched into *out.  vote_ms: create + vote; evolve_ms: evolve + stitch.  who: the public function that was called.
+// stitched into *out, with the round's evidence in *qual where that is asked for (c.qmax says at which cap).  vote_ms: create + vote; evolve_ms: evolve + stitch.  who: the public function that was called.
 extern "C++" template <class Vote>
 static int contig_round(PileRun &c, const char *who, const pba_seqs *contigs, int weight, uint64_t max_boxes,
-                        const std::vector<uint64_t> &first, Vote vote, RoundResult *r, pba_seqs **out) {
+                        const std::vector<uint64_t> &first, Vote vote, RoundResult *r, pba_seqs **out, pba_qual **qual = nullptr) {
     pba_ctx *ctx = c.ctx;
     const uint32_t nt = contigs->n;
     *r = RoundResult{};
@@ -791,7 +954,7 @@ static int contig_round(PileRun &c, const char *who, const pba_seqs *contigs, in
     for (uint32_t k = 0; k < nt; ++k) r->n_bases_in += contigs->h_len[k];
     {
         const auto timed = c.clk.time(ctx->stream, &r->evolve_ms);
-        PBA_TRY(stitch_chunks(ctx, c.chunks, nt, &r->n_bases_out, out));
+        PBA_TRY(stitch_chunks(ctx, c.chunks, nt, &r->n_bases_out, out, qual));
     }
     c.chunks.clear();
     return PBA_OK;
@@ -853,13 +1016,13 @@ static int polish_map(PolishRun &c) {
 }
 
 // one round: c.cur -> c.own (the set of the round before, if it was ours, is dropped)
-static int polish_round(PolishRun &c) {
+static int polish_round(PolishRun &c, pba_qual **qual) {
     PBA_TRY(polish_map(c));
     RoundResult r;
     pba_seqs *next = nullptr;
     PBA_TRY(contig_round(c, "pba_polish_contigs", c.cur, c.weight, c.max_boxes, c.first, [&](uint64_t at, uint64_t n, uint64_t *voted) {
         return pba_pileup_vote_mapped(c.ctx, c.pile, c.cur, c.reads, c.reads_rc, c.rows.data() + at, n, c.R, c.overlap_min, nullptr, voted);
-    }, &r, &next));
+    }, &r, &next, qual));
     c.lg.n_voted = (uint32_t)r.n_voted; c.lg.n_chunks = r.n_chunks; c.lg.n_bases_in = r.n_bases_in; c.lg.n_bases_out = r.n_bases_out;
     c.lg.vote_ms = r.vote_ms; c.lg.evolve_ms = r.evolve_ms;
     if (c.own) pba_seqs_destroy(c.own);
@@ -874,10 +1037,11 @@ int pba_polish_contigs(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *rea
                                      weight, rounds, 0, polished, rows_out, log, log_cap);
 }
 
-int pba_polish_contigs_budget(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t mask,
-                              double R, int trials, int min_len, int maxn, int maxm, int kernel, int strands, int overlap_min, int weight,
-                              int rounds, uint64_t max_boxes, pba_seqs **polished, pba_polish_row *rows_out,
-                              pba_polish_round_log *log, int log_cap) {
+// pba_polish_contigs_budget, and with qual non-null pba_polish_contigs_qual: the last round evolves with its evidence at qmax
+static int polish_run(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t mask,
+                      double R, int trials, int min_len, int maxn, int maxm, int kernel, int strands, int overlap_min, int weight,
+                      int rounds, uint64_t max_boxes, pba_seqs **polished, pba_polish_row *rows_out,
+                      pba_polish_round_log *log, int log_cap, int qmax, pba_qual **qual) {
     if (!ctx || !target || !reads || !polished || (log_cap > 0 && !log)) return PBA_E_INVALID;
     *polished = nullptr;
     PBA_TRY(polish_check(ctx, target, reads, reads_rc, strands, weight, rounds));
@@ -888,12 +1052,31 @@ int pba_polish_contigs_budget(pba_ctx *ctx, const pba_seqs *target, const pba_se
     for (int round = 0; round < rounds; ++round) {
         memset(&c.lg, 0, sizeof c.lg);
         c.lg.round = round + 1;
-        PBA_TRY(polish_round(c));
+        const bool last = round == rounds - 1;
+        c.qmax = qual && last ? qmax : -1;
+        PBA_TRY(polish_round(c, last ? qual : nullptr));
         if (round < log_cap) log[round] = c.lg;
     }
     polish_rows_out(c.crows, c.cur->n, rows_out);
     *polished = c.own; c.own = nullptr;
     return PBA_OK;
+}
+
+int pba_polish_contigs_budget(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t mask,
+                              double R, int trials, int min_len, int maxn, int maxm, int kernel, int strands, int overlap_min, int weight,
+                              int rounds, uint64_t max_boxes, pba_seqs **polished, pba_polish_row *rows_out,
+                              pba_polish_round_log *log, int log_cap) {
+    return polish_run(ctx, target, reads, reads_rc, mask, R, trials, min_len, maxn, maxm, kernel, strands, overlap_min, weight, rounds,
+                      max_boxes, polished, rows_out, log, log_cap, -1, nullptr);
+}
+
+int pba_polish_contigs_qual(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t mask,
+                            double R, int trials, int min_len, int maxn, int maxm, int kernel, int strands, int overlap_min, int weight,
+                            int rounds, uint64_t max_boxes, pba_seqs **polished, pba_polish_row *rows_out,
+                            pba_polish_round_log *log, int log_cap, int qmax, pba_qual **qual) {
+    PBA_TRY(qual_args_ok(ctx, "pba_polish_contigs_qual", qmax, qual));
+    return polish_run(ctx, target, reads, reads_rc, mask, R, trials, min_len, maxn, maxm, kernel, strands, overlap_min, weight, rounds,
+                      max_boxes, polished, rows_out, log, log_cap, qmax, qual);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -918,9 +1101,10 @@ static int laycons_place(LayConsRun &c, const pba_layout *lay, const pba_strand_
     return PBA_OK;
 }
 
-int pba_layout_consensus(pba_ctx *ctx, const pba_layout *lay, const pba_seqs *reads, const pba_seqs *reads_rc,
-                         const pba_strand_overlap *rows, uint64_t n_rows, double R, int overlap_min, int weight, uint64_t max_boxes,
-                         pba_seqs **consensus, pba_polish_row *rows_out, pba_layout_cons_stats *stats) {
+// pba_layout_consensus, and with qual non-null pba_layout_consensus_qual: the round evolves with its evidence at qmax
+static int laycons_run(pba_ctx *ctx, const pba_layout *lay, const pba_seqs *reads, const pba_seqs *reads_rc,
+                       const pba_strand_overlap *rows, uint64_t n_rows, double R, int overlap_min, int weight, uint64_t max_boxes,
+                       pba_seqs **consensus, pba_polish_row *rows_out, pba_layout_cons_stats *stats, int qmax, pba_qual **qual) {
     if (!ctx || !lay || !reads || !consensus || (!rows && n_rows)) return PBA_E_INVALID;
     *consensus = nullptr;
     if (weight < 1 || weight > 0xFFFF) PBA_FAIL(PBA_E_INVALID, "pba_layout_consensus: weight must be in [1, 65535]");
@@ -930,6 +1114,7 @@ int pba_layout_consensus(pba_ctx *ctx, const pba_layout *lay, const pba_seqs *re
     if (reads->non_acgt || (reads_rc && reads_rc->non_acgt)) PBA_FAIL(PBA_E_ALPHABET, "pba_layout_consensus: a set holds bytes outside ACGT");
     HIPCHK(hipSetDevice(ctx->device));
     LayConsRun c{{ctx, reads, reads_rc}};
+    c.qmax = qual ? qmax : -1;
     if (!c.clk.init()) PBA_FAIL(PBA_E_HIP, "pba_layout_consensus: events");
     memset(&c.st, 0, sizeof c.st);
     {
@@ -940,13 +1125,26 @@ int pba_layout_consensus(pba_ctx *ctx, const pba_layout *lay, const pba_seqs *re
     RoundResult r;
     PBA_TRY(contig_round(c, "pba_layout_consensus", c.contigs, weight, max_boxes, c.first, [&](uint64_t at, uint64_t n, uint64_t *voted) {
         return pba_pileup_vote_placed(ctx, c.pile, c.contigs, reads, c.reads_rc, c.places.data() + at, n, R, overlap_min, nullptr, voted);
-    }, &r, consensus));
+    }, &r, consensus, qual));
     c.st.n_contigs = c.contigs->n;
     c.st.n_voted = r.n_voted; c.st.n_chunks = r.n_chunks; c.st.n_bases_in = r.n_bases_in; c.st.n_bases_out = r.n_bases_out;
     c.st.vote_ms = r.vote_ms; c.st.evolve_ms = r.evolve_ms;
     polish_rows_out(c.crows, c.contigs->n, rows_out);
     if (stats) *stats = c.st;
     return PBA_OK;
+}
+
+int pba_layout_consensus(pba_ctx *ctx, const pba_layout *lay, const pba_seqs *reads, const pba_seqs *reads_rc,
+                         const pba_strand_overlap *rows, uint64_t n_rows, double R, int overlap_min, int weight, uint64_t max_boxes,
+                         pba_seqs **consensus, pba_polish_row *rows_out, pba_layout_cons_stats *stats) {
+    return laycons_run(ctx, lay, reads, reads_rc, rows, n_rows, R, overlap_min, weight, max_boxes, consensus, rows_out, stats, -1, nullptr);
+}
+
+int pba_layout_consensus_qual(pba_ctx *ctx, const pba_layout *lay, const pba_seqs *reads, const pba_seqs *reads_rc,
+                              const pba_strand_overlap *rows, uint64_t n_rows, double R, int overlap_min, int weight, uint64_t max_boxes,
+                              pba_seqs **consensus, pba_polish_row *rows_out, pba_layout_cons_stats *stats, int qmax, pba_qual **qual) {
+    PBA_TRY(qual_args_ok(ctx, "pba_layout_consensus_qual", qmax, qual));
+    return laycons_run(ctx, lay, reads, reads_rc, rows, n_rows, R, overlap_min, weight, max_boxes, consensus, rows_out, stats, qmax, qual);
 }
 
 }  // extern "C"

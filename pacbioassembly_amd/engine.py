@@ -70,6 +70,12 @@ PBA_FX_KEEP_CASE, PBA_FX_STRICT_ACGT = _lib.PBA_FX_KEEP_CASE, _lib.PBA_FX_STRICT
 FASTX_REC_DTYPE = np.dtype([("hdr_off", "<u8"), ("seq_off", "<u8"), ("qual_off", "<u8"), ("hdr_len", "<u4"), ("name_len", "<u4"),
                             ("seq_len", "<u4"), ("n_seq_lines", "<u4")])
 assert FASTX_REC_DTYPE.itemsize == C.sizeof(_lib.PbaFastxRec) == 40
+# pba_qual_row: one per sequence of a Qual; pba_qual_span: a maximal run of qv < qmin inside one sequence
+PBA_QUAL_QMAX, PBA_QUAL_QCAP, PBA_QUAL_SUP = _lib.PBA_QUAL_QMAX, _lib.PBA_QUAL_QCAP, _lib.PBA_QUAL_SUP
+QUAL_ROW_DTYPE = np.dtype([(n, "<i4") for n in ("seq", "len", "n_sel", "n_sup", "n_unvoted", "n_below", "n_low_runs", "min_qv",
+                                                "max_depth", "pad")] + [("sum_qv", "<u8"), ("sum_depth", "<u8")])
+QUAL_SPAN_DTYPE = np.dtype([(n, "<i4") for n in ("seq", "beg", "end", "min_qv")])
+assert QUAL_ROW_DTYPE.itemsize == 56 and QUAL_SPAN_DTYPE.itemsize == 16
 
 
 class PbaError(RuntimeError):
@@ -1085,6 +1091,114 @@ class SeqSet:
                        "write_fasta")
         return out[:size.value].tobytes()
 
+    def write_fastq(self, qual: "Qual", names=None, lo: int = 0, hi: Optional[int] = None) -> bytes:
+        """Sequences [lo, hi) with the qualities of `qual` as one FASTQ image (pba_seqs_write_fastq: one kernel, one copy, the
+        bases on one line, quality character '!' + qv).  names: as write_fasta.  qual must have this set's count and lengths."""
+        hi = self.count if hi is None else hi
+        if names is None:
+            nm = no = None
+        else:
+            bn = [x if isinstance(x, bytes) else str(x).encode("latin-1") for x in names]
+            if len(bn) != hi - lo:
+                raise ValueError(f"{len(bn)} names for {hi - lo} sequences")
+            nm_a, no_a = concat(bn)
+            nm_a = np.concatenate([nm_a, np.zeros(1, np.uint8)])
+            nm, no = _ptr(nm_a), _ptr(no_a)
+        size = C.c_uint64()
+        self.ctx.check(self.ctx.lib.pba_seqs_write_fastq(self.ctx.h, self.h, qual.h, lo, hi, nm, no, None, 0, C.byref(size)), "write_fastq")
+        out = np.zeros(max(size.value, 1), np.uint8)
+        self.ctx.check(self.ctx.lib.pba_seqs_write_fastq(self.ctx.h, self.h, qual.h, lo, hi, nm, no, _ptr(out), size.value, C.byref(size)),
+                       "write_fastq")
+        return out[:size.value].tobytes()
+
+
+def qual_phred(agree: int, n: int, qmax: int = PBA_QUAL_QMAX) -> int:
+    """pba_qual_phred (host arithmetic): the largest q in [0, qmax] with (max(n - agree, 0) + 1) * S[q] <= (n + 2) * 1000;
+    -1 for a qmax outside [0, 60]."""
+    return int(_lib.load().pba_qual_phred(agree, n, qmax))
+
+
+class Qual:
+    """The per-base evidence of an evolved set, resident on the device (pba_qual): for every character its qv, the depth and
+    agree of the box it came from and src, the input position (PBA_QUAL_SUP set for a character split from a suppliment)."""
+
+    def __init__(self, ctx: "Context", h):
+        self.ctx, self.h = ctx, h
+
+    @classmethod
+    def from_arrays(cls, ctx: "Context", lengths, qv, depth=None, agree=None, src=None) -> "Qual":
+        """pba_qual_create: sequence k owns the next lengths[k] entries of every array.  depth / agree default to 0, src to the
+        position in its sequence."""
+        lengths = np.ascontiguousarray(lengths, np.uint32)
+        total = int(lengths.astype(np.uint64).sum())
+        arrs = []
+        for a, dt in ((qv, np.uint8), (depth, np.uint16), (agree, np.uint16), (src, np.uint32)):
+            if a is None:
+                arrs.append(None)
+                continue
+            a = np.ascontiguousarray(a, dt)
+            if a.size != total:
+                raise ValueError(f"{a.size} entries for {total} bases")
+            arrs.append(a)
+        h = C.c_void_p()
+        ctx.check(ctx.lib.pba_qual_create(ctx.h, _ptr(lengths) if lengths.size else None, lengths.size,
+                                          *[_ptr(a) if a is not None and a.size else None for a in arrs], C.byref(h)), "qual_create")
+        return cls(ctx, h)
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.ctx.lib.pba_qual_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def count(self) -> int:
+        return self.ctx.lib.pba_qual_count(self.h)
+
+    def lengths(self) -> np.ndarray:
+        out = np.zeros(max(self.count, 1), np.uint32)
+        self.ctx.check(self.ctx.lib.pba_qual_lengths(self.h, _ptr(out), self.count), "qual_lengths")
+        return out[:self.count]
+
+    def get(self, lo: int = 0, hi: Optional[int] = None) -> dict:
+        """{"qv", "depth", "agree", "src"} of sequences [lo, hi), back to back."""
+        hi = self.count if hi is None else hi
+        n = C.c_uint64()
+        st = self.ctx.lib.pba_qual_get(self.ctx.h, self.h, lo, hi, None, None, None, None, 1 << 62, C.byref(n))
+        self.ctx.check(st, "qual_get")
+        cap = n.value
+        out = {"qv": np.zeros(max(cap, 1), np.uint8), "depth": np.zeros(max(cap, 1), np.uint16),
+               "agree": np.zeros(max(cap, 1), np.uint16), "src": np.zeros(max(cap, 1), np.uint32)}
+        self.ctx.check(self.ctx.lib.pba_qual_get(self.ctx.h, self.h, lo, hi, _ptr(out["qv"]), _ptr(out["depth"]), _ptr(out["agree"]),
+                                                 _ptr(out["src"]), cap, C.byref(n)), "qual_get")
+        return {k: v[:cap] for k, v in out.items()}
+
+    def summary(self, qmin: int) -> np.ndarray:
+        """One QUAL_ROW_DTYPE row per sequence, reduced on the device (pba_qual_summary)."""
+        rows = np.zeros(max(self.count, 1), QUAL_ROW_DTYPE)
+        self.ctx.check(self.ctx.lib.pba_qual_summary(self.ctx.h, self.h, qmin, _ptr(rows), self.count), "qual_summary")
+        return rows[:self.count]
+
+    def low_spans(self, qmin: int, min_run: int = 1, cap: Optional[int] = None) -> np.ndarray:
+        """The maximal runs of qv < qmin of at least min_run bases as QUAL_SPAN_DTYPE rows sorted by (seq, beg)
+        (pba_qual_low_spans).  cap: room for that many; None: all of them (a second call where the first guess was short)."""
+        room = 1024 if cap is None else cap
+        while True:
+            out = np.zeros(max(room, 1), QUAL_SPAN_DTYPE)
+            n = C.c_uint64()
+            self.ctx.check(self.ctx.lib.pba_qual_low_spans(self.ctx.h, self.h, qmin, min_run, _ptr(out), room, C.byref(n)), "qual_low_spans")
+            if cap is not None:
+                self.n_low_spans = int(n.value)
+                return out[:min(room, n.value)]
+            if n.value <= room:
+                return out[:n.value]
+            room = int(n.value)
+
 
 class BorrowedSeqSet(SeqSet):
     """A set that belongs to a LocStream slot (LocStream.pending): closing the wrapper frees nothing, and the handle must not
@@ -1271,6 +1385,14 @@ class Pileup:
         self.ctx.check(self.ctx.lib.pba_pileup_evolve(self.ctx.h, self.h, C.byref(h), _ptr(rows)), "pileup_evolve")
         return SeqSet(self.ctx, h), rows[:self.t_hi - self.t_lo]
 
+    def evolve_qual(self, qmax: int = PBA_QUAL_QMAX):
+        """evolve() with the evidence of every character (pba_pileup_evolve_qual).  Returns (SeqSet, rows of CORRECT_ROW_DTYPE,
+        Qual); the pile-up is spent afterwards.  A qmax outside [0, 60] is refused and leaves the pile-up usable."""
+        rows = np.zeros(max(self.t_hi - self.t_lo, 1), CORRECT_ROW_DTYPE)
+        h, qh = C.c_void_p(), C.c_void_p()
+        self.ctx.check(self.ctx.lib.pba_pileup_evolve_qual(self.ctx.h, self.h, qmax, C.byref(h), _ptr(rows), C.byref(qh)), "pileup_evolve_qual")
+        return SeqSet(self.ctx, h), rows[:self.t_hi - self.t_lo], Qual(self.ctx, qh)
+
 
 class Layout:
     """The layout of a read set from its overlap rows (pba_layout): containments, the best dovetail at every read end,
@@ -1367,9 +1489,58 @@ def _layout_consensus(self, lay, reads, rows, R, overlap_min=64, weight=1, max_b
     return SeqSet(self, h), rows_out[:nc], stats
 
 
+def _layout_consensus_qual(self, lay, reads, rows, R, overlap_min=64, weight=1, max_boxes=0, reads_rc=None, qmax=PBA_QUAL_QMAX):
+    """layout_consensus with the evidence of the contigs it returns (pba_layout_consensus_qual): its returns with the Qual
+    appended."""
+    rows = np.ascontiguousarray(rows, STRAND_OVERLAP_DTYPE)
+    nc = int(self.lib.pba_layout_contigs(lay.h))
+    rows_out = np.zeros(max(nc, 1), POLISH_ROW_DTYPE)
+    st = _lib.PbaLayoutConsStats()
+    h, qh = C.c_void_p(), C.c_void_p()
+    rc_h = reads_rc.h if reads_rc is not None else None
+    self.check(self.lib.pba_layout_consensus_qual(self.h, lay.h, reads.h, rc_h, _ptr(rows), rows.size, R, overlap_min, weight, max_boxes,
+                                                  C.byref(h), _ptr(rows_out), C.byref(st), qmax, C.byref(qh)), "layout_consensus_qual")
+    stats = {n: getattr(st.place, n) for n, _ in _lib.PbaPlaceStats._fields_}
+    stats.update({n: getattr(st, n) for n, _ in _lib.PbaLayoutConsStats._fields_ if n != "place"})
+    return SeqSet(self, h), rows_out[:nc], stats, Qual(self, qh)
+
+
+def _polish_contigs_qual(self, target, reads, mask, R, trials=50, min_len=500, maxn=0, maxm=0, kernel=PBA_KERNEL_AUTO, strands=3,
+                         overlap_min=64, weight=1, rounds=1, reads_rc=None, max_boxes=0, qmax=PBA_QUAL_QMAX):
+    """polish_contigs with the evidence of the LAST round (pba_polish_contigs_qual; src addresses the contigs that entered
+    that round): its returns with the Qual appended."""
+    rows = np.zeros(max(target.count, 1), POLISH_ROW_DTYPE)
+    log = np.zeros(max(rounds, 1), POLISH_LOG_DTYPE)
+    h, qh = C.c_void_p(), C.c_void_p()
+    rc_h = reads_rc.h if reads_rc is not None else None
+    st = self.lib.pba_polish_contigs_qual(self.h, target.h, reads.h, rc_h, mask, R, trials, min_len, maxn, maxm, kernel, strands,
+                                          overlap_min, weight, rounds, max_boxes, C.byref(h), _ptr(rows), _ptr(log), log.size, qmax,
+                                          C.byref(qh))
+    self.check(st, "polish_contigs_qual")
+    return SeqSet(self, h), rows[:target.count], log[:max(rounds, 0)], Qual(self, qh)
+
+
+def _correct_reads_qual(self, reads, mask, R, max_trial=32, overlap_min=64, strands=3, weight=1, t_lo=0, t_hi=None,
+                        kernel=PBA_KERNEL_AUTO, reads_rc=None, max_boxes=0, qmax=PBA_QUAL_QMAX):
+    """correct_reads with the evidence of the corrected reads (pba_correct_reads_qual), whatever the chunk cut: its returns
+    with the Qual appended."""
+    t_hi = reads.count if t_hi is None else t_hi
+    rows = np.zeros(max(t_hi - t_lo, 1), CORRECT_ROW_DTYPE)
+    st2 = (_lib.PbaOverlapStats * 2)()
+    h, qh = C.c_void_p(), C.c_void_p()
+    rc_h = reads_rc.h if reads_rc is not None else None
+    st = self.lib.pba_correct_reads_qual(self.h, reads.h, rc_h, t_lo, t_hi, mask, R, max_trial, overlap_min, kernel, strands, weight,
+                                         max_boxes, C.byref(h), _ptr(rows), C.byref(st2), qmax, C.byref(qh))
+    self.check(st, "correct_reads_qual")
+    return SeqSet(self, h), rows[:max(t_hi - t_lo, 0)], _stats_pair(st2), Qual(self, qh)
+
+
 Context.layout = _layout
 Context.layout_reads = _layout_reads
 Context.layout_consensus = _layout_consensus
+Context.layout_consensus_qual = _layout_consensus_qual
+Context.polish_contigs_qual = _polish_contigs_qual
+Context.correct_reads_qual = _correct_reads_qual
 
 
 class Clip:
