@@ -47,9 +47,11 @@
 
 #include "align_rowsweep.h"
 #include "dev_common.h"
+#include "text_ring.h"
 
 #define PBA_BV_MAX_NB 8
 #define PBA_BV_FIN_WORDS(nb) ((2 * (nb) + 1) * 64)     // u32 of LDS per wavefront for the last column's deltas (bitvec_pass: fin)
+#define PBA_BV_LDS_BYTES(nb) (PBA_BV_FIN_WORDS(nb) * 4 + PBA_TXR_BYTES)   // per wavefront: the fin words, then the text ring (text_ring.h)
 #define PBA_BV_BAND_NUM 9      // first-pass half width = max(max_dst/2, 9/16 * max_dst) + 1
 #define PBA_BV_BAND_DEN 16
 
@@ -146,7 +148,8 @@ __device__ __forceinline__ uint32_t bit_mask(uint32_t x, int k) {
 // masks in SGPR pairs), and the lane-to-lane hand-off of those deltas is a SCALAR rotate of the two masks -- no
 // DPP, no VALU.  The diagonal's D0 bits are collected with one bitop3 (in the diagonal's block only, at one or two
 // blocks per lane) under a wave-uniform one-hot that a scalar shift advances; text
-// elements come from two 32-step bit-plane registers.  Everything rare is scheduled: the events of the sweep fall at
+// elements come from two 32-step bit-plane registers, or (RING: the score-only forms of the aligning kernels) as ready mask
+// pairs from the wavefront's text ring in LDS (text_ring.h), two steps' with one read.  Everything rare is scheduled: the events of the sweep fall at
 // steps known in advance, kept as wave-uniform timers, and the step loop runs from one to the next without a test.
 //
 // TRACE: also store, for every step and block, the two words the traceback needs (bv_trace_walk below):
@@ -171,7 +174,7 @@ __device__ __forceinline__ void bv_ckpt_store(uint32_t *tr, int tb, int lane, co
         ck[NB * 128 + 64 + lane] = lane == 0 ? (uint32_t)hp_last : lane == 1 ? (uint32_t)(hp_last >> 32) : lane == 2 ? (uint32_t)hn_last : (uint32_t)(hn_last >> 32);
 }
 
-template <int NB, int TRACE = 0, bool BAIL = false>
+template <int NB, int TRACE = 0, bool BAIL = false, bool RING = false>
 __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, const PackedFetch &colsF, int m, int wleft, int w,
                                            double R, int &best_out, int &besti_out, int &diag_out, uint32_t *fin,
                                            uint32_t *tr = nullptr, bool swap_roles = false, int bail_w = 0) {
@@ -194,8 +197,9 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     (void)nb_m; (void)r_m;
 
     uint32_t Pv[NB], Mv[NB], Plo[NB], Phi[NB], acc[NB];
-    int s_cur = lane;
+    int s_cur = lane;      // (the forms without the text ring: LANE_SB below)
     uint32_t opened = 0;   // 0 / 1 in a VGPR (a bool would live in an SGPR pair and be re-merged with exec every step)
+    (void)opened;
     if (s_cur < S) {
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) load_planes32(rowsF, s_cur * RB + 32 * nb, Plo[nb], Phi[nb]);
@@ -221,6 +225,15 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     int T_diag = 1, s_dg = 0;
     int T_seg = min(32, m) + 1, s_sg = 0;
     int s_next = 1;                              // the earliest of the five
+    // Which superblock a lane holds, and whether its window is open, belong to the schedule too: a lane moves on to s + 64
+    // when superblock s closes, closes fire in the order of s, so the lanes hold s_cl .. s_cl + 63; the open windows are those
+    // of s_cl .. s_op - 1.  The RING forms keep neither in a vector register: the few places that ask (a chunk's start, the
+    // end) derive them, which is what lets the ring's two-step stretch into 64 registers without a spilled word more.  The
+    // other forms (LANE_SB) keep both in the lane, updated by the events, as they always did.  (Macros, not lambdas: two
+    // more closures over the schedule's scalars cost k_cigar_pairs<4> and k_vote_pairs<4, true, false> a wave per SIMD.)
+    constexpr bool LANE_SB = !RING;
+#define PBA_BV_LANE_SB() (LANE_SB ? s_cur : s_cl + ((lane - s_cl) & (PBA_WAVE - 1)))
+#define PBA_BV_LANE_OPEN() (LANE_SB ? opened != 0 : PBA_BV_LANE_SB() < s_op)
     // Where the diagonal is: at any step it is in one block of one lane, or in none (the one-step gap between two
     // superblocks, and past row m).  Both are wave-uniform and belong to the schedule: `one` is the one-hot of the diagonal
     // cell's bit in its block's word (0: in no block), qd that block.  The diagonal-entry event and segment_done set them; the
@@ -236,6 +249,12 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     (void)dmw; (void)one; (void)qd;
 
     uint32_t wl = 0, wh = 0;                     // text bit planes: bit k = low / high bit of the element of step tb+k
+    // RING: no planes -- the text comes from the wavefront's ring in LDS (text_ring.h), PBA_TXR_BYTES behind the fin words:
+    // ta is this lane's cell for the step at hand, one cell further every step
+    typedef __attribute__((address_space(3))) uint64_t txr_cell;
+    txr_cell *const ring = (txr_cell *)(fin + PBA_BV_FIN_WORDS(NB));
+    const txr_cell *ta = ring;
+    (void)wl; (void)wh; (void)ring; (void)ta;
     // wave-uniform, in scalar registers: the running D(i,i) at the end of the last segment judged (segments end in row
     // order, so it simply carries on from lane to lane) and the first failing row (0: none so far)
     int score = 0, fail_row = 0;
@@ -250,8 +269,23 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     // step it takes superblock s (0 < s < S) up to the step before the lane above closes
     uint64_t valid = (S >= PBA_WAVE ? ~0ull : (1ull << S) - 1ull) & ~1ull;
 
-    // text planes for the 32 steps starting at the wave-uniform step tb (element of step t is t - s_cur - 1)
-    auto load_text = [&](int tb) { load_planes32(colsF, tb - s_cur - 1, wl, wh); };
+    // text planes for the 32 steps starting at the wave-uniform step tb (element of step t is t - 1 - the lane's superblock)
+    // RING: the wavefront fetches the chunk's 32 new elements once and every lane writes one cell -- lanes 0..31
+    // element first + lane at its slot, lanes 32..63 the same elements' second copies where a slot has one (else the
+    // first copy once more) -- then takes its own address.  A wavefront's LDS operations complete in order: no wait.
+    auto load_text = [&](int tb) {
+        if constexpr (RING) {
+            const int first = txr_fetch_first(tb, s_cl);
+            uint32_t plo, phi;
+            load_planes32(colsF, first, plo, phi);
+            const int c = lane & (PBA_TXR_CHUNK - 1), slot = txr_slot(first + c), mir = txr_mirror(slot);
+            const int dst = (lane >= PBA_TXR_CHUNK && mir >= 0) ? mir : slot;
+            ring[dst] = (uint64_t)(0u - ((plo >> c) & 1u)) | ((uint64_t)(0u - ((phi >> c) & 1u)) << 32);
+            ta = ring + txr_addr(tb, PBA_BV_LANE_SB());
+        } else {
+            load_planes32(colsF, tb - PBA_BV_LANE_SB() - 1, wl, wh);
+        }
+    };
 
     // The 32-row diagonal segment of superblock s ending at row i (a multiple of 32, or m) is complete: check its rows
     // against seq_aligner.h:185 and carry the diagonal score on.  Judged on the scalar side: s, i, the running score and
@@ -311,17 +345,19 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
             const int s = s_cl;                                                       \
             if (lane == (s & (PBA_WAVE - 1))) {                                       \
                 if (s >= s_m) {              /* its window ended with the last column: keep that column */ \
-                    fin[2 * NB * PBA_WAVE + lane] = (uint32_t)s_cur;                  \
+                    fin[2 * NB * PBA_WAVE + lane] = (uint32_t)(LANE_SB ? s_cur : s);  \
                     _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) { fin[2 * nb * PBA_WAVE + lane] = Pv[nb]; fin[(2 * nb + 1) * PBA_WAVE + lane] = Mv[nb]; } \
                 }                                                                     \
                 /* the lane's next superblock: its rows, and its slice of the text (a lane that opens its first window \
                    already got its planes at the start of the chunk: no load, no wait -- during the ramp one lane opens \
                    per step, and false candidates are all ramp) */                    \
-                s_cur += PBA_WAVE; opened = 0;                                        \
+                if constexpr (LANE_SB) { s_cur += PBA_WAVE; opened = 0; }             \
+                const int sn = LANE_SB ? s_cur : s + PBA_WAVE;                        \
                 if (s + PBA_WAVE < S) {                                               \
-                    _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) load_planes32(rowsF, s_cur * RB + 32 * nb, Plo[nb], Phi[nb]); \
+                    _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) load_planes32(rowsF, sn * RB + 32 * nb, Plo[nb], Phi[nb]); \
                 }                                                                     \
-                load_text(t - ((t - 1) & 31));                                        \
+                if constexpr (RING) ta = ring + txr_addr(t, sn);      /* 64 elements back; they are in the ring */ \
+                else load_text(t - ((t - 1) & 31));                                   \
             }                                                                         \
             /* this lane takes the lane above's hout again if it has a superblock left; the lane below stops taking this one's a step later */ \
             T_hin = t + 1; l_hn = (s + 1) & (PBA_WAVE - 1);                           \
@@ -332,7 +368,7 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
         if (t == T_open) {                                                            \
             if (lane == (s_op & (PBA_WAVE - 1))) {                                    \
                 _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) { Pv[nb] = ~0u; Mv[nb] = 0u; } \
-                opened = 1;                                                           \
+                if constexpr (LANE_SB) opened = 1;                                    \
             }                                                                         \
             s_op += 1;                                                                \
             T_open = s_op < S ? max(1, s_op * RB + 1 - wleft) + s_op : INT_MAX;       \
@@ -347,7 +383,7 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
             T_diag = s_dg * RB < m ? s_dg * (RB + 1) + 1 : INT_MAX;                   \
         }                                                                             \
         s_next = min(DIAG ? min(min(T_seg, T_diag), min(T_open, T_close)) : min(T_open, T_close), T_hin); \
-        if constexpr (TRACE == 1) st_on = ((__builtin_amdgcn_ballot_w64(opened != 0) >> (lane & 48)) & 0xFFFFull) != 0; \
+        if constexpr (TRACE == 1) st_on = ((__builtin_amdgcn_ballot_w64(PBA_BV_LANE_OPEN()) >> (lane & 48)) & 0xFFFFull) != 0; \
     }
 
     // hin of each lane's first block: the lane above's hout of the previous step, rotated one lane up, where that
@@ -388,11 +424,15 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     // One stretch of phase 1: plain steps from k up to kstop.  QD: the block the diagonal is in, as a constant (its word
     // alone collects), or -1: every block's word collects (garbage in all but the diagonal's, cleared at the segment's end).
     // LANE_HOT: every block's word collects under the lane's own one-hot.
-#define PBA_BV_STRETCH1(QD)                                                          \
-        do {                                                                         \
-        const int t = tb + k;                                                        \
+#define PBA_BV_TEXT(OFS)                                                             \
+        uint32_t clo, chi;                                                           \
+        if constexpr (RING) { const uint64_t cell = ta[OFS]; clo = (uint32_t)cell; chi = (uint32_t)(cell >> 32); } \
+        else { clo = bit_mask(wl, k + (OFS)); chi = bit_mask(wh, k + (OFS)); }
+#define PBA_BV_STEP1(QD, OFS)                                                        \
+        {                                                                            \
+        const int t = tb + k + (OFS);                                                \
         (void)t;                                                                     \
-        const uint32_t clo = bit_mask(wl, k), chi = bit_mask(wh, k);                 \
+        PBA_BV_TEXT(OFS)                                                             \
         PBA_BV_HIN();                                                                \
         _Pragma("unroll")                                                            \
         for (int nb = 0; nb < NB; ++nb) {                                            \
@@ -412,7 +452,24 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
         /* next row of the block, on the scalar side; re-armed every 32 rows.  (LANE_HOT: a full-rate add the compiler cannot \
            turn back into the slower shift) */                                       \
         if constexpr (LANE_HOT) asm("v_add_u32 %0, %1, %1" : "=v"(dmw) : "v"(dmw)); else oh <<= 1; \
-        } while (++k < kstop)
+        }
+    // RING: the stretch runs two steps per turn -- both steps' cells come with one LDS instruction, and the address add, the
+    // counter, the compare and the branch are paid once per two steps; an odd stretch (every stretch of a ramp is one step) takes
+    // its odd step first.
+#define PBA_BV_STRETCH1(QD)                                                          \
+        if constexpr (RING) {                                                        \
+            if ((kstop - k) & 1) { PBA_BV_STEP1(QD, 0) ta += 1; k += 1; }            \
+            while (k < kstop) {                                                      \
+                PBA_BV_STEP1(QD, 0)                                                  \
+                /* the first step's Pv / Mv as registers: seen through, the compiler folds them into the second step's \
+                   expressions and spends two instructions more per block on that */ \
+                _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) asm("" : "+v"(Pv[nb]), "+v"(Mv[nb])); \
+                PBA_BV_STEP1(QD, 1)                                                  \
+                ta += 2; k += 2;                                                     \
+            }                                                                        \
+        } else {                                                                     \
+            do { PBA_BV_STEP1(QD, 0) } while (++k < kstop);                          \
+        }
     // ------------------------------------------------------------------ phase 1: down to cell (m,m)
     // The step loop is cut into chunks of 32 steps (one pair of text planes): the scalar unit is shared by the CU's
     // four SIMDs, so every SALU instruction of the step costs four issue cycles -- the inner loop carries nothing
@@ -422,7 +479,7 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     // branch on a lane mask.
     for (int tbv = 1; tbv <= t1; tbv += 32) {
         const int tb = __builtin_amdgcn_readfirstlane(tbv);   // (the early exit below makes the compiler treat tbv as divergent)
-        if constexpr (TRACE == 2) bv_ckpt_store<NB>(tr, tb, lane, Pv, Mv, s_cur, opened, hp_last, hn_last);
+        if constexpr (TRACE == 2) bv_ckpt_store<NB>(tr, tb, lane, Pv, Mv, PBA_BV_LANE_SB(), LANE_SB ? opened : (PBA_BV_LANE_OPEN() ? 1u : 0u), hp_last, hn_last);
         load_text(tb);                           // next text planes
         if (fail_row) break;
         int kend = min(32, t1 - tb + 1);
@@ -460,7 +517,7 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     for (int tb = t1 + 1; tb <= t_end;) {
         const int k0 = (tb - 1) & 31;            // phase 2 starts inside a chunk whose planes are already loaded
         if (k0 == 0) {
-            if constexpr (TRACE == 2) bv_ckpt_store<NB>(tr, tb, lane, Pv, Mv, s_cur, opened, hp_last, hn_last);
+            if constexpr (TRACE == 2) bv_ckpt_store<NB>(tr, tb, lane, Pv, Mv, PBA_BV_LANE_SB(), LANE_SB ? opened : (PBA_BV_LANE_OPEN() ? 1u : 0u), hp_last, hn_last);
             load_text(tb);
         }
         const int kend = min(32, k0 + (t_end - tb + 1));
@@ -476,7 +533,7 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
         do {
         const int t = tc + k;
         (void)t;
-        const uint32_t clo = bit_mask(wl, k), chi = bit_mask(wh, k);
+        PBA_BV_TEXT(0)
         PBA_BV_HIN();
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
@@ -489,11 +546,14 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
             }
         }
         hp_last = hp; hn_last = hn;
+        if constexpr (RING) ta += 1;
         } while (++k < kstop);
         }
         tb += kend - k0;
     }
 #undef PBA_BV_STRETCH1
+#undef PBA_BV_STEP1
+#undef PBA_BV_TEXT
 #undef PBA_BV_BLOCK
 #undef PBA_BV_TRP
 #undef PBA_BV_HIN
@@ -502,11 +562,13 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     // D(i,m) = D(m,m) + the vertical deltas of column m over rows m+1..i (seq_aligner.h:192-211 scans exactly these cells,
     // upward from the diagonal, and keeps the first strict minimum).  A lane whose window is still open holds the
     // column in Pv / Mv, the others put it aside when their window closed.
-    if (opened && s_cur >= s_m && s_cur < S) {
-        fin[2 * NB * PBA_WAVE + lane] = (uint32_t)s_cur;
+    if (const int sb = PBA_BV_LANE_SB(); PBA_BV_LANE_OPEN() && sb >= s_m && sb < S) {
+        fin[2 * NB * PBA_WAVE + lane] = (uint32_t)sb;
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) { fin[2 * nb * PBA_WAVE + lane] = Pv[nb]; fin[(2 * nb + 1) * PBA_WAVE + lane] = Mv[nb]; }
     }
+#undef PBA_BV_LANE_OPEN
+#undef PBA_BV_LANE_SB
     const int fin_s = (int)fin[2 * NB * PBA_WAVE + lane];      // (a lane reads what it wrote itself: no barrier)
     int b_tot[NB], b_min[NB], b_pos[NB];          // per block of this lane's last superblock: sum, lowest prefix sum, its bit
 #pragma unroll
@@ -586,12 +648,19 @@ __device__ __forceinline__ bool bv_goal_certified(int best, int wl, int w, int m
 // need is valid).  full_band = false runs the narrow first pass and reports PBA_RC_UNCERTIFIED when the
 // goal row cannot be certified; the host then re-launches those pairs with full_band = true.
 // There is deliberately no device function call in here: everything inlines into the kernel.
-// lds: PBA_BV_FIN_WORDS(NB) u32 of this wavefront's own (>= 256 bytes: the m <= 10 corner runs the row sweep in it)
+// lds: PBA_BV_LDS_BYTES(NB) of this wavefront's own: the fin words (>= 256 bytes: the m <= 10 corner runs the row sweep in
+// them), then the text ring
 // need_diag: the caller reports D(m,m) (locator.cpp:86): a narrow pass whose window cannot vouch for that cell too
 // answers PBA_RC_UNCERTIFIED; without it o.diag is -1 in that case.
 // BAIL: give a narrow first pass up early when the pair is heading for a cost its window cannot certify (bitvec_pass:
 // bail_w).  For callers whose true pairs are expected beyond the first-pass window (the all-vs-all walk: two noisy reads);
 // compiled out elsewhere -- the test costs the step loop three scalar registers, 6 % of k_locate's time at 8 waves per SIMD.
+// The score-only sweeps of the aligning kernels (k_align_pairs, k_locate, k_spaced_round) take their text from the ring.  The
+// BAIL form does not: the all-vs-all walk lives on ramps, where a stretch is one step and a chunk's write is paid for a few
+// steps.  -DPBA_BV_RING=0 builds every form with the register planes (tools/build_variant.py: the parent's step).
+#ifndef PBA_BV_RING
+#define PBA_BV_RING 1
+#endif
 template <int NB, bool BAIL = false>
 __device__ __forceinline__ void align_bitvec(const PackedFetch &fa, int la, const PackedFetch &fb, int lb, double R,
                                              int maxn, int maxm, bool full_band, uint16_t *lds, int lds_cells,
@@ -614,7 +683,7 @@ __device__ __forceinline__ void align_bitvec(const PackedFetch &fa, int la, cons
     // all-vs-all run differ by ~28 %, against a window sized for a read against its genome) is given up after ~1000 rows
     // instead of being swept to the end for an answer nobody can use.
     const int bail_w = (BAIL && !full_band && w < md) ? w : 0;
-    const int fr = bitvec_pass<NB, 0, BAIL>(rowsF, min(n, m + w), colsF, m, w, wl, R, best, besti, diag, (uint32_t *)lds, nullptr, false, bail_w);
+    const int fr = bitvec_pass<NB, 0, BAIL, PBA_BV_RING && !BAIL>(rowsF, min(n, m + w), colsF, m, w, wl, R, best, besti, diag, (uint32_t *)lds, nullptr, false, bail_w);
     if (fr) {
         bool gave_up = false;
         if constexpr (BAIL) gave_up = fr == PBA_BV_BAIL;

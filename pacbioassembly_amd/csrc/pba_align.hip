@@ -305,9 +305,10 @@ static int fetch_results(pba_ctx *ctx, const void *d_out, pba_result *out, size_
 static void launch_align_pairs(pba_ctx *ctx, const Plan &pl, int nb, const SeqSetDev &A, const SeqSetDev &B, const pba_pair *d_pairs,
                                const uint32_t *ids, uint32_t cnt, pba_result *d_out) {
 #define PBA_PAIRS_LAUNCH(NBV)                                                                                        \
-    hipLaunchKernelGGL(k_align_pairs<NBV>, dim3(persistent_grid(ctx, cnt, Wpb<NBV>::v, pl.lds)),                      \
-                       dim3(PBA_WAVE * Wpb<NBV>::v), pl.lds * Wpb<NBV>::v, ctx->stream, A, B, d_pairs, ids, cnt, pl.cfg, \
+    hipLaunchKernelGGL(k_align_pairs<NBV>, dim3(persistent_grid(ctx, cnt, Wpb<NBV>::v, ll.lds)),                      \
+                       dim3(PBA_WAVE * Wpb<NBV>::v), ll.lds * Wpb<NBV>::v, ctx->stream, A, B, d_pairs, ids, cnt, ll.cfg, \
                        d_out, ctx->d_queue)
+    const LaunchLds ll = launch_lds(pl, nb);
     PBA_DISPATCH_NB(nb, PBA_PAIRS_LAUNCH);
 #undef PBA_PAIRS_LAUNCH
 }

@@ -353,11 +353,12 @@ static int locate_walk(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target
     const LocSet set = {contig ? ix->d_cum : nullptr, contig ? ix->n_seqs : 0u, d_ctg.as<int32_t>()};
     auto launch = [&](int nb, const uint32_t *ids, uint32_t cnt) {
 #define PBA_LOC_LAUNCH_AS(NBV, SETV)                                                                                 \
-    hipLaunchKernelGGL((k_locate<NBV, SETV>), dim3(persistent_grid(ctx, cnt, Wpb<NBV>::v, pl.lds)),                   \
-                       dim3(PBA_WAVE * Wpb<NBV>::v), pl.lds * Wpb<NBV>::v, ctx->stream, ix->dev(), target->dev(),     \
-                       target_seq, reads->dev(), ids, cnt, trials, min_len, pl.cfg, d_rows.as<pba_loc_row>(),        \
+    hipLaunchKernelGGL((k_locate<NBV, SETV>), dim3(persistent_grid(ctx, cnt, Wpb<NBV>::v, ll.lds)),                   \
+                       dim3(PBA_WAVE * Wpb<NBV>::v), ll.lds * Wpb<NBV>::v, ctx->stream, ix->dev(), target->dev(),     \
+                       target_seq, reads->dev(), ids, cnt, trials, min_len, ll.cfg, d_rows.as<pba_loc_row>(),        \
                        d_aux.as<LocAux>(), ctx->d_queue, set)
 #define PBA_LOC_LAUNCH(NBV) do { if (contig) PBA_LOC_LAUNCH_AS(NBV, true); else PBA_LOC_LAUNCH_AS(NBV, false); } while (0)
+        const LaunchLds ll = launch_lds(pl, nb);
         PBA_DISPATCH_NB(nb, PBA_LOC_LAUNCH);
 #undef PBA_LOC_LAUNCH
 #undef PBA_LOC_LAUNCH_AS
@@ -561,10 +562,11 @@ int spaced_round_subset(pba_ctx *ctx, const pba_index *ix, const pba_seqs *ref, 
     std::vector<pba_ss_row> h_rows(n);
     auto launch = [&](int nb, const uint32_t *ids, uint32_t cnt) {
 #define PBA_SS_LAUNCH(NBV)                                                                                           \
-    hipLaunchKernelGGL(k_spaced_round<NBV>, dim3(persistent_grid(ctx, cnt, Wpb<NBV>::v, pl.lds)),                     \
-                       dim3(PBA_WAVE * Wpb<NBV>::v), pl.lds * Wpb<NBV>::v, ctx->stream, ix->dev(), ref->dev(),       \
-                       ref_seq, ref_org, reads->dev(), ids, cnt, max_trial, overlap_min, buggy_seed_at, pl.cfg,      \
+    hipLaunchKernelGGL(k_spaced_round<NBV>, dim3(persistent_grid(ctx, cnt, Wpb<NBV>::v, ll.lds)),                     \
+                       dim3(PBA_WAVE * Wpb<NBV>::v), ll.lds * Wpb<NBV>::v, ctx->stream, ix->dev(), ref->dev(),       \
+                       ref_seq, ref_org, reads->dev(), ids, cnt, max_trial, overlap_min, buggy_seed_at, ll.cfg,      \
                        d_rows.as<pba_ss_row>(), d_redo.as<int>(), ctx->d_queue)
+        const LaunchLds ll = launch_lds(pl, nb);
         PBA_DISPATCH_NB(nb, PBA_SS_LAUNCH);
 #undef PBA_SS_LAUNCH
     };

@@ -368,6 +368,20 @@ static inline int make_plan(pba_ctx *ctx, double R, int maxn, int maxm, int kern
     return PBA_OK;
 }
 
+// LDS of one launch of a score-only kernel (k_align_pairs, k_locate, k_spaced_round) in ring nb: the fin words of THAT ring, not
+// of the plan's widest, and behind them the sweep's text ring (text_ring.h).  k_locate<2> of a 15 kb batch planned for a
+// re-run in ring 4 then takes 2 560 bytes per wavefront: with LocWalkLds 32 wavefronts fit a CU's 160 KB, which the widest
+// ring's fin words plus the text ring would not.  nb = 0 (row sweep): the plan's band row.
+struct LaunchLds { size_t lds; AlignCfg cfg; };
+static inline LaunchLds launch_lds(const Plan &pl, int nb) {
+    LaunchLds l{pl.lds, pl.cfg};
+    if (nb) {
+        l.lds = ((size_t)PBA_BV_LDS_BYTES(nb) + 15) / 16 * 16;
+        l.cfg.row_cap = (int)(l.lds / 2);
+    }
+    return l;
+}
+
 // Workgroups for a persistent launch: enough to fill every CU (up to 8 waves per SIMD, as many as the LDS
 // allows), never more than there are work items.  Any residency works: the queue needs no co-residency.
 static inline uint32_t persistent_grid(const pba_ctx *ctx, uint32_t n_items, int waves_per_wg, size_t lds_per_wave) {
