@@ -88,7 +88,23 @@ int pba_ctx_create(int device_id, pba_ctx **ctx);
 void pba_ctx_destroy(pba_ctx *ctx);
 /* text of the last failure on this ctx (never NULL) */
 const char *pba_ctx_error(const pba_ctx *ctx);
-/* run on a caller-owned hipStream_t (e.g. torch's current stream); NULL = the ctx's own */
+/* Streams.  Run on a caller-owned hipStream_t (e.g. torch's current stream); NULL = the ctx's own.  The contract:
+ *  - Every call enqueues its device work on the ctx's stream -- the one set when the call is made -- and returns with that work
+ *    complete (it ends in a synchronise of that stream).  The one exception is pba_*_stream_submit, which enqueues on the
+ *    object's copy stream and returns at once; the matching collect orders the walk behind it with an event.
+ *  - Device buffers, d_* parameters: a buffer the caller hands in (read, written or both) must have been written ON THE CTX'S
+ *    STREAM -- then the call is ordered behind the write, pending or not, and no synchronise is owed -- or be complete before
+ *    the call.  What a call writes into a d_* buffer is complete when it returns.  The ten entry points that take one are
+ *    pba_seqs_from_device_text, pba_seqs_export, pba_seqs_from_device_packed, pba_index_scan, pba_index_from_entries,
+ *    pba_overlap_probes, pba_overlap_all_probes, pba_probe_table_create, pba_census_mask_probes and (pba_dist.h)
+ *    pba_dist_all_gather; tests/test_gpu_caller_stream.py holds the first nine to it with the producer still pending.
+ *  - The ctx's own stream is created hipStreamNonBlocking: it is NOT ordered against the legacy default stream.  Work a
+ *    host queued on the default stream (torch's default stream is that one) is not waited for by a ctx on its own stream:
+ *    synchronise, or put both on a created stream.
+ *  - NULL selects the own stream, and the legacy default stream's handle IS NULL (torch: handle 0): it cannot be selected.
+ *    A host that works on the default stream synchronises before a call, or works on a created stream and sets that.
+ *  - The stream must outlive its use: set another (or NULL) before destroying it.  pba_loc_stream / pba_map_stream objects
+ *    record the ctx's stream at create and are tied to it (see there). */
 int pba_ctx_set_stream(pba_ctx *ctx, void *hip_stream);
 int pba_ctx_sync(pba_ctx *ctx);
 /* The ctx keeps the work buffers of its drivers between calls (candidate arrays, per-read rows, traceback scratch: mapping
@@ -560,7 +576,12 @@ int pba_cons_assemble(pba_ctx *ctx, pba_cons *c, const pba_seqs *reads, double R
 /* Submit batch k+1 before collecting batch k to hide the upload.             */
 /* The pinned buffer of a slot must not be written between its submit and the */
 /* collect of that batch (nothing can check this).  One host thread, no graph */
-/* capture; the ctx's stream must stay the same from create to destroy.       */
+/* capture.  The object records the ctx's stream at create and is tied to it: */
+/* submit, pending and collect with the ctx on another stream return          */
+/* PBA_E_INVALID (text in pba_ctx_error), enqueue nothing and leave the       */
+/* object as it was -- usable once the ctx is back on that stream.  Destroy   */
+/* is legal whatever stream the ctx is on: it synchronises the copy stream    */
+/* and the recorded stream, which must still exist.                           */
 /* ------------------------------------------------------------------------ */
 typedef struct pba_loc_stream pba_loc_stream;
 enum { PBA_STREAM_TEXT = 0, PBA_STREAM_RECORDS = 1 };
@@ -604,7 +625,8 @@ typedef struct {
     uint64_t n_bytes;              /* input bytes copied */
 } pba_stream_profile;
 int pba_loc_stream_last_profile(const pba_loc_stream *s, pba_stream_profile *out);
-/* waits for the copy stream, then frees; legal with batches pending */
+/* waits for the copy stream and for the ctx's stream as recorded at create, then frees; legal with batches pending and with
+ * the ctx on any stream */
 void pba_loc_stream_destroy(pba_loc_stream *s);
 
 /* ------------------------------------------------------------------------ */
@@ -643,7 +665,8 @@ int pba_map_stream_collect(pba_map_stream *s, pba_map_row *rows, uint32_t cap, u
 int pba_map_stream_pending(pba_map_stream *s, const pba_seqs **fwd, const pba_seqs **rc);
 /* as pba_loc_stream_last_profile: pack_ms covers the packs of both strands, locate_ms both walks */
 int pba_map_stream_last_profile(const pba_map_stream *s, pba_stream_profile *out);
-/* waits for the copy stream, then frees; legal with batches pending */
+/* waits for the copy stream and for the ctx's stream as recorded at create, then frees; legal with batches pending and with
+ * the ctx on any stream */
 void pba_map_stream_destroy(pba_map_stream *s);
 
 /* ------------------------------------------------------------------------ */

@@ -121,6 +121,7 @@ struct StreamCore {
     uint64_t slot_bytes, pk_cap, rc_cap, plane_cap;      // plane_cap: word pairs between the slacks
     uint32_t slot_reads;
     hipStream_t copy;
+    hipStream_t stream;                          // the ctx's stream at create: the walks run on it, and on no other (on_stream)
     hipEvent_t ev_loc0, ev_loc1;                 // the walk(s) of a batch, on the ctx's stream
     bool have_loc1, spent;
     StreamSlot slot[2];
@@ -152,10 +153,18 @@ static int core_fail(StreamCore &c, int st, const char *fn, const char *what) {
     return ctx_fail_as(c.ctx, st, who, what);
 }
 
+// submit, pending and collect with the ctx on another stream than at create: refused before anything is looked at or enqueued,
+// and the object stays usable (the walks of a slot are ordered among themselves and against ev_loc0 / ev_loc1 on ONE stream)
+static int on_stream(StreamCore &c, const char *fn) {
+    if (c.ctx->stream == c.stream) return PBA_OK;
+    return core_fail(c, PBA_E_INVALID, fn, "the ctx is on another stream than at create (pba_ctx_set_stream)");
+}
+
+// (legal whatever stream the ctx is on now: what was enqueued went to the copy stream and to the stream recorded at create)
 static void core_free(StreamCore &c) {
     (void)hipSetDevice(c.ctx->device);
     if (c.copy) (void)hipStreamSynchronize(c.copy);
-    (void)hipStreamSynchronize(c.ctx->stream);
+    (void)hipStreamSynchronize(c.stream);
     for (StreamSlot &sl : c.slot) {
         for (void *h : {(void *)sl.h_bytes, (void *)sl.h_offs, (void *)sl.h_off, (void *)sl.h_poff, (void *)sl.h_roff, (void *)sl.h_len,
                         (void *)sl.h_item, (void *)sl.h_bad})
@@ -222,7 +231,7 @@ static bool slot_alloc(StreamCore &c, StreamSlot &sl) {
 // what both creates do once their own checks are through; on failure the caller frees the core
 static int core_create(StreamCore &c, pba_ctx *ctx, const char *name, int form, int min_len, bool rc, uint64_t slot_bytes,
                        uint32_t slot_reads) {
-    c.ctx = ctx; c.name = name; c.form = form; c.min_len = min_len; c.rc = rc; c.slot_bytes = slot_bytes; c.slot_reads = slot_reads;
+    c.ctx = ctx; c.stream = ctx->stream; c.name = name; c.form = form; c.min_len = min_len; c.rc = rc; c.slot_bytes = slot_bytes; c.slot_reads = slot_reads;
     const SlotCaps caps = slot_caps(form == PBA_STREAM_TEXT, slot_bytes, slot_reads, rc);
     c.pk_cap = caps.pk_cap; c.rc_cap = caps.rc_cap; c.plane_cap = caps.plane_cap;
     bool ok = hipStreamCreateWithFlags(&c.copy, hipStreamNonBlocking) == hipSuccess;
@@ -286,6 +295,7 @@ static int core_buffer(StreamCore &c, void **bytes, uint64_t **offsets) {
 
 static int core_submit(StreamCore &c, uint32_t n) {
     if (c.spent || c.npend >= 2) return PBA_E_INVALID;
+    PBA_TRY(on_stream(c, "submit"));
     pba_ctx *ctx = c.ctx;
     StreamSlot &sl = c.slot[(c.head + c.npend) & 1];
     pba_seqs *q = sl.set, *r = sl.rc;
@@ -352,6 +362,7 @@ static int core_submit(StreamCore &c, uint32_t n) {
 // the oldest pending slot once its packs are through, the verdict of the pack on both of its sets
 static int core_pending(StreamCore &c, StreamSlot **out) {
     if (c.spent || c.npend == 0) return PBA_E_INVALID;
+    PBA_TRY(on_stream(c, "pending"));
     StreamSlot &sl = c.slot[c.head];
     const hipError_t e = hipEventSynchronize(sl.ev_pack);
     if (e != hipSuccess) return spend(c, core_fail(c, PBA_E_HIP, "pending", hipGetErrorString(e)));
@@ -366,6 +377,7 @@ static int core_pending(StreamCore &c, StreamSlot **out) {
 template <class Walk>
 static int core_collect(StreamCore &c, bool have_rows, uint32_t cap, uint32_t *n, Walk walk) {
     if (c.spent || !n || c.npend == 0) return PBA_E_INVALID;
+    PBA_TRY(on_stream(c, "collect"));
     pba_ctx *ctx = c.ctx;
     StreamSlot &sl = c.slot[c.head];
     if (cap < sl.n || (!have_rows && sl.n)) return core_fail(c, PBA_E_INVALID, "collect", "cap below the batch size");

@@ -45,6 +45,8 @@ def all_gather_entries(mine: torch.Tensor, n_mine: int):
     dist.all_reduce(counts)
     allent = torch.empty(cap * world, dtype=torch.int64, device=mine.device)
     dist.all_gather_into_tensor(allent, mine)
+    # (.item() synchronises torch's stream, which waits for both collectives: allent is complete when this returns, which is
+    # what pba_index_from_entries / pba_probe_table_create on a ctx on ANOTHER stream are owed -- include/pba.h: "Streams")
     return allent, int(counts.sum().item())
 
 
@@ -75,7 +77,7 @@ def all_gather_packed(packed: torch.Tensor, offsets: np.ndarray, lengths: np.nda
     ol_t = torch.from_numpy(ol).to(dev)
     all_ol = torch.empty(world * 2 * cmax, dtype=torch.int64, device=dev)
     dist.all_gather_into_tensor(all_ol, ol_t)
-    all_ol = all_ol.view(world, 2, cmax).cpu().numpy()
+    all_ol = all_ol.view(world, 2, cmax).cpu().numpy()      # (.cpu() synchronises torch's stream behind all three collectives: allp is complete)
     offs = np.concatenate([all_ol[r, 0, :counts[r]].astype(np.uint64) + np.uint64(r * stride) for r in range(world)])
     lens = np.concatenate([all_ol[r, 1, :counts[r]].astype(np.uint32) for r in range(world)])
     return allp, offs, lens

@@ -250,7 +250,19 @@ class Context:
             raise PbaError(st, f"{what}: {self.lib.pba_ctx_error(self.h).decode()}")
 
     def set_stream(self, stream_handle: Optional[int]):
-        self.check(self.lib.pba_ctx_set_stream(self.h, C.c_void_p(stream_handle or 0)), "set_stream")
+        """Run on a caller-owned stream (pba_ctx_set_stream; include/pba.h: "Streams"): its handle, e.g. the cuda_stream of a
+        torch.cuda.Stream(); None = back to the ctx's own.  Every call enqueues on the stream set when it is made and returns
+        with that work complete (LocStream / MapStream.submit excepted).  A device buffer handed in must have been written on
+        that stream, or be complete before the call.  The ctx's own stream is non-blocking: it is not ordered against the
+        legacy default stream, which is torch's default stream.  That stream's handle is 0, which the library reads as "the
+        own stream": it cannot be selected.  So 0 is refused here (ValueError) rather than taken for None --
+        set_stream(torch.cuda.current_stream().cuda_stream) on torch's default stream would silently run the engine unordered
+        against the work queued there.  A host on the default stream synchronises before a call, or works on a created stream.
+        LocStream / MapStream objects are tied to the stream the ctx was on when they were made."""
+        if stream_handle is not None and int(stream_handle) == 0:
+            raise ValueError("set_stream(0): 0 is the legacy default stream's handle, which cannot be selected "
+                             "(None selects the ctx's own stream; use a created stream, or synchronise)")
+        self.check(self.lib.pba_ctx_set_stream(self.h, C.c_void_p(stream_handle)), "set_stream")
 
     def sync(self):
         self.check(self.lib.pba_ctx_sync(self.h), "sync")
