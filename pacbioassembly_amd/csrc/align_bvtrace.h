@@ -23,6 +23,7 @@
 #define PBA_ALIGN_BVTRACE_H
 
 #include "align_bitvec.h"
+#include "align_common.h"
 
 // scratch words a traced pass needs: steps * NB blocks * 2 words * 64 lanes (m columns, the longer side swept down to
 // row min(n, m + w); the last superblock takes the last column at step m + S - 1)
@@ -90,6 +91,37 @@ struct OpSink {
         for (int x = lane; x < k; x += PBA_WAVE)
             if ((uint64_t)x < ops_cap) ops_out[x] = (uint8_t)ld_coherent_u8(tmp + (k - 1 - x));
         return k;
+    }
+};
+
+// What the sinks that need an op's cell share: lane (k & 63) keeps op k and its cell (i, j) until the group of 64 is full,
+// then Derived::flush(cnt) takes the ops of lanes 0 .. cnt-1 together.  OpSink carries no cell and writes its bytes straight
+// away: it stays apart.
+template <class Derived>
+struct GroupQueue {
+    int k;                      // ops taken so far
+    int p_i, p_j;               // this lane's pending op: its cell
+    uint32_t p_op;
+    __device__ __forceinline__ void reset() { k = 0; p_i = 0; p_j = 0; p_op = 0u; }
+    __device__ __forceinline__ void put(int op, int i, int j) {
+        const int lane = threadIdx.x & (PBA_WAVE - 1);
+        if (lane == (k & (PBA_WAVE - 1))) { p_op = (uint32_t)op; p_i = i; p_j = j; }
+        ++k;
+        if ((k & (PBA_WAVE - 1)) == 0) static_cast<Derived *>(this)->flush(PBA_WAVE);
+    }
+    // n MATCH ops down a diagonal from cell (i, j): op k + r is the MATCH at (i - r, j - r)
+    __device__ __forceinline__ void put_run(int n, int i, int j) {
+        const int lane = threadIdx.x & (PBA_WAVE - 1);
+        while (n > 0) {
+            const int at = k & (PBA_WAVE - 1), take = min(n, PBA_WAVE - at);
+            if (lane >= at && lane < at + take) { p_op = 1u; p_i = i - (lane - at); p_j = j - (lane - at); }
+            k += take; n -= take; i -= take; j -= take;
+            if ((k & (PBA_WAVE - 1)) == 0) static_cast<Derived *>(this)->flush(PBA_WAVE);
+        }
+    }
+    // the group that never filled: every finish() opens with it
+    __device__ __forceinline__ void flush_tail() {
+        if (k & (PBA_WAVE - 1)) static_cast<Derived *>(this)->flush(k & (PBA_WAVE - 1));
     }
 };
 
@@ -342,5 +374,60 @@ __device__ __forceinline__ bool align_bitvec_trace(const PackedFetch &fa, int la
     }
     return true;
 }
+
+// ---- the persistent loop of every traced kernel ---------------------------------------------------------------------------
+// Each wavefront has its own LDS slice and its own scratch area of wave_words u32 (cap_words of parent bits or checkpoints,
+// then the goal-first temporary of the pair in flight) and pulls pairs until the queue is dry.  ids (nullable): the subset
+// of pairs to process (second, full-band launch).  What differs between the outlets is the Job's, a by-value policy:
+//   Job::Sink                                        the sink the walk feeds
+//   open(sink, q, pr, fa, fb, A, tmp, tmp_words)     the sink of pair q; tmp: the temporary behind cap_words
+//   overlap_min()                                    the gate of the walk (0: none)
+//   close(sink, q, walked)                           what pair q leaves in memory, walked or not
+template <int NB, bool CK, class Job>
+__device__ __forceinline__ void trace_pairs_loop(const SeqSetDev &A, const SeqSetDev &B, const pba_pair *pairs, const uint32_t *ids,
+                                                 uint32_t n, const AlignCfg &cfg, pba_result *out, uint32_t *scratch,
+                                                 uint64_t wave_words, uint64_t cap_words, const Job &job, uint32_t *queue) {
+    extern __shared__ __align__(16) uint8_t lds_all[];
+    __shared__ uint2 s_tile[4][CK ? PBA_BV_TILE_WORDS(NB) : 1];
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / PBA_WAVE));
+    uint8_t *lds = lds_all + (size_t)wave * cfg.row_cap * 2;
+    uint32_t *mine = scratch + ((uint64_t)blockIdx.x * 4 + wave) * wave_words;
+    for (;;) {
+        const uint32_t slot = next_slot(queue);
+        if (slot >= n) break;
+        const uint32_t q = ids ? ids[slot] : slot;
+        const pba_pair pr = pairs[q];
+        const PackedFetch fa = fetch_of(A, pr.a_seq, pr.a_pos, (pr.flags & PBA_A_BACKWARD) ? -1 : 1);
+        const PackedFetch fb = fetch_of(B, pr.b_seq, pr.b_pos, (pr.flags & PBA_B_BACKWARD) ? -1 : 1);
+        AlnOut o;
+        typename Job::Sink sink;
+        job.open(sink, q, pr, fa, fb, A, mine + cap_words, wave_words - cap_words);
+        const bool walked = align_bitvec_trace<NB, CK>(fa, pr.a_len, fb, pr.b_len, cfg.R, cfg.maxn, cfg.maxm, cfg.full_band != 0,
+                                                       (uint16_t *)lds, cfg.row_cap, mine, cap_words, job.overlap_min(), sink, o,
+                                                       s_tile[wave]);
+        store_result(out + q, o);
+        job.close(sink, q, walked);
+    }
+}
+
+// edit scripts: pair q's ops to ops[ops_off[q] ..), their number to nedit[q].  The slot is read when the pair opens and kept
+// by the sink across the walk: read in close() instead, the four registers it frees lift k_trace_pairs<2, true> from 6 to 7
+// waves per SIMD, and this HBM-bound kernel measured 2.5 - 3.5 % slower there.
+struct ScriptJob {
+    struct Sink : OpSink { uint8_t *out; uint64_t cap; };
+    uint8_t *ops;
+    const uint64_t *ops_off;
+    int32_t *nedit;
+    __device__ __forceinline__ void open(Sink &s, uint32_t q, const pba_pair &, const PackedFetch &, const PackedFetch &, const SeqSetDev &,
+                                         uint32_t *tmp, uint64_t) const {
+        const uint64_t o0 = ops_off[q], o1 = ops_off[q + 1];
+        s.tmp = (uint8_t *)tmp; s.k = 0; s.pend = 0u; s.out = ops + o0; s.cap = o1 - o0;
+    }
+    __device__ __forceinline__ int overlap_min() const { return 0; }
+    __device__ __forceinline__ void close(Sink &s, uint32_t q, bool walked) const {
+        const int ne = walked ? s.finish(s.out, s.cap) : 0;
+        if ((threadIdx.x & (PBA_WAVE - 1)) == 0) nedit[q] = ne;
+    }
+};
 
 #endif

@@ -1,5 +1,5 @@
 // align_windows.h -- per-window alignment counts straight from the traceback walk (align_bvtrace.h): a fourth sink beside
-// OpSink (bytes), VoteSink (votes) and CigarSink (runs).  The a sequence carries a fixed grid of W-base windows on its own
+// OpSink (bytes), VoteSink (votes) and CigarSink (runs); the op queue is GroupQueue's, the classes of the ops OpClasses'.  The a sequence carries a fixed grid of W-base windows on its own
 // coordinates; every op of the path is counted (=, X, I, D: align_cigar.h's codes) in the window of the a-element it belongs
 // to, and one pba_aln_counts per window goes to memory.  No script and no run exists anywhere.
 //
@@ -16,28 +16,24 @@
 #ifndef PBA_ALIGN_WINDOWS_H
 #define PBA_ALIGN_WINDOWS_H
 
-#include "align_bvtrace.h"
+#include "align_cigar.h"
 
-struct WindowSink {
-    PackedFetch fa, fb;         // element i-1 of a, j-1 of b, direction included
+struct WindowSink : GroupQueue<WindowSink> {
+    OpClasses cls;
     pba_aln_counts *out;        // this pair's slot
-    uint64_t cap;               // windows the slot holds: with fewer than n_win nothing is written
+    int cap;                    // windows the slot holds (n_win is an int: a larger slot counts as INT_MAX): with fewer than n_win nothing is written
     int a_pos, a_step, W, g0;   // x(e) = a_pos + a_step * e;  g0 = g(0)
-    bool b_is_query, reversed;
-    int k;                      // ops taken so far
-    int p_i, p_j;               // this lane's pending op: its cell
-    uint32_t p_op;
-    // wave-uniform: the windows of the pair (-1 before the first op), the open window and its counts, the pair's counts
+    bool reversed;
+    // wave-uniform: the windows of the pair (-1 before the first op), the open window and its counts
     int n_win, cur_w;
     int o_eq, o_x, o_ins, o_del;
-    int n_eq, n_x, n_ins, n_del;
 
     __device__ __forceinline__ void init(const PackedFetch &a, const PackedFetch &b, int pos, bool a_backward, int w, pba_aln_counts *slot,
                                          uint64_t slot_cap, bool swap, bool rev) {
-        fa = a; fb = b; out = slot; cap = slot_cap; a_pos = pos; a_step = a_backward ? -1 : 1; W = w; g0 = pos / w;
-        b_is_query = swap; reversed = rev;
-        k = 0; p_i = 0; p_j = 0; p_op = 0u; n_win = -1; cur_w = -1;
-        o_eq = 0; o_x = 0; o_ins = 0; o_del = 0; n_eq = 0; n_x = 0; n_ins = 0; n_del = 0;
+        cls.init(a, b, swap); out = slot; cap = (int)min(slot_cap, (uint64_t)INT_MAX); a_pos = pos; a_step = a_backward ? -1 : 1; W = w; g0 = pos / w;
+        reversed = rev;
+        reset(); n_win = -1; cur_w = -1;
+        o_eq = 0; o_x = 0; o_ins = 0; o_del = 0;
     }
     __device__ __forceinline__ int window_of(int e) const {
         const int g = (a_pos + a_step * e) / W - g0;
@@ -45,22 +41,16 @@ struct WindowSink {
     }
     // one window to its final place: a 16-byte vector store by the calling lane; never outside the slot
     __device__ __forceinline__ void store(int w, int eq, int x, int ins, int del) const {
-        if (w < 0 || w >= n_win || (uint64_t)n_win > cap) return;
+        if (w < 0 || w >= n_win || n_win > cap) return;
         *(int4 *)(out + (reversed ? n_win - 1 - w : w)) = make_int4(eq, x, ins, del);
     }
     // lanes 0 .. cnt-1 hold an op each: classify, find the window boundaries, write the windows that close, keep the last open
     __device__ __forceinline__ void flush(int cnt) {
         const int lane = threadIdx.x & (PBA_WAVE - 1);
-        uint32_t code = 0u;
-        int w = 0;
-        if (lane < cnt) {
-            if (p_op == 1u) code = fa(p_i - 1) == fb(p_j - 1) ? (uint32_t)PBA_CIG_EQ : (uint32_t)PBA_CIG_X;   // per element
-            else code = ((p_op == 2u) != b_is_query) ? (uint32_t)PBA_CIG_DEL : (uint32_t)PBA_CIG_INS;
-            w = window_of(max(p_i - 1, 0));                                      // (MATCH and DELETE sit at i >= 1)
-        }
-        const uint64_t E = __builtin_amdgcn_ballot_w64(code == (uint32_t)PBA_CIG_EQ), X = __builtin_amdgcn_ballot_w64(code == (uint32_t)PBA_CIG_X);
-        const uint64_t I = __builtin_amdgcn_ballot_w64(code == (uint32_t)PBA_CIG_INS), D = __builtin_amdgcn_ballot_w64(code == (uint32_t)PBA_CIG_DEL);
-        n_eq += __builtin_popcountll(E); n_x += __builtin_popcountll(X); n_ins += __builtin_popcountll(I); n_del += __builtin_popcountll(D);
+        const int w = lane < cnt ? window_of(max(p_i - 1, 0)) : 0;             // (MATCH and DELETE sit at i >= 1)
+        OpBallots ob;
+        cls.classify(p_op, p_i, p_j, cnt, ob);
+        const uint64_t E = ob.E, X = ob.X, I = ob.I, D = ob.D;
         const int w0 = __builtin_amdgcn_readfirstlane(w);
         if (n_win < 0) n_win = w0 + 1;                                          // the first op sits at the goal cell
         if (cur_w >= 0 && cur_w != w0) {                                        // the carried window closed at the group's edge
@@ -91,32 +81,34 @@ struct WindowSink {
         o_eq = __builtin_popcountll(E & m); o_x = __builtin_popcountll(X & m); o_ins = __builtin_popcountll(I & m); o_del = __builtin_popcountll(D & m);
         cur_w = __builtin_amdgcn_readlane(w, last);
     }
-    __device__ __forceinline__ void put(int op, int i, int j) {
-        const int lane = threadIdx.x & (PBA_WAVE - 1);
-        if (lane == (k & (PBA_WAVE - 1))) { p_op = (uint32_t)op; p_i = i; p_j = j; }
-        ++k;
-        if ((k & (PBA_WAVE - 1)) == 0) flush(PBA_WAVE);
-    }
-    // n MATCH ops down a diagonal from cell (i, j): op k + r is the MATCH at (i - r, j - r)
-    __device__ __forceinline__ void put_run(int n, int i, int j) {
-        const int lane = threadIdx.x & (PBA_WAVE - 1);
-        while (n > 0) {
-            const int at = k & (PBA_WAVE - 1), take = min(n, PBA_WAVE - at);
-            if (lane >= at && lane < at + take) { p_op = 1u; p_i = i - (lane - at); p_j = j - (lane - at); }
-            k += take; n -= take; i -= take; j -= take;
-            if ((k & (PBA_WAVE - 1)) == 0) flush(PBA_WAVE);
-        }
-    }
     // Closes the open window; returns n_win (a path without ops: one empty window).  Lane 0 writes the counts.
     __device__ __forceinline__ int finish(pba_aln_counts *counts) {
         const int lane = threadIdx.x & (PBA_WAVE - 1);
-        if (k & (PBA_WAVE - 1)) flush(k & (PBA_WAVE - 1));
+        flush_tail();
         if (n_win < 0) { n_win = 1; cur_w = 0; }
         if (lane == 0) {
             store(cur_w, o_eq, o_x, o_ins, o_del);
-            counts->n_eq = n_eq; counts->n_x = n_x; counts->n_ins = n_ins; counts->n_del = n_del;
+            cls.store(counts);
         }
         return n_win;
+    }
+};
+
+// per-window counts: pair q's windows to its slot, their number to n[q], their sum to counts[q].  No temporary: a closed window
+// goes straight to its final place.
+struct WindowJob {
+    using Sink = WindowSink;
+    SlotsInto s;
+    __device__ __forceinline__ void open(WindowSink &k, uint32_t q, const pba_pair &pr, const PackedFetch &fa, const PackedFetch &fb,
+                                         const SeqSetDev &, uint32_t *, uint64_t) const {
+        const uint32_t fl = s.flags_of(q);
+        const uint64_t o0 = s.off[q], o1 = s.off[q + 1];
+        k.init(fa, fb, pr.a_pos, (pr.flags & PBA_A_BACKWARD) != 0, s.W, (pba_aln_counts *)s.slot + o0, o1 - o0,
+               (fl & PBA_CIG_B_IS_QUERY) != 0, (fl & PBA_CIG_REVERSED) != 0);
+    }
+    __device__ __forceinline__ int overlap_min() const { return 0; }
+    __device__ __forceinline__ void close(WindowSink &k, uint32_t q, bool walked) const {
+        s.close(q, walked, walked ? k.finish(s.counts + q) : 0);
     }
 };
 

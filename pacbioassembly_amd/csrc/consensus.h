@@ -16,6 +16,7 @@
 #ifndef PBA_CONSENSUS_H
 #define PBA_CONSENSUS_H
 
+#include "align_bvtrace.h"
 #include "dev_common.h"
 
 struct ConsDev {
@@ -24,7 +25,7 @@ struct ConsDev {
     char *txt;
 };
 
-// Where a batch of walks votes (k_vote_pairs, pba_align.hip), and a pile-up's arena as its own kernels see it.  One
+// Where a batch of walks votes (VoteJob below, run by k_vote_pairs in pba_align.hip), and a pile-up's arena as its own kernels see it.  One
 // reference: boxes C, pair.a_pos counted from box `beg`, live range [pre, post).  box_off non-null: C is a pile-up's arena
 // (pba_pileup.hip; txt unused), one segment per pair's own a_seq -- target t owns boxes [box_off[t - t_lo], + len(t)) and
 // beg / pre / post are unused.
@@ -103,47 +104,52 @@ k_cons_elect(ConsDev C, int beg, int pre, int post, uint32_t n, const int *pos, 
 // op at cell (i, j) into its vote.  The cell says it all: a MATCH / DELETE at (i, j) consumes a-element i-1, i.e. the
 // box `it0 +/- (i-1)`; an INSERT at (i, j) comes after i consumed elements, i.e. supplies box `it0 + i - 1` forward
 // (`--it; supply; ++it`) or `it0 - i` backward (apply_edits, ref_seq.h:25-41); the value is b-element j-1.
-// 64 votes are gathered (one per lane) and applied together, each lane fetching its own b element.
-struct VoteSink {
+// 64 votes are gathered (one per lane, GroupQueue: align_bvtrace.h) and applied together, each lane working out its own box
+// and fetching its own b element.
+struct VoteSink : GroupQueue<VoteSink> {
     ConsDev C;
     int it0, pre, post;         // box of the start position; the live range of boxes
     bool fwd;
     PackedFetch fb;             // the segment (b)
-    int k;
-    int p_at, p_j;              // this lane's pending vote: box, b element + 1 (0: none)
-    uint32_t p_op;
-    __device__ __forceinline__ void apply() {
-        if (p_op && p_at >= pre && p_at < post) {
-            if (p_op == 3) atomicAdd(C.tot + p_at, 1);                                  // ignore
-            else {
-                const int c = fb(p_j - 1);                                              // 2-bit code == C2I of the base
-                if (p_op == 1) { cons_bump(C.sel + p_at, c, 1u); atomicAdd(C.tot + p_at, 1); }   // select
-                else cons_bump(C.sup + p_at, c, 1u);                                    // supply
-            }
-        }
-        p_op = 0;
+    __device__ __forceinline__ void init(const ConsDev &c, int box0, int w_pre, int w_post, bool forward, const PackedFetch &b) {
+        C = c; it0 = box0; pre = w_pre; post = w_post; fwd = forward; fb = b;
+        reset();
     }
-    __device__ __forceinline__ void put(int op, int i, int j) {
-        const int lane = threadIdx.x & (PBA_WAVE - 1);
-        const int at = op == 2 ? (fwd ? it0 + i - 1 : it0 - i) : (fwd ? it0 + (i - 1) : it0 - (i - 1));
-        if (lane == (k & (PBA_WAVE - 1))) { p_op = (uint32_t)op; p_at = at; p_j = j; }
-        ++k;
-        if ((k & (PBA_WAVE - 1)) == 0) apply();
-    }
-    // n MATCH votes down a diagonal from cell (i, j): vote k + r is the MATCH at (i - r, j - r)
-    __device__ __forceinline__ void put_run(int n, int i, int j) {
-        const int lane = threadIdx.x & (PBA_WAVE - 1);
-        while (n > 0) {
-            const int at = k & (PBA_WAVE - 1), take = min(n, PBA_WAVE - at);
-            if (lane >= at && lane < at + take) {
-                const int r = lane - at;
-                p_op = 1u; p_at = fwd ? it0 + (i - r - 1) : it0 - (i - r - 1); p_j = j - r;
-            }
-            k += take; n -= take; i -= take; j -= take;
-            if ((k & (PBA_WAVE - 1)) == 0) apply();
+    __device__ __forceinline__ void flush(int cnt) {
+        if ((int)(threadIdx.x & (PBA_WAVE - 1)) >= cnt) return;
+        const int at = p_op == 2u ? (fwd ? it0 + p_i - 1 : it0 - p_i) : (fwd ? it0 + (p_i - 1) : it0 - (p_i - 1));
+        if (at < pre || at >= post) return;
+        if (p_op == 3u) atomicAdd(C.tot + at, 1);                                       // ignore
+        else {
+            const int c = fb(p_j - 1);                                                  // 2-bit code == C2I of the base
+            if (p_op == 1u) { cons_bump(C.sel + at, c, 1u); atomicAdd(C.tot + at, 1); }   // select
+            else cons_bump(C.sup + at, c, 1u);                                          // supply
         }
     }
-    __device__ __forceinline__ void finish() { apply(); }
+    __device__ __forceinline__ void finish() { flush_tail(); }
+};
+
+// votes: pair q's path into the boxes V names, gated by overlap_min; a is the reference, pair.a_pos the position the votes
+// start at.  SEG: V is a pile-up's arena (VoteInto with box_off), one segment per target read: pair q votes into the window
+// of ITS a_seq, the box of a_pos at that segment's offset + a_pos.  The arena holds fewer than 2^31 boxes (the host refuses
+// or chunks beyond that), so the window fits VoteSink's ints.  Nothing but the boxes is written.
+template <bool SEG>
+struct VoteJob {
+    using Sink = VoteSink;
+    VoteInto V;
+    int gate;
+    __device__ __forceinline__ void open(VoteSink &s, uint32_t, const pba_pair &pr, const PackedFetch &, const PackedFetch &fb,
+                                         const SeqSetDev &A, uint32_t *, uint64_t) const {
+        int it0 = V.beg + pr.a_pos, w_pre = V.pre, w_post = V.post;
+        if constexpr (SEG) {
+            w_pre = (int)V.box_off[pr.a_seq - V.t_lo];
+            w_post = w_pre + (int)A.len[pr.a_seq];
+            it0 = w_pre + pr.a_pos;
+        }
+        s.init(V.C, it0, w_pre, w_post, !(pr.flags & PBA_A_BACKWARD), fb);
+    }
+    __device__ __forceinline__ int overlap_min() const { return gate; }
+    __device__ __forceinline__ void close(VoteSink &s, uint32_t, bool walked) const { if (walked) s.finish(); }
 };
 
 // evolve: [pre, post) of `in` -> boxes and text from index `beg` of `out`; *n_out = boxes kept

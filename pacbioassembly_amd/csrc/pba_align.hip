@@ -62,153 +62,40 @@ k_align_bytes_trace(const uint8_t *a, int a_dir, int la, const uint8_t *b, int b
     store_result(out, o);
 }
 
-// ---- traceback on the bit-vector array (align_bvtrace.h): persistent wavefronts, each with its own scratch area
-// of wave_words u32 (cap_words of parent bits, then the goal-first ops of the pair in flight).
-// ids (nullable): the subset of pairs to process (second, full-band launch)
+// ---- traceback on the bit-vector array: the persistent loop of align_bvtrace.h (trace_pairs_loop) under each of its four
+// jobs -- scripts (align_bvtrace.h: ScriptJob), votes (consensus.h: VoteJob), runs (align_cigar.h: CigarJob), per-window counts
+// (align_windows.h: WindowJob).  A kernel is its job's name for the profiler and its launch bounds; the job is its argument.
 // CK: the checkpoint form of the traced pass (align_bvtrace.h): scratch holds one checkpoint per 32 steps, the walk re-runs
-// chunks into this wavefront's LDS tile; else every step's parent words are streamed to scratch.
+// chunks into this wavefront's LDS tile; else every step's parent words are streamed to scratch.  Runs and windows: that
+// form only.
 #ifndef PBA_TR_OCC12
 #define PBA_TR_OCC12 6        // waves per SIMD of the checkpoint-form trace kernels at one or two blocks per lane (tuning hook;
                               // 32 768 reads of BASELINE configs[1], same box: 4 -> 63.0 ms, 5 -> 60.0, 6 -> 50.7, 8 -> 52.3)
 #endif
+#define PBA_TRACED_ARGS SeqSetDev A, SeqSetDev B, const pba_pair *pairs, const uint32_t *ids, uint32_t n, AlignCfg cfg, pba_result *out, \
+                        uint32_t *scratch, uint64_t wave_words, uint64_t cap_words
 template <int NB, bool CK>
 __global__ void __launch_bounds__(PBA_WAVE * 4, NB <= 4 ? (CK && NB <= 2 ? PBA_TR_OCC12 : 4) : 2)
-k_trace_pairs(SeqSetDev A, SeqSetDev B, const pba_pair *pairs, const uint32_t *ids, uint32_t n, AlignCfg cfg,
-              pba_result *out, uint32_t *scratch, uint64_t wave_words, uint64_t cap_words, uint8_t *ops,
-              const uint64_t *ops_off, int32_t *nedit, uint32_t *queue) {
-    extern __shared__ __align__(16) uint8_t lds_all[];
-    __shared__ uint2 s_tile[4][CK ? PBA_BV_TILE_WORDS(NB) : 1];
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / PBA_WAVE));
-    uint8_t *lds = lds_all + (size_t)wave * cfg.row_cap * 2;
-    uint32_t *mine = scratch + ((uint64_t)blockIdx.x * 4 + wave) * wave_words;
-    for (;;) {
-        const uint32_t slot = next_slot(queue);
-        if (slot >= n) break;
-        const uint32_t q = ids ? ids[slot] : slot;
-        const pba_pair pr = pairs[q];
-        const PackedFetch fa = fetch_of(A, pr.a_seq, pr.a_pos, (pr.flags & PBA_A_BACKWARD) ? -1 : 1);
-        const PackedFetch fb = fetch_of(B, pr.b_seq, pr.b_pos, (pr.flags & PBA_B_BACKWARD) ? -1 : 1);
-        AlnOut o;
-        int ne = 0;
-        const uint64_t o0 = ops_off[q], o1 = ops_off[q + 1];
-        OpSink sink{(uint8_t *)(mine + cap_words), 0, 0u};
-        if (align_bitvec_trace<NB, CK>(fa, pr.a_len, fb, pr.b_len, cfg.R, cfg.maxn, cfg.maxm, cfg.full_band != 0, (uint16_t *)lds,
-                                       cfg.row_cap, mine, cap_words, 0, sink, o, s_tile[wave]))
-            ne = sink.finish(ops + o0, o1 - o0);
-        store_result(out + q, o);
-        if ((threadIdx.x & (PBA_WAVE - 1)) == 0) nedit[q] = ne;
-    }
+k_trace_pairs(PBA_TRACED_ARGS, ScriptJob job, uint32_t *queue) {
+    trace_pairs_loop<NB, CK>(A, B, pairs, ids, n, cfg, out, scratch, wave_words, cap_words, job, queue);
 }
-
-// The same sweep and walk, but the path goes straight into the vote boxes of an unlocked reference (consensus.h:
-// VoteSink) -- ref_seq::try_align's align + OVERLAP_MIN gate + elect (ref_seq.h:264-267) for a batch, no script in
-// memory.  a is the reference: pair.a_pos is the position the votes start at.
-// SEG: V is a pile-up's arena (consensus.h: VoteInto with box_off), one segment per target read: pair q votes into the
-// window of ITS a_seq, the box of a_pos at that segment's offset + a_pos.
-// The arena holds fewer than 2^31 boxes (the host refuses or chunks beyond that), so the window fits VoteSink's ints.
+// ref_seq::try_align's align + OVERLAP_MIN gate + elect (ref_seq.h:264-267) for a batch, no script in memory
 template <int NB, bool CK, bool SEG = false>
 __global__ void __launch_bounds__(PBA_WAVE * 4, NB <= 4 ? (CK && NB <= 2 ? PBA_TR_OCC12 : 4) : 2)
-k_vote_pairs(SeqSetDev A, SeqSetDev B, const pba_pair *pairs, const uint32_t *ids, uint32_t n, AlignCfg cfg, int overlap_min,
-             pba_result *out, uint32_t *scratch, uint64_t wave_words, uint64_t cap_words, VoteInto V, uint32_t *queue) {
-    extern __shared__ __align__(16) uint8_t lds_all[];
-    __shared__ uint2 s_tile[4][CK ? PBA_BV_TILE_WORDS(NB) : 1];
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / PBA_WAVE));
-    uint8_t *lds = lds_all + (size_t)wave * cfg.row_cap * 2;
-    uint32_t *mine = scratch + ((uint64_t)blockIdx.x * 4 + wave) * wave_words;
-    for (;;) {
-        const uint32_t slot = next_slot(queue);
-        if (slot >= n) break;
-        const uint32_t q = ids ? ids[slot] : slot;
-        const pba_pair pr = pairs[q];
-        const bool fwd = !(pr.flags & PBA_A_BACKWARD);
-        const PackedFetch fa = fetch_of(A, pr.a_seq, pr.a_pos, fwd ? 1 : -1);
-        const PackedFetch fb = fetch_of(B, pr.b_seq, pr.b_pos, (pr.flags & PBA_B_BACKWARD) ? -1 : 1);
-        AlnOut o;
-        int it0 = V.beg + pr.a_pos, w_pre = V.pre, w_post = V.post;
-        if constexpr (SEG) {
-            w_pre = (int)V.box_off[pr.a_seq - V.t_lo];
-            w_post = w_pre + (int)A.len[pr.a_seq];
-            it0 = w_pre + pr.a_pos;
-        }
-        VoteSink sink{V.C, it0, w_pre, w_post, fwd, fb, 0, 0, 0, 0u};
-        if (align_bitvec_trace<NB, CK>(fa, pr.a_len, fb, pr.b_len, cfg.R, cfg.maxn, cfg.maxm, cfg.full_band != 0, (uint16_t *)lds,
-                                       cfg.row_cap, mine, cap_words, overlap_min, sink, o, s_tile[wave]))
-            sink.finish();
-        store_result(out + q, o);
-    }
+k_vote_pairs(PBA_TRACED_ARGS, VoteJob<SEG> job, uint32_t *queue) {
+    trace_pairs_loop<NB, CK>(A, B, pairs, ids, n, cfg, out, scratch, wave_words, cap_words, job, queue);
 }
-
-// The same sweep and walk once more, the path run-length encoded on its way out (align_cigar.h: CigarSink): pair q's runs go
-// to cig[cig_off[q] ..), their number to ncig[q], the bases of each kind to counts[q].  Checkpoint form only.  The
-// wavefront's goal-first temporary sits behind cap_words, as OpSink's does: wave_words - cap_words runs.
-// pair_flags (nullable): PBA_CIG_* per pair, else `flags` for all of them.
 template <int NB>
 __global__ void __launch_bounds__(PBA_WAVE * 4, NB <= 4 ? (NB <= 2 ? PBA_TR_OCC12 : 4) : 2)
-k_cigar_pairs(SeqSetDev A, SeqSetDev B, const pba_pair *pairs, const uint32_t *ids, uint32_t n, AlignCfg cfg, pba_result *out,
-              uint32_t *scratch, uint64_t wave_words, uint64_t cap_words, uint32_t *cig, const uint64_t *cig_off, int32_t *ncig,
-              pba_aln_counts *counts, const uint32_t *pair_flags, uint32_t flags, uint32_t *queue) {
-    extern __shared__ __align__(16) uint8_t lds_all[];
-    __shared__ uint2 s_tile[4][PBA_BV_TILE_WORDS(NB)];
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / PBA_WAVE));
-    uint8_t *lds = lds_all + (size_t)wave * cfg.row_cap * 2;
-    uint32_t *mine = scratch + ((uint64_t)blockIdx.x * 4 + wave) * wave_words;
-    for (;;) {
-        const uint32_t slot = next_slot(queue);
-        if (slot >= n) break;
-        const uint32_t q = ids ? ids[slot] : slot;
-        const pba_pair pr = pairs[q];
-        const PackedFetch fa = fetch_of(A, pr.a_seq, pr.a_pos, (pr.flags & PBA_A_BACKWARD) ? -1 : 1);
-        const PackedFetch fb = fetch_of(B, pr.b_seq, pr.b_pos, (pr.flags & PBA_B_BACKWARD) ? -1 : 1);
-        const uint32_t fl = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pair_flags ? pair_flags[q] : flags));
-        AlnOut o;
-        int nr = 0;
-        const uint64_t o0 = cig_off[q], o1 = cig_off[q + 1];
-        CigarSink sink;
-        sink.init(fa, fb, mine + cap_words, (uint32_t)(wave_words - cap_words), (fl & PBA_CIG_B_IS_QUERY) != 0);
-        if (align_bitvec_trace<NB, true>(fa, pr.a_len, fb, pr.b_len, cfg.R, cfg.maxn, cfg.maxm, cfg.full_band != 0, (uint16_t *)lds,
-                                         cfg.row_cap, mine, cap_words, 0, sink, o, s_tile[wave]))
-            nr = sink.finish(cig + o0, o1 - o0, (fl & PBA_CIG_REVERSED) != 0, counts + q);
-        else if ((threadIdx.x & (PBA_WAVE - 1)) == 0) counts[q] = pba_aln_counts{0, 0, 0, 0};
-        store_result(out + q, o);
-        if ((threadIdx.x & (PBA_WAVE - 1)) == 0) ncig[q] = nr;
-    }
+k_cigar_pairs(PBA_TRACED_ARGS, CigarJob job, uint32_t *queue) {
+    trace_pairs_loop<NB, true>(A, B, pairs, ids, n, cfg, out, scratch, wave_words, cap_words, job, queue);
 }
-
-// ... and once more with the path counted per window of a's own grid (align_windows.h: WindowSink): pair q's windows go to
-// win[win_off[q] ..), their number to nwin[q], their sum to counts[q].  Checkpoint form only.  No temporary: a closed window
-// goes straight to its final place.  pair_flags (nullable): PBA_CIG_* per pair, else `flags` for all of them.
 template <int NB>
 __global__ void __launch_bounds__(PBA_WAVE * 4, NB <= 4 ? (NB <= 2 ? PBA_TR_OCC12 : 4) : 2)
-k_window_pairs(SeqSetDev A, SeqSetDev B, const pba_pair *pairs, const uint32_t *ids, uint32_t n, AlignCfg cfg, pba_result *out,
-               uint32_t *scratch, uint64_t wave_words, uint64_t cap_words, pba_aln_counts *win, const uint64_t *win_off, int32_t *nwin,
-               pba_aln_counts *counts, const uint32_t *pair_flags, uint32_t flags, int W, uint32_t *queue) {
-    extern __shared__ __align__(16) uint8_t lds_all[];
-    __shared__ uint2 s_tile[4][PBA_BV_TILE_WORDS(NB)];
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / PBA_WAVE));
-    uint8_t *lds = lds_all + (size_t)wave * cfg.row_cap * 2;
-    uint32_t *mine = scratch + ((uint64_t)blockIdx.x * 4 + wave) * wave_words;
-    for (;;) {
-        const uint32_t slot = next_slot(queue);
-        if (slot >= n) break;
-        const uint32_t q = ids ? ids[slot] : slot;
-        const pba_pair pr = pairs[q];
-        const bool a_back = (pr.flags & PBA_A_BACKWARD) != 0;
-        const PackedFetch fa = fetch_of(A, pr.a_seq, pr.a_pos, a_back ? -1 : 1);
-        const PackedFetch fb = fetch_of(B, pr.b_seq, pr.b_pos, (pr.flags & PBA_B_BACKWARD) ? -1 : 1);
-        const uint32_t fl = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pair_flags ? pair_flags[q] : flags));
-        AlnOut o;
-        int nw = 0;
-        const uint64_t o0 = win_off[q], o1 = win_off[q + 1];
-        WindowSink sink;
-        sink.init(fa, fb, pr.a_pos, a_back, W, win + o0, o1 - o0, (fl & PBA_CIG_B_IS_QUERY) != 0, (fl & PBA_CIG_REVERSED) != 0);
-        if (align_bitvec_trace<NB, true>(fa, pr.a_len, fb, pr.b_len, cfg.R, cfg.maxn, cfg.maxm, cfg.full_band != 0, (uint16_t *)lds,
-                                         cfg.row_cap, mine, cap_words, 0, sink, o, s_tile[wave]))
-            nw = sink.finish(counts + q);
-        else if ((threadIdx.x & (PBA_WAVE - 1)) == 0) counts[q] = pba_aln_counts{0, 0, 0, 0};
-        store_result(out + q, o);
-        if ((threadIdx.x & (PBA_WAVE - 1)) == 0) nwin[q] = nw;
-    }
+k_window_pairs(PBA_TRACED_ARGS, WindowJob job, uint32_t *queue) {
+    trace_pairs_loop<NB, true>(A, B, pairs, ids, n, cfg, out, scratch, wave_words, cap_words, job, queue);
 }
+#undef PBA_TRACED_ARGS
 
 // find_path (seq_aligner.h:214-233) walked iteratively from the goal cell; one thread per pair.  The walk meets the ops
 // goal-first and the caller gets them origin-first, the first min(nedit, cap) of them (pba.h): so the path is walked twice,
@@ -343,52 +230,31 @@ static int trace_pass_size(pba_ctx *ctx, const pba_pair *pairs, const uint32_t *
     return scratch_reserve(ctx, (size_t)tp->grid * 4 * tp->wave_words * 4);
 }
 
-// What a launch of k_trace_pairs / k_vote_pairs works on (all pointers: device).
+// What every launch of a traced kernel works on, whatever its job (all pointers: device).
 struct TracedLaunch {
     SeqSetDev A, B;
     const pba_pair *pairs;
     pba_result *out;
     size_t lds;                           // per wavefront
-    bool ck;                              // the checkpoint form (a pile-up's votes: that form only)
-    uint8_t *ops;                         // the sink: scripts (ops / ops_off / nedit) ...
-    const uint64_t *ops_off;
-    int32_t *nedit;
-    const VoteInto *vote;                 // ... or, non-null, votes gated by overlap_min (host pointer; passed by value)
-    int overlap_min;
-    const CigarInto *cig;                 // ... or, non-null, runs (host pointer; its members are passed)
-    const WindowInto *win;                // ... or, non-null, per-window counts (host pointer; its members are passed)
+    bool ck;                              // the checkpoint form
 };
 // (PBA_DISPATCH_NB without its case 0: these kernels have no row-sweep form)
 #define PBA_DISPATCH_BV_NB(nb, K) \
     switch (nb) { case 1: K(1); break; case 2: K(2); break; case 3: K(3); break; case 4: K(4); break; case 6: K(6); break; default: K(8); break; }
-static void launch_traced(pba_ctx *ctx, const TracedLaunch &t, int nb, const AlignCfg &cfg, const uint32_t *ids, uint32_t cnt,
-                          const TracePass &tp) {
-    const dim3 grid(tp.grid), block(PBA_WAVE * 4);
-    uint32_t *const scr = (uint32_t *)ctx->d_scratch;
-#define PBA_SCRIPTS(NBV) {                                                                                            \
-        const auto k = t.ck ? k_trace_pairs<NBV, true> : k_trace_pairs<NBV, false>;                                   \
-        hipLaunchKernelGGL(k, grid, block, t.lds * 4, ctx->stream, t.A, t.B, t.pairs, ids, cnt, cfg, t.out, scr, tp.wave_words, \
-                           tp.cap_words, t.ops, t.ops_off, t.nedit, ctx->d_queue); }
-#define PBA_VOTES(NBV) {                                                                                              \
-        auto k = k_vote_pairs<NBV, true, true>;                                                                      \
-        if (!t.vote->box_off) k = t.ck ? k_vote_pairs<NBV, true, false> : k_vote_pairs<NBV, false, false>;           \
-        hipLaunchKernelGGL(k, grid, block, t.lds * 4, ctx->stream, t.A, t.B, t.pairs, ids, cnt, cfg, t.overlap_min, t.out, scr, \
-                           tp.wave_words, tp.cap_words, *t.vote, ctx->d_queue); }
-#define PBA_RUNS(NBV)                                                                                                 \
-        hipLaunchKernelGGL(k_cigar_pairs<NBV>, grid, block, t.lds * 4, ctx->stream, t.A, t.B, t.pairs, ids, cnt, cfg, t.out, scr, \
-                           tp.wave_words, tp.cap_words, t.cig->cig, t.cig->off, t.cig->ncig, t.cig->counts, t.cig->pair_flags, \
-                           t.cig->flags, ctx->d_queue)
-#define PBA_WINS(NBV)                                                                                                 \
-        hipLaunchKernelGGL(k_window_pairs<NBV>, grid, block, t.lds * 4, ctx->stream, t.A, t.B, t.pairs, ids, cnt, cfg, t.out, scr, \
-                           tp.wave_words, tp.cap_words, t.win->win, t.win->off, t.win->nwin, t.win->counts, t.win->pair_flags, \
-                           t.win->flags, t.win->W, ctx->d_queue)
-    if (t.win) { PBA_DISPATCH_BV_NB(nb, PBA_WINS); }
-    else if (t.cig) { PBA_DISPATCH_BV_NB(nb, PBA_RUNS); }
-    else if (!t.vote) { PBA_DISPATCH_BV_NB(nb, PBA_SCRIPTS); } else { PBA_DISPATCH_BV_NB(nb, PBA_VOTES); }
-#undef PBA_WINS
-#undef PBA_RUNS
-#undef PBA_VOTES
-#undef PBA_SCRIPTS
+// the kernel of a job at NB blocks per lane (ck: only where the job has both forms)
+template <int NB> static auto traced_kernel(const ScriptJob &, bool ck) { return ck ? k_trace_pairs<NB, true> : k_trace_pairs<NB, false>; }
+template <int NB> static auto traced_kernel(const VoteJob<false> &, bool ck) { return ck ? k_vote_pairs<NB, true, false> : k_vote_pairs<NB, false, false>; }
+template <int NB> static auto traced_kernel(const VoteJob<true> &, bool) { return k_vote_pairs<NB, true, true>; }
+template <int NB> static auto traced_kernel(const CigarJob &, bool) { return k_cigar_pairs<NB>; }
+template <int NB> static auto traced_kernel(const WindowJob &, bool) { return k_window_pairs<NB>; }
+template <class Job>
+static void launch_traced(pba_ctx *ctx, const TracedLaunch &t, const Job &job, int nb, const AlignCfg &cfg, const uint32_t *ids,
+                          uint32_t cnt, const TracePass &tp) {
+#define PBA_TRACED(NBV)                                                                                               \
+    hipLaunchKernelGGL(traced_kernel<NBV>(job, t.ck), dim3(tp.grid), dim3(PBA_WAVE * 4), t.lds * 4, ctx->stream, t.A, t.B, t.pairs, \
+                       ids, cnt, cfg, t.out, (uint32_t *)ctx->d_scratch, tp.wave_words, tp.cap_words, job, ctx->d_queue)
+    PBA_DISPATCH_BV_NB(nb, PBA_TRACED);
+#undef PBA_TRACED
 }
 
 // (the entry points below have C linkage from their declarations in pba.h / pba_host.h)
@@ -517,16 +383,15 @@ static int text_pair_bitvec(pba_ctx *ctx, const char *a, int a_fwd, const char *
     HIPCHK(hipMemcpyAsync(d_in, h, t.bytes, hipMemcpyHostToDevice, ctx->stream));
     const SeqSetDev S{d_in + t.o_packed, (const uint64_t *)(d_in + t.o_off), (const uint32_t *)(d_in + t.o_len),
                       (const uint32_t *)(d_in + t.o_plane), (const uint64_t *)(d_in + t.o_poff)};
-    TracedLaunch tl{};
-    tl.A = tl.B = S; tl.pairs = (const pba_pair *)(d_in + t.o_pair); tl.out = (pba_result *)d_res; tl.lds = pl.lds; tl.ck = ck;
-    tl.ops = d_res + kTxtOutOps; tl.ops_off = (const uint64_t *)(d_in + t.o_ooff); tl.nedit = (int32_t *)(d_res + 32);
+    const TracedLaunch tl{S, S, (const pba_pair *)(d_in + t.o_pair), (pba_result *)d_res, pl.lds, ck};
+    const ScriptJob job{d_res + kTxtOutOps, (const uint64_t *)(d_in + t.o_ooff), (int32_t *)(d_res + 32)};
     TracePass tp{};
     auto before = [&](int pass, const std::vector<uint32_t> &) {     // whichever of the workgroup's four wavefronts takes the pair
         return want_trace ? trace_pass_size(ctx, &pr, nullptr, 1, R, pass ? pl.nb2 : pl.nb1, pass != 0, ck, ops_room - 64, pl.lds,
                                             ~0ull, &tp) : (int)PBA_OK;
     };
     auto launch = [&](int nb, const uint32_t *ids, uint32_t cnt) {
-        if (want_trace) launch_traced(ctx, tl, nb, pl.cfg, ids, cnt, tp);
+        if (want_trace) launch_traced(ctx, tl, job, nb, pl.cfg, ids, cnt, tp);
         else launch_align_pairs(ctx, pl, nb, S, S, tl.pairs, ids, cnt, tl.out);
     };
     auto fetch = [&]() {
@@ -746,16 +611,15 @@ static int trace_rowsweep(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, co
     return PBA_OK;
 }
 
-// Edit scripts of a batch (vote == nullptr: ops / ops_off / nedit receive them) or their votes (vote != nullptr: the
-// paths go straight into the boxes it names, gated by overlap_min; ops / ops_off / nedit unused), their runs (cig) or their
-// per-window counts (win): one sink a call.
-int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R,
-                       int maxn, int maxm, int kernel, pba_result *out, uint8_t *ops, const uint64_t *ops_off,
-                       int32_t *nedit, const VoteInto *vote, int overlap_min, const CigarInto *cig, const WindowInto *win) {
-    const bool seg = vote && vote->box_off;
-    const bool sunk = vote || cig || win;                    // the path goes to a sink of its own: no script leaves the device
-    if (!ctx || !A || !B || (!pairs && n) || (!out && n) || (!sunk && ((!ops_off && n) || (!nedit && n))) ||
-        (vote != nullptr) + (cig != nullptr) + (win != nullptr) > 1) return PBA_E_INVALID;
+// The paths of a batch, to the one outlet `into` names (pba_host.h: TraceInto).  Scripts alone leave the device here; the other
+// outlets write device arrays of the caller's.
+int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R, int maxn, int maxm,
+                int kernel, pba_result *out, const TraceInto &into) {
+    const bool scripts = into.kind == TraceInto::SCRIPTS;    // else the path goes to a sink of its own: no script leaves the device
+    uint8_t *const ops = into.ops;
+    const uint64_t *const ops_off = into.ops_off;
+    int32_t *const nedit = into.nedit;
+    if (!ctx || !A || !B || (!pairs && n) || (!out && n) || (scripts && ((!ops_off && n) || (!nedit && n)))) return PBA_E_INVALID;
     if (n == 0) return PBA_OK;
     if (n > 0x7FFFFFFFull) PBA_FAIL(PBA_E_INVALID, "too many pairs in one batch");
     if (A->non_acgt || B->non_acgt) PBA_FAIL(PBA_E_ALPHABET, "a sequence set holds bytes outside ACGT: use pba_align_text_trace");
@@ -763,33 +627,26 @@ int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pa
     tu_attrs(ctx);
     int mdmax;
     uint64_t ops_max;
-    int st = check_pairs(ctx, A, B, pairs, n, R, sunk ? nullptr : ops_off, &mdmax, &ops_max);
+    int st = check_pairs(ctx, A, B, pairs, n, R, scripts ? ops_off : nullptr, &mdmax, &ops_max);
     if (st != PBA_OK) return st;
     Plan pl;
     st = make_plan(ctx, R, maxn, maxm, kernel, mdmax, &pl);
     if (st != PBA_OK) return st;
-    TracedLaunch t{};
-    if (vote) {
-        if (pl.nb1 == 0) PBA_FAIL(PBA_E_TOOLONG, "votes from the walk need the bit-vector kernel (band too wide)");
-        ops_max = 0;                                             // no goal-first temporary
+    if (!scripts && pl.nb1 == 0) {
+        char msg[96];
+        snprintf(msg, sizeof msg, "%s from the walk need the bit-vector kernel (band too wide)", into.name());
+        PBA_FAIL(PBA_E_TOOLONG, msg);
     }
-    if (cig) {
-        if (pl.nb1 == 0) PBA_FAIL(PBA_E_TOOLONG, "runs from the walk need the bit-vector kernel (band too wide)");
-        ops_max = cig->run_max * 4;                              // the goal-first temporary holds runs, 4 bytes each
-    }
-    if (win) {
-        if (pl.nb1 == 0) PBA_FAIL(PBA_E_TOOLONG, "windows from the walk need the bit-vector kernel (band too wide)");
-        ops_max = 0;                                             // no goal-first temporary
-    }
+    const uint64_t tmp_bytes = into.tmp_bytes(ops_max);
     TraceBufs d;
-    d.ops_total = sunk ? 0 : ops_off[n] - ops_off[0];
+    d.ops_total = scripts ? ops_off[n] - ops_off[0] : 0;
     HIPCHK(hipMalloc(&d.pairs.p, sizeof(pba_pair) * n));
     HIPCHK(hipMalloc(&d.out.p, sizeof(pba_result) * n));
     HIPCHK(hipMalloc(&d.ops.p, d.ops_total + 16));
     HIPCHK(hipMalloc(&d.ooff.p, sizeof(uint64_t) * (n + 1)));
     HIPCHK(hipMalloc(&d.ne.p, sizeof(int32_t) * n));
     std::vector<uint64_t> rel(n + 1, 0);
-    if (!sunk) for (size_t q = 0; q <= n; ++q) rel[q] = ops_off[q] - ops_off[0];
+    if (scripts) for (size_t q = 0; q <= n; ++q) rel[q] = ops_off[q] - ops_off[0];
     HIPCHK(hipMemcpyAsync(d.pairs.p, pairs, sizeof(pba_pair) * n, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(d.ooff.p, rel.data(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, ctx->stream));
     const TraceHooks hooks = trace_hooks_from_env();
@@ -802,23 +659,30 @@ int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pa
     // bit-vector array: 2 bits per processed cell in a per-wavefront scratch area, walked by the same wavefront.
     // First launch: every pair, narrow window, scratch sized for it (so more wavefronts fit the budget); second
     // launch: the pairs that came back uncertified, reference band.
-    t.A = A->dev(); t.B = B->dev(); t.pairs = d.pairs.as<pba_pair>(); t.out = d.out.as<pba_result>(); t.lds = pl.lds;
-    t.ck = seg || cig || win || !hooks.stream;
-    t.ops = d.ops.as<uint8_t>(); t.ops_off = d.ooff.as<uint64_t>(); t.nedit = d.ne.as<int32_t>();
-    t.vote = vote; t.overlap_min = overlap_min; t.cig = cig; t.win = win;
+    const TracedLaunch t{A->dev(), B->dev(), d.pairs.as<pba_pair>(), d.out.as<pba_result>(), pl.lds, into.ck_only() || !hooks.stream};
     TracePass tp{};
     auto before = [&](int pass, const std::vector<uint32_t> &redo) {
         return trace_pass_size(ctx, pairs, pass ? redo.data() : nullptr, pass ? (uint32_t)redo.size() : (uint32_t)n, R,
-                               pass ? pl.nb2 : pl.nb1, pass != 0, t.ck, ops_max, pl.lds, budget, &tp);
+                               pass ? pl.nb2 : pl.nb1, pass != 0, t.ck, tmp_bytes, pl.lds, budget, &tp);
     };
-    auto launch = [&](int nb, const uint32_t *ids, uint32_t cnt) { launch_traced(ctx, t, nb, pl.cfg, ids, cnt, tp); };
+    auto launch = [&](int nb, const uint32_t *ids, uint32_t cnt) {          // the tag becomes the job's type here, nowhere else
+        switch (into.kind) {
+        case TraceInto::SCRIPTS: launch_traced(ctx, t, ScriptJob{d.ops.as<uint8_t>(), d.ooff.as<uint64_t>(), d.ne.as<int32_t>()}, nb, pl.cfg, ids, cnt, tp); break;
+        case TraceInto::VOTES:
+            if (into.vote.box_off) launch_traced(ctx, t, VoteJob<true>{into.vote, into.overlap_min}, nb, pl.cfg, ids, cnt, tp);
+            else launch_traced(ctx, t, VoteJob<false>{into.vote, into.overlap_min}, nb, pl.cfg, ids, cnt, tp);
+            break;
+        case TraceInto::RUNS: launch_traced(ctx, t, CigarJob{into.slots}, nb, pl.cfg, ids, cnt, tp); break;
+        case TraceInto::WINDOWS: launch_traced(ctx, t, WindowJob{into.slots}, nb, pl.cfg, ids, cnt, tp); break;
+        }
+    };
     auto collect = [&](std::vector<uint32_t> &redo) { return fetch_results(ctx, d.out.p, out, n, &redo); };
-    auto finish = [&](bool redone) { return trace_results(ctx, d, n, redone, out, ops, ops_off, nedit, sunk); };
+    auto finish = [&](bool redone) { return trace_results(ctx, d, n, redone, out, ops, ops_off, nedit, !scripts); };
     return narrow_then_redo(ctx, pl, nullptr, (uint32_t)n, launch, collect, finish, before);
 }
 
 int pba_align_batch_trace(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R,
                           int maxn, int maxm, int kernel, pba_result *out, uint8_t *ops, const uint64_t *ops_off,
                           int32_t *nedit) {
-    return trace_batch(ctx, A, B, pairs, n, R, maxn, maxm, kernel, out, ops, ops_off, nedit);
+    return trace_batch(ctx, A, B, pairs, n, R, maxn, maxm, kernel, out, TraceInto::scripts(ops, ops_off, nedit));
 }

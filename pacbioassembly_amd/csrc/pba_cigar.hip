@@ -1,12 +1,13 @@
 // pba_cigar.hip -- run-length alignments (CIGAR over = X I D) for explicit pairs, mapped reads and overlap rows: the host
-// side of the third sink of the traced bit-vector pass (align_cigar.h: CigarSink, run by k_cigar_pairs in pba_align.hip
-// through trace_batch), the compaction of a chunk's bounded slots into one dense array, and the host twins of the sink.
+// side of the runs outlet of the traced bit-vector pass (align_cigar.h: CigarJob, run by k_cigar_pairs in pba_align.hip;
+// TraceInto::runs through trace_batch), the compaction of a chunk's bounded slots into one dense array, and the host twins
+// of the sink.  The slot runner, the chunk loop and the row layout are shared with pba_windows.hip (pba_rows.h, aln_rows.h).
 // One process per GPU, one pba_ctx per process, one HIP stream per ctx.  Everything that needs the device fails loudly
 // (PBA_E_NODEVICE / PBA_E_HIP): there is no CPU path behind those entry points.
 //
 // A run is len << 4 | op (include/pba.h).  A pair's slot is sized by pba_cigar_bound, a proven bound on the runs of a
 // success; the sink never writes beyond a slot and reports the count, so a wrong bound would surface as PBA_E_HIP here.
-#include "pba_host.h"
+#include "pba_rows.h"
 
 #include <string>
 
@@ -24,17 +25,13 @@ int pba_cigar_from_script(const uint8_t *ops, int32_t nedit, const char *a_elems
     const bool swap = (flags & PBA_CIG_B_IS_QUERY) != 0, rev = (flags & PBA_CIG_REVERSED) != 0;
     std::vector<uint32_t> runs;                 // origin-first
     pba_aln_counts c{0, 0, 0, 0};
-    int i = 0, j = 0;
-    for (int32_t k = 0; k < nedit; ++k) {
-        uint32_t code;
-        if (ops[k] == 1) { code = a_elems[i] == b_elems[j] ? PBA_CIG_EQ : PBA_CIG_X; ++i; ++j; }
-        else if (ops[k] == 2) { code = swap ? PBA_CIG_INS : PBA_CIG_DEL; ++j; }       // INSERT consumes b only
-        else if (ops[k] == 3) { code = swap ? PBA_CIG_DEL : PBA_CIG_INS; ++i; }       // DELETE consumes a only
-        else return -1;
-        if (code == PBA_CIG_EQ) ++c.n_eq; else if (code == PBA_CIG_X) ++c.n_x; else if (code == PBA_CIG_INS) ++c.n_ins; else ++c.n_del;
+    const bool ok = script_walk(ops, nedit, a_elems, b_elems, swap, [&](uint32_t code, int, int, int) {
+        aln_count(c, code);
         if (!runs.empty() && (runs.back() & 15u) == code) runs.back() += 16u;
         else runs.push_back(16u | code);
-    }
+        return true;
+    });
+    if (!ok) return -1;
     const size_t nr = runs.size();
     for (size_t x = 0; x < nr && x < (size_t)cap; ++x) cigar[x] = rev ? runs[nr - 1 - x] : runs[x];
     if (counts) *counts = c;
@@ -107,47 +104,13 @@ k_cig_compact(const uint32_t *cig, const uint64_t *slot_off, const uint64_t *den
 }
 
 // ---- one batch -----------------------------------------------------------------------------------------------------------
-// The device side of a batch of runs: slot q = [off[q], off[q + 1]) of d_cig.
-struct CigBufs { DevBuf cig, off, ncig, counts, pflags; };
-
-// slots on the device, the batch through trace_batch, counts and results back on the host (synchronised)
-static int cigar_run(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R, int maxn,
-                     int maxm, uint32_t flags, const uint32_t *pair_flags, const uint64_t *rel_off /* n + 1, from 0 */,
-                     uint64_t run_max, pba_result *out, int32_t *ncig, pba_aln_counts *counts, CigBufs &d) {
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipMalloc(&d.cig.p, sizeof(uint32_t) * (rel_off[n] + 16)));
-    HIPCHK(hipMalloc(&d.off.p, sizeof(uint64_t) * (n + 1)));
-    HIPCHK(hipMalloc(&d.ncig.p, sizeof(int32_t) * n));
-    HIPCHK(hipMalloc(&d.counts.p, sizeof(pba_aln_counts) * n));
-    HIPCHK(hipMemcpyAsync(d.off.p, rel_off, sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemsetAsync(d.ncig.p, 0, sizeof(int32_t) * n, ctx->stream));
-    HIPCHK(hipMemsetAsync(d.counts.p, 0, sizeof(pba_aln_counts) * n, ctx->stream));
-    if (pair_flags) {
-        HIPCHK(hipMalloc(&d.pflags.p, sizeof(uint32_t) * n));
-        HIPCHK(hipMemcpyAsync(d.pflags.p, pair_flags, sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream));
-    }
-    const CigarInto into{d.cig.as<uint32_t>(), d.off.as<uint64_t>(), d.ncig.as<int32_t>(), d.counts.as<pba_aln_counts>(),
-                         d.pflags.as<uint32_t>(), flags, run_max};
-    PBA_TRY(trace_batch(ctx, A, B, pairs, n, R, maxn, maxm, PBA_KERNEL_BITVEC, out, nullptr, nullptr, nullptr, nullptr, 0, &into));
-    HIPCHK(hipMemcpyAsync(ncig, d.ncig.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(counts, d.counts.p, sizeof(pba_aln_counts) * n, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (size_t q = 0; q < n; ++q)
-        if (ncig[q] < 0 || (uint64_t)ncig[q] > rel_off[q + 1] - rel_off[q]) {
-            snprintf(ctx->err, sizeof ctx->err, "pair %llu (a_len %d, b_len %d) has %d runs, its slot holds %llu: the run bound does not hold",
-                     (unsigned long long)q, pairs[q].a_len, pairs[q].b_len, ncig[q], (unsigned long long)(rel_off[q + 1] - rel_off[q]));
-            return PBA_E_HIP;
-        }
-    return PBA_OK;
-}
-
 // The real runs of a finished batch, dense and in pair order, on the host (synchronised): doff[0 .. n] their offsets.  Only
 // they cross to the host, not the bounded slots.  They land in *dense or, where the caller has room of its own, at `into`.
-static int cigar_compact(pba_ctx *ctx, const CigBufs &d, size_t n, std::vector<uint64_t> &doff, std::vector<uint32_t> *dense, uint32_t *into) {
+static int cigar_compact(pba_ctx *ctx, const SlotBufs &d, size_t n, std::vector<uint64_t> &doff, std::vector<uint32_t> *dense, uint32_t *into) {
     DevBuf d_doff, d_dense;
     doff.resize(n + 1);
     HIPCHK(hipMalloc(&d_doff.p, sizeof(uint64_t) * (n + 1)));
-    hipLaunchKernelGGL(k_cig_scan, dim3(1), dim3(1024), 0, ctx->stream, d.ncig.as<int32_t>(), d.off.as<uint64_t>(), (uint32_t)n,
+    hipLaunchKernelGGL(k_cig_scan, dim3(1), dim3(1024), 0, ctx->stream, d.n.as<int32_t>(), d.off.as<uint64_t>(), (uint32_t)n,
                        d_doff.as<uint64_t>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(doff.data(), d_doff.p, sizeof(uint64_t) * (n + 1), hipMemcpyDeviceToHost, ctx->stream));
@@ -155,7 +118,7 @@ static int cigar_compact(pba_ctx *ctx, const CigBufs &d, size_t n, std::vector<u
     if (dense) { dense->resize(doff[n]); into = dense->data(); }
     if (!doff[n]) return PBA_OK;
     HIPCHK(hipMalloc(&d_dense.p, sizeof(uint32_t) * doff[n]));            // (the scan's total: every gathered run lands inside)
-    hipLaunchKernelGGL(k_cig_compact, dim3((uint32_t)n), dim3(PBA_WAVE), 0, ctx->stream, d.cig.as<uint32_t>(), d.off.as<uint64_t>(),
+    hipLaunchKernelGGL(k_cig_compact, dim3((uint32_t)n), dim3(PBA_WAVE), 0, ctx->stream, d.slot.as<uint32_t>(), d.off.as<uint64_t>(),
                        d_doff.as<uint64_t>(), (uint32_t)n, d_dense.as<uint32_t>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(into, d_dense.p, sizeof(uint32_t) * doff[n], hipMemcpyDeviceToHost, ctx->stream));
@@ -184,8 +147,10 @@ int pba_align_batch_cigar(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, co
         run_max = std::max(run_max, bound);
     }
     if (rel[n] && !cigar) return PBA_E_INVALID;
-    CigBufs d;
-    PBA_TRY(cigar_run(ctx, A, B, pairs, n, R, maxn, maxm, flags, nullptr, rel.data(), run_max, out, ncig, counts, d));
+    SlotBufs d;
+    SlotsInto extra{};
+    extra.flags = flags; extra.run_max = run_max;
+    PBA_TRY(slots_run<uint32_t>(ctx, A, B, pairs, n, R, maxn, maxm, extra, nullptr, rel.data(), out, ncig, counts, d));
     // The dense runs land at the head of the caller's own array and move out to their slots from the last pair down: a
     // pair's slot never starts before its dense place (every slot holds its pair's runs, so the offsets dominate), and what
     // lies behind it has moved already.  No second array on the host.
@@ -202,77 +167,26 @@ int pba_align_batch_cigar(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, co
 // ---- rows ----------------------------------------------------------------------------------------------------------------
 static const uint64_t kCigChunkSlots = 1ull << 28;      // bounded slots of one chunk of rows on the device (1 GiB)
 
-// The jobs (in row order) in chunks whose bounded slots stay under max_slots, each chunk as up to two batches (A[s] against
-// B[s]); every batch compacted on the device, its real runs copied to the host and laid out in row order.  row_n[k]: runs
-// of row k (0 for a row without a job).
+// The jobs through the chunk loop (pba_rows.h); every batch compacted on the device, only its real runs copied to the host and
+// kept per job, then laid out in row order.
 static int rows_cigar(pba_ctx *ctx, const char *who, const pba_seqs *const A[2], const pba_seqs *const B[2],
                       const std::vector<RowJob> &jobs, uint64_t n_rows, double R, uint32_t *cigar, uint64_t cap, uint64_t *cig_off,
                       uint64_t *n_slots, pba_aln_counts *counts, pba_result *res, uint64_t max_slots) {
-    if (max_slots == 0) max_slots = kCigChunkSlots;
-    std::vector<uint32_t> row_n(n_rows, 0);
-    uint64_t pos = 0;                                   // dense position of the next job's runs
-    bool fits = true;
-    std::vector<pba_pair> pairs;
-    std::vector<uint32_t> pflags, which, dense;
-    std::vector<uint64_t> rel, doff;
-    std::vector<pba_result> out;
-    std::vector<int32_t> ncig;
-    std::vector<pba_aln_counts> cnt;
-    for (size_t j0 = 0; j0 < jobs.size();) {
-        size_t j1 = j0;
-        uint64_t slots = 0;
-        while (j1 < jobs.size()) {                      // greedy take: at least one row
-            const uint64_t b = pba_cigar_bound(jobs[j1].pr.a_len, jobs[j1].pr.b_len, R);
-            if (j1 > j0 && slots + b > max_slots) break;
-            slots += b; ++j1;
+    std::vector<std::vector<uint32_t>> of(jobs.size());
+    std::vector<uint32_t> dense;
+    std::vector<uint64_t> doff;
+    const auto sink = [&](const SlotBatch &b) -> int {
+        PBA_TRY(cigar_compact(ctx, *b.d, b.nb, doff, &dense, nullptr));
+        for (size_t q = 0; q < b.nb; ++q) {
+            if (doff[q + 1] - doff[q] != (uint64_t)b.have[q]) PBA_FAIL(PBA_E_HIP, "the compaction's offsets disagree with the run counts");
+            of[b.at[q]].assign(dense.begin() + (ptrdiff_t)doff[q], dense.begin() + (ptrdiff_t)doff[q + 1]);
         }
-        std::vector<std::vector<uint32_t>> runs_of(j1 - j0);
-        for (int s = 0; s < 2; ++s) {
-            pairs.clear(); pflags.clear(); which.clear(); rel.assign(1, 0);
-            uint64_t run_max = 0;
-            for (size_t j = j0; j < j1; ++j) {
-                if (jobs[j].batch != s) continue;
-                const uint64_t b = pba_cigar_bound(jobs[j].pr.a_len, jobs[j].pr.b_len, R);
-                pairs.push_back(jobs[j].pr); pflags.push_back(jobs[j].flags); which.push_back((uint32_t)(j - j0));
-                rel.push_back(rel.back() + b);
-                run_max = std::max(run_max, b);
-            }
-            const size_t nb = pairs.size();
-            if (!nb) continue;
-            out.resize(nb); ncig.resize(nb); cnt.resize(nb);
-            CigBufs d;
-            PBA_TRY(cigar_run(ctx, A[s], B[s], pairs.data(), nb, R, 0, 0, 0u, pflags.data(), rel.data(), run_max, out.data(),
-                              ncig.data(), cnt.data(), d));
-            for (size_t q = 0; q < nb; ++q) {           // held to the row: the same roles, the same lengths, the same R
-                const RowJob &jb = jobs[j0 + which[q]];
-                if (res) res[jb.row] = out[q];
-                if (counts) counts[jb.row] = cnt[q];
-                if (!walk_agrees(out[q], jb.cost, jb.matlen_a, jb.matlen_b)) {
-                    snprintf(ctx->err, sizeof ctx->err,
-                             "%s: row %llu re-runs to rc %d cost %d matlen %d/%d, the row says cost %d matlen %d/%d: not a row of these "
-                             "sets under this R", who, (unsigned long long)jb.row, out[q].rc, out[q].cost, out[q].matlen_a,
-                             out[q].matlen_b, jb.cost, jb.matlen_a, jb.matlen_b);
-                    return PBA_E_INVALID;
-                }
-            }
-            PBA_TRY(cigar_compact(ctx, d, nb, doff, &dense, nullptr));
-            for (size_t q = 0; q < nb; ++q) {
-                if (doff[q + 1] - doff[q] != (uint64_t)ncig[q]) PBA_FAIL(PBA_E_HIP, "the compaction's offsets disagree with the run counts");
-                runs_of[which[q]].assign(dense.begin() + (ptrdiff_t)doff[q], dense.begin() + (ptrdiff_t)doff[q + 1]);
-            }
-        }
-        for (size_t j = j0; j < j1; ++j) {              // row order; whole rows only, up to the first that does not fit
-            const std::vector<uint32_t> &r = runs_of[j - j0];
-            row_n[jobs[j].row] = (uint32_t)r.size();
-            if (fits && pos + r.size() <= cap) { if (!r.empty()) memcpy(cigar + pos, r.data(), sizeof(uint32_t) * r.size()); }
-            else fits = false;
-            pos += r.size();
-        }
-        j0 = j1;
-    }
-    cig_off[0] = 0;
-    for (uint64_t k = 0; k < n_rows; ++k) cig_off[k + 1] = cig_off[k] + row_n[k];
-    *n_slots = cig_off[n_rows];
+        return PBA_OK;
+    };
+    const auto bound = [R](const pba_pair &p) -> uint64_t { return pba_cigar_bound(p.a_len, p.b_len, R); };
+    PBA_TRY(rows_chunks<uint32_t>(ctx, who, A, B, jobs, R, bound, SlotsInto{}, 0u, counts, res, max_slots ? max_slots : kCigChunkSlots,
+                                  nullptr, sink));
+    rows_layout(of, job_rows(jobs), n_rows, cigar, cap, cig_off, n_slots);
     return PBA_OK;
 }
 

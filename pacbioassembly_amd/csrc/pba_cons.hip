@@ -134,7 +134,7 @@ int pba_cons_vote_pairs(pba_ctx *ctx, pba_cons *c, const pba_seqs *A, uint32_t r
             PBA_FAIL(PBA_E_INVALID, "pba_cons_vote_pairs: a must be the reference, both accessors in one direction");
     }
     const VoteInto into = c->vote_into(c->beg);                   // A[ref_seq] is the text of [beg, end)
-    return trace_batch(ctx, A, B, pairs, n, R, maxn, maxm, PBA_KERNEL_BITVEC, out, nullptr, nullptr, nullptr, &into, overlap_min);
+    return trace_batch(ctx, A, B, pairs, n, R, maxn, maxm, PBA_KERNEL_BITVEC, out, TraceInto::votes(into, overlap_min));
 }
 
 // the text of boxes [first, first+len) as a one-sequence set (packed on the device from the object's own text array)
@@ -213,8 +213,8 @@ int pba_cons_round(pba_ctx *ctx, pba_cons *c, const pba_seqs *reads, const uint3
         if (st == PBA_OK && !vp.empty()) {                                              // elect, ref_seq.h:267
             std::vector<pba_result> out(vp.size());
             const VoteInto into = c->vote_into(c->pre);                                 // ext is the text of [pre, post)
-            st = trace_batch(ctx, ext, reads, vp.data(), vp.size(), R, maxn, maxm, PBA_KERNEL_BITVEC, out.data(), nullptr, nullptr,
-                             nullptr, &into, overlap_min);
+            st = trace_batch(ctx, ext, reads, vp.data(), vp.size(), R, maxn, maxm, PBA_KERNEL_BITVEC, out.data(),
+                             TraceInto::votes(into, overlap_min));
             for (size_t q = 0; st == PBA_OK && q < vp.size(); ++q) {
                 const pba_ss_row &w = rows[vread[q]];
                 if (!walk_agrees(out[q], w.cost, w.matlen_a, w.matlen_b)) {

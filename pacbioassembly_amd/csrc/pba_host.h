@@ -21,6 +21,7 @@
 #include <new>
 #include <vector>
 
+#include "align_cigar.h"
 #include "align_common.h"
 #include "consensus.h"
 #include "dev_common.h"
@@ -550,28 +551,26 @@ static inline bool scan_inclusive(pba_ctx *ctx, uint32_t *a, uint64_t n, uint32_
     return false;
 }
 
-// Where a batch of walks leaves its runs (k_cigar_pairs, pba_align.hip).  All pointers: device, owned by the caller, who
-// copies them back once trace_batch has returned (synchronised).  Pair q's slot is cig[off[q] .. off[q + 1]).
-struct CigarInto {
-    uint32_t *cig;
-    const uint64_t *off;
-    int32_t *ncig;
-    pba_aln_counts *counts;
-    const uint32_t *pair_flags;           // PBA_CIG_* per pair; nullable: `flags` for every pair
-    uint32_t flags;
-    uint64_t run_max;                     // the widest slot any pair may fill: sizes the wavefronts' goal-first temporaries
-};
-
-// Where a batch of walks leaves its per-window counts (k_window_pairs, pba_align.hip; align_windows.h).  All pointers: device,
-// owned by the caller.  Pair q's slot is win[off[q] .. off[q + 1]): nothing is written unless all of its windows fit.
-struct WindowInto {
-    pba_aln_counts *win;
-    const uint64_t *off;
-    int32_t *nwin;
-    pba_aln_counts *counts;
-    const uint32_t *pair_flags;           // PBA_CIG_* per pair; nullable: `flags` for every pair
-    uint32_t flags;
-    int W;                                // window size on a's own coordinates, >= 1
+// Where the paths of a call of trace_batch go: exactly one outlet, made by name.  Scripts reach the caller's host arrays; votes
+// go into the boxes `vote` names (device), gated by overlap_min; runs and per-window counts into the bounded slots of `slots`
+// (align_cigar.h: SlotsInto, device).  What the host must know of an outlet to size and launch its pass is said here.
+struct TraceInto {
+    enum Kind { SCRIPTS, VOTES, RUNS, WINDOWS } kind;
+    uint8_t *ops; const uint64_t *ops_off; int32_t *nedit;
+    VoteInto vote; int overlap_min;
+    SlotsInto slots;
+    static TraceInto scripts(uint8_t *ops, const uint64_t *ops_off, int32_t *nedit) {
+        TraceInto t{}; t.kind = SCRIPTS; t.ops = ops; t.ops_off = ops_off; t.nedit = nedit; return t;
+    }
+    static TraceInto votes(const VoteInto &v, int overlap_min) { TraceInto t{}; t.kind = VOTES; t.vote = v; t.overlap_min = overlap_min; return t; }
+    static TraceInto runs(const SlotsInto &s) { TraceInto t{}; t.kind = RUNS; t.slots = s; return t; }
+    static TraceInto windows(const SlotsInto &s) { TraceInto t{}; t.kind = WINDOWS; t.slots = s; return t; }
+    // bytes of goal-first temporary a wavefront needs behind its parent bits (ops_max: the longest script of the batch)
+    uint64_t tmp_bytes(uint64_t ops_max) const { return kind == SCRIPTS ? ops_max : (kind == RUNS ? slots.run_max * 4 : 0); }
+    // the checkpoint form only (a pile-up's votes, runs, windows); the others take the streamed form under PBA_TRACE_STREAM
+    bool ck_only() const { return kind == RUNS || kind == WINDOWS || (kind == VOTES && vote.box_off); }
+    // "<name> from the walk need the bit-vector kernel (band too wide)"; scripts have the row-sweep form and never say it
+    const char *name() const { return kind == VOTES ? "votes" : (kind == RUNS ? "runs" : (kind == WINDOWS ? "windows" : "scripts")); }
 };
 
 // One row's alignment to re-run for its runs or its windows: its pair, the batch it goes with (0: strand +1, 1: strand -1),
@@ -584,12 +583,9 @@ extern "C" {
 PBA_INTERNAL int sort_partition_global(pba_ctx *ctx, uint64_t *d_part, uint32_t n);
 // an index build of at most n_upper entries takes tiles of 4 096 entries in its generic level kernels (pba_core.hip)
 PBA_INTERNAL bool index_small_tiles(uint64_t n_upper);
-// edit scripts of a batch, or (vote non-null) their votes into the boxes it names, gated by overlap_min, or (cig non-null)
-// their runs, or (win non-null) their per-window counts, into the device arrays it names (pba_align.hip)
+// the paths of a batch to the outlet `into` names (pba_align.hip)
 PBA_INTERNAL int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R,
-                             int maxn, int maxm, int kernel, pba_result *out, uint8_t *ops, const uint64_t *ops_off,
-                             int32_t *nedit, const VoteInto *vote = nullptr, int overlap_min = 0, const CigarInto *cig = nullptr,
-                             const WindowInto *win = nullptr);
+                             int maxn, int maxm, int kernel, pba_result *out, const TraceInto &into);
 // The re-run jobs of overlap / mapped rows, in row order, after the checks both the CIGAR and the window entry points make of
 // their sets and rows (who: the public function's name); counts / res (nullable, n entries): zeroed, res rc = -1 (pba_cigar.hip)
 PBA_INTERNAL int overlap_rows_jobs(pba_ctx *ctx, const char *who, const pba_seqs *reads, const pba_seqs *reads_rc,

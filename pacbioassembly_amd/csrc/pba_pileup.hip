@@ -347,8 +347,8 @@ static int pile_vote_batches(pba_ctx *ctx, pba_pileup *p, const pba_seqs *A, con
     for (int s = 0; s < 2; ++s) {
         if (pairs[s].empty()) continue;
         out.resize(pairs[s].size());
-        const int st = trace_batch(ctx, A, s ? rc : fwd, pairs[s].data(), pairs[s].size(), R, 0, 0, PBA_KERNEL_BITVEC, out.data(), nullptr,
-                                   nullptr, nullptr, &into, overlap_min);
+        const int st = trace_batch(ctx, A, s ? rc : fwd, pairs[s].data(), pairs[s].size(), R, 0, 0, PBA_KERNEL_BITVEC, out.data(),
+                                   TraceInto::votes(into, overlap_min));
         if (st != PBA_OK) {
             // PBA_E_TOOLONG / PBA_E_INVALID come from the plan and the pair checks, before any launch.  Anything else may have
             // left votes behind, and so has an earlier batch of this call: the boxes no longer say which rows they hold.

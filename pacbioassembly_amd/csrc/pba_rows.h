@@ -1,0 +1,125 @@
+// pba_rows.h -- the host side the bounded-slot outlets of the traced pass share (pba_cigar.hip: runs, T = uint32_t;
+// pba_windows.hip: per-window counts, T = pba_aln_counts): one batch of slots through trace_batch, and the chunk loop of the
+// row-level entry points.  (The script walker and the row layout need no device: aln_rows.h.)
+#ifndef PBA_ROWS_H
+#define PBA_ROWS_H
+
+#include <type_traits>
+
+#include "aln_rows.h"
+#include "pba_host.h"
+
+// The device side of a batch of slots: slot q = [off[q], off[q + 1]) of `slot`, n[q] elements in it.
+struct SlotBufs { DevBuf slot, off, n, counts, pflags; };
+
+// Slots on the device, the batch through trace_batch, counts and results back on the host (synchronised); the elements stay
+// on the device.  extra: run_max (runs) or W (windows), and the flags of every pair where pair_flags is null.  Every count is
+// held to its slot: the sinks never write beyond one, so a bound that does not hold surfaces here as PBA_E_HIP.
+template <class T>
+static int slots_run(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R, int maxn, int maxm,
+                     SlotsInto extra, const uint32_t *pair_flags, const uint64_t *rel_off /* n + 1, from 0 */, pba_result *out,
+                     int32_t *have, pba_aln_counts *counts, SlotBufs &d) {
+    constexpr bool windows = std::is_same<T, pba_aln_counts>::value;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipMalloc(&d.slot.p, sizeof(T) * (rel_off[n] + (windows ? 1 : 16))));
+    HIPCHK(hipMalloc(&d.off.p, sizeof(uint64_t) * (n + 1)));
+    HIPCHK(hipMalloc(&d.n.p, sizeof(int32_t) * n));
+    HIPCHK(hipMalloc(&d.counts.p, sizeof(pba_aln_counts) * n));
+    HIPCHK(hipMemcpyAsync(d.off.p, rel_off, sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemsetAsync(d.n.p, 0, sizeof(int32_t) * n, ctx->stream));
+    HIPCHK(hipMemsetAsync(d.counts.p, 0, sizeof(pba_aln_counts) * n, ctx->stream));
+    if (pair_flags) {
+        HIPCHK(hipMalloc(&d.pflags.p, sizeof(uint32_t) * n));
+        HIPCHK(hipMemcpyAsync(d.pflags.p, pair_flags, sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream));
+    }
+    extra.slot = d.slot.p; extra.off = d.off.as<uint64_t>(); extra.n = d.n.as<int32_t>(); extra.counts = d.counts.as<pba_aln_counts>();
+    extra.pair_flags = d.pflags.as<uint32_t>();
+    PBA_TRY(trace_batch(ctx, A, B, pairs, n, R, maxn, maxm, PBA_KERNEL_BITVEC, out, windows ? TraceInto::windows(extra) : TraceInto::runs(extra)));
+    HIPCHK(hipMemcpyAsync(have, d.n.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(counts, d.counts.p, sizeof(pba_aln_counts) * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (size_t q = 0; q < n; ++q)
+        if (have[q] < 0 || (uint64_t)have[q] > rel_off[q + 1] - rel_off[q]) {
+            char pair[96];
+            if (windows) snprintf(pair, sizeof pair, "a_pos %d, a_len %d, b_len %d", pairs[q].a_pos, pairs[q].a_len, pairs[q].b_len);
+            else snprintf(pair, sizeof pair, "a_len %d, b_len %d", pairs[q].a_len, pairs[q].b_len);
+            snprintf(ctx->err, sizeof ctx->err, "pair %llu (%s) has %d %s, its slot holds %llu: the %s bound does not hold", (unsigned long long)q,
+                     pair, have[q], windows ? "windows" : "runs", (unsigned long long)(rel_off[q + 1] - rel_off[q]), windows ? "window" : "run");
+            return PBA_E_HIP;
+        }
+    return PBA_OK;
+}
+
+// What a finished batch of a chunk hands on: its device arrays, its pairs' slots (rel, from 0) and counts, and which job of
+// `jobs` pair q is (jobs[at[q]]).
+struct SlotBatch { const SlotBufs *d; size_t nb; const uint64_t *rel; const int32_t *have; const size_t *at; };
+
+// The rows driver: the jobs (in row order) in chunks whose bounded slots (bound(pair) each) stay under max_slots, each chunk as
+// up to two batches (A[s] against B[s]), every pair held to its row; `sink` takes each finished batch while its elements are on
+// the device.  extra: W for windows.  drop_flags: PBA_CIG_* taken out of every job's flags.  (bound is called twice a row, a
+// million times for a set of 100 k reads: a template parameter, so that it inlines.)
+template <class T, class Bound>
+static int rows_chunks(pba_ctx *ctx, const char *who, const pba_seqs *const A[2], const pba_seqs *const B[2], const std::vector<RowJob> &jobs,
+                       double R, Bound bound, SlotsInto extra, uint32_t drop_flags,
+                       pba_aln_counts *counts, pba_result *res, uint64_t max_slots, uint32_t *n_chunks,
+                       const std::function<int(const SlotBatch &)> &sink) {
+    std::vector<pba_pair> pairs;
+    std::vector<uint32_t> pflags;
+    std::vector<size_t> at;
+    std::vector<uint64_t> rel;
+    std::vector<pba_result> out;
+    std::vector<int32_t> have;
+    std::vector<pba_aln_counts> cnt;
+    for (size_t j0 = 0; j0 < jobs.size();) {
+        size_t j1 = j0;
+        uint64_t slots = 0;
+        while (j1 < jobs.size()) {                      // greedy take: at least one row
+            const uint64_t b = bound(jobs[j1].pr);
+            if (j1 > j0 && slots + b > max_slots) break;
+            slots += b; ++j1;
+        }
+        if (n_chunks) ++*n_chunks;
+        for (int s = 0; s < 2; ++s) {
+            pairs.clear(); pflags.clear(); at.clear(); rel.assign(1, 0);
+            extra.run_max = 0;
+            for (size_t j = j0; j < j1; ++j) {
+                if (jobs[j].batch != s) continue;
+                const uint64_t b = bound(jobs[j].pr);
+                pairs.push_back(jobs[j].pr); pflags.push_back(jobs[j].flags & ~drop_flags); at.push_back(j);
+                rel.push_back(rel.back() + b);
+                extra.run_max = std::max(extra.run_max, b);
+            }
+            const size_t nb = pairs.size();
+            if (!nb) continue;
+            out.resize(nb); have.resize(nb); cnt.resize(nb);
+            SlotBufs d;
+            PBA_TRY(slots_run<T>(ctx, A[s], B[s], pairs.data(), nb, R, 0, 0, extra, pflags.data(), rel.data(), out.data(), have.data(),
+                                 cnt.data(), d));
+            for (size_t q = 0; q < nb; ++q) {           // held to the row: the same roles, the same lengths, the same R
+                const RowJob &jb = jobs[at[q]];
+                if (res) res[jb.row] = out[q];
+                if (counts) counts[jb.row] = cnt[q];
+                if (!walk_agrees(out[q], jb.cost, jb.matlen_a, jb.matlen_b)) {
+                    snprintf(ctx->err, sizeof ctx->err,
+                             "%s: row %llu re-runs to rc %d cost %d matlen %d/%d, the row says cost %d matlen %d/%d: not a row of these "
+                             "sets under this R", who, (unsigned long long)jb.row, out[q].rc, out[q].cost, out[q].matlen_a,
+                             out[q].matlen_b, jb.cost, jb.matlen_a, jb.matlen_b);
+                    return PBA_E_INVALID;
+                }
+            }
+            const SlotBatch sb{&d, nb, rel.data(), have.data(), at.data()};
+            PBA_TRY(sink(sb));
+        }
+        j0 = j1;
+    }
+    return PBA_OK;
+}
+
+// the rows of the jobs, for rows_layout
+static inline std::vector<uint64_t> job_rows(const std::vector<RowJob> &jobs) {
+    std::vector<uint64_t> r(jobs.size());
+    for (size_t j = 0; j < jobs.size(); ++j) r[j] = jobs[j].row;
+    return r;
+}
+
+#endif

@@ -1,15 +1,14 @@
 // pba_windows.hip -- per-window alignment counts and rows trimmed where they break (include/pba.h): the host side
-// of the fourth sink of the traced bit-vector pass (align_windows.h: WindowSink, run by k_window_pairs in pba_align.hip through
-// trace_batch), the trim kernel over windows, the host twins of both, and the row-level entry points.
+// of the windows outlet of the traced bit-vector pass (align_windows.h: WindowJob, run by k_window_pairs in pba_align.hip;
+// TraceInto::windows through trace_batch), the trim kernel over windows, the host twins of both, and the row-level entry
+// points.  The slot runner, the chunk loop and the row layout are shared with pba_cigar.hip (pba_rows.h, aln_rows.h).
 // One process per GPU, one pba_ctx per process, one HIP stream per ctx.  Everything that needs the device fails loudly
 // (PBA_E_NODEVICE / PBA_E_HIP): there is no CPU path behind those entry points.
 //
 // A window is one pba_aln_counts.  A pair's slot is sized by pba_windows_bound, the windows its clipped len_a touches; the
 // sink knows n_win from the goal cell, never writes beyond a slot and reports the count, so a wrong bound would surface as
 // PBA_E_HIP here.
-#include "pba_host.h"
-
-#include <functional>
+#include "pba_rows.h"
 
 static const uint32_t kWinFlags = PBA_CIG_REVERSED | PBA_CIG_B_IS_QUERY;
 
@@ -32,59 +31,21 @@ int pba_windows_from_script(const uint8_t *ops, int32_t nedit, const char *a_ele
     if (nedit < 0 || cap < 0 || W < 1 || a_pos < 0 || (flags & ~kWinFlags) || (nedit && (!ops || !a_elems || !b_elems)) || (cap && !win)) return -1;
     const bool swap = (flags & PBA_CIG_B_IS_QUERY) != 0, rev = (flags & PBA_CIG_REVERSED) != 0;
     std::vector<pba_aln_counts> w(1, pba_aln_counts{0, 0, 0, 0});       // origin-first
-    int i = 0, j = 0;
-    for (int32_t k = 0; k < nedit; ++k) {
-        const int e = ops[k] == 2 ? std::max(i - 1, 0) : i;             // INSERT: the a-element before it
-        if (a_backward && a_pos - e < 0) return -1;
+    const bool ok = script_walk(ops, nedit, a_elems, b_elems, swap, [&](uint32_t code, int op, int i, int) {
+        const int e = op == 2 ? std::max(i - 1, 0) : i;                 // INSERT: the a-element before it
+        if (a_backward && a_pos - e < 0) return false;
         const size_t at = (size_t)window_of(a_pos, a_backward, W, e);
         if (at >= w.size()) w.resize(at + 1, pba_aln_counts{0, 0, 0, 0});
-        pba_aln_counts &c = w[at];
-        if (ops[k] == 1) { if (a_elems[i] == b_elems[j]) ++c.n_eq; else ++c.n_x; ++i; ++j; }
-        else if (ops[k] == 2) { if (swap) ++c.n_ins; else ++c.n_del; ++j; }      // INSERT consumes b only
-        else if (ops[k] == 3) { if (swap) ++c.n_del; else ++c.n_ins; ++i; }      // DELETE consumes a only
-        else return -1;
-    }
+        aln_count(w[at], code);
+        return true;
+    });
+    if (!ok) return -1;
     const size_t nw = w.size();
     for (size_t x = 0; x < nw && x < (size_t)cap; ++x) win[x] = rev ? w[nw - 1 - x] : w[x];
     return (int)nw;
 }
 
 // ---- one batch -----------------------------------------------------------------------------------------------------------
-// The device side of a batch of windows: slot q = [off[q], off[q + 1]) of win.
-struct WinBufs { DevBuf win, off, nwin, counts, pflags; };
-
-// slots on the device, the batch through trace_batch, counts and results back on the host (synchronised); the windows stay
-static int windows_run(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R, int maxn, int maxm,
-                       int W, uint32_t flags, const uint32_t *pair_flags, const uint64_t *rel_off /* n + 1, from 0 */, pba_result *out,
-                       int32_t *nwin, pba_aln_counts *counts, WinBufs &d) {
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipMalloc(&d.win.p, sizeof(pba_aln_counts) * (rel_off[n] + 1)));
-    HIPCHK(hipMalloc(&d.off.p, sizeof(uint64_t) * (n + 1)));
-    HIPCHK(hipMalloc(&d.nwin.p, sizeof(int32_t) * n));
-    HIPCHK(hipMalloc(&d.counts.p, sizeof(pba_aln_counts) * n));
-    HIPCHK(hipMemcpyAsync(d.off.p, rel_off, sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemsetAsync(d.nwin.p, 0, sizeof(int32_t) * n, ctx->stream));
-    HIPCHK(hipMemsetAsync(d.counts.p, 0, sizeof(pba_aln_counts) * n, ctx->stream));
-    if (pair_flags) {
-        HIPCHK(hipMalloc(&d.pflags.p, sizeof(uint32_t) * n));
-        HIPCHK(hipMemcpyAsync(d.pflags.p, pair_flags, sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream));
-    }
-    const WindowInto into{d.win.as<pba_aln_counts>(), d.off.as<uint64_t>(), d.nwin.as<int32_t>(), d.counts.as<pba_aln_counts>(),
-                          d.pflags.as<uint32_t>(), flags, W};
-    PBA_TRY(trace_batch(ctx, A, B, pairs, n, R, maxn, maxm, PBA_KERNEL_BITVEC, out, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &into));
-    HIPCHK(hipMemcpyAsync(nwin, d.nwin.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(counts, d.counts.p, sizeof(pba_aln_counts) * n, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (size_t q = 0; q < n; ++q)
-        if (nwin[q] < 0 || (uint64_t)nwin[q] > rel_off[q + 1] - rel_off[q]) {
-            snprintf(ctx->err, sizeof ctx->err, "pair %llu (a_pos %d, a_len %d, b_len %d) has %d windows, its slot holds %llu: the window bound does not hold",
-                     (unsigned long long)q, pairs[q].a_pos, pairs[q].a_len, pairs[q].b_len, nwin[q],
-                     (unsigned long long)(rel_off[q + 1] - rel_off[q]));
-            return PBA_E_HIP;
-        }
-    return PBA_OK;
-}
-
 static inline uint64_t pair_windows_bound(const pba_pair &p, double R, int W) {
     return pba_windows_bound(p.a_pos, p.a_len, p.b_len, R, W, (p.flags & PBA_A_BACKWARD) != 0);
 }
@@ -110,11 +71,13 @@ int pba_align_batch_windows(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, 
         rel[q + 1] = win_off[q + 1] - win_off[0];
     }
     if (rel[n] && !win) return PBA_E_INVALID;
-    WinBufs d;
-    PBA_TRY(windows_run(ctx, A, B, pairs, n, R, maxn, maxm, W, flags, nullptr, rel.data(), out, nwin, counts, d));
+    SlotBufs d;
+    SlotsInto extra{};
+    extra.flags = flags; extra.W = W;
+    PBA_TRY(slots_run<pba_aln_counts>(ctx, A, B, pairs, n, R, maxn, maxm, extra, nullptr, rel.data(), out, nwin, counts, d));
     // only what a pair has goes to the caller's array: the rest of a slot, and the slot of a failing pair, stay untouched
     std::vector<pba_aln_counts> h(rel[n] + 1);
-    HIPCHK(hipMemcpyAsync(h.data(), d.win.p, sizeof(pba_aln_counts) * rel[n], hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(h.data(), d.slot.p, sizeof(pba_aln_counts) * rel[n], hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     for (size_t q = 0; q < n; ++q)
         if (nwin[q]) memcpy(win + win_off[q], h.data() + rel[q], sizeof(pba_aln_counts) * (size_t)nwin[q]);
@@ -254,93 +217,32 @@ int pba_windows_trim(pba_ctx *ctx, const pba_aln_counts *win, const uint64_t *wi
 // ---- rows ----------------------------------------------------------------------------------------------------------------
 static const uint64_t kWinChunkSlots = 1ull << 26;      // bounded window slots of one chunk of rows on the device (1 GiB)
 
-// What a finished batch of a chunk hands on: its device arrays, its pairs' slots (rel, from 0) and counts, and which job of
-// `jobs` pair q is (jobs[at[q]]).
-struct WinBatch { const WinBufs *d; size_t nb; const uint64_t *rel; const int32_t *nwin; const size_t *at; };
-
-// The rows driver: the jobs (in row order) in chunks whose bounded slots stay under max_slots, each chunk as up to two batches
-// (A[s] against B[s]), every pair held to its row; `sink` takes each finished batch while its windows are on the device.
+// the windows of a chunk loop (pba_rows.h) over the jobs' pairs under W
 static int rows_windows(pba_ctx *ctx, const char *who, const pba_seqs *const A[2], const pba_seqs *const B[2], const std::vector<RowJob> &jobs,
                         double R, int W, uint32_t drop_flags, pba_aln_counts *counts, pba_result *res, uint64_t max_slots, uint32_t *n_chunks,
-                        const std::function<int(const WinBatch &)> &sink) {
-    if (max_slots == 0) max_slots = kWinChunkSlots;
-    std::vector<pba_pair> pairs;
-    std::vector<uint32_t> pflags;
-    std::vector<size_t> at;
-    std::vector<uint64_t> rel;
-    std::vector<pba_result> out;
-    std::vector<int32_t> nwin;
-    std::vector<pba_aln_counts> cnt;
-    for (size_t j0 = 0; j0 < jobs.size();) {
-        size_t j1 = j0;
-        uint64_t slots = 0;
-        while (j1 < jobs.size()) {                      // greedy take: at least one row
-            const uint64_t b = pair_windows_bound(jobs[j1].pr, R, W);
-            if (j1 > j0 && slots + b > max_slots) break;
-            slots += b; ++j1;
-        }
-        if (n_chunks) ++*n_chunks;
-        for (int s = 0; s < 2; ++s) {
-            pairs.clear(); pflags.clear(); at.clear(); rel.assign(1, 0);
-            for (size_t j = j0; j < j1; ++j) {
-                if (jobs[j].batch != s) continue;
-                pairs.push_back(jobs[j].pr); pflags.push_back(jobs[j].flags & ~drop_flags); at.push_back(j);
-                rel.push_back(rel.back() + pair_windows_bound(jobs[j].pr, R, W));
-            }
-            const size_t nb = pairs.size();
-            if (!nb) continue;
-            out.resize(nb); nwin.resize(nb); cnt.resize(nb);
-            WinBufs d;
-            PBA_TRY(windows_run(ctx, A[s], B[s], pairs.data(), nb, R, 0, 0, W, 0u, pflags.data(), rel.data(), out.data(), nwin.data(),
-                                cnt.data(), d));
-            for (size_t q = 0; q < nb; ++q) {           // held to the row: the same roles, the same lengths, the same R
-                const RowJob &jb = jobs[at[q]];
-                if (res) res[jb.row] = out[q];
-                if (counts) counts[jb.row] = cnt[q];
-                if (!walk_agrees(out[q], jb.cost, jb.matlen_a, jb.matlen_b)) {
-                    snprintf(ctx->err, sizeof ctx->err,
-                             "%s: row %llu re-runs to rc %d cost %d matlen %d/%d, the row says cost %d matlen %d/%d: not a row of these "
-                             "sets under this R", who, (unsigned long long)jb.row, out[q].rc, out[q].cost, out[q].matlen_a,
-                             out[q].matlen_b, jb.cost, jb.matlen_a, jb.matlen_b);
-                    return PBA_E_INVALID;
-                }
-            }
-            const WinBatch wb{&d, nb, rel.data(), nwin.data(), at.data()};
-            PBA_TRY(sink(wb));
-        }
-        j0 = j1;
-    }
-    return PBA_OK;
+                        const std::function<int(const SlotBatch &)> &sink) {
+    SlotsInto extra{};
+    extra.W = W;
+    const auto bound = [R, W](const pba_pair &p) -> uint64_t { return pair_windows_bound(p, R, W); };
+    return rows_chunks<pba_aln_counts>(ctx, who, A, B, jobs, R, bound, extra, drop_flags, counts, res, max_slots ? max_slots : kWinChunkSlots,
+                                       n_chunks, sink);
 }
 
-// the windows of the jobs dense and in row order on the host: whole rows only, up to the first that does not fit
+// the windows of the jobs dense and in row order on the host: every job's windows kept until the rows are laid out
 static int rows_windows_out(pba_ctx *ctx, const char *who, const pba_seqs *const A[2], const pba_seqs *const B[2],
                             const std::vector<RowJob> &jobs, uint64_t n_rows, double R, int W, pba_aln_counts *win, uint64_t cap,
                             uint64_t *win_off, uint64_t *n_slots, pba_aln_counts *counts, pba_result *res, uint64_t max_slots) {
-    // every job's count first (win_off is complete whatever fits), its windows kept per job until the rows are laid out
     std::vector<std::vector<pba_aln_counts>> of(jobs.size());
     std::vector<pba_aln_counts> h;
-    const auto sink = [&](const WinBatch &b) -> int {
+    const auto sink = [&](const SlotBatch &b) -> int {
         h.resize(b.rel[b.nb] + 1);
-        HIPCHK(hipMemcpyAsync(h.data(), b.d->win.p, sizeof(pba_aln_counts) * b.rel[b.nb], hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(h.data(), b.d->slot.p, sizeof(pba_aln_counts) * b.rel[b.nb], hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        for (size_t q = 0; q < b.nb; ++q) of[b.at[q]].assign(h.begin() + (ptrdiff_t)b.rel[q], h.begin() + (ptrdiff_t)(b.rel[q] + (uint64_t)b.nwin[q]));
+        for (size_t q = 0; q < b.nb; ++q) of[b.at[q]].assign(h.begin() + (ptrdiff_t)b.rel[q], h.begin() + (ptrdiff_t)(b.rel[q] + (uint64_t)b.have[q]));
         return PBA_OK;
     };
     PBA_TRY(rows_windows(ctx, who, A, B, jobs, R, W, 0u, counts, res, max_slots, nullptr, sink));
-    std::vector<uint32_t> row_n(n_rows, 0);
-    uint64_t pos = 0;
-    bool fits = true;
-    for (size_t j = 0; j < jobs.size(); ++j) {
-        const std::vector<pba_aln_counts> &r = of[j];
-        row_n[jobs[j].row] = (uint32_t)r.size();
-        if (fits && pos + r.size() <= cap) { if (!r.empty()) memcpy(win + pos, r.data(), sizeof(pba_aln_counts) * r.size()); }
-        else fits = false;
-        pos += r.size();
-    }
-    win_off[0] = 0;
-    for (uint64_t k = 0; k < n_rows; ++k) win_off[k + 1] = win_off[k] + row_n[k];
-    *n_slots = win_off[n_rows];
+    rows_layout(of, job_rows(jobs), n_rows, win, cap, win_off, n_slots);
     return PBA_OK;
 }
 
@@ -416,12 +318,12 @@ int pba_overlap_rows_trim_budget(pba_ctx *ctx, const pba_seqs *reads, const pba_
     for (int k = 0; k < 3; ++k) HIPCHK(hipEventCreate(&ev[k]));
     HIPCHK(hipEventRecord(ev[0], ctx->stream));         // (a chunk's traced pass runs from the end of the trim before it)
     std::vector<pba_trim_span> spans;
-    const auto sink = [&](const WinBatch &b) -> int {
+    const auto sink = [&](const SlotBatch &b) -> int {
         DevBuf d_spans;
         HIPCHK(hipMalloc(&d_spans.p, sizeof(pba_trim_span) * b.nb));
         HIPCHK(hipEventRecord(ev[1], ctx->stream));
-        hipLaunchKernelGGL(k_trim_rows, dim3((uint32_t)b.nb), dim3(PBA_WAVE), 0, ctx->stream, b.d->win.as<pba_aln_counts>(),
-                           b.d->off.as<uint64_t>(), b.d->nwin.as<int32_t>(), (uint32_t)b.nb, d_thr.as<int32_t>(), thr_max, min_span,
+        hipLaunchKernelGGL(k_trim_rows, dim3((uint32_t)b.nb), dim3(PBA_WAVE), 0, ctx->stream, b.d->slot.as<pba_aln_counts>(),
+                           b.d->off.as<uint64_t>(), b.d->n.as<int32_t>(), (uint32_t)b.nb, d_thr.as<int32_t>(), thr_max, min_span,
                            d_spans.as<pba_trim_span>());
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ev[2], ctx->stream));

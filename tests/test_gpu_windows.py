@@ -14,7 +14,9 @@ from conftest import MASK_PAT
 from map_ref import many_contig_case, rc
 from pacbioassembly_amd import engine as eng
 from pacbioassembly_amd.engine import ALN_COUNTS_DTYPE, PAIR_DTYPE, RESULT_DTYPE, STRAND_OVERLAP_DTYPE, TRIM_ROW_DTYPE, PbaError
+from test_align_rings_cpu import EDGE_R, excursion_case, must_redo
 from test_cigar_cpu import overlap_case
+from test_gpu_align_rings import EDGE_ROWS, forced
 from test_gpu_parity import check_result
 
 pytestmark = pytest.mark.gpu
@@ -41,7 +43,7 @@ def batch_of(cases, W, seed=1):
     return B
 
 
-def raw_windows(ctx, S, pairs, W, flags, slack=2, off=None):
+def raw_windows(ctx, S, pairs, W, flags, slack=2, off=None, R=R):
     """pba_align_batch_windows over slots of the bound + slack, prefilled: (status, results, windows, offsets, nwin, counts)"""
     n = pairs.size
     if off is None:
@@ -187,6 +189,61 @@ def test_batch_refusals(ctx):
     assert ctx.lib.pba_align_batch_windows(ctx.h, N.h, S.h, pairs.ctypes.data, n, R, 0, 0, 16, 0, out.ctypes.data, win.ctypes.data,
                                            off.ctypes.data, nwin.ctypes.data, counts.ctypes.data) == -6
     assert ctx.lib.pba_align_batch_windows(ctx.h, S.h, S.h, None, 0, R, 0, 0, 16, 0, None, None, None, None, None) == 0      # no pairs
+
+
+# ----------------------------------------------------------------------------- every ring, and the re-run
+RING_W = 37                                                      # does not divide 64: the window boundaries fall on varying lanes
+
+
+def check_rings(ctx, oracle, B, R):
+    """k_window_pairs over the batches test_gpu_cigar.py runs through k_cigar_pairs: every successful pair's windows equal
+    windows_ref of the oracle's script under W = 37, origin-first with default names and goal-first with b as the query; the
+    rest of every slot keeps its sentinel, a failing pair's whole slot does, counts is the windows' total.  The profile of
+    each of the two calls."""
+    S = ctx.seqs_from_list(B.seqs, strict_acgt=True)
+    pairs = np.array(B.pairs, PAIR_DTYPE)
+    exp = ar.expected(oracle, B, R)                              # once, for both calls
+    profs = []
+    for flags in (0, cr.REVERSED | cr.B_IS_QUERY):
+        st, out, win, off, nwin, counts = raw_windows(ctx, S, pairs, RING_W, flags, R=R)
+        assert st == 0, ctx.lib.pba_ctx_error(ctx.h).decode()
+        profs.append(ctx.last_profile())
+        for q, x in enumerate(exp):
+            tag = (B.meta[q]["tag"], flags)
+            check_result(out[q], x, tag)
+            o0, o1 = int(off[q]), int(off[q + 1])
+            if x["rc"] < 0:
+                assert nwin[q] == 0 and all((win[f][o0:o1] == SENTINEL).all() for f in wr.CNT) and tuple(counts[q]) == (0, 0, 0, 0), tag
+                continue
+            a, b = B.elems(q)
+            want = wr.from_script(x["ops"], a, b, B.pairs[q][1], bool(B.pairs[q][6] & 1), RING_W, flags)
+            assert int(nwin[q]) == len(want), (tag, int(nwin[q]), len(want))
+            got = [tuple(int(v) for v in w) for w in win[o0:o0 + len(want)]]
+            assert got == [wr.tup(w) for w in want], (tag, got, want)
+            assert all((win[f][o0 + len(want):o1] == SENTINEL).all() for f in wr.CNT), tag
+            assert tuple(int(v) for v in counts[q]) == wr.tup(wr.total(want)), tag
+    return profs
+
+
+@pytest.mark.parametrize("row", EDGE_ROWS)
+def test_every_ring(ctx, oracle, row):
+    """k_window_pairs<nb1> on the edge set built for that ring, behind its pilot"""
+    for prof in check_rings(ctx, oracle, forced(row, ar.edge_pairs(row[0], EDGE_R)), EDGE_R):
+        assert prof["nb_first"] == row[0]
+
+
+def test_rerun_excursions(ctx, oracle):
+    B, w, wl = excursion_case()
+    need = len(must_redo(ar.expected(oracle, B, ar.EXC_R), B.meta, w, wl))
+    for prof in check_rings(ctx, oracle, B, ar.EXC_R):
+        assert prof["nb_first"] == 1 and prof["nb_redo"] == 2 and prof["n_redo"] >= need
+
+
+@pytest.mark.parametrize("row", sorted(ar.WIDE))
+def test_rerun_reference_band(ctx, oracle, row):
+    B, R = ar.wide_pairs(row)
+    for prof in check_rings(ctx, oracle, B.subset([0]), R):
+        assert prof["nb_redo"] == row[1] and prof["n_redo"] == 1
 
 
 # ----------------------------------------------------------------------------- the trim kernel
