@@ -45,6 +45,8 @@
 
 #include <limits.h>
 
+#include <type_traits>
+
 #include "align_rowsweep.h"
 #include "dev_common.h"
 #include "text_ring.h"
@@ -132,6 +134,24 @@ __device__ __forceinline__ uint32_t eq_mask(uint32_t a, uint32_t b, uint32_t c) 
     asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x09" : "=v"(d) : "v"(a), "v"(b), "v"(c));   // ~0xF0 & ~(0xCC ^ 0xAA)
     return d;
 }
+// a wave-uniform 64-bit value the compiler does not know to be one, back in a scalar register pair
+__device__ __forceinline__ uint64_t bv_uniform64(uint64_t x) {
+    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x) |
+           (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(x >> 32)) << 32;
+}
+// a | ~b and a & b of two lane masks, on the scalar unit whatever the compiler thinks of their uniformity: as plain C++ the
+// masked carries of the streamed trace form's step loop (a divergent store inside it) are kept in vector register pairs,
+// rotated there, and handed to v_addc_co_u32 as its carry-in, which takes none.  Every place that forms hpm / hnm uses these.
+__device__ __forceinline__ uint64_t bv_orn2(uint64_t a, uint64_t b) {
+    uint64_t d;
+    asm("s_orn2_b64 %0, %1, %2" : "=s"(d) : "s"(a), "s"(b) : "scc");
+    return d;
+}
+__device__ __forceinline__ uint64_t bv_and2(uint64_t a, uint64_t b) {
+    uint64_t d;
+    asm("s_and_b64 %0, %1, %2" : "=s"(d) : "s"(a), "s"(b) : "scc");
+    return d;
+}
 // sign-extended bit k of x (k wave-uniform): 0 or ~0
 __device__ __forceinline__ uint32_t bit_mask(uint32_t x, int k) {
     uint32_t d;
@@ -209,22 +229,23 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
 
     // The event schedule.  Nothing in it depends on the data: superblock s lives in lane s & 63, and each kind of event
     // falls at a step that is a function of (s, m, nr, w, wleft) alone, strictly increasing in s -- at most one event of
-    // a kind per step.  So the schedule is five wave-uniform timers, each with the superblock it fires for, advanced
+    // a kind per step.  So the schedule is three wave-uniform timers, each with the superblock it fires for, advanced
     // with scalar arithmetic in the handler; no lane carries a timer and the step loop tests nothing.
     //   open  (s): max(1, s*RB + 1 - wleft) + s             the window of superblock s opens: Pv = ~0, Mv = 0
-    //   close (s): min(m, s*RB + RB + w) + s + 1            first step after the window: the lane moves on to s + 64
-    //   hin   (s): close(s) + 1                             lane (s+1) & 63 stops taking this lane's hout: during step
-    //                                                       close(s) it still takes the one of step close(s) - 1, the
-    //                                                       last of the window.  A scalar bit operation, no lane involved
-    //   diag  (s): s*(RB+1) + 1, while s*RB < m             the diagonal enters the superblock's first row
+    //   close (s): min(m, s*RB + RB + w) + s + 1            first step after the window: the lane moves on to s + 64,
+    //                                                       and from this step on its hout is no window cell (`live`)
     //   seg      : i + s + 1 for rows i = 32, 64, .., m     the 32-row diagonal segment ending at row i (of superblock
-    //                                                       s = (i-1)/RB) was completed by the step before
+    //                                                       s = (i-1)/RB) was completed by the step before.  Where it
+    //                                                       ends its superblock it also lets the diagonal into the next
+    //                                                       one, which it reaches two steps later (`one`)
+    //   diag  (s): s*(RB+1) + 1, while s*RB < m             the forms without DIAG_FOLD only (below): the diagonal enters
+    //                                                       the superblock's first row
     int T_open = 1, s_op = 0;
     int T_close = min(m, RB + w) + 1, s_cl = 0;
-    int T_hin = INT_MAX, l_hn = 0;               // (armed by each close)
-    int T_diag = 1, s_dg = 0;
+    int T_diag = 1, s_dg = 0;                    // (the forms without DIAG_FOLD, below)
     int T_seg = min(32, m) + 1, s_sg = 0;
-    int s_next = 1;                              // the earliest of the five
+    int s_next = 1;                              // the earliest of them
+    (void)T_diag; (void)s_dg;
     // Which superblock a lane holds, and whether its window is open, belong to the schedule too: a lane moves on to s + 64
     // when superblock s closes, closes fire in the order of s, so the lanes hold s_cl .. s_cl + 63; the open windows are those
     // of s_cl .. s_op - 1.  The RING forms keep neither in a vector register: the few places that ask (a chunk's start, the
@@ -236,15 +257,27 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
 #define PBA_BV_LANE_OPEN() (LANE_SB ? opened != 0 : PBA_BV_LANE_SB() < s_op)
     // Where the diagonal is: at any step it is in one block of one lane, or in none (the one-step gap between two
     // superblocks, and past row m).  Both are wave-uniform and belong to the schedule: `one` is the one-hot of the diagonal
-    // cell's bit in its block's word (0: in no block), qd that block.  The diagonal-entry event and segment_done set them; the
-    // step shifts `one` on the scalar side.
-    uint32_t one = 0;
+    // cell's bit in its block's word, qd that block.  `one` is 64 bits wide and the block's word is its HIGH half: bit 32 + r
+    // is row r of the block, and the step's one scalar shift moves it a row down.  segment_done sets both: a segment that
+    // ends inside its superblock re-arms bit 32; one that ends its superblock (rows left) arms bit 31 -- the gap step between
+    // the two superblocks, in which the high half is 0 and nothing collects, shifts it to bit 32, and the first row of the
+    // next superblock collects at bit 0 of its word; the segment holding row m leaves 0.  Superblock 0 is entered in front of
+    // the loop.  There is no diagonal-entry event.
+    // DIAG_FOLD: not with six blocks per lane -- the pair of registers `one` travels in between stretches takes k_locate<6>
+    // from 80 to 84 vector registers, a wave per SIMD.  That ring keeps the 32-bit one-hot and
+    // the diagonal-entry event of the LANE_HOT form (T_diag).
+    constexpr bool DIAG_FOLD = !BAIL && NB != 6;
+    constexpr int OH_SH = DIAG_FOLD ? 32 : 0;    // where the block's word sits in `one`
+    typedef typename std::conditional<DIAG_FOLD, uint64_t, uint32_t>::type onehot_t;
+    onehot_t one = DIAG_FOLD ? (onehot_t)1 << OH_SH : 0;
     int qd = 0;
     // Not in the BAIL form (the all-vs-all walk): its candidates are mostly false ones that die within their first segments,
     // on the ramp, where a window opens at every step and a stretch is one step long -- there the scalar one-hot's two
     // instructions per stretch (read in front, written back behind) cost more than the step saves (measured: walk + 4 to 6 %,
     // DESIGN.md 4.3 round 8).  That form keeps the one-hot in the diagonal's lane, advanced by a vector add: dmw.
     constexpr bool LANE_HOT = BAIL;
+    // There the lane below cannot be armed a step early: the add doubles dmw, and no 32-bit value doubles to 1.  That form
+    // keeps its diagonal-entry event (T_diag).
     uint32_t dmw = 0;                            // LANE_HOT: bit of the diagonal cell in its block's word (0: not in this lane)
     (void)dmw; (void)one; (void)qd;
 
@@ -265,9 +298,24 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     // they were live through the whole step loop, and at 64 registers per lane the compiler spilled them to scratch memory.
     fin[2 * NB * PBA_WAVE + lane] = 0xFFFFFFFFu;
     uint64_t hp_last = ~0ull, hn_last = 0ull;    // lane masks: delta +1 / -1 leaving each lane's last block in the previous step
-    // lanes whose first block still receives the lane above's hout (the others see "+1 per column"): lane s & 63 from the
-    // step it takes superblock s (0 < s < S) up to the step before the lane above closes
-    uint64_t valid = (S >= PBA_WAVE ? ~0ull : (1ull << S) - 1ull) & ~1ull;
+    // What a lane hands out is masked, not what a lane takes in.  live: the lanes whose hout of the step just run is a window
+    // cell that the lane below takes; hpm / hnm: that step's carries under it -- "+1 per column", the row above a window,
+    // where the bit is clear -- which the next step rotates one lane up.
+    // Derivation, from the taking side: let valid(t) bit k say that lane k's first block takes lane k - 1's hout of step
+    // t - 1 at step t.  It holds for lane s & 63 from the step it takes superblock s (0 < s < S) through step close(s - 1),
+    // whose column is the last of the window above.  live after step t is valid(t + 1) rotated one lane down:
+    //   * at the start valid is lanes 1 .. min(S, 64) - 1 (lane 0's superblock 0 has the top border above it, and the lanes
+    //     >= S hold nothing), so live is lanes 0 .. min(S, 64) - 2;
+    //   * lane s & 63 hands out its last window cell in step close(s) - 1, taken at step close(s): its bit is cleared by
+    //     the close event itself, which runs in front of step close(s) and so first masks that step's carries;
+    //   * lane (s - 1) & 63, which holds superblock s + 63 by then, hands out to superblock s + 64 from the step lane s & 63
+    //     takes that superblock, close(s): its bit is set there when s + 64 < S, and this one must already hold for the
+    //     carries of step close(s) - 1 -- the window of s + 64 may open at close(s) itself (bv_max_span) and take them.
+    //     They are still at hand unmasked (hp_last / hn_last), so the event forms hpm / hnm again under the new bit, then
+    //     clears its own.  (When s + 64 >= S the bit stays as close(s - 1) left it: clear.)
+    // hp_last / hn_last stay the raw carries of the step: what a checkpoint holds (bv_ckpt_store, bitvec_rerun).
+    uint64_t live = (S >= PBA_WAVE ? ~0ull : (1ull << S) - 1ull) >> 1;
+    uint64_t hpm = ~0ull, hnm = 0ull;
 
     // text planes for the 32 steps starting at the wave-uniform step tb (element of step t is t - 1 - the lane's superblock)
     // RING: the wavefront fetches the chunk's 32 new elements once and every lane writes one cell -- lanes 0..31
@@ -294,7 +342,8 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     // result is a scalar condition.  What is left for the lane: its acc[] cleared.  The one-hot is re-armed on the scalar side.
     // Every lane ORs D0 bits into its acc[qd] under the wave's one-hot, whether the diagonal is in it or not; only acc[q] of
     // lane s & 63 is ever read, here.  That is harmless only because a lane's acc[] is cleared when the diagonal enters the
-    // lane (the diagonal-entry event) and at every segment end (below): both clears must stay.
+    // lane (below, at the segment end in front of it; without DIAG_FOLD: the diagonal-entry event) and at every segment
+    // end: both clears must stay.
     // Returns 0, or the first failing row (PBA_BV_BAIL: the sweep is given up); a sweep ends at its first failure, so
     // no segment is judged after one.
     auto segment_done = [&](int s, int i) -> int {
@@ -320,17 +369,21 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
                 ((float)end - 4.0f * __builtin_sqrtf((float)end)) * (float)m > (float)i * (float)bail_w) fr = PBA_BV_BAIL;
         }
         score = end;                                     // D(i,i): the next segment starts from it, in whichever lane
-        if (lane == L) {
+        // the diagonal leaves this lane's rows for the lane below (its word is cleared here, one step early: nothing
+        // collects in the gap step), or enters this lane's next block at bit 0
+        const bool leaves = rr == RB - 1 && i != m;
+        if (lane == L || (DIAG_FOLD && leaves && lane == ((s + 1) & (PBA_WAVE - 1)))) {
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) acc[nb] = 0; // the next block's word starts clean
-            if constexpr (LANE_HOT) dmw = (i == m || rr == RB - 1) ? 0u : 1u;   // (as `one` below)
+            if constexpr (LANE_HOT) dmw = (i == m || rr == RB - 1) ? 0u : 1u;
         }
-        one = (i == m || rr == RB - 1) ? 0u : 1u;        // the diagonal leaves this lane's rows, or enters its next block at bit 0
-        qd = (q + 1) % NB;
+        if constexpr (DIAG_FOLD) one = i == m ? 0 : (onehot_t)1 << (leaves ? OH_SH - 1 : OH_SH);
+        else one = (i == m || rr == RB - 1) ? 0u : 1u;
+        qd = (q + 1) % NB;                               // (0 where the diagonal leaves the superblock)
         return fr;
     };
 
-    // The events due at step t (== s_next), before the step runs: segment end, close / move on, open, diagonal entry.
+    // The events due at step t (== s_next), before the step runs: segment end, close / move on, open (without DIAG_FOLD: diagonal entry).
     // DIAG: phase 1 (the diagonal is still being swept).  Sets seg_fail when a segment's check failed.
 #define PBA_BV_EVENTS(DIAG)                                                           \
     {                                                                                 \
@@ -340,7 +393,6 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
             if (i == m) T_seg = INT_MAX;                                              \
             else { s_sg = s + (i == s * RB + RB ? 1 : 0); T_seg = min(i + 32, m) + s_sg + 1; } \
         }                                                                             \
-        if (t == T_hin) { valid &= ~(1ull << l_hn); T_hin = INT_MAX; }                \
         if (t == T_close) {                                                           \
             const int s = s_cl;                                                       \
             if (lane == (s & (PBA_WAVE - 1))) {                                       \
@@ -359,9 +411,13 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
                 if constexpr (RING) ta = ring + txr_addr(t, sn);      /* 64 elements back; they are in the ring */ \
                 else load_text(t - ((t - 1) & 31));                                   \
             }                                                                         \
-            /* this lane takes the lane above's hout again if it has a superblock left; the lane below stops taking this one's a step later */ \
-            T_hin = t + 1; l_hn = (s + 1) & (PBA_WAVE - 1);                           \
-            if (s + PBA_WAVE < S) valid |= 1ull << (s & (PBA_WAVE - 1)); else valid &= ~(1ull << (s & (PBA_WAVE - 1))); \
+            /* the lane above hands out to this lane's next superblock, the carries of the step before included; this \
+               lane's own hout is no window cell from this step on (`live` above) */  \
+            if (s + PBA_WAVE < S) {                                                   \
+                live |= 1ull << ((s - 1) & (PBA_WAVE - 1));                           \
+                hpm = bv_orn2(hp_last, live); hnm = bv_and2(hn_last, live);           \
+            }                                                                         \
+            live &= ~(1ull << (s & (PBA_WAVE - 1)));                                  \
             s_cl = s + 1;                                                             \
             T_close = s_cl < S ? min(m, s_cl * RB + RB + w) + s_cl + 1 : INT_MAX;     \
         }                                                                             \
@@ -373,24 +429,31 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
             s_op += 1;                                                                \
             T_open = s_op < S ? max(1, s_op * RB + 1 - wleft) + s_op : INT_MAX;       \
         }                                                                             \
-        if (DIAG && t == T_diag) {                                                    \
-            if (lane == (s_dg & (PBA_WAVE - 1))) {                                    \
-                _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) acc[nb] = 0;        \
-                if constexpr (LANE_HOT) dmw = 1u;                                      \
+        if constexpr (!DIAG_FOLD) {                                                   \
+            if (DIAG && t == T_diag) {                                                \
+                if (lane == (s_dg & (PBA_WAVE - 1))) {                                \
+                    _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) acc[nb] = 0;    \
+                    if constexpr (LANE_HOT) dmw = 1u;                                 \
+                }                                                                     \
+                one = 1u; qd = 0;                                                     \
+                s_dg += 1;                                                            \
+                T_diag = s_dg * RB < m ? s_dg * (RB + 1) + 1 : INT_MAX;               \
             }                                                                         \
-            one = 1u; qd = 0;                                                         \
-            s_dg += 1;                                                                \
-            T_diag = s_dg * RB < m ? s_dg * (RB + 1) + 1 : INT_MAX;                   \
         }                                                                             \
-        s_next = min(DIAG ? min(min(T_seg, T_diag), min(T_open, T_close)) : min(T_open, T_close), T_hin); \
+        s_next = min(T_open, T_close);                                                \
+        if (DIAG) s_next = min(s_next, DIAG_FOLD ? T_seg : min(T_seg, T_diag));       \
         if constexpr (TRACE == 1) st_on = ((__builtin_amdgcn_ballot_w64(PBA_BV_LANE_OPEN()) >> (lane & 48)) & 0xFFFFull) != 0; \
     }
 
     // hin of each lane's first block: the lane above's hout of the previous step, rotated one lane up, where that
-    // lane was still inside its window; elsewhere the row above the window counts "+1 per column"
+    // hout was a window cell this lane takes; elsewhere the row above the window counts "+1 per column" (`live` above:
+    // masked where it is handed out, PBA_BV_HOUT)
 #define PBA_BV_HIN()                                                                  \
-    uint64_t hp = (((hp_last << 1) | (hp_last >> 63)) & valid) | ~valid;              \
-    uint64_t hn = ((hn_last << 1) | (hn_last >> 63)) & valid;
+    uint64_t hp = (hpm << 1) | (hpm >> 63);                                           \
+    uint64_t hn = (hnm << 1) | (hnm >> 63);
+#define PBA_BV_HOUT()                                                                 \
+    hp_last = hp; hn_last = hn;                                                       \
+    hpm = bv_orn2(hp, live); hnm = bv_and2(hn, live);
 
     // one block update (hp / hn: lane masks of the delta entering at the block's top row, replaced by the one leaving)
     // D0 (bit r set iff D(i,j) == D(i-1,j-1)) doubles as Myers' Xv in the two vertical updates (Hyyro's form of
@@ -446,9 +509,9 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
             /* keep the diagonal cell's D0 bit: in every lane, under the wave's one-hot (what a lane without the diagonal \
                collects is cleared when the diagonal enters it) */                   \
             if constexpr (LANE_HOT) acc[nb] = or_of_and(acc[nb], d0, dmw); else       \
-            if ((QD) < 0 || nb == (QD)) acc[nb] = or_of_and_s(acc[nb], d0, oh);      \
+            if ((QD) < 0 || nb == (QD)) acc[nb] = or_of_and_s(acc[nb], d0, (uint32_t)(oh >> OH_SH)); \
         }                                                                            \
-        hp_last = hp; hn_last = hn;                                                  \
+        PBA_BV_HOUT()                                                                \
         /* next row of the block, on the scalar side; re-armed every 32 rows.  (LANE_HOT: a full-rate add the compiler cannot \
            turn back into the slower shift) */                                       \
         if constexpr (LANE_HOT) asm("v_add_u32 %0, %1, %1" : "=v"(dmw) : "v"(dmw)); else oh <<= 1; \
@@ -500,7 +563,9 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
         // Not in the streamed trace form, where the second copy costs k_trace_pairs<2, false> a wave per SIMD, and not for
         // NB >= 3, where the copies cost registers or scratch in every kernel: there every block's
         // word collects under the scalar one-hot.
-        uint32_t oh = LANE_HOT ? 0u : __builtin_amdgcn_readfirstlane(one);
+        onehot_t oh = 0;
+        if constexpr (DIAG_FOLD) oh = (onehot_t)bv_uniform64(one);
+        else if constexpr (!LANE_HOT) oh = __builtin_amdgcn_readfirstlane(one);
         if constexpr (NB == 2 && TRACE != 1 && !LANE_HOT) {
             if (__builtin_amdgcn_readfirstlane(qd) == 0) { PBA_BV_STRETCH1(0); } else { PBA_BV_STRETCH1(1); }
         } else {
@@ -511,7 +576,10 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     }
     if (fail_row == 0) fail_row = segment_done(s_m, m);   // the segment that ended in the last step: the one holding row m
     if (fail_row) return __builtin_amdgcn_readfirstlane(fail_row);
-    s_next = min(min(T_open, T_close), T_hin);   // the diagonal is done: what is left opens and closes windows
+    s_next = min(T_open, T_close);               // the diagonal is done: what is left opens and closes windows
+    // (Formed again from the raw carries rather than carried over: phase 1's loop has an early exit, and the compiler takes
+    // what that loop leaves behind for divergent -- two values fewer to bring back to the scalar side.)
+    hpm = bv_orn2(hp_last, live); hnm = bv_and2(hn_last, live);
 
     // ------------------------------------------------------------------ phase 2: the superblocks below row m take the last column
     for (int tb = t1 + 1; tb <= t_end;) {
@@ -545,7 +613,7 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
                     PBA_BV_TRP()[nb * 64] = make_uint2(eq | ~d0, swap_roles ? Pv[nb] : php);
             }
         }
-        hp_last = hp; hn_last = hn;
+        PBA_BV_HOUT()
         if constexpr (RING) ta += 1;
         } while (++k < kstop);
         }
@@ -556,6 +624,7 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
 #undef PBA_BV_TEXT
 #undef PBA_BV_BLOCK
 #undef PBA_BV_TRP
+#undef PBA_BV_HOUT
 #undef PBA_BV_HIN
 #undef PBA_BV_EVENTS
     // ------------------------------------------------------------------ the free end: first strict minimum down the last column
