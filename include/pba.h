@@ -1460,6 +1460,70 @@ int pba_overlap_strands_masked(pba_ctx *ctx, const pba_seqs *reads, const pba_se
 int pba_census_last_stats(const pba_census *c, pba_census_stats *out);
 void pba_census_destroy(pba_census *c);
 
+/* ---- variant sites from pile-ups, and every row's allele at each site ----
+ * A box where a second allele holds a share of the depth is a site: a heterozygous position, or a column where the copies of
+ * a repeat differ.  The rule looks at box i of a target as it stands BEFORE evolve, `weight` the pile-up's:
+ *   N = tot - 1 + weight (pba_qual_phred's N); c[A], c[C], c[G], c[T] = the four sel counters (the target's own base carries
+ *   weight), c[DEL] = N - (c[A] + c[C] + c[G] + c[T]); major = the first maximal allele in the order A, C, G, T, DEL; minor =
+ *   the first maximal allele among the other four; own = the target's own base.
+ * Box i is a selection site (PBA_SITE_SEL) iff N >= min_depth, c[minor] >= min_alt and c[minor] * 1000 >= min_permille * N.
+ * It is a supply site (PBA_SITE_SUP) under the same three tests with max4(sup) in place of c[minor]: its minor is the winning
+ * sup base, n_minor that counter, n_major 0 (major stays the box's major allele).  A box can be both: two records, SEL first.
+ * Alleles are codes 0..3 = A, C, G, T and PBA_ALLELE_DEL.  The limits of the boxes apply unchanged (no counter above 65 535). */
+#define PBA_SITE_SEL 1
+#define PBA_SITE_SUP 2
+#define PBA_ALLELE_DEL 4
+typedef struct { int32_t target, pos; uint8_t kind, own, major, minor; uint32_t n, n_major, n_minor; } pba_site;
+typedef struct pba_sites pba_sites;   /* the sites of a target range, resident on the device, independent of the pile-up */
+/* One flag pass over the flat arena of a live pile-up (20 bytes a box), a scan of the per-word counts, one compaction pass:
+ * the records of targets [t_lo, t_hi) sorted by (target, pos, kind).  `target` is the set the pile-up was made from (the boxes
+ * keep no text: own is read from it; another count or other lengths: PBA_E_INVALID).  The pile-up is only read: dump and evolve
+ * afterwards give what they gave before.  A spent pile-up, min_depth < 1, min_alt < 1 or min_permille outside [0, 1000]:
+ * PBA_E_INVALID, nothing is made.  The object owns its arrays and survives the pile-up's evolve and destroy. */
+int pba_pileup_sites(pba_ctx *ctx, const pba_pileup *p, const pba_seqs *target, int min_depth, int min_alt, int min_permille,
+                     pba_sites **out);
+/* The same object from a caller's list for the sequences [t_lo, t_hi) of seqs (known sites; pba_qual_create's counterpart).
+ * Checked on the host: sorted strictly by (target, pos, kind), targets in the range, positions inside their sequences, kind
+ * SEL or SUP, own and a SUP's minor 0..3, major and a SEL's minor 0..4; else PBA_E_INVALID and no object.  2^32 sites or more:
+ * PBA_E_TOOLONG.  n == 0 is legal. */
+int pba_sites_create(pba_ctx *ctx, const pba_seqs *seqs, uint32_t t_lo, uint32_t t_hi, const pba_site *recs, uint64_t n, pba_sites **out);
+uint64_t pba_sites_count(const pba_sites *s);
+/* records [*lo, *hi) are target's; a target outside the range: PBA_E_INVALID */
+int pba_sites_target_range(const pba_sites *s, uint32_t target, uint64_t *lo, uint64_t *hi);
+/* records [lo, hi) from the device; lo > hi or hi beyond the count: PBA_E_INVALID */
+int pba_sites_get(pba_ctx *ctx, const pba_sites *s, uint64_t lo, uint64_t hi, pba_site *out);
+void pba_sites_destroy(pba_sites *s);
+
+/* Every row's allele at the SEL sites of its target, from the traceback walk of the row's re-run: no script, no temporary.  a is
+ * the target (the side the boxes belong to): a MATCH gives the row's base (0..3) at the site, a DELETE PBA_ALLELE_DEL; an
+ * INSERT consumes no target base and gives nothing.  A row has exactly one record per SEL site inside the target interval its
+ * path covers, in ascending site order whatever its dir.  SUP sites get NO per-row record (a row can supply one box several
+ * times).  site: index into the object's records.  sum[k]: the row's totals; n_own / n_major / n_minor count the records whose
+ * allele is the site's own / major / minor (own usually is one of the two), n_other those that are neither major nor minor.
+ *   pba_overlap_rows_alleles: the pairs are pba_overlap_row_pair's, every row held to its own cost and matlens (a
+ *     disagreement is PBA_E_INVALID), as pba_overlap_rows_cigar holds it.
+ *   pba_map_rows_alleles: the VOTING roles of a mapped row, pba_map_row_pair's (a = contig), under pba_pileup_vote_mapped's
+ *     gate (rc >= 0 and matlen_a >= overlap_min), not held to the row's cost: the records then match, vote for vote, the boxes
+ *     the sites were read from.  found == 0 rows and rows that miss the gate: no records, zero totals.
+ * off (n + 1 entries) is always complete and *n_total the total; records are copied for the rows, in order, up to the first
+ * row whose end exceeds cap (pba_map_rows_cigar's contract).  `sites` must be made from the target set (count and lengths; else
+ * PBA_E_INVALID) and a row's target must lie in its range.  _budget: max_slots bounded slots per chunk (0: the default). */
+typedef struct { uint32_t site; uint32_t allele; } pba_allele;
+typedef struct { int32_t n_sites, n_own, n_major, n_minor, n_other; } pba_allele_counts;
+int pba_overlap_rows_alleles(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, const pba_strand_overlap *rows, uint64_t n,
+                             double R, const pba_sites *sites, pba_allele *out, uint64_t cap, uint64_t *off, uint64_t *n_total,
+                             pba_allele_counts *sum, pba_result *res);
+int pba_overlap_rows_alleles_budget(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, const pba_strand_overlap *rows,
+                                    uint64_t n, double R, const pba_sites *sites, pba_allele *out, uint64_t cap, uint64_t *off,
+                                    uint64_t *n_total, pba_allele_counts *sum, pba_result *res, uint64_t max_slots);
+int pba_map_rows_alleles(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc, const pba_map_row *rows,
+                         uint64_t n, double R, int overlap_min, const pba_sites *sites, pba_allele *out, uint64_t cap, uint64_t *off,
+                         uint64_t *n_total, pba_allele_counts *sum, pba_result *res);
+int pba_map_rows_alleles_budget(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
+                                const pba_map_row *rows, uint64_t n, double R, int overlap_min, const pba_sites *sites, pba_allele *out,
+                                uint64_t cap, uint64_t *off, uint64_t *n_total, pba_allele_counts *sum, pba_result *res,
+                                uint64_t max_slots);
+
 const char *pba_strerror(int status);
 
 #ifdef __cplusplus

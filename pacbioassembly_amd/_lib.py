@@ -370,6 +370,16 @@ SYMBOLS = {
                                           C.POINTER(_P)]),
     "pba_layout_consensus_qual": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.c_double, C.c_int, C.c_int, C.c_uint64, C.POINTER(_P), _P, _P,
                                             C.c_int, C.POINTER(_P)]),
+    "pba_pileup_sites": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "pba_sites_create": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.POINTER(_P)]),
+    "pba_sites_count": (C.c_uint64, [_P]),
+    "pba_sites_target_range": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "pba_sites_get": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, _P]),
+    "pba_sites_destroy": (None, [_P]),
+    "pba_overlap_rows_alleles": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_double, _P, _P, C.c_uint64, _P, C.POINTER(C.c_uint64), _P, _P]),
+    "pba_overlap_rows_alleles_budget": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_double, _P, _P, C.c_uint64, _P, C.POINTER(C.c_uint64), _P, _P, C.c_uint64]),
+    "pba_map_rows_alleles": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.c_double, C.c_int, _P, _P, C.c_uint64, _P, C.POINTER(C.c_uint64), _P, _P]),
+    "pba_map_rows_alleles_budget": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.c_double, C.c_int, _P, _P, C.c_uint64, _P, C.POINTER(C.c_uint64), _P, _P, C.c_uint64]),
     "pba_strerror": (C.c_char_p, [C.c_int]),
 }
 

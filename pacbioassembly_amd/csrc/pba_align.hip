@@ -62,12 +62,12 @@ k_align_bytes_trace(const uint8_t *a, int a_dir, int la, const uint8_t *b, int b
     store_result(out, o);
 }
 
-// ---- traceback on the bit-vector array: the persistent loop of align_bvtrace.h (trace_pairs_loop) under each of its four
+// ---- traceback on the bit-vector array: the persistent loop of align_bvtrace.h (trace_pairs_loop) under each of its five
 // jobs -- scripts (align_bvtrace.h: ScriptJob), votes (consensus.h: VoteJob), runs (align_cigar.h: CigarJob), per-window counts
-// (align_windows.h: WindowJob).  A kernel is its job's name for the profiler and its launch bounds; the job is its argument.
+// (align_windows.h: WindowJob), alleles at selection sites (align_alleles.h: AlleleJob).  A kernel is its job's name for the profiler and its launch bounds; the job is its argument.
 // CK: the checkpoint form of the traced pass (align_bvtrace.h): scratch holds one checkpoint per 32 steps, the walk re-runs
-// chunks into this wavefront's LDS tile; else every step's parent words are streamed to scratch.  Runs and windows: that
-// form only.
+// chunks into this wavefront's LDS tile; else every step's parent words are streamed to scratch.  Runs, windows and
+// alleles: that form only.
 #ifndef PBA_TR_OCC12
 #define PBA_TR_OCC12 6        // waves per SIMD of the checkpoint-form trace kernels at one or two blocks per lane (tuning hook;
                               // 32 768 reads of BASELINE configs[1], same box: 4 -> 63.0 ms, 5 -> 60.0, 6 -> 50.7, 8 -> 52.3)
@@ -93,6 +93,11 @@ k_cigar_pairs(PBA_TRACED_ARGS, CigarJob job, uint32_t *queue) {
 template <int NB>
 __global__ void __launch_bounds__(PBA_WAVE * 4, NB <= 4 ? (NB <= 2 ? PBA_TR_OCC12 : 4) : 2)
 k_window_pairs(PBA_TRACED_ARGS, WindowJob job, uint32_t *queue) {
+    trace_pairs_loop<NB, true>(A, B, pairs, ids, n, cfg, out, scratch, wave_words, cap_words, job, queue);
+}
+template <int NB>
+__global__ void __launch_bounds__(PBA_WAVE * 4, NB <= 4 ? (NB <= 2 ? PBA_TR_OCC12 : 4) : 2)
+k_allele_pairs(PBA_TRACED_ARGS, AlleleJob job, uint32_t *queue) {
     trace_pairs_loop<NB, true>(A, B, pairs, ids, n, cfg, out, scratch, wave_words, cap_words, job, queue);
 }
 #undef PBA_TRACED_ARGS
@@ -247,6 +252,7 @@ template <int NB> static auto traced_kernel(const VoteJob<false> &, bool ck) { r
 template <int NB> static auto traced_kernel(const VoteJob<true> &, bool) { return k_vote_pairs<NB, true, true>; }
 template <int NB> static auto traced_kernel(const CigarJob &, bool) { return k_cigar_pairs<NB>; }
 template <int NB> static auto traced_kernel(const WindowJob &, bool) { return k_window_pairs<NB>; }
+template <int NB> static auto traced_kernel(const AlleleJob &, bool) { return k_allele_pairs<NB>; }
 template <class Job>
 static void launch_traced(pba_ctx *ctx, const TracedLaunch &t, const Job &job, int nb, const AlignCfg &cfg, const uint32_t *ids,
                           uint32_t cnt, const TracePass &tp) {
@@ -674,6 +680,7 @@ int trace_batch(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pa
             break;
         case TraceInto::RUNS: launch_traced(ctx, t, CigarJob{into.slots}, nb, pl.cfg, ids, cnt, tp); break;
         case TraceInto::WINDOWS: launch_traced(ctx, t, WindowJob{into.slots}, nb, pl.cfg, ids, cnt, tp); break;
+        case TraceInto::ALLELES: launch_traced(ctx, t, AlleleJob{into.slots, into.sites, into.overlap_min}, nb, pl.cfg, ids, cnt, tp); break;
         }
     };
     auto collect = [&](std::vector<uint32_t> &redo) { return fetch_results(ctx, d.out.p, out, n, &redo); };

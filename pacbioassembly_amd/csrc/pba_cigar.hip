@@ -202,8 +202,10 @@ static int rows_cigar_check(pba_ctx *ctx, const char *who, const pba_seqs *reads
     return PBA_OK;
 }
 
-int map_rows_jobs(pba_ctx *ctx, const char *who, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
-                  const pba_map_row *rows, uint64_t n, double R, pba_aln_counts *counts, pba_result *res, std::vector<RowJob> *jobs) {
+// voting: the roles of pba_map_row_pair (a = contig), not held to the row; else pba_map_row_aln_pair's, the walk that found it
+static int map_jobs(pba_ctx *ctx, const char *who, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
+                    const pba_map_row *rows, uint64_t n, double R, pba_aln_counts *counts, pba_result *res, std::vector<RowJob> *jobs,
+                    bool voting) {
     PBA_TRY(rows_cigar_check(ctx, who, reads, reads_rc, target, n, R));
     for (uint64_t k = 0; k < n; ++k) {
         const pba_map_row &r = rows[k];
@@ -214,14 +216,22 @@ int map_rows_jobs(pba_ctx *ctx, const char *who, const pba_seqs *target, const p
         if (r.read < 0 || (uint32_t)r.read >= reads->n) return ctx_fail_as(ctx, PBA_E_INVALID, who, "a row's read is not a read of the set");
         if (r.strand == -1 && !reads_rc) return ctx_fail_as(ctx, PBA_E_INVALID, who, "a strand -1 row needs reads_rc");
         RowJob jb{};
-        const int st = pba_map_row_aln_pair(&r, target->h_len[r.contig], reads->h_len[r.read], R, &jb.pr);
+        const int st = (voting ? pba_map_row_pair : pba_map_row_aln_pair)(&r, target->h_len[r.contig], reads->h_len[r.read], R, &jb.pr);
         if (st == PBA_E_TOOLONG) return ctx_fail_as(ctx, PBA_E_TOOLONG, who, "a row's accessor is longer than the engine limit");
         if (st != PBA_OK) return ctx_fail_as(ctx, PBA_E_INVALID, who, "a row's strand or anchor is not valid for its sequences");
         jb.row = k; jb.flags = 0u; jb.batch = r.strand == 1 ? 0 : 1;
-        jb.cost = r.cost; jb.matlen_a = r.matlen_a; jb.matlen_b = r.matlen_b;
+        jb.cost = r.cost; jb.matlen_a = r.matlen_a; jb.matlen_b = r.matlen_b; jb.not_held = voting ? 1 : 0;
         jobs->push_back(jb);
     }
     return PBA_OK;
+}
+int map_rows_jobs(pba_ctx *ctx, const char *who, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
+                  const pba_map_row *rows, uint64_t n, double R, pba_aln_counts *counts, pba_result *res, std::vector<RowJob> *jobs) {
+    return map_jobs(ctx, who, target, reads, reads_rc, rows, n, R, counts, res, jobs, false);
+}
+int map_rows_vote_jobs(pba_ctx *ctx, const char *who, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
+                       const pba_map_row *rows, uint64_t n, double R, pba_aln_counts *counts, pba_result *res, std::vector<RowJob> *jobs) {
+    return map_jobs(ctx, who, target, reads, reads_rc, rows, n, R, counts, res, jobs, true);
 }
 
 int pba_map_rows_cigar_budget(pba_ctx *ctx, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,

@@ -1,6 +1,6 @@
 // pba_host.h -- host-side objects and helpers shared by the translation units of libpba.so (pba_core.hip: context,
 // sequence sets; pba_index.hip: seed index; pba_align.hip: explicit pairs and edit scripts; pba_drivers.hip: the reference's ordered
-// first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction; pba_stream.hip: streamed locate and mapping; pba_layout.hip: layout; pba_clip.hip: clipping; pba_hpc.hip: homopolymer compression; pba_census.hip: seed-key census; pba_cigar.hip: run-length alignments and PAF; pba_windows.hip: per-window counts and trimmed rows;
+// first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction; pba_stream.hip: streamed locate and mapping; pba_layout.hip: layout; pba_clip.hip: clipping; pba_hpc.hip: homopolymer compression; pba_census.hip: seed-key census; pba_cigar.hip: run-length alignments and PAF; pba_windows.hip: per-window counts and trimmed rows; pba_sites.hip: variant sites and per-row alleles;
 // pba_fastx.hip: FASTA / FASTQ in, FASTA out; pba_qual.hip: per-base evidence, its summaries and spans, FASTQ out).  Internal: nothing here is part of the C ABI (include/pba.h).
 // (What host and device share about the seed index -- the visiting rule, compress / compress_masks -- is index_plan.h's.)
 // Also here, once for all of them: the clip of seq_aligner.h:94-102 (text_clip), the launch plan (make_plan), the host
@@ -21,6 +21,7 @@
 #include <new>
 #include <vector>
 
+#include "align_alleles.h"
 #include "align_cigar.h"
 #include "align_common.h"
 #include "consensus.h"
@@ -553,29 +554,35 @@ static inline bool scan_inclusive(pba_ctx *ctx, uint32_t *a, uint64_t n, uint32_
 
 // Where the paths of a call of trace_batch go: exactly one outlet, made by name.  Scripts reach the caller's host arrays; votes
 // go into the boxes `vote` names (device), gated by overlap_min; runs and per-window counts into the bounded slots of `slots`
-// (align_cigar.h: SlotsInto, device).  What the host must know of an outlet to size and launch its pass is said here.
+// (align_cigar.h: SlotsInto, device); alleles likewise, at the SEL sites `sites` names (align_alleles.h), gated by overlap_min.
+// What the host must know of an outlet to size and launch its pass is said here.
 struct TraceInto {
-    enum Kind { SCRIPTS, VOTES, RUNS, WINDOWS } kind;
+    enum Kind { SCRIPTS, VOTES, RUNS, WINDOWS, ALLELES } kind;
     uint8_t *ops; const uint64_t *ops_off; int32_t *nedit;
     VoteInto vote; int overlap_min;
     SlotsInto slots;
+    AllelesInto sites;
     static TraceInto scripts(uint8_t *ops, const uint64_t *ops_off, int32_t *nedit) {
         TraceInto t{}; t.kind = SCRIPTS; t.ops = ops; t.ops_off = ops_off; t.nedit = nedit; return t;
     }
     static TraceInto votes(const VoteInto &v, int overlap_min) { TraceInto t{}; t.kind = VOTES; t.vote = v; t.overlap_min = overlap_min; return t; }
     static TraceInto runs(const SlotsInto &s) { TraceInto t{}; t.kind = RUNS; t.slots = s; return t; }
     static TraceInto windows(const SlotsInto &s) { TraceInto t{}; t.kind = WINDOWS; t.slots = s; return t; }
+    static TraceInto alleles(const SlotsInto &s, const AllelesInto &a, int overlap_min) {
+        TraceInto t{}; t.kind = ALLELES; t.slots = s; t.sites = a; t.overlap_min = overlap_min; return t;
+    }
     // bytes of goal-first temporary a wavefront needs behind its parent bits (ops_max: the longest script of the batch)
     uint64_t tmp_bytes(uint64_t ops_max) const { return kind == SCRIPTS ? ops_max : (kind == RUNS ? slots.run_max * 4 : 0); }
-    // the checkpoint form only (a pile-up's votes, runs, windows); the others take the streamed form under PBA_TRACE_STREAM
-    bool ck_only() const { return kind == RUNS || kind == WINDOWS || (kind == VOTES && vote.box_off); }
+    // the checkpoint form only (a pile-up's votes, runs, windows, alleles); the others take the streamed form under PBA_TRACE_STREAM
+    bool ck_only() const { return kind == RUNS || kind == WINDOWS || kind == ALLELES || (kind == VOTES && vote.box_off); }
     // "<name> from the walk need the bit-vector kernel (band too wide)"; scripts have the row-sweep form and never say it
-    const char *name() const { return kind == VOTES ? "votes" : (kind == RUNS ? "runs" : (kind == WINDOWS ? "windows" : "scripts")); }
+    const char *name() const { return kind == VOTES ? "votes" : (kind == RUNS ? "runs" : (kind == WINDOWS ? "windows" : (kind == ALLELES ? "alleles" : "scripts"))); }
 };
 
-// One row's alignment to re-run for its runs or its windows: its pair, the batch it goes with (0: strand +1, 1: strand -1),
-// the PBA_CIG_* flags that put it in the target's forward order, what the row says of it.
-struct RowJob { pba_pair pr; uint64_t row; uint32_t flags; int batch; int32_t cost, matlen_a, matlen_b; };
+// One row's alignment to re-run for its runs, its windows or its alleles: its pair, the batch it goes with (0: strand +1,
+// 1: strand -1), the PBA_CIG_* flags that put it in the target's forward order, what the row says of it.  not_held: the pair
+// is not the walk that found the row (a mapped row's voting roles, a = contig), so it is not held to the row's cost.
+struct RowJob { pba_pair pr; uint64_t row; uint32_t flags; int batch; int32_t cost, matlen_a, matlen_b; int not_held; };
 
 // ---- internal entry points that cross translation units
 extern "C" {
@@ -594,6 +601,10 @@ PBA_INTERNAL int overlap_rows_jobs(pba_ctx *ctx, const char *who, const pba_seqs
 PBA_INTERNAL int map_rows_jobs(pba_ctx *ctx, const char *who, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
                                const pba_map_row *rows, uint64_t n, double R, pba_aln_counts *counts, pba_result *res,
                                std::vector<RowJob> *jobs);
+// ... and of mapped rows in their VOTING roles (pba_map_row_pair: a = contig), marked not_held (pba_cigar.hip)
+PBA_INTERNAL int map_rows_vote_jobs(pba_ctx *ctx, const char *who, const pba_seqs *target, const pba_seqs *reads, const pba_seqs *reads_rc,
+                                    const pba_map_row *rows, uint64_t n, double R, pba_aln_counts *counts, pba_result *res,
+                                    std::vector<RowJob> *jobs);
 // one locked round over a subset of the reads (pba_drivers.hip)
 PBA_INTERNAL int spaced_round_subset(pba_ctx *ctx, const pba_index *ix, const pba_seqs *ref, uint32_t ref_seq, const pba_seqs *reads,
                                      double R, int max_trial, int overlap_min, int buggy_seed_at, int kernel,
@@ -623,6 +634,9 @@ PBA_INTERNAL int seqs_pack(pba_ctx *ctx, const uint8_t *d_text, const uint64_t *
 PBA_INTERNAL int qual_adopt(pba_ctx *ctx, uint32_t n, const uint64_t *h_off, void *arr[4], pba_qual **out);
 // pba_map_reads' checks of its index and target (pba_drivers.hip)
 PBA_INTERNAL int map_target_ok(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target);
+// a live pile-up as the site scan reads it; a spent one is PBA_E_INVALID under who's name (pba_pileup.hip)
+struct PileView { ConsDev C; const unsigned long long *d_box_off; const uint64_t *box_off; uint32_t t_lo, t_hi, n_reads; int weight; uint64_t n_boxes; };
+PBA_INTERNAL int pile_view(pba_ctx *ctx, const char *who, const pba_pileup *p, PileView *v);
 }  // extern "C"
 
 #endif

@@ -305,6 +305,12 @@ int pba_pileup_create(pba_ctx *ctx, const pba_seqs *reads, uint32_t t_lo, uint32
     return PBA_OK;
 }
 
+int pile_view(pba_ctx *ctx, const char *who, const pba_pileup *p, PileView *v) {
+    if (p->spent) return ctx_fail_as(ctx, PBA_E_INVALID, who, "the pile-up is spent");
+    *v = PileView{p->boxes.dev, p->d_box_off, p->box_off.data(), p->t_lo, p->t_hi, p->n_reads, p->weight, p->n_boxes};
+    return PBA_OK;
+}
+
 void pba_pileup_destroy(pba_pileup *p) {
     if (!p) return;
     (void)hipSetDevice(p->device);

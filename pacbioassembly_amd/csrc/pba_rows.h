@@ -1,10 +1,9 @@
 // pba_rows.h -- the host side the bounded-slot outlets of the traced pass share (pba_cigar.hip: runs, T = uint32_t;
-// pba_windows.hip: per-window counts, T = pba_aln_counts): one batch of slots through trace_batch, and the chunk loop of the
-// row-level entry points.  (The script walker and the row layout need no device: aln_rows.h.)
+// pba_windows.hip: per-window counts, T = pba_aln_counts; pba_sites.hip: alleles at selection sites, T = pba_allele): one batch
+// of slots through trace_batch, and the chunk loop of the row-level entry points (a job marked not_held is not held to its row).
+// (The script walker and the row layout need no device: aln_rows.h.)
 #ifndef PBA_ROWS_H
 #define PBA_ROWS_H
-
-#include <type_traits>
 
 #include "aln_rows.h"
 #include "pba_host.h"
@@ -13,15 +12,21 @@
 struct SlotBufs { DevBuf slot, off, n, counts, pflags; };
 
 // Slots on the device, the batch through trace_batch, counts and results back on the host (synchronised); the elements stay
-// on the device.  extra: run_max (runs) or W (windows), and the flags of every pair where pair_flags is null.  Every count is
-// held to its slot: the sinks never write beyond one, so a bound that does not hold surfaces here as PBA_E_HIP.
+// on the device.  extra: run_max (runs) or W (windows), and the flags of every pair where pair_flags is null; sites and gate:
+// alleles only (counts then carry n_own, n_major, n_minor, n_other in their four ints).  Every count is held to its slot: the
+// sinks never write beyond one, so a bound that does not hold surfaces here as PBA_E_HIP.
+template <class T> struct SlotKind;      // what the slots of T hold: the outlet, its words for the message, the slack behind the slots
+template <> struct SlotKind<uint32_t> { static constexpr TraceInto::Kind kind = TraceInto::RUNS; static constexpr int pad = 16; static constexpr const char *many = "runs", *one = "run"; };
+template <> struct SlotKind<pba_aln_counts> { static constexpr TraceInto::Kind kind = TraceInto::WINDOWS; static constexpr int pad = 1; static constexpr const char *many = "windows", *one = "window"; };
+template <> struct SlotKind<pba_allele> { static constexpr TraceInto::Kind kind = TraceInto::ALLELES; static constexpr int pad = 1; static constexpr const char *many = "alleles", *one = "site"; };
 template <class T>
 static int slots_run(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const pba_pair *pairs, size_t n, double R, int maxn, int maxm,
                      SlotsInto extra, const uint32_t *pair_flags, const uint64_t *rel_off /* n + 1, from 0 */, pba_result *out,
-                     int32_t *have, pba_aln_counts *counts, SlotBufs &d) {
-    constexpr bool windows = std::is_same<T, pba_aln_counts>::value;
+                     int32_t *have, pba_aln_counts *counts, SlotBufs &d, const AllelesInto *sites = nullptr, int gate = 0) {
+    using K = SlotKind<T>;
+    constexpr bool windows = K::kind != TraceInto::RUNS;      // the pair's a_pos matters to the bound
     HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipMalloc(&d.slot.p, sizeof(T) * (rel_off[n] + (windows ? 1 : 16))));
+    HIPCHK(hipMalloc(&d.slot.p, sizeof(T) * (rel_off[n] + K::pad)));
     HIPCHK(hipMalloc(&d.off.p, sizeof(uint64_t) * (n + 1)));
     HIPCHK(hipMalloc(&d.n.p, sizeof(int32_t) * n));
     HIPCHK(hipMalloc(&d.counts.p, sizeof(pba_aln_counts) * n));
@@ -34,7 +39,9 @@ static int slots_run(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const p
     }
     extra.slot = d.slot.p; extra.off = d.off.as<uint64_t>(); extra.n = d.n.as<int32_t>(); extra.counts = d.counts.as<pba_aln_counts>();
     extra.pair_flags = d.pflags.as<uint32_t>();
-    PBA_TRY(trace_batch(ctx, A, B, pairs, n, R, maxn, maxm, PBA_KERNEL_BITVEC, out, windows ? TraceInto::windows(extra) : TraceInto::runs(extra)));
+    PBA_TRY(trace_batch(ctx, A, B, pairs, n, R, maxn, maxm, PBA_KERNEL_BITVEC, out,
+                        K::kind == TraceInto::ALLELES ? TraceInto::alleles(extra, *sites, gate)
+                                                      : (K::kind == TraceInto::WINDOWS ? TraceInto::windows(extra) : TraceInto::runs(extra))));
     HIPCHK(hipMemcpyAsync(have, d.n.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(counts, d.counts.p, sizeof(pba_aln_counts) * n, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -44,7 +51,7 @@ static int slots_run(pba_ctx *ctx, const pba_seqs *A, const pba_seqs *B, const p
             if (windows) snprintf(pair, sizeof pair, "a_pos %d, a_len %d, b_len %d", pairs[q].a_pos, pairs[q].a_len, pairs[q].b_len);
             else snprintf(pair, sizeof pair, "a_len %d, b_len %d", pairs[q].a_len, pairs[q].b_len);
             snprintf(ctx->err, sizeof ctx->err, "pair %llu (%s) has %d %s, its slot holds %llu: the %s bound does not hold", (unsigned long long)q,
-                     pair, have[q], windows ? "windows" : "runs", (unsigned long long)(rel_off[q + 1] - rel_off[q]), windows ? "window" : "run");
+                     pair, have[q], K::many, (unsigned long long)(rel_off[q + 1] - rel_off[q]), K::one);
             return PBA_E_HIP;
         }
     return PBA_OK;
@@ -62,7 +69,7 @@ template <class T, class Bound>
 static int rows_chunks(pba_ctx *ctx, const char *who, const pba_seqs *const A[2], const pba_seqs *const B[2], const std::vector<RowJob> &jobs,
                        double R, Bound bound, SlotsInto extra, uint32_t drop_flags,
                        pba_aln_counts *counts, pba_result *res, uint64_t max_slots, uint32_t *n_chunks,
-                       const std::function<int(const SlotBatch &)> &sink) {
+                       const std::function<int(const SlotBatch &)> &sink, const AllelesInto *sites = nullptr, int gate = 0) {
     std::vector<pba_pair> pairs;
     std::vector<uint32_t> pflags;
     std::vector<size_t> at;
@@ -94,12 +101,12 @@ static int rows_chunks(pba_ctx *ctx, const char *who, const pba_seqs *const A[2]
             out.resize(nb); have.resize(nb); cnt.resize(nb);
             SlotBufs d;
             PBA_TRY(slots_run<T>(ctx, A[s], B[s], pairs.data(), nb, R, 0, 0, extra, pflags.data(), rel.data(), out.data(), have.data(),
-                                 cnt.data(), d));
+                                 cnt.data(), d, sites, gate));
             for (size_t q = 0; q < nb; ++q) {           // held to the row: the same roles, the same lengths, the same R
                 const RowJob &jb = jobs[at[q]];
                 if (res) res[jb.row] = out[q];
                 if (counts) counts[jb.row] = cnt[q];
-                if (!walk_agrees(out[q], jb.cost, jb.matlen_a, jb.matlen_b)) {
+                if (!jb.not_held && !walk_agrees(out[q], jb.cost, jb.matlen_a, jb.matlen_b)) {
                     snprintf(ctx->err, sizeof ctx->err,
                              "%s: row %llu re-runs to rc %d cost %d matlen %d/%d, the row says cost %d matlen %d/%d: not a row of these "
                              "sets under this R", who, (unsigned long long)jb.row, out[q].rc, out[q].cost, out[q].matlen_a,

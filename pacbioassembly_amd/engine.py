@@ -76,6 +76,13 @@ QUAL_ROW_DTYPE = np.dtype([(n, "<i4") for n in ("seq", "len", "n_sel", "n_sup", 
                                                 "max_depth", "pad")] + [("sum_qv", "<u8"), ("sum_depth", "<u8")])
 QUAL_SPAN_DTYPE = np.dtype([(n, "<i4") for n in ("seq", "beg", "end", "min_qv")])
 assert QUAL_ROW_DTYPE.itemsize == 56 and QUAL_SPAN_DTYPE.itemsize == 16
+# pba_site: one per (box, kind) the site rule calls; pba_allele: a row's allele at a SEL site; pba_allele_counts: a row's totals
+PBA_SITE_SEL, PBA_SITE_SUP, PBA_ALLELE_DEL = 1, 2, 4
+SITE_DTYPE = np.dtype([("target", "<i4"), ("pos", "<i4"), ("kind", "u1"), ("own", "u1"), ("major", "u1"), ("minor", "u1"), ("n", "<u4"),
+                       ("n_major", "<u4"), ("n_minor", "<u4")])
+ALLELE_DTYPE = np.dtype([("site", "<u4"), ("allele", "<u4")])
+ALLELE_COUNTS_DTYPE = np.dtype([(n, "<i4") for n in ("n_sites", "n_own", "n_major", "n_minor", "n_other")])
+assert SITE_DTYPE.itemsize == 24 and ALLELE_DTYPE.itemsize == 8 and ALLELE_COUNTS_DTYPE.itemsize == 20
 
 
 class PbaError(RuntimeError):
@@ -1767,6 +1774,107 @@ def _clip_reads_trimmed(self, reads, mask, R, W=100, max_err=0.25, min_span=64, 
     return clipped, table, rows, stats, trims, tstats
 
 
+class Sites:
+    """The variant sites of a target range, resident on the device (pba_sites): records of SITE_DTYPE sorted by (target, pos,
+    kind).  Independent of the pile-up it was scanned from."""
+
+    def __init__(self, ctx: "Context", h):
+        self.ctx, self.h = ctx, h
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.ctx.lib.pba_sites_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def count(self) -> int:
+        return int(self.ctx.lib.pba_sites_count(self.h))
+
+    def target_range(self, target: int):
+        """(lo, hi): records [lo, hi) are the target's."""
+        lo, hi = C.c_uint64(), C.c_uint64()
+        self.ctx.check(self.ctx.lib.pba_sites_target_range(self.h, target, C.byref(lo), C.byref(hi)), "sites_target_range")
+        return int(lo.value), int(hi.value)
+
+    def get(self, lo: int = 0, hi: Optional[int] = None) -> np.ndarray:
+        hi = self.count if hi is None else hi
+        out = np.zeros(max(hi - lo, 1), SITE_DTYPE)
+        self.ctx.check(self.ctx.lib.pba_sites_get(self.ctx.h, self.h, lo, hi, _ptr(out)), "sites_get")
+        return out[:max(hi - lo, 0)]
+
+
+def _pileup_sites(self, min_depth: int, min_alt: int, min_permille: int) -> "Sites":
+    """The sites of the boxes as they stand, before evolve (pba_pileup_sites); the pile-up is only read."""
+    h = C.c_void_p()
+    self.ctx.check(self.ctx.lib.pba_pileup_sites(self.ctx.h, self.h, self.reads.h, min_depth, min_alt, min_permille, C.byref(h)), "pileup_sites")
+    return Sites(self.ctx, h)
+
+
+Pileup.sites = _pileup_sites
+
+
+def _sites_create(self, seqs, recs, t_lo: int = 0, t_hi: Optional[int] = None) -> "Sites":
+    """A Sites from a list of SITE_DTYPE records for the sequences [t_lo, t_hi) of seqs (pba_sites_create)."""
+    recs = np.ascontiguousarray(recs, SITE_DTYPE)
+    h = C.c_void_p()
+    self.check(self.lib.pba_sites_create(self.h, seqs.h, t_lo, seqs.count if t_hi is None else t_hi, _ptr(recs) if recs.size else None,
+                                         recs.size, C.byref(h)), "sites_create")
+    return Sites(self, h)
+
+
+def _rows_alleles(self, fn, what, head, rows, dtype, mid, sites, cap, max_slots):
+    rows = np.ascontiguousarray(rows, dtype)
+    n = rows.size
+    off = np.zeros(n + 1, np.uint64)
+    sums = np.zeros(max(n, 1), ALLELE_COUNTS_DTYPE)
+    res = np.zeros(max(n, 1), RESULT_DTYPE)
+    total = C.c_uint64()
+    if cap is None:                                  # one call to learn the total, one to fetch
+        self.check(fn(self.h, *head, _ptr(rows), n, *mid, sites.h, None, 0, _ptr(off), C.byref(total), None, None, max_slots), what)
+        cap = total.value
+    out = np.zeros(max(int(cap), 1), ALLELE_DTYPE)
+    self.check(fn(self.h, *head, _ptr(rows), n, *mid, sites.h, _ptr(out), int(cap), _ptr(off), C.byref(total), _ptr(sums), _ptr(res), max_slots),
+               what)
+    whole = int(off[np.searchsorted(off, cap, side="right") - 1]) if n else 0      # the rows that fit cap, whole
+    return out[:whole], off, sums[:n], res[:n]
+
+
+def _overlap_alleles(self, reads, rows, R, sites, reads_rc=None, cap=None, max_slots=0):
+    """Every overlap_strands row's allele at the SEL sites of its target (pba_overlap_rows_alleles_budget).  Returns (records of
+    ALLELE_DTYPE for the rows that fit cap, offsets -- n + 1, always complete --, per-row totals, results)."""
+    head = (reads.h, reads_rc.h if reads_rc is not None else None)
+    return _rows_alleles(self, self.lib.pba_overlap_rows_alleles_budget, "overlap_alleles", head, rows, STRAND_OVERLAP_DTYPE, (R,), sites, cap,
+                         max_slots)
+
+
+def _map_alleles(self, target, reads, rows, R, sites, overlap_min=64, reads_rc=None, cap=None, max_slots=0):
+    """Every map_reads row's allele at the SEL sites of its contig, in the row's voting roles under vote_mapped's gate
+    (pba_map_rows_alleles_budget).  Returns what overlap_alleles returns."""
+    head = (target.h, reads.h, reads_rc.h if reads_rc is not None else None)
+    return _rows_alleles(self, self.lib.pba_map_rows_alleles_budget, "map_alleles", head, rows, MAP_ROW_DTYPE, (R, overlap_min), sites, cap,
+                         max_slots)
+
+
+def sites_tsv_lines(sites, names=None):
+    """One line per record (a Sites, or records of SITE_DTYPE): target, 1-based position, kind, own / major / minor as letters
+    (`-` for DEL), n, n_major, n_minor."""
+    letters = "ACGT-"
+    for r in (sites.get() if isinstance(sites, Sites) else sites):
+        t = int(r["target"])
+        yield "\t".join([str(names[t]) if names is not None else str(t), str(int(r["pos"]) + 1), "SEL" if int(r["kind"]) == PBA_SITE_SEL else "SUP",
+                          letters[int(r["own"])], letters[int(r["major"])], letters[int(r["minor"])], str(int(r["n"])), str(int(r["n_major"])),
+                          str(int(r["n_minor"]))])
+
+
+Context.sites_create = _sites_create
+Context.overlap_alleles = _overlap_alleles
+Context.map_alleles = _map_alleles
 Context.align_batch_windows = _align_batch_windows
 Context.map_windows = _map_windows
 Context.overlap_windows = _overlap_windows
