@@ -49,11 +49,25 @@
 
 #include "align_rowsweep.h"
 #include "dev_common.h"
+#include "eq_table.h"
 #include "text_ring.h"
+
+// The score-only sweeps of the aligning kernels at one and two blocks per lane read their match masks from a per-lane table
+// in LDS (eq_table.h) instead of computing them every step.  -DPBA_BV_EQTAB=0 builds those forms with the register planes
+// and the mask-pair ring of every other ring form (tools/build_variant.py).
+#ifndef PBA_BV_EQTAB
+#define PBA_BV_EQTAB 1
+#endif
+#ifndef PBA_BV_RING                                    // (align_bitvec below: 0 builds every form with the register planes)
+#define PBA_BV_RING 1
+#endif
+#define PBA_BV_EQTAB_NB(nb) (PBA_BV_EQTAB && PBA_BV_RING && (nb) <= 2)
 
 #define PBA_BV_MAX_NB 8
 #define PBA_BV_FIN_WORDS(nb) ((2 * (nb) + 1) * 64)     // u32 of LDS per wavefront for the last column's deltas (bitvec_pass: fin)
-#define PBA_BV_LDS_BYTES(nb) (PBA_BV_FIN_WORDS(nb) * 4 + PBA_TXR_BYTES)   // per wavefront: the fin words, then the text ring (text_ring.h)
+// per wavefront of a score-only launch: the fin words, then the text ring (text_ring.h); in the table forms the table with the
+// fin Pv / Mv words on it, the ring of 4-byte cells and the fin superblock word (eq_table.h)
+#define PBA_BV_LDS_BYTES(nb) (PBA_BV_EQTAB_NB(nb) ? eqt_lds_words(nb) * 4 : PBA_BV_FIN_WORDS(nb) * 4 + PBA_TXR_BYTES)
 #define PBA_BV_BAND_NUM 9      // first-pass half width = max(max_dst/2, 9/16 * max_dst) + 1
 #define PBA_BV_BAND_DEN 16
 
@@ -169,7 +183,9 @@ __device__ __forceinline__ uint32_t bit_mask(uint32_t x, int k) {
 // DPP, no VALU.  The diagonal's D0 bits are collected with one bitop3 (in the diagonal's block only, at one or two
 // blocks per lane) under a wave-uniform one-hot that a scalar shift advances; text
 // elements come from two 32-step bit-plane registers, or (RING: the score-only forms of the aligning kernels) as ready mask
-// pairs from the wavefront's text ring in LDS (text_ring.h), two steps' with one read.  Everything rare is scheduled: the events of the sweep fall at
+// pairs from the wavefront's text ring in LDS (text_ring.h), two steps' with one read; in rings 1 and 2 of those forms the
+// match masks themselves come from the lane's table in LDS (eq_table.h: the ring's cell is the letter's row offset, one address
+// add and one ds_read2st64_b32 per step replace the xor and the bitop3 of every block).  Everything rare is scheduled: the events of the sweep fall at
 // steps known in advance, kept as wave-uniform timers, and the step loop runs from one to the next without a test.
 //
 // TRACE: also store, for every step and block, the two words the traceback needs (bv_trace_walk below):
@@ -216,13 +232,34 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     const int t_end = m + S - 1;                // step at which the last superblock takes the last column
     (void)nb_m; (void)r_m;
 
+    // EQT: the match masks come from the lane's table in LDS (eq_table.h) -- `fin` is then the wavefront's whole region: the
+    // table (with the fin Pv / Mv words on the lane's own rows), the ring, the fin superblock word.  The row planes are
+    // live only while a lane fills its rows, not in the step loop.
+    constexpr bool EQT = RING && PBA_BV_EQTAB_NB(NB);
+    constexpr int FIN_SB = EQT ? PBA_EQT_LETTERS * NB * PBA_EQT_LANES + PBA_TXR_SLOTS : 2 * NB * PBA_WAVE;   // eqt_sb_word(NB); else behind the fin words
+    typedef __attribute__((address_space(3))) uint32_t lds_u32;
+    lds_u32 *const tab_lane = (lds_u32 *)fin + lane;   // the lane's column of the table
+    (void)tab_lane;
+    // a lane's four match masks per block, from the row planes of superblock sb: row (l, nb) = ~(Plo ^ mask(l0)) & ~(Phi ^ mask(l1))
+#define PBA_BV_FILL_ROWS(sb)                                                          \
+    _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) {                               \
+        uint32_t plo_, phi_;                                                          \
+        load_planes32(rowsF, (sb) * RB + 32 * nb, plo_, phi_);                        \
+        tab_lane[(0 * NB + nb) * PBA_EQT_LANES] = ~(plo_ | phi_);                     \
+        tab_lane[(1 * NB + nb) * PBA_EQT_LANES] = plo_ & ~phi_;                       \
+        tab_lane[(2 * NB + nb) * PBA_EQT_LANES] = ~plo_ & phi_;                       \
+        tab_lane[(3 * NB + nb) * PBA_EQT_LANES] = plo_ & phi_;                        \
+    }
+
     uint32_t Pv[NB], Mv[NB], Plo[NB], Phi[NB], acc[NB];
     int s_cur = lane;      // (the forms without the text ring: LANE_SB below)
     uint32_t opened = 0;   // 0 / 1 in a VGPR (a bool would live in an SGPR pair and be re-merged with exec every step)
-    (void)opened;
+    (void)opened; (void)Plo; (void)Phi;
     if (s_cur < S) {
+        if constexpr (EQT) { PBA_BV_FILL_ROWS(s_cur) } else {
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) load_planes32(rowsF, s_cur * RB + 32 * nb, Plo[nb], Phi[nb]);
+        }
     }
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) { Pv[nb] = ~0u; Mv[nb] = 0u; acc[nb] = 0u; }
@@ -284,10 +321,18 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     uint32_t wl = 0, wh = 0;                     // text bit planes: bit k = low / high bit of the element of step tb+k
     // RING: no planes -- the text comes from the wavefront's ring in LDS (text_ring.h), PBA_TXR_BYTES behind the fin words:
     // ta is this lane's cell for the step at hand, one cell further every step
-    typedef __attribute__((address_space(3))) uint64_t txr_cell;
-    txr_cell *const ring = (txr_cell *)(fin + PBA_BV_FIN_WORDS(NB));
+    // EQT: the ring's cell is the byte offset of the letter's rows in the lane's table (eq_table.h: eqt_cell), behind the table.
+    // Every cell gets a letter in front of the sweep: a lane steps before its window opens and after it has closed, through
+    // cells no chunk of this sweep has written, and what it finds there is an address.
+    typedef __attribute__((address_space(3))) typename std::conditional<EQT, uint32_t, uint64_t>::type txr_cell;
+    txr_cell *const ring = (txr_cell *)(fin + (EQT ? PBA_EQT_LETTERS * NB * PBA_EQT_LANES : PBA_BV_FIN_WORDS(NB)));
     const txr_cell *ta = ring;
     (void)wl; (void)wh; (void)ring; (void)ta;
+    if constexpr (EQT) {
+        static_assert(PBA_TXR_SLOTS <= 3 * PBA_WAVE && PBA_TXR_SLOTS > 2 * PBA_WAVE, "three cells per lane cover the ring");
+        ring[lane] = 0; ring[PBA_WAVE + lane] = 0;
+        if (lane < PBA_TXR_SLOTS - 2 * PBA_WAVE) ring[2 * PBA_WAVE + lane] = 0;
+    }
     // wave-uniform, in scalar registers: the running D(i,i) at the end of the last segment judged (segments end in row
     // order, so it simply carries on from lane to lane) and the first failing row (0: none so far)
     int score = 0, fail_row = 0;
@@ -296,7 +341,7 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     // They live in LDS (fin: PBA_BV_FIN_WORDS(NB) u32 of this wavefront's own: [2*nb][lane] Pv, [2*nb+1][lane] Mv, [2*NB][lane]
     // the superblock): written once per superblock that reaches the last column, read once at the end -- as registers
     // they were live through the whole step loop, and at 64 registers per lane the compiler spilled them to scratch memory.
-    fin[2 * NB * PBA_WAVE + lane] = 0xFFFFFFFFu;
+    fin[FIN_SB + lane] = 0xFFFFFFFFu;
     uint64_t hp_last = ~0ull, hn_last = 0ull;    // lane masks: delta +1 / -1 leaving each lane's last block in the previous step
     // What a lane hands out is masked, not what a lane takes in.  live: the lanes whose hout of the step just run is a window
     // cell that the lane below takes; hpm / hnm: that step's carries under it -- "+1 per column", the row above a window,
@@ -328,7 +373,8 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
             load_planes32(colsF, first, plo, phi);
             const int c = lane & (PBA_TXR_CHUNK - 1), slot = txr_slot(first + c), mir = txr_mirror(slot);
             const int dst = (lane >= PBA_TXR_CHUNK && mir >= 0) ? mir : slot;
-            ring[dst] = (uint64_t)(0u - ((plo >> c) & 1u)) | ((uint64_t)(0u - ((phi >> c) & 1u)) << 32);
+            if constexpr (EQT) ring[dst] = (((plo >> c) & 1u) | (((phi >> c) & 1u) << 1)) * (uint32_t)(NB * PBA_EQT_LANES * 4);   // eqt_cell(letter)
+            else ring[dst] = (uint64_t)(0u - ((plo >> c) & 1u)) | ((uint64_t)(0u - ((phi >> c) & 1u)) << 32);
             ta = ring + txr_addr(tb, PBA_BV_LANE_SB());
         } else {
             load_planes32(colsF, tb - PBA_BV_LANE_SB() - 1, wl, wh);
@@ -397,7 +443,7 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
             const int s = s_cl;                                                       \
             if (lane == (s & (PBA_WAVE - 1))) {                                       \
                 if (s >= s_m) {              /* its window ended with the last column: keep that column */ \
-                    fin[2 * NB * PBA_WAVE + lane] = (uint32_t)(LANE_SB ? s_cur : s);  \
+                    fin[FIN_SB + lane] = (uint32_t)(LANE_SB ? s_cur : s);  \
                     _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) { fin[2 * nb * PBA_WAVE + lane] = Pv[nb]; fin[(2 * nb + 1) * PBA_WAVE + lane] = Mv[nb]; } \
                 }                                                                     \
                 /* the lane's next superblock: its rows, and its slice of the text (a lane that opens its first window \
@@ -405,8 +451,12 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
                    per step, and false candidates are all ramp) */                    \
                 if constexpr (LANE_SB) { s_cur += PBA_WAVE; opened = 0; }             \
                 const int sn = LANE_SB ? s_cur : s + PBA_WAVE;                        \
+                /* EQT: its match masks.  Never after the fin words went onto the lane's rows above: s >= s_m and \
+                   S - s_m < 64 (the windows span at most bv_max_span rows) give s + 64 >= S (eq_table.h) */ \
                 if (s + PBA_WAVE < S) {                                               \
+                    if constexpr (EQT) { PBA_BV_FILL_ROWS(sn) } else {                \
                     _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) load_planes32(rowsF, sn * RB + 32 * nb, Plo[nb], Phi[nb]); \
+                    }                                                                 \
                 }                                                                     \
                 if constexpr (RING) ta = ring + txr_addr(t, sn);      /* 64 elements back; they are in the ring */ \
                 else load_text(t - ((t - 1) & 31));                                   \
@@ -461,7 +511,7 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     // then -1, and both forms give Pv' = 1, Mv' = 0)
 #define PBA_BV_BLOCK(nb, PH_PRE, MH_PRE, D0, EQ)                                     \
     {                                                                                \
-        const uint32_t Eq = eq_mask(Plo[nb] ^ clo, Phi[nb], chi);                    \
+        const uint32_t Eq = EQT ? eqr[nb] : eq_mask(Plo[nb] ^ clo, Phi[nb], chi);    \
         EQ = Eq;                                                                     \
         const uint32_t pv = Pv[nb], mv = Mv[nb];                                     \
         uint64_t unused;                                                             \
@@ -487,10 +537,20 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     // One stretch of phase 1: plain steps from k up to kstop.  QD: the block the diagonal is in, as a constant (its word
     // alone collects), or -1: every block's word collects (garbage in all but the diagonal's, cleared at the segment's end).
     // LANE_HOT: every block's word collects under the lane's own one-hot.
+    // EQT: the step's match masks were read ahead (eqn[OFS][], PBA_BV_ROWS)
 #define PBA_BV_TEXT(OFS)                                                             \
-        uint32_t clo, chi;                                                           \
-        if constexpr (RING) { const uint64_t cell = ta[OFS]; clo = (uint32_t)cell; chi = (uint32_t)(cell >> 32); } \
+        uint32_t clo = 0, chi = 0, eqr[NB];                                          \
+        _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) eqr[nb] = eqn[OFS][nb];    \
+        (void)clo; (void)chi; (void)eqr;                                             \
+        if constexpr (EQT) { }                                                       \
+        else if constexpr (RING) { const uint64_t cell = ta[OFS]; clo = (uint32_t)cell; chi = (uint32_t)(cell >> 32); } \
         else { clo = bit_mask(wl, k + (OFS)); chi = bit_mask(wh, k + (OFS)); }
+    // EQT: the match masks of the step whose cell is cq[OFS] -- the lane's own address plus the cell, both blocks with one read
+#define PBA_BV_ROWS(OFS)                                                             \
+        {                                                                            \
+        const lds_u32 *const row = (const lds_u32 *)((const __attribute__((address_space(3))) uint8_t *)tab_lane + cq[OFS]); \
+        _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) eqn[OFS][nb] = row[nb * PBA_EQT_LANES]; \
+        }
 #define PBA_BV_STEP1(QD, OFS)                                                        \
         {                                                                            \
         const int t = tb + k + (OFS);                                                \
@@ -519,8 +579,24 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     // RING: the stretch runs two steps per turn -- both steps' cells come with one LDS instruction, and the address add, the
     // counter, the compare and the branch are paid once per two steps; an odd stretch (every stretch of a ramp is one step) takes
     // its odd step first.
+    // EQT: two LDS trips stand between a step and its masks, the cell and then the rows.  A turn takes both steps' cells with
+    // one read and both steps' rows in front of its first step, so the second step never waits.  (Reading the next turn's
+    // cells a turn ahead was written too: the compiler moves that read back to the top of the turn that uses it, and at
+    // eight waves per SIMD the other waves cover the trip.  DESIGN.md 4.3, round 12.)
 #define PBA_BV_STRETCH1(QD)                                                          \
-        if constexpr (RING) {                                                        \
+        uint32_t cq[2] = {0u, 0u}, eqn[2][NB] = {};                                  \
+        (void)cq; (void)eqn;                                                         \
+        if constexpr (EQT) {                                                         \
+            if ((kstop - k) & 1) { cq[0] = ta[0]; PBA_BV_ROWS(0) PBA_BV_STEP1(QD, 0) ta += 1; k += 1; } \
+            while (k < kstop) {                                                      \
+                cq[0] = ta[0]; cq[1] = ta[1];                                        \
+                PBA_BV_ROWS(0) PBA_BV_ROWS(1)                                        \
+                PBA_BV_STEP1(QD, 0)                                                  \
+                _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) asm("" : "+v"(Pv[nb]), "+v"(Mv[nb])); \
+                PBA_BV_STEP1(QD, 1)                                                  \
+                ta += 2; k += 2;                                                     \
+            }                                                                        \
+        } else if constexpr (RING) {                                                 \
             if ((kstop - k) & 1) { PBA_BV_STEP1(QD, 0) ta += 1; k += 1; }            \
             while (k < kstop) {                                                      \
                 PBA_BV_STEP1(QD, 0)                                                  \
@@ -601,6 +677,9 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
         do {
         const int t = tc + k;
         (void)t;
+        uint32_t cq[1] = {0u}, eqn[1][NB] = {};
+        (void)cq; (void)eqn;
+        if constexpr (EQT) { cq[0] = ta[0]; PBA_BV_ROWS(0) }
         PBA_BV_TEXT(0)
         PBA_BV_HIN();
 #pragma unroll
@@ -621,7 +700,9 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     }
 #undef PBA_BV_STRETCH1
 #undef PBA_BV_STEP1
+#undef PBA_BV_ROWS
 #undef PBA_BV_TEXT
+#undef PBA_BV_FILL_ROWS
 #undef PBA_BV_BLOCK
 #undef PBA_BV_TRP
 #undef PBA_BV_HOUT
@@ -632,13 +713,13 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     // upward from the diagonal, and keeps the first strict minimum).  A lane whose window is still open holds the
     // column in Pv / Mv, the others put it aside when their window closed.
     if (const int sb = PBA_BV_LANE_SB(); PBA_BV_LANE_OPEN() && sb >= s_m && sb < S) {
-        fin[2 * NB * PBA_WAVE + lane] = (uint32_t)sb;
+        fin[FIN_SB + lane] = (uint32_t)sb;
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) { fin[2 * nb * PBA_WAVE + lane] = Pv[nb]; fin[(2 * nb + 1) * PBA_WAVE + lane] = Mv[nb]; }
     }
 #undef PBA_BV_LANE_OPEN
 #undef PBA_BV_LANE_SB
-    const int fin_s = (int)fin[2 * NB * PBA_WAVE + lane];      // (a lane reads what it wrote itself: no barrier)
+    const int fin_s = (int)fin[FIN_SB + lane];      // (a lane reads what it wrote itself: no barrier)
     int b_tot[NB], b_min[NB], b_pos[NB];          // per block of this lane's last superblock: sum, lowest prefix sum, its bit
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
@@ -718,7 +799,8 @@ __device__ __forceinline__ bool bv_goal_certified(int best, int wl, int w, int m
 // goal row cannot be certified; the host then re-launches those pairs with full_band = true.
 // There is deliberately no device function call in here: everything inlines into the kernel.
 // lds: PBA_BV_LDS_BYTES(NB) of this wavefront's own: the fin words (>= 256 bytes: the m <= 10 corner runs the row sweep in
-// them), then the text ring
+// them), then the text ring; in rings 1 and 2 the match-mask table, the ring and the fin superblock word (eq_table.h: the
+// corner's row then lies in the table, which every sweep fills for itself)
 // need_diag: the caller reports D(m,m) (locator.cpp:86): a narrow pass whose window cannot vouch for that cell too
 // answers PBA_RC_UNCERTIFIED; without it o.diag is -1 in that case.
 // BAIL: give a narrow first pass up early when the pair is heading for a cost its window cannot certify (bitvec_pass:

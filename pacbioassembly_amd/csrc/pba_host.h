@@ -371,9 +371,10 @@ static inline int make_plan(pba_ctx *ctx, double R, int maxn, int maxm, int kern
 }
 
 // LDS of one launch of a score-only kernel (k_align_pairs, k_locate, k_spaced_round) in ring nb: the fin words of THAT ring, not
-// of the plan's widest, and behind them the sweep's text ring (text_ring.h).  k_locate<2> of a 15 kb batch planned for a
-// re-run in ring 4 then takes 2 560 bytes per wavefront: with LocWalkLds 32 wavefronts fit a CU's 160 KB, which the widest
-// ring's fin words plus the text ring would not.  nb = 0 (row sweep): the plan's band row.
+// of the plan's widest, and behind them the sweep's text ring (text_ring.h); in rings 1 and 2 the match-mask table with the
+// fin words on it, the ring and the fin superblock word (eq_table.h).  k_locate<2> of a 15 kb batch planned for a
+// re-run in ring 4 then takes 2 944 bytes per wavefront: with LocWalkLds (1 792) that is 4 736 of the 5 120 a wavefront may
+// have with 32 of them on a CU's 160 KB, which the widest ring's fin words would not fit.  nb = 0 (row sweep): the plan's band row.
 struct LaunchLds { size_t lds; AlignCfg cfg; };
 static inline LaunchLds launch_lds(const Plan &pl, int nb) {
     LaunchLds l{pl.lds, pl.cfg};

@@ -9,6 +9,9 @@
 // cells with one ds_read2_b64 -- at an address that advances by one cell per step.  (One byte per element and plane, read
 // sign-extended, was built first: two LDS instructions per step cost the step what the two v_bfe_i32 they replaced had,
 // DESIGN.md 4.3 round 10.)
+// In rings 1 and 2 the match masks themselves come from a table in LDS (eq_table.h): there a cell is 4 bytes, the byte
+// offset of the letter's rows in the lane's table, and two steps' cells come with one ds_read2_b32.  Slots, mirror,
+// addresses and the writer are the same; only the cell's size and value differ.
 //
 // Elements.  The lanes hold the 64 superblocks s_cl .. s_cl + 63 (s_cl: the next superblock to close, align_bitvec.h's
 // schedule), so step t reads the 64 consecutive elements t - 1 - s_cl - 63 .. t - 1 - s_cl.

@@ -34,7 +34,7 @@ for sub in ("pmc_fetch", "pmc_write"):
 json.dump(hbm, open(f"profiles/{rp}_bench_pmc_hbm.json", "w"), indent=1)
 sq = {"note": "SQ_* per dispatch, averaged; SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_ANY are in quad-cycles; GRBM_GUI_ACTIVE is summed over the 8 XCDs",
       "kernels": {}}
-for sub in ("pmc_sq", "pmc_grbm"):
+for sub in ("pmc_sq", "pmc_lds", "pmc_grbm"):
     for k, d in counters(sub).items():
         sq["kernels"].setdefault(k, {}).update({c: v for c, v in d.items()})
 json.dump(sq, open(f"profiles/{rp}_bench_pmc_sq.json", "w"), indent=1)
