@@ -23,7 +23,8 @@
 // processes column j at step t = j + s, so a column flows down the lanes one lane per step.  The
 // horizontal deltas leaving the bottom row of a superblock are carry-outs of v_addc_co_u32, i.e. lane
 // masks in SGPR pairs, and reach the next lane through a scalar 64-bit rotate of those masks (no DPP,
-// no VALU).  Only the columns of a superblock's window are processed (lo..hi); cells left of the
+// no VALU).  (The score-only sweeps at one and two blocks per lane keep the lanes in the order of their superblocks
+// instead -- lane k holds the k-th superblock not yet closed, lane_shift.h -- and the rotate is a shift.)  Only the columns of a superblock's window are processed (lo..hi); cells left of the
 // window are taken as "+1 per row" and the row above the window as "+1 per column", which are real
 // (if expensive) paths, so everything computed is an upper bound W >= U that equals U whenever U's
 // optimal path stays inside the windows.
@@ -50,6 +51,7 @@
 #include "align_rowsweep.h"
 #include "dev_common.h"
 #include "eq_table.h"
+#include "lane_shift.h"
 #include "text_ring.h"
 
 // The score-only sweeps of the aligning kernels at one and two blocks per lane read their match masks from a per-lane table
@@ -62,6 +64,11 @@
 #define PBA_BV_RING 1
 #endif
 #define PBA_BV_EQTAB_NB(nb) (PBA_BV_EQTAB && PBA_BV_RING && (nb) <= 2)
+// The table forms keep the lanes in the order of their superblocks, lane 0 the top of the band (lane_shift.h): the hand-off
+// is two scalar shifts and an or.  -DPBA_BV_SHIFT=0 builds them with the ring of lanes and the `live` mask of every other form.
+#ifndef PBA_BV_SHIFT
+#define PBA_BV_SHIFT 1
+#endif
 
 #define PBA_BV_MAX_NB 8
 #define PBA_BV_FIN_WORDS(nb) ((2 * (nb) + 1) * 64)     // u32 of LDS per wavefront for the last column's deltas (bitvec_pass: fin)
@@ -166,6 +173,23 @@ __device__ __forceinline__ uint64_t bv_and2(uint64_t a, uint64_t b) {
     asm("s_and_b64 %0, %1, %2" : "=s"(d) : "s"(a), "s"(b) : "scc");
     return d;
 }
+// the shifted form's hand-off (lane_shift.h: lsh_hin_plus, lsh_hin_minus), on the scalar unit for the same reason
+__device__ __forceinline__ uint64_t bv_shl1(uint64_t a) {
+    uint64_t d;
+    asm("s_lshl_b64 %0, %1, 1" : "=s"(d) : "s"(a) : "scc");
+    return d;
+}
+__device__ __forceinline__ uint64_t bv_shl1_or1(uint64_t a) {
+    uint64_t d;
+    asm("s_lshl_b64 %0, %1, 1\n\ts_or_b64 %0, %0, 1" : "=&s"(d) : "s"(a) : "scc");
+    return d;
+}
+// lane k's copy of lane k + 1's x (lane_shift.h: lsh_src_lane); the last lane keeps its own.  A whole-wave DPP shift: one
+// instruction, no address register and no LDS trip (ds_bpermute_b32 does the same through the LDS crossbar, and its
+// address cost k_locate<2> and k_spaced_round<1> a spilled word each)
+__device__ __forceinline__ uint32_t bv_lane_below(uint32_t x) {
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
+}
 // sign-extended bit k of x (k wave-uniform): 0 or ~0
 __device__ __forceinline__ uint32_t bit_mask(uint32_t x, int k) {
     uint32_t d;
@@ -238,8 +262,12 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     constexpr bool EQT = RING && PBA_BV_EQTAB_NB(NB);
     constexpr int FIN_SB = EQT ? PBA_EQT_LETTERS * NB * PBA_EQT_LANES + PBA_TXR_SLOTS : 2 * NB * PBA_WAVE;   // eqt_sb_word(NB); else behind the fin words
     typedef __attribute__((address_space(3))) uint32_t lds_u32;
-    lds_u32 *const tab_lane = (lds_u32 *)fin + lane;   // the lane's column of the table
-    (void)tab_lane;
+    // SHIFT: lane k holds superblock s_cl + k and works in column (lane + s_cl) & 63 of the table (lane_shift.h); the close
+    // event moves the lanes' state one lane up.  Else superblock s stays in lane s & 63, which is its column.
+    constexpr bool SHIFT = EQT && PBA_BV_SHIFT;
+    // The lane's column of the table is formed from `lane` and the schedule's scalar where it is used (a stretch forms it once,
+    // in front of its loop): kept in a register of its own and moved on by the close it cost k_locate a spilled word more.
+#define tab_lane ((lds_u32 *)fin + (SHIFT ? lsh_col(lane, s_cl) : lane))
     // a lane's four match masks per block, from the row planes of superblock sb: row (l, nb) = ~(Plo ^ mask(l0)) & ~(Phi ^ mask(l1))
 #define PBA_BV_FILL_ROWS(sb)                                                          \
     _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) {                               \
@@ -256,6 +284,8 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     uint32_t opened = 0;   // 0 / 1 in a VGPR (a bool would live in an SGPR pair and be re-merged with exec every step)
     (void)opened; (void)Plo; (void)Phi;
     if (s_cur < S) {
+        constexpr int s_cl = 0;   // (tab_lane: the sweep starts with superblock s in lane s, column s)
+        (void)s_cl;
         if constexpr (EQT) { PBA_BV_FILL_ROWS(s_cur) } else {
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) load_planes32(rowsF, s_cur * RB + 32 * nb, Plo[nb], Phi[nb]);
@@ -264,7 +294,8 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) { Pv[nb] = ~0u; Mv[nb] = 0u; acc[nb] = 0u; }
 
-    // The event schedule.  Nothing in it depends on the data: superblock s lives in lane s & 63, and each kind of event
+    // The event schedule.  Nothing in it depends on the data: superblock s lives in lane s & 63 (SHIFT: in lane s - s_cl, and
+    // the close moves every lane's state one lane up -- the schedule is the same, PBA_BV_LANE_OF), and each kind of event
     // falls at a step that is a function of (s, m, nr, w, wleft) alone, strictly increasing in s -- at most one event of
     // a kind per step.  So the schedule is three wave-uniform timers, each with the superblock it fires for, advanced
     // with scalar arithmetic in the handler; no lane carries a timer and the step loop tests nothing.
@@ -290,7 +321,8 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     // other forms (LANE_SB) keep both in the lane, updated by the events, as they always did.  (Macros, not lambdas: two
     // more closures over the schedule's scalars cost k_cigar_pairs<4> and k_vote_pairs<4, true, false> a wave per SIMD.)
     constexpr bool LANE_SB = !RING;
-#define PBA_BV_LANE_SB() (LANE_SB ? s_cur : s_cl + ((lane - s_cl) & (PBA_WAVE - 1)))
+#define PBA_BV_LANE_SB() (LANE_SB ? s_cur : SHIFT ? lsh_sb(lane, s_cl) : s_cl + ((lane - s_cl) & (PBA_WAVE - 1)))
+#define PBA_BV_LANE_OF(s) (SHIFT ? lsh_lane(s, s_cl) : (s) & (PBA_WAVE - 1))   /* the lane of superblock s, s_cl as it is now */
 #define PBA_BV_LANE_OPEN() (LANE_SB ? opened != 0 : PBA_BV_LANE_SB() < s_op)
     // Where the diagonal is: at any step it is in one block of one lane, or in none (the one-step gap between two
     // superblocks, and past row m).  Both are wave-uniform and belong to the schedule: `one` is the one-hot of the diagonal
@@ -359,6 +391,8 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     //     They are still at hand unmasked (hp_last / hn_last), so the event forms hpm / hnm again under the new bit, then
     //     clears its own.  (When s + 64 >= S the bit stays as close(s - 1) left it: clear.)
     // hp_last / hn_last stay the raw carries of the step: what a checkpoint holds (bv_ckpt_store, bitvec_rerun).
+    // SHIFT has neither `live` nor the raw carries: lane 0 is the one lane that takes the border, in every step but the one
+    // right behind a close (lane_shift.h reads the derivation above for that mapping).
     uint64_t live = (S >= PBA_WAVE ? ~0ull : (1ull << S) - 1ull) >> 1;
     uint64_t hpm = ~0ull, hnm = 0ull;
 
@@ -394,7 +428,7 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     // no segment is judged after one.
     auto segment_done = [&](int s, int i) -> int {
         const int rr = i - 1 - s * RB, cnt = (rr & 31) + 1, i0 = i - cnt, q = rr >> 5;
-        const int L = s & (PBA_WAVE - 1);
+        const int L = PBA_BV_LANE_OF(s);
         uint32_t dw = 0;
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) if (q == nb) dw = __builtin_amdgcn_readlane(acc[nb], L);
@@ -418,7 +452,7 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
         // the diagonal leaves this lane's rows for the lane below (its word is cleared here, one step early: nothing
         // collects in the gap step), or enters this lane's next block at bit 0
         const bool leaves = rr == RB - 1 && i != m;
-        if (lane == L || (DIAG_FOLD && leaves && lane == ((s + 1) & (PBA_WAVE - 1)))) {
+        if (lane == L || (DIAG_FOLD && leaves && lane == PBA_BV_LANE_OF(s + 1))) {
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) acc[nb] = 0; // the next block's word starts clean
             if constexpr (LANE_HOT) dmw = (i == m || rr == RB - 1) ? 0u : 1u;
@@ -441,6 +475,23 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
         }                                                                             \
         if (t == T_close) {                                                           \
             const int s = s_cl;                                                       \
+            if constexpr (SHIFT) {                                                    \
+                /* lane_shift.h: lane 0 keeps its last column, every lane takes the state of the lane below it, the last \
+                   lane its next superblock's rows in the column lane 0 leaves */ \
+                if (lane == 0 && s >= s_m) {                                        \
+                    tab_lane[FIN_SB] = (uint32_t)s;                                   \
+                    _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) { tab_lane[2 * nb * PBA_WAVE] = Pv[nb]; tab_lane[(2 * nb + 1) * PBA_WAVE] = Mv[nb]; } \
+                }                                                                     \
+                _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) {                   \
+                    Pv[nb] = bv_lane_below(Pv[nb]); \
+                    Mv[nb] = bv_lane_below(Mv[nb]); \
+                    acc[nb] = bv_lane_below(acc[nb]); \
+                }                                                                     \
+                s_cl = s + 1;                /* from here on the lanes' columns are those of s + 1 .. s + 64 */ \
+                if (lane == PBA_WAVE - 1 && s + PBA_WAVE < S) { PBA_BV_FILL_ROWS(s + PBA_WAVE) } \
+                ta = ring + lsh_ring_addr(t, lane, s_cl);                             \
+                closed = true;               /* this step takes the carries unshifted: the lanes moved (PBA_BV_HIN) */ \
+            } else {                                                                \
             if (lane == (s & (PBA_WAVE - 1))) {                                       \
                 if (s >= s_m) {              /* its window ended with the last column: keep that column */ \
                     fin[FIN_SB + lane] = (uint32_t)(LANE_SB ? s_cur : s);  \
@@ -468,11 +519,12 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
                 hpm = bv_orn2(hp_last, live); hnm = bv_and2(hn_last, live);           \
             }                                                                         \
             live &= ~(1ull << (s & (PBA_WAVE - 1)));                                  \
+            }                                                                         \
             s_cl = s + 1;                                                             \
             T_close = s_cl < S ? min(m, s_cl * RB + RB + w) + s_cl + 1 : INT_MAX;     \
         }                                                                             \
         if (t == T_open) {                                                            \
-            if (lane == (s_op & (PBA_WAVE - 1))) {                                    \
+            if (lane == PBA_BV_LANE_OF(s_op)) {                                       \
                 _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) { Pv[nb] = ~0u; Mv[nb] = 0u; } \
                 if constexpr (LANE_SB) opened = 1;                                    \
             }                                                                         \
@@ -498,12 +550,16 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     // hin of each lane's first block: the lane above's hout of the previous step, rotated one lane up, where that
     // hout was a window cell this lane takes; elsewhere the row above the window counts "+1 per column" (`live` above:
     // masked where it is handed out, PBA_BV_HOUT)
-#define PBA_BV_HIN()                                                                  \
-    uint64_t hp = (hpm << 1) | (hpm >> 63);                                           \
-    uint64_t hn = (hnm << 1) | (hnm >> 63);
+    // SHIFT: lane 0 is the top of the band and takes the border, every other lane its neighbour's hout as it is; CLOSED: the
+    // one step behind a close, where the lanes have moved one up instead and the carries are taken where they are (lane_shift.h)
+#define PBA_BV_HIN(CLOSED)                                                            \
+    uint64_t hp = SHIFT ? ((CLOSED) ? hpm : bv_shl1_or1(hpm)) : (hpm << 1) | (hpm >> 63); \
+    uint64_t hn = SHIFT ? ((CLOSED) ? hnm : bv_shl1(hnm)) : (hnm << 1) | (hnm >> 63);
 #define PBA_BV_HOUT()                                                                 \
+    if constexpr (SHIFT) { hpm = hp; hnm = hn; } else {                               \
     hp_last = hp; hn_last = hn;                                                       \
-    hpm = bv_orn2(hp, live); hnm = bv_and2(hn, live);
+    hpm = bv_orn2(hp, live); hnm = bv_and2(hn, live);                                 \
+    }
 
     // one block update (hp / hn: lane masks of the delta entering at the block's top row, replaced by the one leaving)
     // D0 (bit r set iff D(i,j) == D(i-1,j-1)) doubles as Myers' Xv in the two vertical updates (Hyyro's form of
@@ -551,12 +607,13 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
         const lds_u32 *const row = (const lds_u32 *)((const __attribute__((address_space(3))) uint8_t *)tab_lane + cq[OFS]); \
         _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) eqn[OFS][nb] = row[nb * PBA_EQT_LANES]; \
         }
-#define PBA_BV_STEP1(QD, OFS)                                                        \
+#define PBA_BV_STEP1(QD, OFS) PBA_BV_STEP1X(QD, OFS, false)
+#define PBA_BV_STEP1X(QD, OFS, CLOSED)                                               \
         {                                                                            \
         const int t = tb + k + (OFS);                                                \
         (void)t;                                                                     \
         PBA_BV_TEXT(OFS)                                                             \
-        PBA_BV_HIN();                                                                \
+        PBA_BV_HIN(CLOSED);                                                              \
         _Pragma("unroll")                                                            \
         for (int nb = 0; nb < NB; ++nb) {                                            \
             uint32_t d0, php, mhp, eq;                                               \
@@ -623,6 +680,8 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
         if (fail_row) break;
         int kend = min(32, t1 - tb + 1);
         for (int k = 0; k < kend;) {
+        bool closed = false;                     // SHIFT: a close fired in front of this step
+        (void)closed;
         if (tb + k == s_next) {
             const int t = tb + k;
             int seg_fail = 0;
@@ -630,6 +689,19 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
             // a segment that just ended may have failed the reference's check: leave right after this step (false
             // candidates die on their first segment, so they cost 33 steps, not the 64 of a poll per chunk)
             if (seg_fail) { fail_row = seg_fail; kend = k + 1; }
+        }
+        if constexpr (SHIFT) {
+            // the step behind a close, on its own: it takes the carries unshifted.  Every block's word collects under the
+            // one-hot (what lands in a word the diagonal is not in is cleared at the segment's end, as in the rings 3 and up)
+            if (closed) {
+                onehot_t oh = (onehot_t)bv_uniform64(one);
+                uint32_t cq[1] = {ta[0]}, eqn[1][NB];
+                PBA_BV_ROWS(0)
+                PBA_BV_STEP1X(NB == 1 ? 0 : -1, 0, true)
+                one = oh;
+                ta += 1; k += 1;
+                continue;
+            }
         }
         const int kstop = min(kend, s_next - tb);
         // The one-hot goes through the stretch in a local read with v_readfirstlane: `one` is set inside a loop that a
@@ -655,7 +727,8 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     s_next = min(T_open, T_close);               // the diagonal is done: what is left opens and closes windows
     // (Formed again from the raw carries rather than carried over: phase 1's loop has an early exit, and the compiler takes
     // what that loop leaves behind for divergent -- two values fewer to bring back to the scalar side.)
-    hpm = bv_orn2(hp_last, live); hnm = bv_and2(hn_last, live);
+    if constexpr (SHIFT) { hpm = bv_uniform64(hpm); hnm = bv_uniform64(hnm); }        // (SHIFT: the carries as they are, no mask)
+    else { hpm = bv_orn2(hp_last, live); hnm = bv_and2(hn_last, live); }
 
     // ------------------------------------------------------------------ phase 2: the superblocks below row m take the last column
     for (int tb = t1 + 1; tb <= t_end;) {
@@ -667,38 +740,47 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
         const int kend = min(32, k0 + (t_end - tb + 1));
         const int tc = tb - k0;                  // first step of the chunk
         for (int k = k0; k < kend;) {
+        bool closed = false;
+        (void)closed;
         if (tc + k == s_next) {
             const int t = tc + k;
             int seg_fail = 0;
             (void)seg_fail;
             PBA_BV_EVENTS(false);
         }
-        const int kstop = min(kend, s_next - tc);
-        do {
-        const int t = tc + k;
-        (void)t;
-        uint32_t cq[1] = {0u}, eqn[1][NB] = {};
-        (void)cq; (void)eqn;
-        if constexpr (EQT) { cq[0] = ta[0]; PBA_BV_ROWS(0) }
-        PBA_BV_TEXT(0)
-        PBA_BV_HIN();
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            uint32_t d0, php, mhp, eq;
-            PBA_BV_BLOCK(nb, php, mhp, d0, eq);
-            (void)d0; (void)eq; (void)php; (void)mhp;
-            if constexpr (TRACE == 1) {      // whole 128-byte lines only: a 16-lane group stores when any of its lanes is
-                if (st_on)                   // inside its window (masking lane by lane was measured 1.5x SLOWER: partial lines)
-                    PBA_BV_TRP()[nb * 64] = make_uint2(eq | ~d0, swap_roles ? Pv[nb] : php);
-            }
+#define PBA_BV_STEP2(CLOSED)                                                          \
+        {                                                                             \
+        const int t = tc + k;                                                         \
+        (void)t;                                                                      \
+        uint32_t cq[1] = {0u}, eqn[1][NB] = {};                                       \
+        (void)cq; (void)eqn;                                                          \
+        if constexpr (EQT) { cq[0] = ta[0]; PBA_BV_ROWS(0) }                          \
+        PBA_BV_TEXT(0)                                                                \
+        PBA_BV_HIN(CLOSED);                                                           \
+        _Pragma("unroll")                                                             \
+        for (int nb = 0; nb < NB; ++nb) {                                             \
+            uint32_t d0, php, mhp, eq;                                                \
+            PBA_BV_BLOCK(nb, php, mhp, d0, eq);                                       \
+            (void)d0; (void)eq; (void)php; (void)mhp;                                 \
+            if constexpr (TRACE == 1) {      /* whole 128-byte lines only: a 16-lane group stores when any of its lanes is */ \
+                if (st_on)                   /* inside its window (masking lane by lane was measured 1.5x SLOWER: partial lines) */ \
+                    PBA_BV_TRP()[nb * 64] = make_uint2(eq | ~d0, swap_roles ? Pv[nb] : php); \
+            }                                                                         \
+        }                                                                             \
+        PBA_BV_HOUT()                                                                 \
+        if constexpr (RING) ta += 1;                                                  \
         }
-        PBA_BV_HOUT()
-        if constexpr (RING) ta += 1;
-        } while (++k < kstop);
+        if constexpr (SHIFT) {
+            if (closed) { PBA_BV_STEP2(true) k += 1; continue; }   // the step behind a close (phase 1 above)
+        }
+        const int kstop = min(kend, s_next - tc);
+        do { PBA_BV_STEP2(false) } while (++k < kstop);
         }
         tb += kend - k0;
     }
 #undef PBA_BV_STRETCH1
+#undef PBA_BV_STEP2
+#undef PBA_BV_STEP1X
 #undef PBA_BV_STEP1
 #undef PBA_BV_ROWS
 #undef PBA_BV_TEXT
@@ -712,14 +794,18 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
     // D(i,m) = D(m,m) + the vertical deltas of column m over rows m+1..i (seq_aligner.h:192-211 scans exactly these cells,
     // upward from the diagonal, and keeps the first strict minimum).  A lane whose window is still open holds the
     // column in Pv / Mv, the others put it aside when their window closed.
+    // SHIFT: into the superblock's column, sb & 63 -- what follows reads column `lane`, whichever lane wrote it
     if (const int sb = PBA_BV_LANE_SB(); PBA_BV_LANE_OPEN() && sb >= s_m && sb < S) {
-        fin[FIN_SB + lane] = (uint32_t)sb;
+        const int col = SHIFT ? lsh_col(lane, s_cl) : lane;
+        fin[FIN_SB + col] = (uint32_t)sb;
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) { fin[2 * nb * PBA_WAVE + lane] = Pv[nb]; fin[(2 * nb + 1) * PBA_WAVE + lane] = Mv[nb]; }
+        for (int nb = 0; nb < NB; ++nb) { fin[2 * nb * PBA_WAVE + col] = Pv[nb]; fin[(2 * nb + 1) * PBA_WAVE + col] = Mv[nb]; }
     }
 #undef PBA_BV_LANE_OPEN
 #undef PBA_BV_LANE_SB
-    const int fin_s = (int)fin[FIN_SB + lane];      // (a lane reads what it wrote itself: no barrier)
+#undef PBA_BV_LANE_OF
+#undef tab_lane
+    const int fin_s = (int)fin[FIN_SB + lane];      // (a wavefront's LDS operations complete in order: no barrier)
     int b_tot[NB], b_min[NB], b_pos[NB];          // per block of this lane's last superblock: sum, lowest prefix sum, its bit
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
