@@ -1,6 +1,6 @@
 // pba_host.h -- host-side objects and helpers shared by the translation units of libpba.so (pba_core.hip: context,
 // sequence sets; pba_index.hip: seed index; pba_align.hip: explicit pairs and edit scripts; pba_drivers.hip: the reference's ordered
-// first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: read correction; pba_stream.hip: streamed locate and mapping; pba_layout.hip: layout; pba_clip.hip: clipping; pba_hpc.hip: homopolymer compression; pba_census.hip: seed-key census; pba_cigar.hip: run-length alignments and PAF; pba_windows.hip: per-window counts and trimmed rows; pba_sites.hip: variant sites and per-row alleles;
+// first-success loops; pba_overlap.hip: all-vs-all; pba_cons.hip: consensus voting; pba_pileup.hip: the pile-ups' vote boxes, their votes and evolve; pba_pile_drivers.hip: read correction, contig polishing and layout consensus over them; pba_stream.hip: streamed locate and mapping; pba_layout.hip: layout; pba_clip.hip: clipping; pba_hpc.hip: homopolymer compression; pba_census.hip: seed-key census; pba_cigar.hip: run-length alignments and PAF; pba_windows.hip: per-window counts and trimmed rows; pba_sites.hip: variant sites and per-row alleles;
 // pba_fastx.hip: FASTA / FASTQ in, FASTA out; pba_qual.hip: per-base evidence, its summaries and spans, FASTQ out).  Internal: nothing here is part of the C ABI (include/pba.h).
 // (What host and device share about the seed index -- the visiting rule, compress / compress_masks -- is index_plan.h's.)
 // Also here, once for all of them: the clip of seq_aligner.h:94-102 (text_clip), the launch plan (make_plan), the host
@@ -635,9 +635,24 @@ PBA_INTERNAL int seqs_pack(pba_ctx *ctx, const uint8_t *d_text, const uint64_t *
 PBA_INTERNAL int qual_adopt(pba_ctx *ctx, uint32_t n, const uint64_t *h_off, void *arr[4], pba_qual **out);
 // pba_map_reads' checks of its index and target (pba_drivers.hip)
 PBA_INTERNAL int map_target_ok(pba_ctx *ctx, const pba_index *ix, const pba_seqs *target);
-// a live pile-up as the site scan reads it; a spent one is PBA_E_INVALID under who's name (pba_pileup.hip)
+// a live pile-up as the site scan reads it; a spent one is PBA_E_INVALID under who's name (pba_pileup.hip).  Spent is its ONLY
+// failure: correct_vote (pba_pile_drivers.hip) asks it whether a pile-up is spent, so another reason to fail needs another call
 struct PileView { ConsDev C; const unsigned long long *d_box_off; const uint64_t *box_off; uint32_t t_lo, t_hi, n_reads; int weight; uint64_t n_boxes; };
 PBA_INTERNAL int pile_view(pba_ctx *ctx, const char *who, const pba_pileup *p, PileView *v);
+// What the drivers of pba_pile_drivers.hip take from a pile-up (pba_pileup.hip).  A pile-up holds fewer boxes than kPileMaxBoxes.
+// PileText: a pile-up evolved to one contiguous device text, target k at text[off[k] .. off[k+1]); d_off: off on the device
+// (nt + 1 u64).  qmax >= 0: evolve also writes the evidence of every character (qual.h), one entry per text byte.
+static const uint64_t kPileMaxBoxes = (1ull << 31) - 65536;
+struct PileText {
+    DevBuf text, d_off;
+    std::vector<uint64_t> off;
+    int qmax = -1;
+    DevBuf qv, depth, agree, src;
+};
+// evolve to *T (and the rows of rows_out, where given); the boxes are released
+PBA_INTERNAL int pile_evolve_text(pba_ctx *ctx, pba_pileup *p, PileText *T, pba_correct_row *rows_out);
+// the evidence arrays of T into a pba_qual of its nt sequences (they leave T)
+PBA_INTERNAL int pile_text_qual(pba_ctx *ctx, PileText &T, uint32_t nt, pba_qual **qual);
 }  // extern "C"
 
 #endif

@@ -134,12 +134,13 @@ EDGE_INS = (4095, 8191)            # an inserted base right after these contig p
 EDGE_DEL = ((12287, 12288), (16384,))   # contig bases the reads lack (12 287: a tile's last box; 12 288, 16 384: a tile's first box)
 
 
-def edge_case(seed: int):
-    """(contig of 70 001 bases, 24 reads): 6 reads over each planted site, exact copies of 900 bases of the contig apart from
-    the plant, starting 400 - 485 bases before it.  The contig reads ACGT around every site and the inserted base is a T
-    between the C and the G, so that the cheapest alignment is unique and puts the edit on the planted box."""
+def edge_case(seed: int, length: int = 70001):
+    """(contig of `length` bases, 24 reads): 6 reads over each planted site, exact copies of 900 bases of the contig apart from
+    the plant, starting 400 - 485 bases before it (every read ends below 16 900).  The contig reads ACGT around every site and
+    the inserted base is a T between the C and the G, so that the cheapest alignment is unique and puts the edit on the
+    planted box."""
     rng = np.random.default_rng(seed)
-    T = bytearray(rand_text(rng, 70001))
+    T = bytearray(rand_text(rng, length))
     reads = []
     for site in EDGE_INS:
         T[site - 1:site + 3] = b"ACGT"                                  # C at `site`, G behind it

@@ -143,6 +143,71 @@ def test_tiled_kernels_at_tile_edges(ctx):
     assert (np.diff((src & 0x7FFFFFFF).astype(np.int64)) >= 0).all() and int(src[-1]) == len(T) - 1
 
 
+# ----------------------------------------------------------------------------- 3b: the two forms held to each other
+@pytest.fixture(scope="module")
+def form_sets(ctx):
+    """name -> (targets, weight, vote): the pile case (plants at a step's last thread, at lane 63, at lane 0 of wave 1, the
+    tie), the unvoted texts of 63 ... 1 025 bases at both weights, and the tile-edge plants in a contig short enough for the
+    per-target kernels -- there a box's two characters lie inside a step, and straddle a tile's end in the tiled form.  Its
+    rows come from the mapper once, on the short set; the contig's index is the same in both."""
+    contigs, reads, rows = vb.pile_case()
+    Rd = ctx.seqs_from_list(reads, strict_acgt=True)
+    sets = {"pile_case": (list(contigs), 1, lambda p: p.vote_mapped(Rd, rows, vb.R, vb.OVERLAP_MIN))}
+    for w in vb.NOVOTE_WEIGHTS:
+        sets[f"novote_w{w}"] = (list(vb.novote_texts()), w, lambda p: None)
+    T, ereads = edge_case(711, vb.FORM_EDGE_LEN)
+    Re = ctx.seqs_from_list(ereads, strict_acgt=True)
+    erows = map_rows(ctx, ctx.seqs_from_list([T], strict_acgt=True), Re, strands=1)
+    assert erows["found"].all()
+    sets["tile_edges"] = ([T], 1, lambda p: p.vote_mapped(Re, erows, R, OVERLAP_MIN))
+    return sets
+
+
+@pytest.mark.parametrize("name", ["pile_case", "novote_w1", "novote_w65535", "tile_edges"])
+def test_per_target_and_tiled_forms_agree(ctx, form_sets, name):
+    """A set runs the per-target kernels when it stands alone and the tiled ones, for every segment, once one unvoted sequence
+    of 65 537 bases -- the shortest that switches the form -- stands behind it.  Same rows voted into both: the original
+    targets' texts, rows and evidence are equal byte for byte, plainly evolved and with evidence, and the appended target
+    comes back as its own text.  (The threshold is the library's PBA_PILE_LONG_SEG, 65 536 unless a tuning build sets another;
+    nothing exposes it, so vb.FORM_LONG_SEG restates the default.  Against a build with a threshold above 65 537 both pile-ups
+    would run the per-target kernels and this test would compare that form with itself.)"""
+    targets, weight, vote = form_sets[name]
+    extra = vb.form_switch_text()
+    n = len(targets)
+    assert max(len(t) for t in targets) <= 65536 < len(extra) == vb.FORM_SWITCH_LEN == 65537
+    short = ctx.seqs_from_list(targets, strict_acgt=True)
+    long_ = ctx.seqs_from_list(targets + [extra], strict_acgt=True)
+
+    def piles():
+        a, b = Pileup(ctx, short, weight=weight), Pileup(ctx, long_, weight=weight)
+        vote(a); vote(b)
+        return a, b
+
+    a, b = piles()
+    (out_a, crows_a), (out_b, crows_b) = a.evolve(), b.evolve()
+    assert texts_of(out_b) == texts_of(out_a) + [extra]
+    assert crows_b[:n].tobytes() == crows_a.tobytes()
+    assert int(crows_b[n]["n_rows"]) == 0 and int(crows_b[n]["len_out"]) == len(extra)
+    a, b = piles()
+    (qout_a, qrows_a, qual_a), (qout_b, qrows_b, qual_b) = a.evolve_qual(), b.evolve_qual()
+    assert texts_of(qout_a) == texts_of(out_a) and texts_of(qout_b) == texts_of(out_b)
+    assert qrows_a.tobytes() == crows_a.tobytes() and qrows_b.tobytes() == crows_b.tobytes()
+    assert qual_b.lengths().tolist() == qual_a.lengths().tolist() + [len(extra)]
+    got, want = qual_b.get(0, n), qual_a.get()
+    for k in KEYS:
+        assert got[k].dtype == want[k].dtype and got[k].tobytes() == want[k].tobytes(), (name, k)
+    g = qual_b.get(n, n + 1)
+    assert not g["depth"].any() and (g["agree"] == weight).all() and (g["src"] == np.arange(len(extra))).all()
+    if name == "tile_edges":                                                     # the input is what it is named for
+        src = want["src"]
+        assert (src[src >= qr.SUP] & 0x7FFFFFFF).tolist() == list(EDGE_INS)
+        kept = set((src & 0x7FFFFFFF).tolist())
+        assert all(x not in kept for d in EDGE_DEL for x in d)
+    elif name == "pile_case":
+        src = qual_a.get(vb.PILE_C, vb.PILE_C + 1)["src"]
+        assert (src[src >= qr.SUP] & 0x7FFFFFFF).tolist() == sorted(vb.PILE_INS)
+
+
 # ----------------------------------------------------------------------------- 4: no votes
 @pytest.mark.parametrize("weight", vb.NOVOTE_WEIGHTS)
 def test_no_votes(ctx, weight):

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import votebox_inputs as vb
-from polish_helpers import oracle_boxes, oracle_evolve, oracle_vote, yields
+from polish_helpers import EDGE_DEL, EDGE_INS, TILE, edge_case, oracle_boxes, oracle_evolve, oracle_vote, yields
 
 EVOLVE = {s.name: s for s in vb.evolve_states()}
 ELECT = {s.name: s for s in vb.elect_states()}
@@ -241,3 +241,28 @@ def test_pile_case_yields_what_was_planted(oracle):
 def test_novote_lengths_straddle_wave_step_and_chunk():
     assert set(vb.NOVOTE_LENS) == {k + e for k in (64, 256, 512, 1024) for e in (-1, 0, 1)}
     assert [len(t) for t in vb.novote_texts()] == list(vb.NOVOTE_LENS) and vb.NOVOTE_WEIGHTS == (1, 65535)
+
+
+def test_form_sets_sit_on_either_side_of_the_switch():
+    """What test_gpu_qual.py's comparison of the two kernel forms relies on: every original target is served by the per-target
+    kernels, the appended sequence is the shortest that is not, and the 20 000-base edge case carries its plants where
+    EDGE_INS and EDGE_DEL say, in the text and in its reads."""
+    assert vb.FORM_LONG_SEG == 65536 and vb.FORM_SWITCH_LEN == len(vb.form_switch_text()) == 65537
+    assert set(vb.form_switch_text()) <= set(b"ACGT")
+    T, reads = edge_case(711, vb.FORM_EDGE_LEN)
+    originals = list(vb.pile_case()[0]) + list(vb.novote_texts()) + [T]
+    assert max(len(t) for t in originals) <= vb.FORM_LONG_SEG
+    assert len(T) == vb.FORM_EDGE_LEN == 20000 and len(edge_case(711)[0]) == 70001
+    plants = [(s, 0) for s in EDGE_INS] + [(d[0], len(d)) for d in EDGE_DEL]
+    assert [s % TILE for s in EDGE_INS] == [TILE - 1] * 2 and [tuple(b % TILE for b in d) for d in EDGE_DEL] == [(TILE - 1, 0), (0,)]
+    assert len(reads) == 6 * len(plants)
+    for p, (site, lost) in enumerate(plants):
+        assert T[site - 1:site + 3] == (b"ACGA" if lost == 1 else b"ACGT")
+        for k, r in enumerate(reads[6 * p:6 * p + 6]):
+            s = site - 400 - 17 * k
+            at = site - s
+            assert 0 <= s and s + 900 < 16900 <= len(T)
+            if lost:
+                assert len(r) == 900 - lost and r[:at] == T[s:site] and r[at:] == T[site + lost:s + 900]
+            else:
+                assert len(r) == 901 and r[:at + 1] == T[s:site + 1] and r[at + 1:at + 2] == b"T" and r[at + 2:] == T[site + 1:s + 900]

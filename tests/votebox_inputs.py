@@ -608,3 +608,15 @@ NOVOTE_WEIGHTS = (1, 65535)
 def novote_texts():
     rng = np.random.default_rng(7171)
     return tuple(rand_text(rng, n) for n in NOVOTE_LENS)
+
+
+# ----------------------------------------------------------------------------- the two forms of the pile-up kernels
+# (the default of PBA_PILE_LONG_SEG in csrc/pba_pileup.hip, restated: the library does not expose it)
+FORM_LONG_SEG = 65536       # a pile-up runs the per-target kernels while no segment is longer than this, else the tiled ones
+FORM_SWITCH_LEN = FORM_LONG_SEG + 1     # the shortest sequence that, appended to a set, switches all of it to the tiled kernels
+FORM_EDGE_LEN = 20000       # polish_helpers.edge_case in a contig the per-target kernels serve: every plant and read below 16 900
+
+
+@functools.lru_cache(maxsize=None)
+def form_switch_text():
+    return rand_text(np.random.default_rng(8181), FORM_SWITCH_LEN)
