@@ -1524,6 +1524,76 @@ int pba_map_rows_alleles_budget(pba_ctx *ctx, const pba_seqs *target, const pba_
                                 uint64_t cap, uint64_t *off, uint64_t *n_total, pba_allele_counts *sum, pba_result *res,
                                 uint64_t max_slots);
 
+/* ---- overlap rows phased by their alleles; reads corrected from their own copy ----
+ * At a SEL site the rows of a target split into those that come from the target's own copy (haplotype, repeat copy) and those
+ * that come from the other one.  The phase rule decides which, from allele records alone, in integers:
+ *   v         of a record, from its site: +1 if allele == major, -1 if allele == minor, else 0
+ *   o0[s]     the seed orientation of SEL site s: +1 if own == major, -1 if own == minor, else 0; o = +1 reads "major is the
+ *             allele of the target's own copy"
+ *   lab(g)    sign(g) if |g| >= min_margin, else 0; sign(0) = 0
+ *   o(0) = o0; for k = 1 .. n_iter:  h(k)[r] = lab(sum over the records of row r of o(k-1)[site] * v)
+ *                                    f(k)[s] = self_weight * o0[s] + sum over the records at s of h(k)[row] * v
+ *                                    o(k)    = sign(f(k))
+ *   g[r] = sum over the records of row r of o(n_iter)[site] * v; label[r] = lab(g[r]).  There is no early stop.
+ * label +1: the row is from the target's own copy; -1: from the other copy; 0: undecided.  n_iter in [0, PBA_PHASE_MAX_ITER],
+ * min_margin >= 1, self_weight in [0, 65535]; else PBA_E_INVALID.
+ *   pba_phase_row   per row: label, score = g, n_informative = the records with v != 0 at a site whose final o != 0, n_records
+ *   pba_phase_site  per SEL site of the object, in SEL-rank order (pba_sites_count_sel of them): site = index into the records,
+ *                   orient = o(n_iter), score = the last f (self_weight * o0 for n_iter == 0), n_agree / n_disagree = the
+ *                   records with label[row] * v * orient > 0 / < 0 under the final labels
+ *   pba_phase_stats n_same / n_other / n_unphased: rows with label +1 / -1 / 0; n_sites: SEL sites; n_flipped_last: sites with
+ *                   o(n_iter) != o(n_iter - 1), 0 for n_iter == 0; HIP events on the ctx's stream: the traced passes (0 for
+ *                   pba_alleles_phase), the phase kernels */
+#define PBA_PHASE_MAX_ITER 64
+typedef struct { int32_t n_iter, min_margin, self_weight; } pba_phase_params;
+typedef struct { int32_t label, score, n_informative, n_records; } pba_phase_row;
+typedef struct { uint32_t site; int32_t orient, score, n_agree, n_disagree; } pba_phase_site;
+typedef struct {
+    uint64_t n_rows, n_same, n_other, n_unphased, n_sites, n_records, n_flipped_last;
+    float alleles_ms, phase_ms;
+} pba_phase_stats;
+/* the SEL records of the object: what sites_out of the calls below holds */
+uint64_t pba_sites_count_sel(const pba_sites *s);
+/* The phase kernels on records the caller supplies (row r: rec[off[r] .. off[r + 1]), so that the rule can be pinned apart from
+ * the aligner (pba_windows_trim's counterpart).  Checked on the host, each PBA_E_INVALID: off must not decrease; a record's
+ * site must be below pba_sites_count and a SEL record, its allele <= PBA_ALLELE_DEL; a row's sites strictly ascending and of
+ * one target; the parameters in range.  n == 0 is legal (the sites then keep their seed orientation). */
+int pba_alleles_phase(pba_ctx *ctx, const pba_sites *sites, const pba_allele *rec, const uint64_t *off, uint64_t n,
+                      const pba_phase_params *params, pba_phase_row *rows_out, pba_phase_site *sites_out /* nullable */,
+                      pba_phase_stats *stats /* nullable */);
+/* Overlap rows phased.  The records are made as pba_overlap_rows_alleles makes them (every row held to its cost and matlens;
+ * `sites` of the target set, every row's target in their range), gathered chunk after chunk into one device buffer and phased
+ * there: no record crosses the host.  rows_out: n entries; res (nullable) as pba_overlap_rows_alleles returns it. */
+int pba_overlap_rows_phase(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, const pba_strand_overlap *rows, uint64_t n,
+                           double R, const pba_sites *sites, const pba_phase_params *params, pba_phase_row *rows_out,
+                           pba_phase_site *sites_out /* nullable */, pba_phase_stats *stats /* nullable */, pba_result *res /* nullable */);
+int pba_overlap_rows_phase_budget(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, const pba_strand_overlap *rows,
+                                  uint64_t n, double R, const pba_sites *sites, const pba_phase_params *params, pba_phase_row *rows_out,
+                                  pba_phase_site *sites_out /* nullable */, pba_phase_stats *stats /* nullable */,
+                                  pba_result *res /* nullable */, uint64_t max_slots);
+/* Host: the rows with label > 0, and those with label == 0 when keep_unphased, in order and unchanged; returns their number
+ * (out_rows holds up to n; may alias rows), -1 for a NULL.  Unlike trimmed rows these stay valid for every call that re-runs
+ * the alignment (votes, cigars, windows, alleles, layout). */
+int64_t pba_phase_rows_apply(const pba_strand_overlap *rows, const pba_phase_row *phase, uint64_t n, int keep_unphased,
+                             pba_strand_overlap *out_rows);
+/* pba_correct_reads with every target voted by the rows of its own copy only.  Per chunk of targets: overlaps, a pile-up voted
+ * by all rows, pba_pileup_sites under (min_depth, min_alt, min_permille), that pile-up destroyed, the rows phased
+ * (pba_overlap_rows_phase), pba_phase_rows_apply under keep_unphased, a fresh pile-up voted by the kept rows only, evolve; the
+ * texts stitched as pba_correct_reads stitches them.  rows_out[].n_rows counts the rows kept; *phase_stats (nullable) is summed
+ * over the chunks.  Arguments, limits and stats otherwise as pba_correct_reads_budget; the answer does not depend on the cut.
+ * Without a SEL site every label is 0: with keep_unphased the result is pba_correct_reads', byte for byte.  An inconsistency
+ * among the engine's own rows is PBA_E_HIP, as there. */
+int pba_correct_reads_phased(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t t_lo, uint32_t t_hi,
+                             uint32_t mask, double R, int max_trial, int overlap_min, int kernel, int strands, int weight,
+                             int min_depth, int min_alt, int min_permille, const pba_phase_params *params, int keep_unphased,
+                             pba_seqs **corrected, pba_correct_row *rows_out, pba_phase_stats *phase_stats /* nullable */,
+                             pba_overlap_stats stats[2]);
+int pba_correct_reads_phased_budget(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t t_lo, uint32_t t_hi,
+                                    uint32_t mask, double R, int max_trial, int overlap_min, int kernel, int strands, int weight,
+                                    uint64_t max_boxes, int min_depth, int min_alt, int min_permille, const pba_phase_params *params,
+                                    int keep_unphased, pba_seqs **corrected, pba_correct_row *rows_out,
+                                    pba_phase_stats *phase_stats /* nullable */, pba_overlap_stats stats[2]);
+
 const char *pba_strerror(int status);
 
 #ifdef __cplusplus

@@ -380,6 +380,16 @@ SYMBOLS = {
     "pba_overlap_rows_alleles_budget": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_double, _P, _P, C.c_uint64, _P, C.POINTER(C.c_uint64), _P, _P, C.c_uint64]),
     "pba_map_rows_alleles": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.c_double, C.c_int, _P, _P, C.c_uint64, _P, C.POINTER(C.c_uint64), _P, _P]),
     "pba_map_rows_alleles_budget": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.c_double, C.c_int, _P, _P, C.c_uint64, _P, C.POINTER(C.c_uint64), _P, _P, C.c_uint64]),
+    "pba_sites_count_sel": (C.c_uint64, [_P]),
+    "pba_alleles_phase": (C.c_int, [_P, _P, _P, _P, C.c_uint64, _P, _P, _P, _P]),
+    "pba_overlap_rows_phase": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_double, _P, _P, _P, _P, _P, _P]),
+    "pba_overlap_rows_phase_budget": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_double, _P, _P, _P, _P, _P, _P, C.c_uint64]),
+    "pba_phase_rows_apply": (C.c_int64, [_P, _P, C.c_uint64, C.c_int, _P]),
+    "pba_correct_reads_phased": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.POINTER(_P), _P, _P, _P]),
+    "pba_correct_reads_phased_budget": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_int, C.c_int, C.c_int,
+                                                  C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.POINTER(_P), _P,
+                                                  _P, _P]),
     "pba_strerror": (C.c_char_p, [C.c_int]),
 }
 

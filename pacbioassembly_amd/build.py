@@ -21,7 +21,7 @@ LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(LIBDIR, "obj")
 LIB = os.path.join(LIBDIR, "libpba.so")
 
-SOURCES = ["pba_core.hip", "pba_index.hip", "pba_align.hip", "pba_drivers.hip", "pba_overlap.hip", "pba_cons.hip", "pba_pileup.hip", "pba_pile_drivers.hip", "pba_stream.hip", "pba_layout.hip", "pba_clip.hip", "pba_hpc.hip", "pba_census.hip", "pba_cigar.hip", "pba_windows.hip", "pba_fastx.hip", "pba_qual.hip", "pba_sites.hip",
+SOURCES = ["pba_core.hip", "pba_index.hip", "pba_align.hip", "pba_drivers.hip", "pba_overlap.hip", "pba_cons.hip", "pba_pileup.hip", "pba_pile_drivers.hip", "pba_stream.hip", "pba_layout.hip", "pba_clip.hip", "pba_hpc.hip", "pba_census.hip", "pba_cigar.hip", "pba_windows.hip", "pba_fastx.hip", "pba_qual.hip", "pba_sites.hip", "pba_phase.hip",
            "pba_codec.cpp", "pba_synth.cpp"]
 # the exchange over RCCL for C / C++ hosts (include/pba_dist.h): host code only, its own small library next to libpba.so
 DIST_SOURCE = "pba_dist.hip"

@@ -1,5 +1,6 @@
 // pba_pile_drivers.hip -- the drivers over pile-ups (csrc/pba_pileup.hip): pba_correct_reads chains overlap -> vote ->
-// evolve over a read set, pba_polish_contigs polishes a contig set from its mapped reads round after round, and
+// evolve over a read set (pba_correct_reads_phased: with the rows of the other copy phased out between two votes),
+// pba_polish_contigs polishes a contig set from its mapped reads round after round, and
 // pba_layout_consensus votes a layout's reads onto its contigs from their placements.  Host code only: no kernel is
 // launched from here, and the pile-up is reached through its public calls and through pile_evolve_text / PileText
 // (pba_host.h).  The three drivers share their run state (PileRun), the budget of a range and its greedy take, the
@@ -276,6 +277,97 @@ int pba_correct_reads_budget(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs
                              uint64_t max_boxes, pba_seqs **corrected, pba_correct_row *rows_out, pba_overlap_stats stats[2]) {
     return correct_run(ctx, reads, reads_rc, t_lo, t_hi, mask, R, max_trial, overlap_min, kernel, strands, weight, max_boxes, corrected,
                        rows_out, stats, -1, nullptr);
+}
+
+// ---- pba_correct_reads_phased: every target voted by the rows of its own copy only ----
+struct PhaseGate { int min_depth, min_alt, min_permille; pba_phase_params params; int keep_unphased; pba_phase_stats tot; };
+
+static void phase_stats_add(pba_phase_stats &a, const pba_phase_stats &b) {
+    a.n_rows += b.n_rows; a.n_same += b.n_same; a.n_other += b.n_other; a.n_unphased += b.n_unphased; a.n_sites += b.n_sites;
+    a.n_records += b.n_records; a.n_flipped_last += b.n_flipped_last; a.alleles_ms += b.alleles_ms; a.phase_ms += b.phase_ms;
+}
+
+// The chunk's rows narrowed to those that are not from the other copy: the sites of the pile-up all rows voted into (which is
+// destroyed), the rows phased against them, c.rows / c.n_rows replaced by the rows kept.  The rows are the engine's own: one
+// that does not re-run to itself is PBA_E_HIP, as in correct_vote.
+static int correct_phase(CorrectRun &c, PhaseGate &g) {
+    pba_ctx *ctx = c.ctx;
+    const auto timed = c.clk.time(ctx->stream, &c.prof.vote_ms);
+    pba_sites *sites = nullptr;
+    PBA_TRY(pba_pileup_sites(ctx, c.pile, c.reads, g.min_depth, g.min_alt, g.min_permille, &sites));
+    struct Guard { pba_sites *s; ~Guard() { pba_sites_destroy(s); } } guard{sites};
+    pba_pileup_destroy(c.pile); c.pile = nullptr;
+    std::vector<pba_phase_row> ph(std::max<uint64_t>(c.n_rows, 1));
+    pba_phase_stats st;
+    const int rc = pba_overlap_rows_phase(ctx, c.reads, c.reads_rc, c.rows.data(), c.n_rows, c.R, sites, &g.params, ph.data(), nullptr, &st,
+                                          nullptr);
+    if (rc == PBA_E_INVALID) {
+        char keep[sizeof ctx->err];
+        memcpy(keep, ctx->err, sizeof keep);
+        snprintf(ctx->err, sizeof ctx->err, "pba_correct_reads_phased: %.400s", keep);
+        return PBA_E_HIP;
+    }
+    PBA_TRY(rc);
+    phase_stats_add(g.tot, st);
+    const int64_t kept = pba_phase_rows_apply(c.rows.data(), ph.data(), c.n_rows, g.keep_unphased, c.rows.data());
+    if (kept < 0) PBA_FAIL(PBA_E_HIP, "pba_correct_reads_phased: rows");
+    c.n_rows = (uint64_t)kept;
+    return PBA_OK;
+}
+
+int pba_correct_reads_phased_budget(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t t_lo, uint32_t t_hi,
+                                    uint32_t mask, double R, int max_trial, int overlap_min, int kernel, int strands, int weight,
+                                    uint64_t max_boxes, int min_depth, int min_alt, int min_permille, const pba_phase_params *params,
+                                    int keep_unphased, pba_seqs **corrected, pba_correct_row *rows_out, pba_phase_stats *phase_stats,
+                                    pba_overlap_stats stats[2]) {
+    static const char who[] = "pba_correct_reads_phased";
+    if (!ctx || !reads || !corrected || !params || t_lo > t_hi || t_hi > reads->n) return PBA_E_INVALID;
+    *corrected = nullptr;
+    PBA_TRY(correct_check(ctx, reads, reads_rc, max_trial, strands, weight));
+    if (min_depth < 1 || min_alt < 1 || min_permille < 0 || min_permille > 1000)
+        return ctx_fail_as(ctx, PBA_E_INVALID, who, "min_depth and min_alt must be at least 1, min_permille in [0, 1000]");
+    if (params->n_iter < 0 || params->n_iter > PBA_PHASE_MAX_ITER || params->min_margin < 1 || params->self_weight < 0 || params->self_weight > 0xFFFF)
+        return ctx_fail_as(ctx, PBA_E_INVALID, who, "n_iter must be in [0, 64], min_margin at least 1, self_weight in [0, 65535]");
+    HIPCHK(hipSetDevice(ctx->device));
+    CorrectRun c{{ctx, reads, reads_rc}, t_lo, t_hi, R, overlap_min, kernel, strands, weight};
+    PhaseGate g{min_depth, min_alt, min_permille, *params, keep_unphased, {}};
+    if (!c.clk.init()) PBA_FAIL(PBA_E_HIP, "pba_correct_reads_phased: events");
+    memset(&c.prof, 0, sizeof c.prof);
+    memset(c.tot, 0, sizeof c.tot);
+    memset(&g.tot, 0, sizeof g.tot);
+    PBA_TRY(correct_prepare(c, mask, max_trial));
+    uint32_t lo = t_lo, shrink = 0;                  // (the chunk loop of correct_run, with the phase between two votes)
+    while (lo < t_hi) {
+        uint32_t hi = lo;
+        uint64_t boxes = 0;
+        bool halve = false;
+        PileBudget b;
+        PBA_TRY(pile_budget(ctx, max_boxes, shrink, &b));
+        pile_take(reads, lo, t_hi, b.budget, &hi, &boxes);
+        const int st = correct_overlaps(c, lo, hi, &halve);
+        if (halve) { ++shrink; continue; }
+        if (st != PBA_OK) return st;
+        PBA_TRY(correct_vote(c, lo, hi));
+        PBA_TRY(correct_phase(c, g));
+        PBA_TRY(correct_vote(c, lo, hi));
+        PBA_TRY(c.evolve_chunk(&c.prof.evolve_ms, rows_out ? rows_out + (lo - t_lo) : nullptr));
+        c.prof.n_rows += c.n_rows; c.prof.n_bases_in += boxes; ++c.prof.n_chunks;
+        lo = hi;
+    }
+    PBA_TRY(correct_stitch(c, corrected, nullptr));
+    ctx->cprof = c.prof;
+    if (stats) { stats[0] = c.tot[0]; stats[1] = c.tot[1]; }
+    if (phase_stats) *phase_stats = g.tot;
+    return PBA_OK;
+}
+
+int pba_correct_reads_phased(pba_ctx *ctx, const pba_seqs *reads, const pba_seqs *reads_rc, uint32_t t_lo, uint32_t t_hi,
+                             uint32_t mask, double R, int max_trial, int overlap_min, int kernel, int strands, int weight,
+                             int min_depth, int min_alt, int min_permille, const pba_phase_params *params, int keep_unphased,
+                             pba_seqs **corrected, pba_correct_row *rows_out, pba_phase_stats *phase_stats,
+                             pba_overlap_stats stats[2]) {
+    return pba_correct_reads_phased_budget(ctx, reads, reads_rc, t_lo, t_hi, mask, R, max_trial, overlap_min, kernel, strands, weight, 0,
+                                           min_depth, min_alt, min_permille, params, keep_unphased, corrected, rows_out, phase_stats, stats);
 }
 
 // what every *_qual driver checks before anything happens

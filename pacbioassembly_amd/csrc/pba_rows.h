@@ -1,7 +1,8 @@
 // pba_rows.h -- the host side the bounded-slot outlets of the traced pass share (pba_cigar.hip: runs, T = uint32_t;
 // pba_windows.hip: per-window counts, T = pba_aln_counts; pba_sites.hip: alleles at selection sites, T = pba_allele): one batch
 // of slots through trace_batch, and the chunk loop of the row-level entry points (a job marked not_held is not held to its row).
-// (The script walker and the row layout need no device: aln_rows.h.)
+// (The script walker and the row layout need no device: aln_rows.h.)  Behind them the sites object and the slot bound of the
+// alleles outlet, which pba_sites.hip and pba_phase.hip share.  Host code only.
 #ifndef PBA_ROWS_H
 #define PBA_ROWS_H
 
@@ -127,6 +128,45 @@ static inline std::vector<uint64_t> job_rows(const std::vector<RowJob> &jobs) {
     std::vector<uint64_t> r(jobs.size());
     for (size_t j = 0; j < jobs.size(); ++j) r[j] = jobs[j].row;
     return r;
+}
+
+// ---- the sites object (made in pba_sites.hip; its alleles outlet is also driven from pba_phase.hip) ----------------------------
+struct pba_sites {
+    int device;
+    uint32_t t_lo, t_hi, n_seqs;
+    uint64_t n, n_sel, n_boxes, words;
+    pba_site *d_recs;                   // n records, sorted by (target, pos, kind)
+    unsigned long long *d_bm;           // SEL bitmap of the arena, words + 1 (the last: zero)
+    uint32_t *d_rank;                   // inclusive scan of the words' SEL counts
+    uint2 *d_sel;                       // per SEL site, in rank order: { record index, own | major << 4 | minor << 8 }
+    unsigned long long *d_box_off;      // nt + 1
+    // on the host, for the per-row slot bounds, the target ranges and the checks of caller-supplied allele records
+    std::vector<uint64_t> box_off, rec_off, sel_off;    // nt + 1 each
+    std::vector<int32_t> sel_pos;                       // the SEL positions, target by target
+    std::vector<uint32_t> sel_rec;                      // the record index of every SEL site, in rank order
+    AllelesInto view() const { return AllelesInto{d_bm, d_rank, d_sel, d_box_off, t_lo, n_boxes}; }
+};
+
+static const uint64_t kAlleleChunkSlots = 1ull << 27;   // bounded allele slots of one chunk of rows on the device (1 GiB)
+
+// `set` is the set these sites were made from, as far as lengths can tell
+static inline bool sites_same_set(const pba_sites *s, const pba_seqs *set) {
+    if (set->n != s->n_seqs) return false;
+    for (uint32_t k = 0; k < s->t_hi - s->t_lo; ++k)
+        if (s->box_off[k + 1] - s->box_off[k] != set->h_len[s->t_lo + k]) return false;
+    return true;
+}
+
+// The SEL sites in the a-span the accessor could cover at most: the clipped len_a elements from a_pos, by binary search in
+// the host's positions.  0 is a legal bound: the row is still walked and held.
+static inline uint64_t pair_alleles_bound(const pba_sites *s, const pba_pair &p, double R) {
+    const int la = text_clip(p.a_len, p.b_len, R).len_a;
+    if (la < 1) return 0;
+    const int64_t last = (p.flags & PBA_A_BACKWARD) ? (int64_t)p.a_pos - (la - 1) : (int64_t)p.a_pos + (la - 1);
+    const int64_t lo = std::min<int64_t>(p.a_pos, last), hi = std::max<int64_t>(p.a_pos, last);
+    const size_t k = p.a_seq - s->t_lo;
+    const int32_t *b = s->sel_pos.data() + s->sel_off[k], *e = s->sel_pos.data() + s->sel_off[k + 1];
+    return (uint64_t)(std::upper_bound(b, e, (int32_t)std::min<int64_t>(hi, 0x7FFFFFFF)) - std::lower_bound(b, e, (int32_t)std::max<int64_t>(lo, 0)));
 }
 
 #endif

@@ -13,20 +13,7 @@
 #include "pba_rows.h"
 #include "sites.h"
 
-struct pba_sites {
-    int device;
-    uint32_t t_lo, t_hi, n_seqs;
-    uint64_t n, n_sel, n_boxes, words;
-    pba_site *d_recs;                   // n records, sorted by (target, pos, kind)
-    unsigned long long *d_bm;           // SEL bitmap of the arena, words + 1 (the last: zero)
-    uint32_t *d_rank;                   // inclusive scan of the words' SEL counts
-    uint2 *d_sel;                       // per SEL site, in rank order: { record index, own | major << 4 | minor << 8 }
-    unsigned long long *d_box_off;      // nt + 1
-    // on the host, for the per-row slot bounds and the target ranges
-    std::vector<uint64_t> box_off, rec_off, sel_off;    // nt + 1 each
-    std::vector<int32_t> sel_pos;                       // the SEL positions, target by target
-    AllelesInto view() const { return AllelesInto{d_bm, d_rank, d_sel, d_box_off, t_lo, n_boxes}; }
-};
+// (struct pba_sites, sites_same_set and pair_alleles_bound: pba_rows.h, shared with pba_phase.hip)
 
 // ---- the scan ------------------------------------------------------------------------------------------------------------
 // Flag pass: one lane per box (8 + 8 + 4 bytes, coalesced), one wavefront per bitmap word; lane 0 stores the two words and
@@ -109,21 +96,13 @@ static int sites_new(pba_ctx *ctx, const pba_seqs *seqs, uint32_t t_lo, uint32_t
 static void sites_index(pba_sites *s, const pba_site *recs) {
     const uint32_t nt = s->t_hi - s->t_lo;
     s->rec_off.assign((size_t)nt + 1, 0); s->sel_off.assign((size_t)nt + 1, 0);
-    s->sel_pos.clear();
+    s->sel_pos.clear(); s->sel_rec.clear();
     for (uint64_t x = 0; x < s->n; ++x) {
         const size_t k = (size_t)((uint32_t)recs[x].target - s->t_lo);
         ++s->rec_off[k + 1];
-        if (recs[x].kind == PBA_SITE_SEL) { ++s->sel_off[k + 1]; s->sel_pos.push_back(recs[x].pos); }
+        if (recs[x].kind == PBA_SITE_SEL) { ++s->sel_off[k + 1]; s->sel_pos.push_back(recs[x].pos); s->sel_rec.push_back((uint32_t)x); }
     }
     for (uint32_t k = 0; k < nt; ++k) { s->rec_off[k + 1] += s->rec_off[k]; s->sel_off[k + 1] += s->sel_off[k]; }
-}
-
-// `set` is the set these sites were made from, as far as lengths can tell
-static bool sites_same_set(const pba_sites *s, const pba_seqs *set) {
-    if (set->n != s->n_seqs) return false;
-    for (uint32_t k = 0; k < s->t_hi - s->t_lo; ++k)
-        if (s->box_off[k + 1] - s->box_off[k] != set->h_len[s->t_lo + k]) return false;
-    return true;
 }
 
 int pba_pileup_sites(pba_ctx *ctx, const pba_pileup *p, const pba_seqs *target, int min_depth, int min_alt, int min_permille,
@@ -229,6 +208,7 @@ int pba_sites_create(pba_ctx *ctx, const pba_seqs *seqs, uint32_t t_lo, uint32_t
 }
 
 uint64_t pba_sites_count(const pba_sites *s) { return s ? s->n : 0; }
+uint64_t pba_sites_count_sel(const pba_sites *s) { return s ? s->n_sel : 0; }
 
 int pba_sites_target_range(const pba_sites *s, uint32_t target, uint64_t *lo, uint64_t *hi) {
     if (!s || !lo || !hi || target < s->t_lo || target >= s->t_hi) return PBA_E_INVALID;
@@ -252,20 +232,6 @@ void pba_sites_destroy(pba_sites *s) {
 }
 
 // ---- alleles of rows ---------------------------------------------------------------------------------------------------------
-static const uint64_t kAlleleChunkSlots = 1ull << 27;   // bounded allele slots of one chunk of rows on the device (1 GiB)
-
-// The SEL sites in the a-span the accessor could cover at most: the clipped len_a elements from a_pos, by binary search in
-// the host's positions.  0 is a legal bound: the row is still walked and held.
-static uint64_t pair_alleles_bound(const pba_sites *s, const pba_pair &p, double R) {
-    const int la = text_clip(p.a_len, p.b_len, R).len_a;
-    if (la < 1) return 0;
-    const int64_t last = (p.flags & PBA_A_BACKWARD) ? (int64_t)p.a_pos - (la - 1) : (int64_t)p.a_pos + (la - 1);
-    const int64_t lo = std::min<int64_t>(p.a_pos, last), hi = std::max<int64_t>(p.a_pos, last);
-    const size_t k = p.a_seq - s->t_lo;
-    const int32_t *b = s->sel_pos.data() + s->sel_off[k], *e = s->sel_pos.data() + s->sel_off[k + 1];
-    return (uint64_t)(std::upper_bound(b, e, (int32_t)std::min<int64_t>(hi, 0x7FFFFFFF)) - std::lower_bound(b, e, (int32_t)std::max<int64_t>(lo, 0)));
-}
-
 // the alleles of the jobs dense and in row order on the host, the totals row by row
 static int rows_alleles_out(pba_ctx *ctx, const char *who, const pba_seqs *const A[2], const pba_seqs *const B[2], const std::vector<RowJob> &jobs,
                             uint64_t n_rows, double R, int gate, const pba_sites *sites, pba_allele *out, uint64_t cap, uint64_t *off,

@@ -83,6 +83,14 @@ SITE_DTYPE = np.dtype([("target", "<i4"), ("pos", "<i4"), ("kind", "u1"), ("own"
 ALLELE_DTYPE = np.dtype([("site", "<u4"), ("allele", "<u4")])
 ALLELE_COUNTS_DTYPE = np.dtype([(n, "<i4") for n in ("n_sites", "n_own", "n_major", "n_minor", "n_other")])
 assert SITE_DTYPE.itemsize == 24 and ALLELE_DTYPE.itemsize == 8 and ALLELE_COUNTS_DTYPE.itemsize == 20
+# pba_phase_row: a row's label under the phase rule; pba_phase_site: a SEL site's orientation; pba_phase_stats: one call's totals
+PBA_PHASE_MAX_ITER = 64
+PHASE_PARAMS_DTYPE = np.dtype([(n, "<i4") for n in ("n_iter", "min_margin", "self_weight")])
+PHASE_ROW_DTYPE = np.dtype([(n, "<i4") for n in ("label", "score", "n_informative", "n_records")])
+PHASE_SITE_DTYPE = np.dtype([("site", "<u4")] + [(n, "<i4") for n in ("orient", "score", "n_agree", "n_disagree")])
+PHASE_STATS_DTYPE = np.dtype([(n, "<u8") for n in ("n_rows", "n_same", "n_other", "n_unphased", "n_sites", "n_records", "n_flipped_last")] +
+                             [("alleles_ms", "<f4"), ("phase_ms", "<f4")])
+assert PHASE_PARAMS_DTYPE.itemsize == 12 and PHASE_ROW_DTYPE.itemsize == 16 and PHASE_SITE_DTYPE.itemsize == 20 and PHASE_STATS_DTYPE.itemsize == 64
 
 
 class PbaError(RuntimeError):
@@ -1796,6 +1804,10 @@ class Sites:
     def count(self) -> int:
         return int(self.ctx.lib.pba_sites_count(self.h))
 
+    @property
+    def count_sel(self) -> int:
+        return int(self.ctx.lib.pba_sites_count_sel(self.h))
+
     def target_range(self, target: int):
         """(lo, hi): records [lo, hi) are the target's."""
         lo, hi = C.c_uint64(), C.c_uint64()
@@ -1872,6 +1884,90 @@ def sites_tsv_lines(sites, names=None):
                           str(int(r["n_minor"]))])
 
 
+def _phase_params(n_iter, min_margin, self_weight) -> np.ndarray:
+    p = np.zeros(1, PHASE_PARAMS_DTYPE)
+    p["n_iter"], p["min_margin"], p["self_weight"] = n_iter, min_margin, self_weight
+    return p
+
+
+def _stats_dict(st: np.ndarray) -> dict:
+    return {n: (float(st[0][n]) if n.endswith("_ms") else int(st[0][n])) for n in st.dtype.names}
+
+
+def _alleles_phase(self, sites, rows_records, n_iter=2, min_margin=2, self_weight=1, want_sites=True):
+    """The phase rule on allele records the caller supplies (pba_alleles_phase): rows_records is a list of ALLELE_DTYPE arrays (or
+    of lists of (site, allele)), one per row.  Returns (PHASE_ROW_DTYPE records, PHASE_SITE_DTYPE records -- one per SEL site
+    of `sites`, None without want_sites --, stats dict)."""
+    n = len(rows_records)
+    off = np.zeros(n + 1, np.uint64)
+    off[1:] = np.cumsum([len(r) for r in rows_records], dtype=np.uint64) if n else 0
+    flat = np.zeros(int(off[-1]) + 1, ALLELE_DTYPE)
+    for k, r in enumerate(rows_records):
+        if len(r):
+            flat[int(off[k]):int(off[k + 1])] = r if isinstance(r, np.ndarray) else np.array([tuple(x) for x in r], ALLELE_DTYPE)
+    out = np.zeros(max(n, 1), PHASE_ROW_DTYPE)
+    so = np.zeros(max(sites.count_sel, 1), PHASE_SITE_DTYPE) if want_sites else None
+    st = np.zeros(1, PHASE_STATS_DTYPE)
+    p = _phase_params(n_iter, min_margin, self_weight)
+    self.check(self.lib.pba_alleles_phase(self.h, sites.h, _ptr(flat), _ptr(off), n, _ptr(p), _ptr(out), _ptr(so) if want_sites else None,
+                                          _ptr(st)), "alleles_phase")
+    return out[:n], (so[:sites.count_sel] if want_sites else None), _stats_dict(st)
+
+
+def _overlap_phase(self, reads, rows, R, sites, n_iter=2, min_margin=2, self_weight=1, reads_rc=None, max_slots=0, want_sites=True):
+    """overlap_strands rows phased by their alleles at the SEL sites of their targets (pba_overlap_rows_phase_budget): the allele
+    walk and the phase rule on the device.  Returns (PHASE_ROW_DTYPE records, one per row; PHASE_SITE_DTYPE records; stats
+    dict; results)."""
+    rows = np.ascontiguousarray(rows, STRAND_OVERLAP_DTYPE)
+    n = rows.size
+    out = np.zeros(max(n, 1), PHASE_ROW_DTYPE)
+    so = np.zeros(max(sites.count_sel, 1), PHASE_SITE_DTYPE) if want_sites else None
+    st = np.zeros(1, PHASE_STATS_DTYPE)
+    res = np.zeros(max(n, 1), RESULT_DTYPE)
+    p = _phase_params(n_iter, min_margin, self_weight)
+    self.check(self.lib.pba_overlap_rows_phase_budget(self.h, reads.h, reads_rc.h if reads_rc is not None else None, _ptr(rows), n, R, sites.h,
+                                                      _ptr(p), _ptr(out), _ptr(so) if want_sites else None, _ptr(st), _ptr(res), max_slots),
+               "overlap_phase")
+    return out[:n], (so[:sites.count_sel] if want_sites else None), _stats_dict(st), res[:n]
+
+
+def phase_rows_apply(rows: np.ndarray, phase: np.ndarray, keep_unphased: bool = True) -> np.ndarray:
+    """The rows the phase rule puts on the target's own copy (label > 0), with the undecided ones (label == 0) under
+    keep_unphased, in order and unchanged (pba_phase_rows_apply): good for every call that takes overlap rows."""
+    rows = np.ascontiguousarray(rows, STRAND_OVERLAP_DTYPE)
+    phase = np.ascontiguousarray(phase, PHASE_ROW_DTYPE)
+    if rows.size != phase.size:
+        raise PbaError(_lib.PBA_E_INVALID, "phase_rows_apply: one phase record per row")
+    out = np.zeros(max(rows.size, 1), STRAND_OVERLAP_DTYPE)
+    n = _lib.load().pba_phase_rows_apply(_ptr(rows), _ptr(phase), rows.size, int(bool(keep_unphased)), _ptr(out))
+    if n < 0:
+        raise PbaError(_lib.PBA_E_INVALID, "phase_rows_apply")
+    return out[:n]
+
+
+def _correct_reads_phased(self, reads, mask, R, thresholds=(8, 3, 250), n_iter=2, min_margin=2, self_weight=1, keep_unphased=True,
+                          max_trial=32, overlap_min=64, strands=3, weight=1, t_lo=0, t_hi=None, kernel=PBA_KERNEL_AUTO, reads_rc=None,
+                          max_boxes=0):
+    """correct_reads with every target voted only by the rows the phase rule does not put on the other copy
+    (pba_correct_reads_phased_budget): thresholds = (min_depth, min_alt, min_permille) of the site scan.  Returns (SeqSet of the
+    corrected reads, rows of CORRECT_ROW_DTYPE -- n_rows counts the rows kept --, phase stats dict summed over the chunks, [stats
+    of the +1 pass, of the -1 pass])."""
+    t_hi = reads.count if t_hi is None else t_hi
+    rows = np.zeros(max(t_hi - t_lo, 1), CORRECT_ROW_DTYPE)
+    st2 = (_lib.PbaOverlapStats * 2)()
+    pst = np.zeros(1, PHASE_STATS_DTYPE)
+    p = _phase_params(n_iter, min_margin, self_weight)
+    h = C.c_void_p()
+    self.check(self.lib.pba_correct_reads_phased_budget(self.h, reads.h, reads_rc.h if reads_rc is not None else None, t_lo, t_hi, mask, R,
+                                                        max_trial, overlap_min, kernel, strands, weight, max_boxes, *thresholds, _ptr(p),
+                                                        int(bool(keep_unphased)), C.byref(h), _ptr(rows), _ptr(pst), C.byref(st2)),
+               "correct_reads_phased")
+    return SeqSet(self, h), rows[:max(t_hi - t_lo, 0)], _stats_dict(pst), _stats_pair(st2)
+
+
+Context.alleles_phase = _alleles_phase
+Context.overlap_phase = _overlap_phase
+Context.correct_reads_phased = _correct_reads_phased
 Context.sites_create = _sites_create
 Context.overlap_alleles = _overlap_alleles
 Context.map_alleles = _map_alleles
