@@ -69,6 +69,11 @@
 #ifndef PBA_BV_SHIFT
 #define PBA_BV_SHIFT 1
 #endif
+// The one step behind a close of those forms runs inside the close's own iteration of the handler, in front of the stretch
+// that follows it.  -DPBA_BV_CLOSE_INLINE=0: it ends that iteration and runs alone in one of its own.
+#ifndef PBA_BV_CLOSE_INLINE
+#define PBA_BV_CLOSE_INLINE 1
+#endif
 
 #define PBA_BV_MAX_NB 8
 #define PBA_BV_FIN_WORDS(nb) ((2 * (nb) + 1) * 64)     // u32 of LDS per wavefront for the last column's deltas (bitvec_pass: fin)
@@ -690,9 +695,8 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
             // candidates die on their first segment, so they cost 33 steps, not the 64 of a poll per chunk)
             if (seg_fail) { fail_row = seg_fail; kend = k + 1; }
         }
-        if constexpr (SHIFT) {
-            // the step behind a close, on its own: it takes the carries unshifted.  Every block's word collects under the
-            // one-hot (what lands in a word the diagonal is not in is cleared at the segment's end, as in the rings 3 and up)
+        if constexpr (SHIFT && !PBA_BV_CLOSE_INLINE) {
+            // (-DPBA_BV_CLOSE_INLINE=0: the step behind a close ends the handler's iteration and runs on its own in another)
             if (closed) {
                 onehot_t oh = (onehot_t)bv_uniform64(one);
                 uint32_t cq[1] = {ta[0]}, eqn[1][NB];
@@ -703,7 +707,6 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
                 continue;
             }
         }
-        const int kstop = min(kend, s_next - tb);
         // The one-hot goes through the stretch in a local read with v_readfirstlane: `one` is set inside a loop that a
         // failing segment leaves early, so the compiler would carry it in a vector register and shift it there (the
         // same effect as for tbv and score).  qd is constant within a stretch (a segment end is a scheduled event), so with
@@ -714,6 +717,22 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
         onehot_t oh = 0;
         if constexpr (DIAG_FOLD) oh = (onehot_t)bv_uniform64(one);
         else if constexpr (!LANE_HOT) oh = __builtin_amdgcn_readfirstlane(one);
+        if constexpr (SHIFT && PBA_BV_CLOSE_INLINE) {
+            // The step behind a close takes the carries unshifted (PBA_BV_HIN).  It runs here, inside the close's own
+            // iteration, under the one-hot the stretch behind it goes on with: the iteration's one pass through the
+            // stretch's prologue serves both.  Every block's word collects under the one-hot (what lands in a word the
+            // diagonal is not in is cleared at the segment's end, as in the rings 3 and up).  The stretch then runs from
+            // the step behind it: k <= kend and tb + k <= s_next hold (k < kend in front of the step; the events of step t
+            // leave s_next > t), so the stretch's bound is never below k, and it is k where a failed segment or the
+            // chunk's end or another event ends the iteration right here.
+            if (closed) {
+                uint32_t cq[1] = {ta[0]}, eqn[1][NB];
+                PBA_BV_ROWS(0)
+                PBA_BV_STEP1X(NB == 1 ? 0 : -1, 0, true)
+                ta += 1; k += 1;
+            }
+        }
+        const int kstop = min(kend, s_next - tb);
         if constexpr (NB == 2 && TRACE != 1 && !LANE_HOT) {
             if (__builtin_amdgcn_readfirstlane(qd) == 0) { PBA_BV_STRETCH1(0); } else { PBA_BV_STRETCH1(1); }
         } else {
@@ -771,7 +790,11 @@ __device__ __forceinline__ int bitvec_pass(const PackedFetch &rowsF, int nr, con
         if constexpr (RING) ta += 1;                                                  \
         }
         if constexpr (SHIFT) {
-            if (closed) { PBA_BV_STEP2(true) k += 1; continue; }   // the step behind a close (phase 1 above)
+            if (closed) {                                          // the step behind a close (phase 1 above)
+                PBA_BV_STEP2(true)
+                k += 1;
+                if (!PBA_BV_CLOSE_INLINE || k >= min(kend, s_next - tc)) continue;
+            }
         }
         const int kstop = min(kend, s_next - tc);
         do { PBA_BV_STEP2(false) } while (++k < kstop);
